@@ -5,7 +5,7 @@ R=$1; shift
 for r in $(seq 1 $R); do
   for v in "$@"; do
     if [ "$v" = "old" ]; then export NIC_T16=0; unset NIC_LIB_PATH; else export NIC_T16=1; export NIC_LIB_PATH=$PWD/ab/lib$v.so; fi
-    timeout -k 10 120 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --stat-launches 30 2>/dev/null | python -c "
+    timeout -k 10 120 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --stat-launches 30 2>/dev/null | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

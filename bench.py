@@ -23,14 +23,21 @@ Multi-GPU shapes (one process per GPU, RCCL):
   --workload video --gpus N   BASELINE config 4: the 1920 x 1080 x 64 field, z-stripes of the 3D grids, same two scalings.
   --workload fits64 --gpus N  BASELINE config 5: 64 independent 1080p fits, 64 / N per GPU back to back (replicas only, no collective).
 
-Prints ONE JSON line on rank 0 (see the driver contract).  `value` comes from the K timed steps alone.  Beside it:
+Prints ONE JSON line on rank 0 (see the driver contract).  `value` and `ms_per_step` come from the K timed steps alone.  A plain run sets up,
+warms up, times the K steps, decodes once for the PSNR and prints the line; beside `value` it carries
   roofline       dominant kernel (the fused training kernel of --precision), HIP events on its launch stream: `kernel_ms` = mean over
-                 the K timed steps (what `achieved` uses); `stats` = median / p10 / p90 over a separate leg of >= 100 launches run
-                 after the timed region (the K = 20 of the driver's default is 45 ms - too short for percentiles)
+                 the K timed steps (what `achieved` uses)
+--full adds the legs that take runs of their own, after the timed region:
+  roofline.stats median / p10 / p90 over a separate leg of >= 100 launches (the K = 20 of the driver's default is 45 ms - too short for
+                 percentiles)
   roofline_*     the other arithmetic modes measured in the same run on the same inputs (kernel-only legs): f32 / split / bf16
   roofline_4x64  the north star's literal configuration as a WHOLE step: 5-Linear "4 x 64" decoder, bf16 grid storage with fp32 masters,
                  plain-bf16 products, fused step + reduce + one nic_adam_multi over 10 + 2 tensors (16-bit mirrors rewritten)
+  shard_legs     N > 1, strong scaling, stripes: the replicated leg of the same step beside the headline stripes leg
   cpu_baseline   N = 1: the CPU oracle on a bounded strip of the same workload at the fastest thread count found on the box
+--dump-outputs DIR writes what the last timed step handed its caller (the loss, the updated decoder and grids) as DIR/<name>.npy; the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.  The grid gradients are fp32 atomic sums:
+their rounding depends on the flush order and carries over the K + W chained steps (25 steps: ~1e-6 of an array's largest value).
 --precision split (default): every matrix product as hi + lo bf16 pairs on the bf16 matrix pipe with fp32 accumulation (gradients within
 5e-6 of the fp32 kernel; the headline stays on it so that it remains comparable with the reference's fp32 arithmetic); f32:
 v_mfma_f32_32x32x2_f32; bf16: plain bf16 products (NIC_FLAG_BF16; checked against the precision-emulating oracle, tests/test_gpu_bf16.py).
@@ -183,6 +190,39 @@ def pct(xs):
     xs = np.asarray(xs, dtype=np.float64)
     return {"n": int(xs.size), "median": round(float(np.median(xs)), 4), "p10": round(float(np.percentile(xs, 10)), 4),
             "p90": round(float(np.percentile(xs, 90)), 4), "min": round(float(xs.min()), 4), "mean": round(float(xs.mean()), 4)}
+
+
+DUMP_BYTES = 64 << 20               # --dump-outputs: the whole dump stays within this
+DUMP_SAMPLE = 4 << 20               # elements kept of an array that does not fit
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 (float64 for host scalars).  When the whole set exceeds DUMP_BYTES, every array of more
+    than DUMP_SAMPLE elements is replaced by the same fixed, seeded sample of its flattened elements in every run (sorted indices, drawn from a
+    generator seeded by the array's size), so two builds can be compared element for element."""
+    out = {}
+    for name, v in arrays.items():
+        out[name] = v.detach().float().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64)
+    if sum(a.nbytes for a in out.values()) > DUMP_BYTES:
+        for name, a in out.items():
+            if a.size > DUMP_SAMPLE:
+                idx = np.unique(np.random.default_rng(a.size).integers(0, a.size, DUMP_SAMPLE))
+                out[name] = np.ascontiguousarray(a.reshape(-1)[idx])
+    assert sum(a.nbytes for a in out.values()) <= DUMP_BYTES, {k: a.nbytes for k, a in out.items()}
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def step_outputs(fit, out):
+    """what one training step of ``fit`` hands its caller, like ImageCompression.train_step: the loss and the parameters Adam left behind (decoder +
+    grids).  The gradient buckets are the step's scratch - the optimiser consumes them in the same launch (the grid part is zeroed) - and they are
+    the step's least reproducible values: their fp32 atomic sums depend on the order in which workgroups flush"""
+    res = {"loss": out.loss}
+    for i, p in enumerate(fit.params):
+        res[f"decoder_{i}"] = p
+    res["g0"], res["g1"] = fit.master
+    return res
 
 
 ISSUE_SOURCE = "profiles/issue.json"
@@ -586,10 +626,12 @@ def run_sharded(args, rank, world, dev):
                 m.copy_(p)
     timed_kernel_ms = [e.elapsed_ms() for e in ev]                     # the fused kernel alone (nic_mark_kernel_end)
     kern_ms = float(np.mean(timed_kernel_ms))
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(fit, out))
     # the OTHER shard leg of the same strong-scaling step, same run, same timing protocol: replicated parameters, the whole gradient bucket
     # all-reduced (the north star's literal scheme; `--shard replicated` makes it the headline leg instead) - so that one line carries both
     other_leg = None
-    if world > 1 and strong and stripes and not video:
+    if args.full and world > 1 and strong and stripes and not video:
         f2 = Fit(dev, dim, method, grid_base=tuple(s // 4 for s in full), n_linear=args.decoder, precision=args.precision, grid_dtype=gdt)
 
         def step2(i):
@@ -625,7 +667,7 @@ def run_sharded(args, rank, world, dev):
         del rec, ref_img
     # statistics + the other arithmetic modes, after the timed region (every rank runs them: same work everywhere, no collectives)
     extra = {}
-    if args.stat_launches > 0:
+    if args.full and args.stat_launches > 0:
         stat_main = kernel_only_leg(fit, args.stat_launches)
         if fit.mirror is None and fit.nl == 3 and vworld == 1:
             for other in ("split", "f32", "bf16", "fp16"):
@@ -637,7 +679,7 @@ def run_sharded(args, rank, world, dev):
     # masters, plain-bf16 products; fused step + reduce + Adam over all 12 tensors with the 16-bit mirrors rewritten.  Beside it the same
     # decoder on the split-bf16 kernel (fp32 grids), kernel only.
     lit = None
-    if args.stat_launches > 0 and not video and vworld == 1 and not (args.decoder == 5 and args.precision == "bf16" and gdt == torch.bfloat16):
+    if args.full and args.stat_launches > 0 and not video and vworld == 1 and not (args.decoder == 5 and args.precision == "bf16" and gdt == torch.bfloat16):
         f5 = Fit(dev, 2, 1, grid_base=(H // 4, W // 4), n_linear=5, precision="bf16", grid_dtype=torch.bfloat16, seed=1)
         k5, w5 = max(args.stat_launches // 4, 10), 3
         ev5 = [KernelEvents(f5.lib) for _ in range(k5)]
@@ -726,7 +768,7 @@ def run_sharded(args, rank, world, dev):
                       "split_bf16_products_fp32_grids_kernel_only": {"kernel": kernel_name(2, 1, "split", 5), "kernel_ms": round(float(np.median(ks5)), 4),
                                                                      "mpix_s": round(n_mine / float(np.median(ks5)) / 1e3, 1), "stats": pct(ks5)}})
             res["roofline_4x64"] = r
-        if world == 1 and not args.no_cpu_baseline and not video:
+        if args.full and world == 1 and not args.no_cpu_baseline and not video:
             res["cpu_baseline"] = cpu_baseline(img)
         print(json.dumps(res), flush=True)
 
@@ -773,6 +815,9 @@ def run_fits64(args, rank, world, dev):
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs is not None and rank == 0:
+        # every fit's loss; the whole step record of the rank's first fit (64 of them would not fit the dump budget)
+        dump_outputs(args.dump_outputs, {"loss_per_fit": torch.stack([o.loss.reshape(()) for o in outs]), **step_outputs(fits[0], outs[0])})
     if rank == 0:
         rate = NF * HH * WW * args.steps / elapsed / 1e6
         _, fl, byt = work_per_sample(2, 1, args.decoder)
@@ -793,8 +838,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--stat-launches", type=int, default=120, help="launches of the post-run statistics leg (median / p10 / p90 of the kernel time); 0: skip the extra legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the extra legs: kernel-time statistics, the other arithmetic modes, the 4 x 64 whole step, the "
+                         "replicated shard leg (N > 1) and the CPU baseline.  Off: set up, warm up, time the K steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step handed its caller (the loss, the updated decoder and grids) as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all: a fixed seeded sample of an array that does not fit)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--stat-launches", type=int, default=120, help="--full: launches of the post-run statistics leg (median / p10 / p90 of the kernel time); "
+                                                                   "0: skip the extra legs")
     ap.add_argument("--prewarm-ms", type=float, default=300.0, help="untimed kernel launches before the W warm-up steps (clock ramp)")
     ap.add_argument("--precision", choices=["split", "f32", "bf16", "fp16"], default="split",
                     help="split: every matrix product of the step as hi + lo bf16 pairs on the bf16 matrix pipe, fp32 accumulate (gradients "
@@ -861,6 +913,8 @@ def main():
     if args.workload not in ("4k", "video", "fits64"):
         if world != 1:
             ap.error(f"--workload {args.workload} runs on one GPU")
+        if args.dump_outputs is not None:
+            ap.error("--dump-outputs: workloads 4k, video and fits64 only")
         import bench_workloads
         bench_workloads.run(args)
         return

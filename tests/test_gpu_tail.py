@@ -418,14 +418,14 @@ def test_host_origins_by_value_equal_device_origins(dev, kind):
 
 
 def test_bench_line_keeps_the_driver_contract(dev):
-    """``python bench.py --steps K --warmup W`` (what the driver runs): exactly ONE line on stdout, JSON, with the contract's keys, the `roofline` and
+    """``python bench.py --full --steps K --warmup W``: exactly ONE line on stdout, JSON, with the contract's keys, the `roofline` and
     `cpu_baseline` objects, a kernel time that brackets the fused kernel alone (<= the step), and a step that is two launches' worth of time"""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "2", "--stat-launches", "0"], capture_output=True, text=True,
-                       timeout=600, cwd=root)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3", "--warmup", "2", "--stat-launches", "0"], capture_output=True,
+                       text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.split("\n") if l.strip()]
     assert len(lines) == 1, lines
@@ -445,6 +445,42 @@ def test_bench_line_keeps_the_driver_contract(dev):
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and "sample" in cb
 
 
+def test_bench_plain_line_and_output_dump(dev, tmp_path):
+    """``python bench.py --steps K --warmup W --dump-outputs DIR`` (no --full): the headline line without the extra legs, K timed steps, and the last
+    step's outputs (loss, updated decoder and grids) as float32 .npy files within 64 MB - the same files from a second run of the same arguments, up to
+    the rounding of the grid gradients' atomic sums (measured: the loss to the bit, the parameters within 1e-6 of each array's largest value)"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "1", "--dump-outputs", str(d)], capture_output=True,
+                           text=True, timeout=300, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.split("\n") if l.strip()]
+        assert len(lines) == 1, lines
+        line = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+            assert key in line, key
+        for key in ("cpu_baseline", "roofline_f32", "roofline_bf16", "roofline_4x64"):
+            assert key not in line, key
+        assert line["steps"] == 4 and line["warmup"] == 1 and "stat_leg" not in line["roofline"]["stats"]
+        assert line["roofline"]["stats"]["timed_steps"]["n"] == 4
+        assert abs(line["value"] - 3840 * 2160 / line["ms_per_step"] / 1e3) <= 0.01 * line["value"]
+        files = sorted(os.listdir(d))
+        assert set(files) == {"loss.npy", "g0.npy", "g1.npy"} | {f"decoder_{i}.npy" for i in range(6)}, files
+        arrs = {f[:-4]: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        assert arrs["g0"].shape == (12, 961, 541) and abs(float(arrs["loss"]) - line["config"]["final_loss"]) <= 1e-6 + 1e-5 * line["config"]["final_loss"]
+        dumps.append(arrs)
+    for name, a in dumps[0].items():
+        b = dumps[1][name]
+        assert a.shape == b.shape and float(np.abs(a - b).max()) <= 1e-5 * max(float(np.abs(b).max()), 1e-30), name
+
+
 def test_bench_two_ranks_rehearsal_on_one_gpu(dev):
     """the N > 1 path of bench.py end to end on real kernels: two ranks on this one GPU over gloo (NIC_DIST_BACKEND=gloo: the rehearsal mode; the numbers mean
     nothing) - strong scaling, stripe-sharded grids with the interior-row optimiser inside the exchange, and the replicated leg beside it in the same line"""
@@ -453,8 +489,8 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(dev):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, NIC_DIST_BACKEND="gloo")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--stat-launches", "0"],
-                       capture_output=True, text=True, timeout=900, cwd=root, env=env)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                        "--stat-launches", "0"], capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.split("\n") if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
