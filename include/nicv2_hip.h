@@ -459,6 +459,32 @@ typedef struct nic_row_set {
 int nic_stripe_pack(const float *small_buf, int64_t n_small, const nic_row_set *sets, int nsets, float *buf, void *stream);
 int nic_stripe_unpack(float *small_buf, int64_t n_small, const nic_row_set *sets, int nsets, const float *buf, void *stream);
 
+/* ---- multi-resolution hash-grid encoding (no reference counterpart: an Instant-NGP-style extension, neural_image_compression_v2_amd/hashgrid.py).
+ *      A field covers integer sample coordinates i_a in [0, S_a) on `dim` axes, S_max = max_a S_a.  Level l has resolution R_l (host-computed) and
+ *      a table of T = 2^log2_table entries of `features` floats: table = [levels, T, features] fp32.  On axis a, q = (2 i_a + 1) R_l:
+ *      base vertex v_a = floor(q / (2 S_max)) (exact integer), weight w_a = (q mod 2 S_max) / (2 S_max) (fp32).  Entry of vertex v:
+ *      (R_l + 1)^dim <= T: v_x + (R_l + 1) (v_y + (R_l + 1) v_z); otherwise (v_x * 1) ^ (v_y * 2654435761u) ^ (v_z * 805459861u) in wrapping uint32;
+ *      both & (T - 1).  out = [N, levels * features]: column l F + f = sum over the 2^dim corners c of prod_a (c_a ? w_a : 1 - w_a) table[l, idx(v + c), f].
+ *      Samples: crops back to back, x-outer .. last axis inner (like nic_encode); origins = [num_crops, dim] int32 (device).
+ *      nic_hash_encode_backward ADDS dx = d loss / d out into table_grad (fp32 atomics; the caller zeroes it); summation order is not fixed. */
+#define NIC_HASH_MAX_LEVELS 32
+typedef struct nic_hash_desc {
+    int32_t dim;             /* 2 or 3 */
+    int32_t levels;          /* 1 .. NIC_HASH_MAX_LEVELS */
+    int32_t features;        /* 1, 2, 4 or 8 */
+    int32_t log2_table;      /* 10 .. 24 */
+    int32_t S_max;           /* largest field extent; 2 S_max R_l < 2^31 */
+    int32_t num_crops;
+    int32_t extent[3];       /* samples per axis of one crop; extent[2] = 1 in 2D */
+    int32_t resolution[NIC_HASH_MAX_LEVELS];   /* R_l >= 1 */
+    int32_t flags;           /* 0 */
+    int32_t reserved;
+} nic_hash_desc;
+int nic_hash_encode(const nic_hash_desc *desc, const float *table, const int32_t *origins, float *out, void *stream);
+int nic_hash_encode_backward(const nic_hash_desc *desc, const int32_t *origins, const float *dx, float *table_grad, void *stream);
+/* the entry index of vertex (vx, vy, vz) at `level` (vz = 0 in 2D) from the same function the kernels use, or a NIC_E_* code */
+int nic_hash_index_host(const nic_hash_desc *desc, int level, int32_t vx, int32_t vy, int32_t vz);
+
 #ifdef __cplusplus
 }
 #endif

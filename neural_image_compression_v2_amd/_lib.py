@@ -100,6 +100,16 @@ class NicTargetImage(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+NIC_HASH_MAX_LEVELS = 32
+
+
+class NicHashDesc(ctypes.Structure):
+    """struct nic_hash_desc (include/nicv2_hip.h): one hash-grid encode launch (hashgrid.py)"""
+    _fields_ = [("dim", ctypes.c_int32), ("levels", ctypes.c_int32), ("features", ctypes.c_int32), ("log2_table", ctypes.c_int32),
+                ("S_max", ctypes.c_int32), ("num_crops", ctypes.c_int32), ("extent", ctypes.c_int32 * 3),
+                ("resolution", ctypes.c_int32 * NIC_HASH_MAX_LEVELS), ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 _P, _I, _L, _F, _SZ, _DBL = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t, ctypes.c_double
 _D = ctypes.POINTER(NicPathDesc)
 _M = ctypes.POINTER(NicMlp)
@@ -151,6 +161,9 @@ SIGNATURES = {
     "nic_mark_kernel_end": (_I, [_P]),
     "nic_stripe_pack": (_I, [_P, _L, ctypes.POINTER(NicRowSet), _I, _P, _P]),
     "nic_stripe_unpack": (_I, [_P, _L, ctypes.POINTER(NicRowSet), _I, _P, _P]),
+    "nic_hash_encode": (_I, [ctypes.POINTER(NicHashDesc), _P, _P, _P, _P]),
+    "nic_hash_encode_backward": (_I, [ctypes.POINTER(NicHashDesc), _P, _P, _P, _P]),
+    "nic_hash_index_host": (_I, [ctypes.POINTER(NicHashDesc), _I, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -1,0 +1,308 @@
+// Multi-resolution hash-grid encoding (include/nicv2_hip.h: nic_hash_encode / nic_hash_encode_backward; hashgrid.py).  No reference
+// counterpart: the semantics are this project's own and are spelled out in the header.  One wave per patch of 8 x 8 (2D) / 4 x 4 x 4 (3D)
+// samples - the patches of encode_backward_kernel - with x the fastest lane axis: at the finest levels the lanes of a row then read and add into
+// neighbouring entries (hashed: v_x enters the hash with factor 1, so 8 consecutive vertices are a permutation of 8 consecutive entries), at the
+// coarse levels whole rows or the whole wave share a vertex.  Every table address is masked with T - 1: no input can leave a level.
+//
+// -DNIC_HASH_NO_RUNSUM: every live lane issues its own atomics (the A/B of the run sums, ab/bench_hashgrid.py).
+#include "nic_device.hpp"
+
+namespace nic {
+
+__host__ __device__ inline bool hash_level_dense(int dim, int32_t R, int log2_table) {
+    uint64_t p = 1;
+    for (int a = 0; a < dim; ++a) {
+        p *= (uint64_t)R + 1;
+        if (p > (1ull << log2_table)) return false;
+    }
+    return true;
+}
+
+// the entry of vertex (vx, vy, vz) in a level of resolution R (vz = 0 in 2D)
+__host__ __device__ inline uint32_t hash_index(bool dense, uint32_t R, uint32_t mask, uint32_t vx, uint32_t vy, uint32_t vz) {
+    const uint32_t h = dense ? vx + (R + 1u) * (vy + (R + 1u) * vz) : (vx ^ (vy * 2654435761u) ^ (vz * 805459861u));
+    return h & mask;
+}
+
+struct HashParams {
+    nic_hash_desc d;
+    const float* table;
+    const int32_t* origins;
+    const float* dx;
+    float* out;
+    float* grad;
+};
+
+template <int F>
+__device__ __forceinline__ void load_row(const float* p, float (&v)[F]) {
+    if constexpr (F == 1) {
+        v[0] = *p;
+    } else if constexpr (F == 2) {
+        const float2 a = *reinterpret_cast<const float2*>(p);
+        v[0] = a.x; v[1] = a.y;
+    } else {
+#pragma unroll
+        for (int k = 0; k < F; k += 4) {
+            const float4 a = *reinterpret_cast<const float4*>(p + k);
+            v[k] = a.x; v[k + 1] = a.y; v[k + 2] = a.z; v[k + 3] = a.w;
+        }
+    }
+}
+
+template <int F>
+__device__ __forceinline__ void store_row(float* p, const float (&v)[F]) {
+    if constexpr (F == 1) {
+        *p = v[0];
+    } else if constexpr (F == 2) {
+        *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < F; k += 4) *reinterpret_cast<float4*>(p + k) = make_float4(v[k], v[k + 1], v[k + 2], v[k + 3]);
+    }
+}
+
+// the sample of this lane in patch `wv` (clamped to the last patch; `live` = a real sample of a real patch)
+template <int D>
+struct PatchSample {
+    int crop;
+    int idx[3];
+    bool live;
+    int64_t n;
+};
+template <int D>
+__device__ __forceinline__ PatchSample<D> patch_sample(const nic_hash_desc& d, int64_t wv, int64_t n_patches, int lane) {
+    constexpr int PS = D == 2 ? 8 : 4;
+    const int np1 = (d.extent[1] + PS - 1) / PS, np2 = D == 3 ? (d.extent[2] + PS - 1) / PS : 1;
+    const int64_t per_crop = (int64_t)((d.extent[0] + PS - 1) / PS) * np1 * np2;
+    const int64_t wc = wv < n_patches ? wv : n_patches - 1;
+    PatchSample<D> s;
+    s.crop = (int)(wc / per_crop);
+    int64_t pr = wc - (int64_t)s.crop * per_crop;
+    int pt[3] = {0, 0, 0};
+    if (D == 3) { pt[2] = (int)(pr % np2); pr /= np2; }
+    pt[1] = (int)(pr % np1);
+    pt[0] = (int)(pr / np1);
+    if (D == 2) {
+        s.idx[0] = PS * pt[0] + (lane & 7);
+        s.idx[1] = PS * pt[1] + (lane >> 3);
+        s.idx[2] = 0;
+    } else {
+        s.idx[0] = PS * pt[0] + (lane & 3);
+        s.idx[1] = PS * pt[1] + ((lane >> 2) & 3);
+        s.idx[2] = PS * pt[2] + (lane >> 4);
+    }
+    s.live = wv < n_patches;
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        s.live = s.live && s.idx[a] < d.extent[a];
+        s.idx[a] = s.idx[a] < d.extent[a] ? s.idx[a] : d.extent[a] - 1;
+    }
+    const int64_t n_per_crop = (int64_t)d.extent[0] * d.extent[1] * (D == 3 ? d.extent[2] : 1);
+    s.n = (int64_t)s.crop * n_per_crop + ((int64_t)s.idx[0] * d.extent[1] + s.idx[1]) * (D == 3 ? d.extent[2] : 1) + (D == 3 ? s.idx[2] : 0);
+    return s;
+}
+
+// integer sample coordinate per axis, clamped into the field (an origin outside it is refused on the host; this keeps q < 2^31 regardless)
+template <int D>
+__device__ __forceinline__ void sample_coords(const HashParams& p, const PatchSample<D>& s, uint32_t (&i)[3]) {
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        const int c = p.origins[s.crop * D + a] + s.idx[a];
+        i[a] = (uint32_t)(c < 0 ? 0 : (c >= p.d.S_max ? p.d.S_max - 1 : c));
+    }
+    if (D == 2) i[2] = 0;
+}
+
+// base vertex and fp32 weight per axis of one level: q = (2 i + 1) R, v = q / 2 S_max, w = (q mod 2 S_max) / 2 S_max
+template <int D>
+__device__ __forceinline__ void level_cell(const uint32_t (&i)[3], uint32_t R, uint32_t S2, uint32_t (&v)[3], float (&w)[3]) {
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        const uint32_t q = (2u * i[a] + 1u) * R;
+        v[a] = q / S2;
+        w[a] = (float)(q - v[a] * S2) / (float)S2;
+    }
+    if (D == 2) { v[2] = 0; w[2] = 0.f; }
+}
+
+template <int D>
+__device__ __forceinline__ float corner_weight(const float (&w)[3], int c) {
+    float r = ((c & 1) ? w[0] : 1.0f - w[0]) * ((c & 2) ? w[1] : 1.0f - w[1]);
+    if (D == 3) r *= (c & 4) ? w[2] : 1.0f - w[2];
+    return r;
+}
+
+template <int D, int F>
+__global__ void __launch_bounds__(256) hash_encode_kernel(HashParams p) {
+    const nic_hash_desc& d = p.d;
+    const int lane = threadIdx.x & 63;
+    constexpr int PS = D == 2 ? 8 : 4;
+    int64_t n_patches = d.num_crops;
+#pragma unroll
+    for (int a = 0; a < D; ++a) n_patches *= (d.extent[a] + PS - 1) / PS;
+    const uint32_t S2 = 2u * (uint32_t)d.S_max, mask = (1u << d.log2_table) - 1u;
+    const int LF = d.levels * F;
+    for (int64_t wb = (int64_t)blockIdx.x * 4; wb < n_patches; wb += (int64_t)gridDim.x * 4) {
+        const PatchSample<D> s = patch_sample<D>(d, wb + (threadIdx.x >> 6), n_patches, lane);
+        if (!s.live) continue;
+        uint32_t i[3];
+        sample_coords<D>(p, s, i);
+        float* orow = p.out + s.n * LF;
+        for (int l = 0; l < d.levels; ++l) {
+            const uint32_t R = (uint32_t)d.resolution[l];
+            const bool dense = hash_level_dense(D, (int32_t)R, d.log2_table);
+            const float* tab = p.table + ((int64_t)l << d.log2_table) * F;
+            uint32_t v[3];
+            float w[3];
+            level_cell<D>(i, R, S2, v, w);
+            float acc[F];
+#pragma unroll
+            for (int f = 0; f < F; ++f) acc[f] = 0.f;
+#pragma unroll
+            for (int c = 0; c < (1 << D); ++c) {
+                const uint32_t e = hash_index(dense, R, mask, v[0] + (c & 1), v[1] + ((c >> 1) & 1), D == 3 ? v[2] + ((c >> 2) & 1) : 0u);
+                float t[F];
+                load_row<F>(tab + (int64_t)e * F, t);
+                const float cw = corner_weight<D>(w, c);
+#pragma unroll
+                for (int f = 0; f < F; ++f) acc[f] += cw * t[f];
+            }
+            store_row<F>(orow + l * F, acc);
+        }
+    }
+}
+
+template <int D, int F>
+__global__ void __launch_bounds__(256) hash_encode_backward_kernel(HashParams p) {
+    const nic_hash_desc& d = p.d;
+    const int lane = threadIdx.x & 63;
+    constexpr int PS = D == 2 ? 8 : 4;
+    int64_t n_patches = d.num_crops;
+#pragma unroll
+    for (int a = 0; a < D; ++a) n_patches *= (d.extent[a] + PS - 1) / PS;
+    const uint32_t S2 = 2u * (uint32_t)d.S_max, mask = (1u << d.log2_table) - 1u;
+    const int LF = d.levels * F;
+    for (int64_t wb = (int64_t)blockIdx.x * 4; wb < n_patches; wb += (int64_t)gridDim.x * 4) {      // block-uniform trip count: the shuffles see whole waves
+        const PatchSample<D> s = patch_sample<D>(d, wb + (threadIdx.x >> 6), n_patches, lane);
+        uint32_t i[3];
+        sample_coords<D>(p, s, i);
+        const float* drow = p.dx + s.n * LF;
+        for (int l = 0; l < d.levels; ++l) {
+            const uint32_t R = (uint32_t)d.resolution[l];
+            const bool dense = hash_level_dense(D, (int32_t)R, d.log2_table);
+            float* gtab = p.grad + ((int64_t)l << d.log2_table) * F;
+            uint32_t v[3];
+            float w[3];
+            level_cell<D>(i, R, S2, v, w);
+            float g[F];
+            if (s.live) load_row<F>(drow + l * F, g);
+            else {
+#pragma unroll
+                for (int f = 0; f < F; ++f) g[f] = 0.f;
+            }
+#ifndef NIC_HASH_NO_RUNSUM
+            // runs keyed on the base VERTEX (unique per cell, unlike its hashed entry: two cells whose base entries collide still differ in
+            // their other corners); dead lanes get negative keys of their own
+            const int64_t key = (int64_t)v[0] + ((int64_t)R + 1) * ((int64_t)v[1] + ((int64_t)R + 1) * (int64_t)v[2]);
+            const RunMasks m = run_masks(s.live ? key : -1 - (int64_t)lane, lane);
+            const bool issue = s.live && m.head;
+#else
+            const bool issue = s.live;
+#endif
+#pragma unroll
+            for (int c = 0; c < (1 << D); ++c) {
+                const uint32_t e = hash_index(dense, R, mask, v[0] + (c & 1), v[1] + ((c >> 1) & 1), D == 3 ? v[2] + ((c >> 2) & 1) : 0u);
+                const float cw = corner_weight<D>(w, c);
+#pragma unroll
+                for (int f = 0; f < F; ++f) {
+                    float val = cw * g[f];
+#ifndef NIC_HASH_NO_RUNSUM
+                    if (m.any_shared) val = run_sum(val, m);
+#endif
+                    if (issue) atomicAdd(gtab + (int64_t)e * F + f, val);
+                }
+            }
+        }
+    }
+}
+
+static inline int hash_blocks(const nic_hash_desc* d) {
+    const int PS = d->dim == 2 ? 8 : 4;
+    int64_t patches = d->num_crops;
+    for (int a = 0; a < d->dim; ++a) patches *= (d->extent[a] + PS - 1) / PS;
+    const int64_t b = (patches + 3) / 4;                 // one wave per patch, four waves per block
+    return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
+}
+
+}  // namespace nic
+
+using namespace nic;
+
+static int check_hash_desc(const nic_hash_desc* d) {
+    if (!d) return NIC_E_NULL;
+    if (d->dim != 2 && d->dim != 3) return NIC_E_UNSUPPORTED;
+    if (d->features != 1 && d->features != 2 && d->features != 4 && d->features != 8) return NIC_E_UNSUPPORTED;
+    if (d->levels < 1 || d->levels > NIC_HASH_MAX_LEVELS) return NIC_E_ARG;
+    if (d->log2_table < 10 || d->log2_table > 24) return NIC_E_ARG;
+    if (d->S_max < 1 || d->flags != 0) return NIC_E_ARG;
+    for (int l = 0; l < d->levels; ++l)      // q = (2 i + 1) R_l < 2 S_max R_l must stay below 2^31
+        if (d->resolution[l] < 1 || 2 * (int64_t)d->S_max * d->resolution[l] >= (int64_t(1) << 31)) return NIC_E_ARG;
+    if (d->num_crops < 1) return NIC_E_SHAPE;
+    for (int a = 0; a < d->dim; ++a)
+        if (d->extent[a] < 1 || d->extent[a] > d->S_max) return NIC_E_SHAPE;
+    return NIC_OK;
+}
+
+template <int D, int F>
+static void launch_fwd(const HashParams& p, int nb, hipStream_t s) { hipLaunchKernelGGL((hash_encode_kernel<D, F>), dim3(nb), dim3(256), 0, s, p); }
+template <int D, int F>
+static void launch_bwd(const HashParams& p, int nb, hipStream_t s) { hipLaunchKernelGGL((hash_encode_backward_kernel<D, F>), dim3(nb), dim3(256), 0, s, p); }
+
+template <bool BWD, int D>
+static void launch_f(const HashParams& p, int nb, hipStream_t s) {
+    switch (p.d.features) {
+        case 1: BWD ? launch_bwd<D, 1>(p, nb, s) : launch_fwd<D, 1>(p, nb, s); break;
+        case 2: BWD ? launch_bwd<D, 2>(p, nb, s) : launch_fwd<D, 2>(p, nb, s); break;
+        case 4: BWD ? launch_bwd<D, 4>(p, nb, s) : launch_fwd<D, 4>(p, nb, s); break;
+        default: BWD ? launch_bwd<D, 8>(p, nb, s) : launch_fwd<D, 8>(p, nb, s); break;
+    }
+}
+
+template <bool BWD>
+static int hash_launch(const HashParams& p, void* stream) {
+    const int nb = hash_blocks(&p.d);
+    if (p.d.dim == 2) launch_f<BWD, 2>(p, nb, (hipStream_t)stream);
+    else launch_f<BWD, 3>(p, nb, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+
+extern "C" {
+
+int nic_hash_encode(const nic_hash_desc* desc, const float* table, const int32_t* origins, float* out, void* stream) {
+    const int rc = check_hash_desc(desc);
+    if (rc) return rc;
+    if (!table || !origins || !out) return NIC_E_NULL;
+    HashParams p{};
+    p.d = *desc; p.table = table; p.origins = origins; p.out = out;
+    return hash_launch<false>(p, stream);
+}
+
+int nic_hash_encode_backward(const nic_hash_desc* desc, const int32_t* origins, const float* dx, float* table_grad, void* stream) {
+    const int rc = check_hash_desc(desc);
+    if (rc) return rc;
+    if (!origins || !dx || !table_grad) return NIC_E_NULL;
+    HashParams p{};
+    p.d = *desc; p.origins = origins; p.dx = dx; p.grad = table_grad;
+    return hash_launch<true>(p, stream);
+}
+
+int nic_hash_index_host(const nic_hash_desc* desc, int level, int32_t vx, int32_t vy, int32_t vz) {
+    const int rc = check_hash_desc(desc);
+    if (rc) return rc;
+    if (level < 0 || level >= desc->levels) return NIC_E_ARG;
+    const int32_t R = desc->resolution[level];
+    return (int)hash_index(hash_level_dense(desc->dim, R, desc->log2_table), (uint32_t)R, (1u << desc->log2_table) - 1u, (uint32_t)vx,
+                           (uint32_t)vy, desc->dim == 3 ? (uint32_t)vz : 0u);
+}
+
+}  // extern "C"

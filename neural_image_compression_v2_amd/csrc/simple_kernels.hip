@@ -97,38 +97,7 @@ struct EncodeBwdParams {
     int64_t n_per_crop, n_total;
 };
 
-// Consecutive lanes are consecutive samples along the last axis: with cells of 4 .. 4096 samples (the multi-level extension reads pair l at
-// 4^-(l+1)) whole runs of lanes add into the SAME nodes - a coarse pair takes every sample of the launch on a few hundred addresses.  Runs of
-// equal cells are therefore summed across lanes first (segmented shuffle reduction: lane i gathers the values of the up to 2^k following lanes
-// of its run) and only the head of a run issues the atomic: 8.3 M samples on the [12,5,4] grid went from seconds to the cost of the shuffles.
-struct RunMasks {
-    bool same[6];     // lane + 2^k is in this lane's run
-    bool head;        // first lane of its run
-    bool any_shared;  // wave-uniform: some run is longer than one lane
-};
-__device__ __forceinline__ RunMasks run_masks(int64_t key, int lane) {
-    RunMasks m;
-    const int plo = __shfl_up((int)(uint32_t)key, 1), phi = __shfl_up((int)(key >> 32), 1);
-    m.head = lane == 0 || plo != (int)(uint32_t)key || phi != (int)(key >> 32);
-    const unsigned long long hb = __ballot(m.head);
-    const int run = __popcll(hb & (~0ull >> (63 - lane)));
-    m.any_shared = __popcll(hb) != 64;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const int other = __shfl_down(run, 1 << k);
-        m.same[k] = lane + (1 << k) < 64 && other == run;
-    }
-    return m;
-}
-__device__ __forceinline__ float run_sum(float v, const RunMasks& m) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const float o = __shfl_down(v, 1 << k);
-        v += m.same[k] ? o : 0.f;
-    }
-    return v;
-}
-
+// Runs of lanes that add into the same cells are summed first: run_masks / run_sum (nic_device.hpp).
 template <int DIM>
 __global__ void __launch_bounds__(256) encode_backward_kernel(EncodeBwdParams p) {
     const nic_path_desc& d = p.d;

@@ -20,7 +20,7 @@ decoder from the general layer-wise kernels (``nic_decoder_general_*``) and the 
 and the loss are torch tensors there like in the reference (image_compression.py:248-259).  The parity tests hold (b) to the composition of the oracle's
 ``create_decoder_input`` and ``mlp_forward`` and (a) to the same composition with the oracle's bf16-emulating decoder.  Grids per pair are sized ``ceil(S / cell) + 1`` nodes per axis (the reference's
 ``base // 2^i + 1`` on its power-of-two squares), so non-square and non-power-of-two images (3840 x 2160) stay in bounds at every level.
-Hashed indexing is not built: the reference's grids are dense and so are these (a 4K pyramid of 5 pairs is 8.3 M parameters,
+Hashed indexing lives in hashgrid.py (``HashGridField``): the reference's grids are dense and so are these (a 4K pyramid of 5 pairs is 8.3 M parameters,
 7.8 M of them in pair 0).  2D only (config 2 is an image fit).
 """
 from __future__ import annotations
