@@ -485,6 +485,33 @@ int nic_hash_encode_backward(const nic_hash_desc *desc, const int32_t *origins, 
 /* the entry index of vertex (vx, vy, vz) at `level` (vz = 0 in 2D) from the same function the kernels use, or a NIC_E_* code */
 int nic_hash_index_host(const nic_hash_desc *desc, int level, int32_t vx, int32_t vy, int32_t vz);
 
+/* ---- hash-grid codec: quantisation-aware training and a uint8 stored table (hashgrid.py, HashGridField(num_bits=b)).
+ *      Bits b in 1..8; the table is clamped to the dense quantiser's range [-(2^b - 1) / 2^(b+1), 1/2] (models.py:48-51) by the optimiser.
+ *      nic_hash_encode_noisy: out = fl(nic_hash_encode out + noise), noise on EVERY column (the reference's rand_like on the decoder input,
+ *      image_compression.py:250, amplitude 2^-b).  Sample id s = sample_base + n (n = the row of the launch); column c = l F + f is value
+ *      c & 15 of generator block c >> 4: Threefry-4x32-12 of counter (s_lo, (c >> 4) + (s_hi << 8), offset_lo, offset_hi), key (seed_lo,
+ *      seed_hi, "NIC2", 0); value i = byte i & 3 of word i >> 2, u8 -> ((u8 + 1/2) / 256 - 1/2) 2^-b (nic_device.hpp::noise_from_block).
+ *      Straight-through backward: nic_hash_encode_backward serves both forms.
+ *      Compact stored table (uint8): levels back to back, level l holds E_l = min((R_l + 1)^dim, T) entries of `features` bytes in entry order
+ *      (a dense level: exactly the vertices it can address; a hashed one: all T), starting at byte F * sum_{k<l} E_k.  Byte = save4fp
+ *      (nic_save4fp_u8: floor(x (2^b - 1) + 1/2) + 2^(b-1) - 1, truncated to uint8); nic_hash_encode_u8 dequantises each corner with
+ *      nic_load4fp_u8's arithmetic ((u - 2^(b-1) + 1) / (2^b - 1)) and then blends exactly like nic_hash_encode: its output equals
+ *      nic_hash_encode of load4fp(save4fp(table)) bit for bit.  nic_hash_pack_u8 writes the compact table from the fp32 [L, T, F] one
+ *      (the caller clamps first: an out-of-range value wraps in the uint8 cast, like the dense codec).  Every argument error is returned
+ *      on the host before any GPU work; a nonzero desc->flags stays NIC_E_ARG. */
+typedef struct nic_hash_quant {
+    int32_t num_bits;        /* 1 .. 8 */
+    int32_t noise_mode;      /* NIC_NOISE_NONE or NIC_NOISE_KERNEL (NIC_NOISE_TENSOR: NIC_E_UNSUPPORTED) */
+    uint64_t noise_seed;
+    uint64_t noise_offset;   /* e.g. the optimiser step */
+    int64_t sample_base;     /* global id of this launch's row 0 (>= 0) */
+} nic_hash_quant;
+int nic_hash_encode_noisy(const nic_hash_desc *desc, const nic_hash_quant *quant, const float *table, const int32_t *origins, float *out,
+                          void *stream);
+int nic_hash_encode_u8(const nic_hash_desc *desc, int num_bits, const uint8_t *stored, const int32_t *origins, float *out, void *stream);
+int nic_hash_pack_u8(const nic_hash_desc *desc, int num_bits, const float *table, uint8_t *stored, void *stream);   /* [L, T, F] fp32 -> compact */
+int64_t nic_hash_stored_bytes(const nic_hash_desc *desc);   /* F * sum_l E_l, or a negative NIC_E_* code */
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,6 +110,12 @@ class NicHashDesc(ctypes.Structure):
                 ("resolution", ctypes.c_int32 * NIC_HASH_MAX_LEVELS), ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class NicHashQuant(ctypes.Structure):
+    """struct nic_hash_quant (include/nicv2_hip.h): bit depth and in-kernel noise of a hash-grid codec launch (hashgrid.py)"""
+    _fields_ = [("num_bits", ctypes.c_int32), ("noise_mode", ctypes.c_int32), ("noise_seed", ctypes.c_uint64), ("noise_offset", ctypes.c_uint64),
+                ("sample_base", ctypes.c_int64)]
+
+
 _P, _I, _L, _F, _SZ, _DBL = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t, ctypes.c_double
 _D = ctypes.POINTER(NicPathDesc)
 _M = ctypes.POINTER(NicMlp)
@@ -164,6 +170,10 @@ SIGNATURES = {
     "nic_hash_encode": (_I, [ctypes.POINTER(NicHashDesc), _P, _P, _P, _P]),
     "nic_hash_encode_backward": (_I, [ctypes.POINTER(NicHashDesc), _P, _P, _P, _P]),
     "nic_hash_index_host": (_I, [ctypes.POINTER(NicHashDesc), _I, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "nic_hash_encode_noisy": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashQuant), _P, _P, _P, _P]),
+    "nic_hash_encode_u8": (_I, [ctypes.POINTER(NicHashDesc), _I, _P, _P, _P, _P]),
+    "nic_hash_pack_u8": (_I, [ctypes.POINTER(NicHashDesc), _I, _P, _P, _P]),
+    "nic_hash_stored_bytes": (_L, [ctypes.POINTER(NicHashDesc)]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

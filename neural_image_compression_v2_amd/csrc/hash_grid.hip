@@ -5,6 +5,9 @@
 // coarse levels whole rows or the whole wave share a vertex.  Every table address is masked with T - 1: no input can leave a level.
 //
 // -DNIC_HASH_NO_RUNSUM: every live lane issues its own atomics (the A/B of the run sums, ab/bench_hashgrid.py).
+//
+// The codec (nic_hash_encode_noisy / _u8 / nic_hash_pack_u8): the same forward kernel with a table source (fp32 [L, T, F] or the compact uint8
+// table, dequantised per corner with load4fp's arithmetic) and optional in-kernel noise on every column, one generator block per 16 columns.
 #include "nic_device.hpp"
 
 namespace nic {
@@ -31,7 +34,14 @@ struct HashParams {
     const float* dx;
     float* out;
     float* grad;
+    // codec launches only (appended: the plain kernels read the fields above at the offsets they always had)
+    const uint8_t* stored;   // compact uint8 table (HSRC_U8)
+    NoiseSrc noise;          // in-kernel noise (NOISE)
+    uint64_t sample_base;
+    float q_scale, q_bias;   // load4fp: (u - q_bias + 1) / q_scale, q_scale = 2^b - 1, q_bias = 2^(b-1)
 };
+
+enum HashSrc { HSRC_F32 = 0, HSRC_U8 = 1 };
 
 template <int F>
 __device__ __forceinline__ void load_row(const float* p, float (&v)[F]) {
@@ -59,6 +69,35 @@ __device__ __forceinline__ void store_row(float* p, const float (&v)[F]) {
 #pragma unroll
         for (int k = 0; k < F; k += 4) *reinterpret_cast<float4*>(p + k) = make_float4(v[k], v[k + 1], v[k + 2], v[k + 3]);
     }
+}
+
+// one compact uint8 entry of F bytes as ONE load (ubyte / ushort / dword / dwordx2), dequantised like load4fp_kernel (simple_kernels.hip)
+template <int F>
+__device__ __forceinline__ void load_row_u8(const uint8_t* p, float scale, float bias, float (&v)[F]) {
+    uint32_t w[(F + 3) / 4];
+    if constexpr (F == 1) {
+        w[0] = *p;
+    } else if constexpr (F == 2) {
+        w[0] = *reinterpret_cast<const uint16_t*>(p);
+    } else if constexpr (F == 4) {
+        w[0] = *reinterpret_cast<const uint32_t*>(p);
+    } else {
+        const uint2 a = *reinterpret_cast<const uint2*>(p);
+        w[0] = a.x; w[1] = a.y;
+    }
+#pragma unroll
+    for (int f = 0; f < F; ++f) {
+        const float u = (float)((w[f >> 2] >> (8 * (f & 3))) & 0xFFu);
+        v[f] = __fdiv_rn(__fadd_rn(__fsub_rn(u, bias), 1.0f), scale);
+    }
+}
+
+// entries a level stores in the compact table: the (R + 1)^dim vertices of a dense level, all T of a hashed one
+__host__ __device__ inline int64_t hash_level_entries(int dim, int32_t R, int log2_table) {
+    if (!hash_level_dense(dim, R, log2_table)) return int64_t(1) << log2_table;
+    int64_t e = 1;
+    for (int a = 0; a < dim; ++a) e *= (int64_t)R + 1;
+    return e;
 }
 
 // the sample of this lane in patch `wv` (clamped to the last patch; `live` = a real sample of a real patch)
@@ -132,7 +171,7 @@ __device__ __forceinline__ float corner_weight(const float (&w)[3], int c) {
     return r;
 }
 
-template <int D, int F>
+template <int D, int F, int SRC = HSRC_F32, bool NOISE = false>
 __global__ void __launch_bounds__(256) hash_encode_kernel(HashParams p) {
     const nic_hash_desc& d = p.d;
     const int lane = threadIdx.x & 63;
@@ -148,10 +187,17 @@ __global__ void __launch_bounds__(256) hash_encode_kernel(HashParams p) {
         uint32_t i[3];
         sample_coords<D>(p, s, i);
         float* orow = p.out + s.n * LF;
+        [[maybe_unused]] int64_t lev_off = 0;              // HSRC_U8: byte offset of level l = F * sum_{k<l} E_k
+        [[maybe_unused]] U4 nblk{0u, 0u, 0u, 0u};          // NOISE: the generator block of columns (l F) & ~15 ..
         for (int l = 0; l < d.levels; ++l) {
             const uint32_t R = (uint32_t)d.resolution[l];
             const bool dense = hash_level_dense(D, (int32_t)R, d.log2_table);
             const float* tab = p.table + ((int64_t)l << d.log2_table) * F;
+            [[maybe_unused]] const uint8_t* stab = nullptr;
+            if constexpr (SRC == HSRC_U8) {
+                stab = p.stored + lev_off;
+                lev_off += (int64_t)F * hash_level_entries(D, (int32_t)R, d.log2_table);
+            }
             uint32_t v[3];
             float w[3];
             level_cell<D>(i, R, S2, v, w);
@@ -162,10 +208,18 @@ __global__ void __launch_bounds__(256) hash_encode_kernel(HashParams p) {
             for (int c = 0; c < (1 << D); ++c) {
                 const uint32_t e = hash_index(dense, R, mask, v[0] + (c & 1), v[1] + ((c >> 1) & 1), D == 3 ? v[2] + ((c >> 2) & 1) : 0u);
                 float t[F];
-                load_row<F>(tab + (int64_t)e * F, t);
+                if constexpr (SRC == HSRC_U8) load_row_u8<F>(stab + (int64_t)e * F, p.q_scale, p.q_bias, t);
+                else load_row<F>(tab + (int64_t)e * F, t);
                 const float cw = corner_weight<D>(w, c);
 #pragma unroll
                 for (int f = 0; f < F; ++f) acc[f] += cw * t[f];
+            }
+            if constexpr (NOISE) {
+                // 16 % F == 0: a level's F columns lie in one block; it is generated once, at its first column, and reused by the next levels
+                const int c0 = l * F;
+                if ((c0 & 15) == 0) nblk = noise_block(p.noise, p.sample_base + (uint64_t)s.n, c0 >> 4);
+#pragma unroll
+                for (int f = 0; f < F; ++f) acc[f] += noise_from_block(p.noise, nblk, (c0 + f) & 15);
             }
             store_row<F>(orow + l * F, acc);
         }
@@ -226,6 +280,32 @@ __global__ void __launch_bounds__(256) hash_encode_backward_kernel(HashParams p)
     }
 }
 
+// fp32 [L, T, F] -> compact uint8 (save4fp_kernel's arithmetic); one byte per thread, level found from the byte prefix pre[] (static
+// indices: the prefix stays in scalar registers)
+struct HashPackParams {
+    const float* src;
+    uint8_t* dst;
+    int64_t pre[NIC_HASH_MAX_LEVELS + 1];   // byte offset of level l in dst; pre[levels] = total
+    int levels, log2_table, features;
+    float scale, bias;
+};
+__global__ void __launch_bounds__(256) hash_pack_u8_kernel(HashPackParams p) {
+    const int64_t n = p.pre[p.levels];
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+        int l = 0;
+        int64_t base = 0;
+#pragma unroll
+        for (int j = 1; j < NIC_HASH_MAX_LEVELS; ++j) {
+            const bool past = j < p.levels && k >= p.pre[j];
+            l = past ? j : l;
+            base = past ? p.pre[j] : base;
+        }
+        const int64_t src = ((int64_t)l << p.log2_table) * p.features + (k - base);
+        const float v = __fadd_rn(floorf(__fadd_rn(__fmul_rn(p.src[src], p.scale), 0.5f)), p.bias);
+        p.dst[k] = (uint8_t)(int)v;                               // torch float -> uint8 cast truncates
+    }
+}
+
 static inline int hash_blocks(const nic_hash_desc* d) {
     const int PS = d->dim == 2 ? 8 : 4;
     int64_t patches = d->num_crops;
@@ -253,27 +333,48 @@ static int check_hash_desc(const nic_hash_desc* d) {
     return NIC_OK;
 }
 
-template <int D, int F>
-static void launch_fwd(const HashParams& p, int nb, hipStream_t s) { hipLaunchKernelGGL((hash_encode_kernel<D, F>), dim3(nb), dim3(256), 0, s, p); }
-template <int D, int F>
-static void launch_bwd(const HashParams& p, int nb, hipStream_t s) { hipLaunchKernelGGL((hash_encode_backward_kernel<D, F>), dim3(nb), dim3(256), 0, s, p); }
+enum HashKernel { HK_FWD, HK_BWD, HK_FWD_NOISY, HK_FWD_U8 };
 
-template <bool BWD, int D>
+template <int K, int D, int F>
+static void launch_k(const HashParams& p, int nb, hipStream_t s) {
+    if constexpr (K == HK_BWD) hipLaunchKernelGGL((hash_encode_backward_kernel<D, F>), dim3(nb), dim3(256), 0, s, p);
+    else if constexpr (K == HK_FWD_NOISY) hipLaunchKernelGGL((hash_encode_kernel<D, F, HSRC_F32, true>), dim3(nb), dim3(256), 0, s, p);
+    else if constexpr (K == HK_FWD_U8) hipLaunchKernelGGL((hash_encode_kernel<D, F, HSRC_U8, false>), dim3(nb), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((hash_encode_kernel<D, F>), dim3(nb), dim3(256), 0, s, p);
+}
+
+template <int K, int D>
 static void launch_f(const HashParams& p, int nb, hipStream_t s) {
     switch (p.d.features) {
-        case 1: BWD ? launch_bwd<D, 1>(p, nb, s) : launch_fwd<D, 1>(p, nb, s); break;
-        case 2: BWD ? launch_bwd<D, 2>(p, nb, s) : launch_fwd<D, 2>(p, nb, s); break;
-        case 4: BWD ? launch_bwd<D, 4>(p, nb, s) : launch_fwd<D, 4>(p, nb, s); break;
-        default: BWD ? launch_bwd<D, 8>(p, nb, s) : launch_fwd<D, 8>(p, nb, s); break;
+        case 1: launch_k<K, D, 1>(p, nb, s); break;
+        case 2: launch_k<K, D, 2>(p, nb, s); break;
+        case 4: launch_k<K, D, 4>(p, nb, s); break;
+        default: launch_k<K, D, 8>(p, nb, s); break;
     }
 }
 
-template <bool BWD>
+template <int K>
 static int hash_launch(const HashParams& p, void* stream) {
     const int nb = hash_blocks(&p.d);
-    if (p.d.dim == 2) launch_f<BWD, 2>(p, nb, (hipStream_t)stream);
-    else launch_f<BWD, 3>(p, nb, (hipStream_t)stream);
+    if (p.d.dim == 2) launch_f<K, 2>(p, nb, (hipStream_t)stream);
+    else launch_f<K, 3>(p, nb, (hipStream_t)stream);
     return (int)hipGetLastError();
+}
+
+// F * sum_l E_l; pre (optional) gets the byte offset of every level and the total at [levels]
+static int64_t hash_stored_prefix(const nic_hash_desc* d, int64_t* pre) {
+    int64_t off = 0;
+    for (int l = 0; l < d->levels; ++l) {
+        if (pre) pre[l] = off;
+        off += (int64_t)d->features * hash_level_entries(d->dim, d->resolution[l], d->log2_table);
+    }
+    if (pre) pre[d->levels] = off;
+    return off;
+}
+
+static void set_dequant(HashParams& p, int num_bits) {
+    p.q_scale = (float)((1 << num_bits) - 1);
+    p.q_bias = (float)(1 << (num_bits - 1));
 }
 
 extern "C" {
@@ -284,7 +385,7 @@ int nic_hash_encode(const nic_hash_desc* desc, const float* table, const int32_t
     if (!table || !origins || !out) return NIC_E_NULL;
     HashParams p{};
     p.d = *desc; p.table = table; p.origins = origins; p.out = out;
-    return hash_launch<false>(p, stream);
+    return hash_launch<HK_FWD>(p, stream);
 }
 
 int nic_hash_encode_backward(const nic_hash_desc* desc, const int32_t* origins, const float* dx, float* table_grad, void* stream) {
@@ -293,7 +394,7 @@ int nic_hash_encode_backward(const nic_hash_desc* desc, const int32_t* origins, 
     if (!origins || !dx || !table_grad) return NIC_E_NULL;
     HashParams p{};
     p.d = *desc; p.origins = origins; p.dx = dx; p.grad = table_grad;
-    return hash_launch<true>(p, stream);
+    return hash_launch<HK_BWD>(p, stream);
 }
 
 int nic_hash_index_host(const nic_hash_desc* desc, int level, int32_t vx, int32_t vy, int32_t vz) {
@@ -303,6 +404,58 @@ int nic_hash_index_host(const nic_hash_desc* desc, int level, int32_t vx, int32_
     const int32_t R = desc->resolution[level];
     return (int)hash_index(hash_level_dense(desc->dim, R, desc->log2_table), (uint32_t)R, (1u << desc->log2_table) - 1u, (uint32_t)vx,
                            (uint32_t)vy, desc->dim == 3 ? (uint32_t)vz : 0u);
+}
+
+int nic_hash_encode_noisy(const nic_hash_desc* desc, const nic_hash_quant* quant, const float* table, const int32_t* origins, float* out,
+                          void* stream) {
+    const int rc = check_hash_desc(desc);
+    if (rc) return rc;
+    if (!quant || !table || !origins || !out) return NIC_E_NULL;
+    if (quant->num_bits < 1 || quant->num_bits > 8 || quant->sample_base < 0) return NIC_E_ARG;
+    if (quant->noise_mode == NIC_NOISE_TENSOR) return NIC_E_UNSUPPORTED;
+    if (quant->noise_mode != NIC_NOISE_NONE && quant->noise_mode != NIC_NOISE_KERNEL) return NIC_E_ARG;
+    HashParams p{};
+    p.d = *desc; p.table = table; p.origins = origins; p.out = out;
+    if (quant->noise_mode == NIC_NOISE_NONE) return hash_launch<HK_FWD>(p, stream);
+    p.noise.mode = NIC_NOISE_KERNEL;
+    p.noise.k0 = (uint32_t)quant->noise_seed; p.noise.k1 = (uint32_t)(quant->noise_seed >> 32);
+    p.noise.off_lo = (uint32_t)quant->noise_offset; p.noise.off_hi = (uint32_t)(quant->noise_offset >> 32);
+    p.noise.scale = ldexpf(1.0f, -quant->num_bits);
+    p.sample_base = (uint64_t)quant->sample_base;
+    return hash_launch<HK_FWD_NOISY>(p, stream);
+}
+
+int nic_hash_encode_u8(const nic_hash_desc* desc, int num_bits, const uint8_t* stored, const int32_t* origins, float* out, void* stream) {
+    const int rc = check_hash_desc(desc);
+    if (rc) return rc;
+    if (!stored || !origins || !out) return NIC_E_NULL;
+    if (num_bits < 1 || num_bits > 8) return NIC_E_ARG;
+    HashParams p{};
+    p.d = *desc; p.stored = stored; p.origins = origins; p.out = out;
+    set_dequant(p, num_bits);
+    return hash_launch<HK_FWD_U8>(p, stream);
+}
+
+int nic_hash_pack_u8(const nic_hash_desc* desc, int num_bits, const float* table, uint8_t* stored, void* stream) {
+    const int rc = check_hash_desc(desc);
+    if (rc) return rc;
+    if (!table || !stored) return NIC_E_NULL;
+    if (num_bits < 1 || num_bits > 8) return NIC_E_ARG;
+    HashPackParams p{};
+    p.src = table; p.dst = stored;
+    p.levels = desc->levels; p.log2_table = desc->log2_table; p.features = desc->features;
+    p.scale = (float)((1 << num_bits) - 1);
+    p.bias = (float)((1 << (num_bits - 1)) - 1);
+    const int64_t n = hash_stored_prefix(desc, p.pre);
+    const int64_t b = (n + 255) / 256;
+    hipLaunchKernelGGL(hash_pack_u8_kernel, dim3((unsigned)(b > 4096 ? 4096 : b)), dim3(256), 0, (hipStream_t)stream, p);
+    return (int)hipGetLastError();
+}
+
+int64_t nic_hash_stored_bytes(const nic_hash_desc* desc) {
+    const int rc = check_hash_desc(desc);
+    if (rc) return rc;
+    return hash_stored_prefix(desc, nullptr);
 }
 
 }  // extern "C"

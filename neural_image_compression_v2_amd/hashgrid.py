@@ -12,8 +12,16 @@ reference reads dense G0 / G1 pairs only (fp_def.py), and so does ``MultiLevelFi
   (crops back to back, the last axis fastest), so the targets of ``MultiLevelField`` serve unchanged.
 
 The gather / interpolate (``nic_hash_encode``) and its gradient scatter (``nic_hash_encode_backward``) are the HIP kernels of csrc/hash_grid.hip;
-the decoder is ``ColorDecoder`` on the general layer-wise kernels, the optimiser ``FusedAdam``.  No noise and no clamp: there is no quantiser
-behind a hash table."""
+the decoder is ``ColorDecoder`` on the general layer-wise kernels, the optimiser ``FusedAdam``.  Without ``num_bits`` there is no noise and no
+clamp.
+
+The codec (``HashGridField(..., num_bits=b)``; include/nicv2_hip.h, nic_hash_quant) is the dense G0 / G1 codec's, carried over:
+the optimiser clamps the table to the quantiser's range [-(2^b - 1) / 2^(b+1), 1/2]; training adds uniform noise of one quantisation step 2^-b to
+every column of the encoding (``nic_hash_encode_noisy``: in-kernel Threefry keyed by (seed, optimiser step, sample id), straight-through backward);
+``freeze()`` quantises the table in place and only the decoder trains on; ``save_compressed`` stores the compact uint8 table (``nic_hash_pack_u8``:
+a dense level keeps only the (R + 1)^d vertices it can address) with the decoder, and ``load_compressed(...).decode()`` decodes straight from
+those bytes (``nic_hash_encode_u8``).  The schedule is the dense one (image_compression.py:237,385): noise while the epoch is below 0.95 N, then
+freeze - ``fit`` runs it."""
 from __future__ import annotations
 
 import ctypes
@@ -24,7 +32,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 
-from . import _lib, fused
+from . import _lib, fused, models
 from .image_compression import ColorDecoder
 from .optim import CosineAnnealing, FusedAdam
 
@@ -159,6 +167,56 @@ def hash_encode_backward(geo: HashGeometry, org: torch.Tensor, extent: Sequence[
                "nic_hash_encode_backward")
 
 
+@fused._on_tensor_device
+def hash_encode_noisy(geo: HashGeometry, table: torch.Tensor, coord, extent: Sequence[int], num_bits: int, seed: int, offset: int,
+                      sample_base: int = 0) -> torch.Tensor:
+    """``hash_encode`` + uniform noise of one quantisation step 2^-num_bits on every column (nic_hash_encode_noisy): sample id = sample_base +
+    row, keyed by (seed, offset).  The gradient w.r.t. the table is ``hash_encode_backward``'s (straight-through)."""
+    t = _check_table(geo, table.detach())
+    org = geo.upload_origins(coord, extent, t.device)
+    num_crops = org.shape[0]
+    out = torch.empty(_n_samples(num_crops, extent), geo.width, dtype=torch.float32, device=t.device)
+    d = geo.to_desc(num_crops, extent)
+    q = _lib.NicHashQuant(int(num_bits), _lib.NIC_NOISE_KERNEL, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(sample_base))
+    _lib.check(_lib.load().nic_hash_encode_noisy(ctypes.byref(d), ctypes.byref(q), _lib.ptr(t), _lib.ptr(org), _lib.ptr(out), _lib.stream_ptr(t.device)),
+               "nic_hash_encode_noisy")
+    return out
+
+
+def hash_stored_bytes(geo: HashGeometry) -> int:
+    """bytes of the compact uint8 table: F * sum_l min((R_l + 1)^d, T) (nic_hash_stored_bytes)"""
+    n = _lib.load().nic_hash_stored_bytes(ctypes.byref(geo.to_desc(1, [1] * geo.dim)))
+    _lib.check(n if n < 0 else 0, "nic_hash_stored_bytes")
+    return int(n)
+
+
+@fused._on_tensor_device
+def hash_pack_u8(geo: HashGeometry, table: torch.Tensor, num_bits: int) -> torch.Tensor:
+    """the compact uint8 table of an fp32 [L, T, F] one, save4fp's arithmetic per value (nic_hash_pack_u8).  Clamp first: a value outside the
+    quantiser's range wraps in the uint8 cast."""
+    t = _check_table(geo, table.detach())
+    out = torch.empty(hash_stored_bytes(geo), dtype=torch.uint8, device=t.device)
+    _lib.check(_lib.load().nic_hash_pack_u8(ctypes.byref(geo.to_desc(1, [1] * geo.dim)), int(num_bits), _lib.ptr(t), _lib.ptr(out), _lib.stream_ptr(t.device)),
+               "nic_hash_pack_u8")
+    return out
+
+
+@fused._on_tensor_device
+def hash_encode_u8(geo: HashGeometry, stored: torch.Tensor, coord, extent: Sequence[int], num_bits: int) -> torch.Tensor:
+    """``hash_encode`` of the table a compact uint8 one stores (nic_hash_encode_u8): bit for bit ``hash_encode(load4fp(save4fp(table)))``"""
+    if stored.dtype != torch.uint8 or not stored.is_cuda or stored.dim() != 1 or not stored.is_contiguous():
+        raise ValueError("stored must be a contiguous 1-D uint8 tensor on a HIP device")
+    if stored.numel() != hash_stored_bytes(geo):
+        raise ValueError(f"stored holds {stored.numel()} bytes, the geometry needs {hash_stored_bytes(geo)}")
+    org = geo.upload_origins(coord, extent, stored.device)
+    num_crops = org.shape[0]
+    out = torch.empty(_n_samples(num_crops, extent), geo.width, dtype=torch.float32, device=stored.device)
+    d = geo.to_desc(num_crops, extent)
+    _lib.check(_lib.load().nic_hash_encode_u8(ctypes.byref(d), int(num_bits), _lib.ptr(stored), _lib.ptr(org), _lib.ptr(out), _lib.stream_ptr(stored.device)),
+               "nic_hash_encode_u8")
+    return out
+
+
 class HashEncodeFunction(torch.autograd.Function):
     """``hash_encode`` as a differentiable op of the table: backward = ``nic_hash_encode_backward`` into a fresh zero [L, T, F] (what autograd
     through ``index_add`` of the corner entries would give, collisions summed)"""
@@ -182,12 +240,20 @@ def hash_encode_differentiable(geo: HashGeometry, table: torch.Tensor, coord, ex
     return HashEncodeFunction.apply(table, geo, org, tuple(int(e) for e in extent))
 
 
+COMPRESSED_FORMAT = "nicv2-hashgrid-u8/1"
+
+
 class HashGridField:
     """a hash-grid table + one decoder over its [N, L F] encoding, trained like ``MultiLevelField`` (module docstring).  ``field_size``:
-    (S_x, S_y) or (S_x, S_y, S_z), x = the image tensor's first spatial axis like everywhere in this package."""
+    (S_x, S_y) or (S_x, S_y, S_z), x = the image tensor's first spatial axis like everywhere in this package.  ``num_bits``: None = no codec
+    (no noise, no clamp); b in 1..8 = quantisation-aware training for a uint8 table of b-bit values (module docstring), noise keyed by
+    ``noise_seed``."""
 
     def __init__(self, field_size: Union[int, Sequence[int]], levels: int = 16, features: int = 2, log2_table: int = 19, base_resolution: float = 16,
-                 finest_resolution: Optional[float] = None, hidden: int = 64, n_linear: int = 3, device=None, seed: Optional[int] = None):
+                 finest_resolution: Optional[float] = None, hidden: int = 64, n_linear: int = 3, device=None, seed: Optional[int] = None,
+                 num_bits: Optional[int] = None, noise_seed: int = 7):
+        if num_bits is not None and not 1 <= int(num_bits) <= 8:
+            raise ValueError("num_bits in 1 .. 8 (the stored table is uint8), or None")
         self.field_size = (int(field_size),) * 2 if isinstance(field_size, int) else tuple(int(v) for v in field_size)
         self.device = torch.device(device if device is not None else "cuda")
         if self.device.type != "cuda":
@@ -204,6 +270,12 @@ class HashGridField:
         self.optimizer.zero_grad_in_step([self.table])
         self._grad_clean = True
         self.scheduler = None
+        self.hidden, self.n_linear = int(hidden), int(n_linear)
+        self.num_bits = None if num_bits is None else int(num_bits)
+        self.noise_seed, self.steps, self.frozen, self.stored = int(noise_seed), 0, False, None
+        self._pass_samples = 0                       # samples of the current accumulate pass so far: the next chunk's sample_base
+        if self.num_bits is not None:
+            self.optimizer.set_clamp([self.table], *models._q_range(self.num_bits))
 
     @property
     def resolutions(self) -> Tuple[int, ...]:
@@ -219,42 +291,142 @@ class HashGridField:
     def forward(self, coord, extent: Sequence[int]) -> torch.Tensor:
         return self.decoder(self.encode(coord, extent))
 
-    def train_step(self, coord, extent: Sequence[int], target: torch.Tensor, accumulate: bool = False, scale: float = 1.0, step: bool = True) -> torch.Tensor:
+    def train_step(self, coord, extent: Sequence[int], target: torch.Tensor, accumulate: bool = False, scale: float = 1.0, step: bool = True,
+                   noise: Optional[bool] = None) -> torch.Tensor:
         """one step on the crops at ``coord`` with targets [N, 3].  ``accumulate`` / ``scale`` / ``step``: a whole-field pass walked in chunks -
-        gradients add up over the chunks (each chunk's MSE scaled by its share), one optimiser step at the end"""
+        gradients add up over the chunks (each chunk's MSE scaled by its share), one optimiser step at the end.  ``noise``: None = on while a
+        ``num_bits`` field's table trains (offset = the optimiser step count, sample_base = the samples of this pass before this chunk, so no two
+        chunks of a pass share noise).  After ``freeze()`` only the decoder trains: no table gradient is formed."""
+        if self.table is None:
+            raise RuntimeError("a field from load_compressed decodes only")
         params = self.decoder.linear_params()
         grad = self.table.grad
+        frozen = self.frozen
         if not accumulate:
             for p in params:
                 p.grad = None
-            if not self._grad_clean:
+            if not frozen and not self._grad_clean:
                 grad.zero_()
+            self._pass_samples = 0
         org = self.geo.upload_origins(coord, extent, self.device)
-        if tuple(target.shape) != (_n_samples(org.shape[0], extent), 3):
-            raise ValueError(f"target must be [{_n_samples(org.shape[0], extent)}, 3], got {tuple(target.shape)}")
-        x = hash_encode(self.geo, self.table, org, extent).requires_grad_(True)
+        n = _n_samples(org.shape[0], extent)
+        if tuple(target.shape) != (n, 3):
+            raise ValueError(f"target must be [{n}, 3], got {tuple(target.shape)}")
+        if noise is None:
+            noise = self.num_bits is not None and not frozen
+        if noise and self.num_bits is None:
+            raise ValueError("noise needs num_bits: its amplitude is one quantisation step")
+        if noise:
+            x = hash_encode_noisy(self.geo, self.table, org, extent, self.num_bits, self.noise_seed, self.steps, self._pass_samples)
+        else:
+            x = hash_encode(self.geo, self.table, org, extent)
+        self._pass_samples += n
+        if not frozen:
+            x.requires_grad_(True)
         y = fused.DecoderFunction.apply(x, *params)
         loss = ((y - target) ** 2).mean() * scale
         loss.backward()
-        hash_encode_backward(self.geo, org, extent, x.grad, grad)
-        self._grad_clean = False
+        if not frozen:
+            hash_encode_backward(self.geo, org, extent, x.grad, grad)
+            self._grad_clean = False
         if step:
             self.optimizer.step()
-            self._grad_clean = self.optimizer.zeroed_in_last_step(grad)
+            if not frozen:
+                self._grad_clean = self.optimizer.zeroed_in_last_step(grad)
             if self.scheduler is not None:
                 self.scheduler.step()
+            self.steps += 1
         return loss.detach()
 
     @torch.no_grad()
+    def freeze(self) -> None:
+        """quantise the table in place (nic_quantize) and stop updating it: ``train_step`` then trains the decoder alone, without noise
+        (fp_freeze + fp_all_quantize of the dense codec)"""
+        if self.num_bits is None:
+            raise RuntimeError("freeze() needs num_bits: there is no quantiser without it")
+        if self.frozen:
+            return
+        t = self.table.detach()
+        _lib.check(_lib.load().nic_quantize(_lib.ptr(t), _lib.ptr(t), t.numel(), self.num_bits, _lib.stream_ptr(t.device)), "nic_quantize")
+        self.table.grad = None                       # FusedAdam skips a parameter without a gradient
+        self.table.requires_grad_(False)
+        self.frozen = True
+
+    def fit(self, target: torch.Tensor, epochs: int, chunk: Optional[int] = None, freeze_at: float = 0.95) -> List[float]:
+        """``epochs`` whole-field passes on ``target`` [S_x, S_y(, S_z), 3], walked in slabs of ``chunk`` x-rows (one optimiser step per pass,
+        each slab's MSE weighted by its share).  With ``num_bits``: noise while the epoch is below ``freeze_at`` * epochs, then ``freeze()``.
+        Returns the per-pass losses."""
+        size = self.field_size
+        if tuple(target.shape) != (*size, 3):
+            raise ValueError(f"target must be {(*size, 3)}, got {tuple(target.shape)}")
+        chunk = size[0] if chunk is None else int(chunk)
+        starts = list(range(0, size[0], chunk))
+        slabs = [target[x0:x0 + chunk].reshape(-1, 3).contiguous() for x0 in starts]
+        total = sum(s.shape[0] for s in slabs)
+        freeze_epoch = math.ceil(freeze_at * epochs) if self.num_bits is not None else None
+        hist = []
+        for ep in range(epochs):
+            if freeze_epoch is not None and ep >= freeze_epoch and not self.frozen:
+                self.freeze()
+            tot = 0.0
+            for k, x0 in enumerate(starts):
+                ext = (min(chunk, size[0] - x0), *size[1:])
+                tot = tot + self.train_step([[x0] + [0] * (len(size) - 1)], ext, slabs[k], accumulate=k > 0, scale=slabs[k].shape[0] / total,
+                                            step=k == len(starts) - 1)
+            hist.append(tot)
+        return [float(h) for h in hist]
+
+    def stored_bytes(self) -> dict:
+        """bytes ``save_compressed`` stores: the compact uint8 table and the fp32 decoder"""
+        return {"table": hash_stored_bytes(self.geo), "decoder": sum(v.numel() * v.element_size() for v in self.decoder.state_dict().values())}
+
+    @torch.no_grad()
+    def save_compressed(self, path) -> None:
+        """one ``torch.save`` dict: format tag, geometry, num_bits, the compact uint8 table of a clamped copy of the table, the decoder"""
+        if self.num_bits is None:
+            raise RuntimeError("save_compressed needs num_bits")
+        if self.table is None:
+            stored = self.stored
+        else:
+            stored = hash_pack_u8(self.geo, models.quantize_clamp(self.table, self.num_bits), self.num_bits)
+        torch.save({"format": COMPRESSED_FORMAT, "field_size": list(self.field_size), "resolutions": list(self.geo.resolutions),
+                    "features": self.geo.features, "log2_table": self.geo.log2_table, "num_bits": self.num_bits, "hidden": self.hidden,
+                    "n_linear": self.n_linear, "table": stored.cpu(), "decoder": {k: v.detach().cpu() for k, v in self.decoder.state_dict().items()}}, path)
+
+    @classmethod
+    def load_compressed(cls, path, device=None) -> "HashGridField":
+        """a decode-only field from ``save_compressed``'s file: ``decode()`` gathers from the uint8 table (nic_hash_encode_u8), no fp32 table"""
+        d = torch.load(path, map_location="cpu", weights_only=True)
+        if not isinstance(d, dict) or d.get("format") != COMPRESSED_FORMAT:
+            raise ValueError(f"{path}: not a {COMPRESSED_FORMAT} file")
+        self = cls.__new__(cls)
+        self.device = torch.device(device if device is not None else "cuda")
+        if self.device.type != "cuda":
+            raise RuntimeError("HashGridField needs a HIP device: there is no CPU implementation of this path")
+        self.field_size = tuple(int(v) for v in d["field_size"])
+        self.geo = HashGeometry(self.field_size, tuple(int(r) for r in d["resolutions"]), int(d["features"]), int(d["log2_table"]))
+        self.num_bits, self.hidden, self.n_linear = int(d["num_bits"]), int(d["hidden"]), int(d["n_linear"])
+        stored = d["table"]
+        if stored.dtype != torch.uint8 or stored.numel() != hash_stored_bytes(self.geo):
+            raise ValueError(f"{path}: the table holds {stored.numel()} {stored.dtype} values, the geometry needs {hash_stored_bytes(self.geo)} bytes")
+        self.stored = stored.to(self.device).contiguous()
+        self.table = None
+        self.decoder = ColorDecoder(self.geo.width, self.hidden, self.n_linear).to(self.device)
+        self.decoder.load_state_dict(d["decoder"])
+        self.optimizer = self.scheduler = None
+        self.noise_seed, self.steps, self.frozen, self._pass_samples, self._grad_clean = 0, 0, True, 0, True
+        return self
+
+    @torch.no_grad()
     def decode(self, tile: int = 1024) -> torch.Tensor:
-        """the whole field [S_x, S_y(, S_z), 3], in tiles of side <= ``tile``"""
+        """the whole field [S_x, S_y(, S_z), 3], in tiles of side <= ``tile`` (a field from ``load_compressed``: from its uint8 table)"""
         size = self.field_size
         out = torch.empty(*size, 3, dtype=torch.float32, device=self.device)
         params = [p.detach() for p in self.decoder.linear_params()]
-        table = self.table.detach()
+        table = None if self.table is None else self.table.detach()
         for o in itertools.product(*[range(0, s, tile) for s in size]):
             ext = [min(tile, s - a) for s, a in zip(size, o)]
-            x = hash_encode(self.geo, table, [o], ext)
+            x = hash_encode_u8(self.geo, self.stored, [o], ext, self.num_bits) if table is None else hash_encode(self.geo, table, [o], ext)
             sl = tuple(slice(a, a + e) for a, e in zip(o, ext))
             out[sl] = fused.DecoderFunction.apply(x, *params).reshape(*ext, 3)
         return out
