@@ -87,6 +87,7 @@ class MultiLevelField:
         self.noise_seed, self.steps = int(noise_seed), 0
         self._grads = None                                                             # fused route: one gradient tensor per grid / decoder parameter, reused
         self._loss = None
+        self._pass_samples = 0                                                         # samples of the current accumulate pass so far: the next chunk's sample_base
 
     def set_schedule(self, num_epochs: int) -> None:
         self.scheduler = CosineAnnealing(self.optimizer, T_max=num_epochs, eta_min=0)  # image_compression.py:365
@@ -145,10 +146,12 @@ class MultiLevelField:
             self.optimizer.zero_grad_in_step(self.fp)
         gfp, gmlp, gtmp = self._grads
         n = num_crops * int(extent[0]) * int(extent[1])
+        if not accumulate:
+            self._pass_samples = 0
         geo = fused.PathGeometry(dim=2, method=1, step_number=0.25, mip_level=0, extent=tuple(int(e) for e in extent), num_crops=num_crops, channels=self.channels,
                                  pe_channels=self.pe_channels, hidden=64, use_tri_pe=self.use_tri_pe, num_bits=self.num_bits,
                                  noise_mode=_lib.NIC_NOISE_KERNEL if noise else _lib.NIC_NOISE_NONE, noise_seed=self.noise_seed, noise_offset=self.steps,
-                                 loss_scale=float(scale) / (3.0 * n))
+                                 sample_base=self._pass_samples, loss_scale=float(scale) / (3.0 * n))
         if not accumulate and not getattr(self, "_grid_grads_clean", False):
             for g in gfp:
                 g.zero_()
@@ -157,6 +160,7 @@ class MultiLevelField:
             # a whole step in this launch: the optimiser rides on the reduction of the decoder records (nic_path_desc.tail) - two launches per step
             tail = self.optimizer.step_tail(list(zip(self.fp, gfp)), list(zip(params, gmlp)))
         out = fused.fused_ml_forward_backward(geo, self.fp, coord, params, target, grads=gfp, mlp_grads=gtmp if accumulate else gmlp, loss=self._loss, tail=tail)
+        self._pass_samples += n                                                        # the chunks of one pass never share in-kernel noise
         if accumulate:
             for a, b in zip(gmlp, gtmp):
                 a.add_(b)

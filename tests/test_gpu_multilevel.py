@@ -192,3 +192,37 @@ def test_multilevel_field_fused_fit(dev):
     f = finals["fused"][1]
     a, b = f.decode(tile=100, fused_forward=True), f.decode(tile=100)
     assert relmax(a, b) < 5e-3
+
+
+def test_multilevel_field_chunks_of_a_pass_draw_distinct_noise(dev):
+    """a fused, noisy pass walked in two equal chunks (accumulate / scale=0.5 / step on the last) gives the loss and gradients of ONE launch over
+    both crops with the same in-kernel noise: the second chunk's samples continue the first's numbering (sample_base) instead of repeating its
+    noise.  Gradients to 1e-5 relative (the fp32 atomics of the grid gradients change only the rounding)."""
+    from neural_image_compression_v2_amd import _lib, fused
+    from neural_image_compression_v2_amd.multilevel import MultiLevelField
+    S, half = (256, 192), (128, 192)
+    f = MultiLevelField(S, 3, channels=4, hidden=64, n_linear=3, device=dev, seed=0, fused_step=True)
+    tgt = torch.rand(S[0], S[1], 3, generator=torch.Generator().manual_seed(4)).to(dev)
+    params = f.decoder.linear_params()
+    geo = fused.PathGeometry(dim=2, method=1, step_number=0.25, mip_level=0, extent=half, num_crops=2, channels=4, pe_channels=6, use_tri_pe=f.use_tri_pe,
+                             num_bits=f.num_bits, noise_mode=_lib.NIC_NOISE_KERNEL, noise_seed=f.noise_seed, noise_offset=f.steps)
+    one = fused.fused_ml_forward_backward(geo, f.fp, [[0, 0], [128, 0]], params, tgt.reshape(-1, 3))
+    want_fp, want_mlp, want_loss = [t.clone() for t in one.grad_fp], [t.clone() for t in one.grad_mlp], float(one.loss)
+    seen = {}
+    step = f.optimizer.step
+
+    def snapshot_then_step(*a, **kw):                        # the gradients the optimiser is about to consume
+        seen["fp"] = [t.grad.clone() for t in f.fp]
+        seen["mlp"] = [p.grad.clone() for p in params]
+        return step(*a, **kw)
+
+    f.optimizer.step = snapshot_then_step
+    tot = 0.0
+    for k, x0 in enumerate((0, 128)):
+        tot += float(f.train_step([[x0, 0]], half, tgt[x0:x0 + 128].reshape(-1, 3), accumulate=k > 0, scale=0.5, step=k == 1))
+    assert "fp" in seen and f.steps == 1
+    assert abs(tot - want_loss) <= 1e-5 * want_loss, (tot, want_loss)
+    for i, (a, b) in enumerate(zip(seen["fp"], want_fp)):
+        assert relmax(a, b) <= 1e-5, f"grid {i}: {relmax(a, b):.2e}"
+    for i, (a, b) in enumerate(zip(seen["mlp"], want_mlp)):
+        assert relmax(a, b) <= 1e-5, f"decoder tensor {i}: {relmax(a, b):.2e}"

@@ -416,6 +416,19 @@ def test_split_bf16_training_step(dev, case):
         (((y - target.to(dev)) ** 2).mean()).backward()
         assert_rel(g0d.grad, ref.grad_g0, 1e-4, "autograd (dY entry point) grad G0")
         assert_rel(pd[0].grad, ref.grad_mlp[0], 1e-4, "autograd (dY entry point) grad W1")
+        assert_rel(g1d.grad, ref.grad_g1, 1e-4, "autograd (dY entry point) grad G1")
+        for nme, q, b in zip(["W1", "b1", "W2", "b2", "W3", "b3"], pd, ref.grad_mlp):
+            assert_rel(q.grad, b, 1e-4, f"autograd (dY entry point) grad {nme}")
+        # targets read from a resident image: the MSE step on the stack of the same crops, y bit for bit, loss and gradients to fp32 rounding
+        isz = [max(o[a] for o in origins) + extent[a] for a in range(dim)]
+        img = torch.rand(3, *isz, generator=g).to(dev)
+        stack = torch.cat([img[(slice(None), *(slice(o[a], o[a] + extent[a]) for a in range(dim)))].reshape(3, -1).T for o in origins])
+        want = fused.fused_forward_backward(geo, g0.to(dev), g1.to(dev), origins, params, stack, want_y=True)
+        got = fused.fused_forward_backward(geo, g0.to(dev), g1.to(dev), origins, params, fused.TargetImage(img), want_y=True)
+        assert_exact(got.y, want.y, "resident image y")
+        assert_rel(got.loss, want.loss, 1e-6, "resident image loss")
+        for nme, a, b in zip(["G0", "G1", "W1", "b1", "W2", "b2", "W3", "b3"], [got.grad_g0, got.grad_g1] + got.grad_mlp, [want.grad_g0, want.grad_g1] + want.grad_mlp):
+            assert_rel(a, b, 1e-6, f"resident image grad {nme}")
 
 
 def _t16_cases(seed=77, n=14):
