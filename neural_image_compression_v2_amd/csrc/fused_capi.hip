@@ -1,7 +1,6 @@
-// C ABI of the fused encode + decoder kernels (include/nicv2_hip.h): argument checks, launch geometry,
+// C ABI of the fused encode + decoder kernels (include/nicv2_hip.h): argument checks, kernel choice, launch geometry,
 // workspace bookkeeping.  No allocation, no synchronisation: capture-safe.
-#include "fused_launch.hpp"
-#include "fused_t16.hpp"
+#include "fused_dispatch.hpp"
 #include <stdlib.h>
 #include <string.h>
 
@@ -19,36 +18,69 @@ int cu_count() {
     return n;
 }
 
-// non-default channel counts (FEATURE_PYRAMID_CHANNELS, PE_CHANNELS: var2.py:68-69) exist on the plain-bf16 kernels (NIC_FLAG_BF16), 3 Linear layers:
-// (layout, C, P) - one translation unit each (fused_qc_*.hip)
+// ---- the instantiations that lists decide: the only copy.  _build.py compiles one object per entry (fused_qc.hip / fused_ml.hip with the
+// entry as NIC_ENTRY), the table below holds one record per entry, fused.py and the tests read the lists from here.
+// non-default channel counts (FEATURE_PYRAMID_CHANNELS, PE_CHANNELS: var2.py:68-69) on the plain-bf16 kernels (NIC_FLAG_BF16), 3 Linear layers:
+// (layout, C, P)
 #define NIC_CP_LIST(X)                                                                                                       \
     X(1, 4, 6) X(1, 8, 6) X(1, 16, 6) X(1, 12, 4) X(1, 12, 8) X(2, 4, 6) X(2, 8, 6) X(2, 16, 6) X(2, 12, 4) X(2, 12, 8)     \
     X(3, 4, 6) X(3, 8, 6) X(4, 4, 6) X(4, 8, 6) X(4, 16, 6)
-bool cp_default(const nic_path_desc* d) { return d->channels == kC && d->pe_channels == kP; }
-bool cp_listed(int layout, int c, int pch) {
-#define X(L, C, P) if (layout == L && c == C && pch == P) return true;
-    NIC_CP_LIST(X)
+// multi-level layouts (fused_q16.hpp::QML), both positional encodings: (levels, C, n_linear) with P = 6
+#define NIC_ML_LIST(X) X(2, 4, 3) X(3, 4, 3) X(5, 4, 3) X(2, 4, 5) X(3, 4, 5) X(2, 12, 3) X(3, 12, 3)
+
+// ---- every instantiated kernel set (fused_dispatch.hpp), built once: the fixed families, then the lists above
+struct Table {
+    const FusedKernel *b, *e;
+    const FusedKernel* begin() const { return b; }
+    const FusedKernel* end() const { return e; }
+};
+Table kernels() {
+    static const FusedKernel t[] = {
+        fused_kernels<1, SRC_ENCODE>(), fused_kernels<2, SRC_ENCODE>(), fused_kernels<3, SRC_ENCODE>(), fused_kernels<4, SRC_ENCODE>(),
+        fused_kernels<1, SRC_MEMORY>(), fused_kernels<2, SRC_MEMORY>(), fused_kernels<3, SRC_MEMORY>(), fused_kernels<4, SRC_MEMORY>(),
+        train16_kernels<1>(), train16_kernels<2>(),
+        mlpn_kernels<1, 3>(), mlpn_kernels<1, 5>(), mlpn_kernels<2, 3>(), mlpn_kernels<2, 5>(),
+        q16_kernels<1, 3>(), q16_kernels<1, 5>(), q16_kernels<2, 3>(), q16_kernels<2, 5>(),
+        q16_kernels<3, 3>(), q16_kernels<3, 5>(), q16_kernels<4, 3>(), q16_kernels<4, 5>(),
+#define X(L, C, P) q16_cp_kernels<L, C, P>(),
+        NIC_CP_LIST(X)
 #undef X
-    return false;
+#define X(LV, C, NL) ml_kernels<LV, C, NL>(),
+        NIC_ML_LIST(X)
+#undef X
+    };
+    return {t, t + sizeof(t) / sizeof(t[0])};
 }
+const FusedKernel* find(Family f, int layout, int c, int p, int n_linear) {
+    for (const FusedKernel& k : kernels())
+        if (k.family == f && k.layout == layout && k.c == c && k.p == p && k.n_linear == n_linear) return &k;
+    return nullptr;
+}
+
+bool cp_default(const nic_path_desc* d) { return d->channels == kC && d->pe_channels == kP; }
 // layout id (see nic_device.hpp) or a negative error
 int pick_layout(const nic_path_desc* d) {
     if (!d) return NIC_E_NULL;
     if (d->hidden != kH) return NIC_E_UNSUPPORTED;                       // HIDDEN_LAYER_CHANNELS: 64 only (every tile shape of the kernels hangs on it)
-    if (!cp_default(d)) {
-        if (!(d->flags & NIC_FLAG_BF16)) return NIC_E_UNSUPPORTED;      // other channel counts: the plain-bf16 kernels
-        int layout = NIC_E_UNSUPPORTED;
-        if (d->dim == 2 && d->method == 1) layout = d->pe_mode == NIC_PE_TRIANGULAR ? 1 : (d->pe_mode == NIC_PE_SINUSOIDAL ? 2 : NIC_E_UNSUPPORTED);
-        else if (d->dim == 3 && d->method == 3 && d->pe_mode == NIC_PE_TRIANGULAR) layout = 3;
-        else if (d->dim == 3 && d->method == 4 && d->pe_mode == NIC_PE_SINUSOIDAL) layout = 4;
-        return (layout > 0 && cp_listed(layout, d->channels, d->pe_channels)) ? layout : NIC_E_UNSUPPORTED;
-    }
-    if (d->dim == 2 && d->method == 1) return d->pe_mode == NIC_PE_TRIANGULAR ? 1 : (d->pe_mode == NIC_PE_SINUSOIDAL ? 2 : NIC_E_UNSUPPORTED);
-    if (d->dim == 3 && d->method == 3) return d->pe_mode == NIC_PE_TRIANGULAR ? 3 : NIC_E_UNSUPPORTED;   // fp_def.py:169
-    if (d->dim == 3 && d->method == 4) return d->pe_mode == NIC_PE_SINUSOIDAL ? 4 : NIC_E_UNSUPPORTED;   // fp_def.py:208
-    return NIC_E_UNSUPPORTED;
+    int layout = NIC_E_UNSUPPORTED;
+    if (d->dim == 2 && d->method == 1) layout = d->pe_mode == NIC_PE_TRIANGULAR ? 1 : (d->pe_mode == NIC_PE_SINUSOIDAL ? 2 : NIC_E_UNSUPPORTED);
+    else if (d->dim == 3 && d->method == 3 && d->pe_mode == NIC_PE_TRIANGULAR) layout = 3;     // fp_def.py:169
+    else if (d->dim == 3 && d->method == 4 && d->pe_mode == NIC_PE_SINUSOIDAL) layout = 4;     // fp_def.py:208
+    if (layout < 0 || cp_default(d)) return layout;
+    // other channel counts: the plain-bf16 kernels, where NIC_CP_LIST instantiates them
+    return (d->flags & NIC_FLAG_BF16) && find(FAM_Q16, layout, d->channels, d->pe_channels, 3) ? layout : NIC_E_UNSUPPORTED;
 }
 int layout_of_cin(int cin) { return cin == 73 ? 1 : (cin == 127 ? 3 : (cin == 79 ? 4 : NIC_E_UNSUPPORTED)); }
+
+int mlp_depth(const nic_mlp* m) { return m->n_linear == 0 ? 3 : m->n_linear; }
+bool depth_unsupported(const nic_mlp* m) { const int n = mlp_depth(m); return n != 3 && n != 5 && n >= 2 && n <= NIC_MAX_LINEAR; }
+bool mlp_ok(const nic_mlp* m) {
+    if (!m) return false;
+    const int n = mlp_depth(m);
+    if (n != 3 && n != 5) return false;
+    for (int i = 0; i < n; ++i) if (!m->w[i] || !m->b[i]) return false;
+    return true;
+}
 
 // 2D training steps with split-bf16 products run on the 8-wave / 16-sample kernel (fused_train16.hpp: two waves per SIMD).
 // NIC_T16=0 in the environment keeps them on the 4-wave / 32-sample fused_kernel (A/B timing, and the reference the parity tests
@@ -61,31 +93,49 @@ bool use_t16(int layout, const nic_path_desc* d) {
     }
     return enabled && (layout == 1 || layout == 2) && (d->flags & NIC_FLAG_SPLIT_BF16) != 0 && (d->flags & NIC_FLAG_SPLIT_TILE32) == 0;
 }
-FusedInfo info_t16() { return FusedInfo{0, train16_record_floats(), 16, 1, 1, 73, 8}; }
 
-FusedInfo info_of(int layout) {
-    switch (layout) {
-        case 1: return fused_info<1>();
-        case 2: return fused_info<2>();
-        case 3: return fused_info<3>();
-        default: return fused_info<4>();
-    }
+enum Purpose { TRAIN, INFER, INFER_U8, MULTI_LEVEL };
+// what an entry point refuses before it looks at its arguments: the layout and the decoder depth
+int refuse_early(const nic_path_desc* d, const nic_mlp* m, Purpose why) {
+    const int layout = pick_layout(d);
+    if (layout < 0) return layout;
+    // the stored-codec kernels are the 32-sample / depth-generic families, built for C = 12, P = 6 (with NIC_FLAG_BF16 pick_layout also answers for
+    // the plain-bf16 kernels' other widths, which have no uint8 grid kind): the caller decodes through fp_load + the layer-wise route instead
+    if (why == INFER_U8 && !cp_default(d)) return NIC_E_UNSUPPORTED;
+    if (m && depth_unsupported(m)) return NIC_E_UNSUPPORTED;            // the fused kernels exist for 3 and 5 Linear layers
+    return NIC_OK;
 }
-int launch(int layout, int src, int mode, const FusedParams& p, int grid, hipStream_t s) {
-    switch (layout) {
-        case 1: return launch_fused<1>(src, mode, p, grid, s);
-        case 2: return launch_fused<2>(src, mode, p, grid, s);
-        case 3: return launch_fused<3>(src, mode, p, grid, s);
-        default: return launch_fused<4>(src, mode, p, grid, s);
+// the kernel set of a call (after refuse_early and the argument checks; MULTI_LEVEL: `levels` pairs), or a negative NIC_E_*
+int select_kernel(const nic_path_desc* d, const nic_mlp* m, Purpose why, const FusedKernel*& k, int levels = 0) {
+    const int n = mlp_depth(m), f = d->flags;
+    if (why == MULTI_LEVEL) {
+        k = find(FAM_ML, levels, d->channels, kP, n);
+        return k && !(f & (NIC_FLAG_GRID_BF16 | NIC_FLAG_GRID_FP16)) ? NIC_OK : NIC_E_UNSUPPORTED;       // listed, fp32 grids
     }
-}
-int reduce(int layout, const float* partials, int n_waves, nic_mlp_grads g, float* loss, float loss_scale, hipStream_t s) {
-    switch (layout) {
-        case 1: return launch_reduce<1>(partials, n_waves, g, loss, loss_scale, s);
-        case 2: return launch_reduce<2>(partials, n_waves, g, loss, loss_scale, s);
-        case 3: return launch_reduce<3>(partials, n_waves, g, loss, loss_scale, s);
-        default: return launch_reduce<4>(partials, n_waves, g, loss, loss_scale, s);
+    const int layout = pick_layout(d);
+    const bool two_d = layout == 1 || layout == 2;
+    if (why == INFER_U8) {                                              // 5-layer decoders: the depth-generic kernel, 2D (grid kind 3 = the codec)
+        if (n != 3 && !two_d) return NIC_E_UNSUPPORTED;
+        k = find(n != 3 ? FAM_MLPN : FAM_FUSED, layout, kC, kP, n);
+        return NIC_OK;
     }
+    if ((f & NIC_FLAG_GRID_BF16) && (f & NIC_FLAG_GRID_FP16)) return NIC_E_ARG;
+    if (f & (NIC_FLAG_BF16 | NIC_FLAG_FP16)) {
+        // plain 16-bit products: the quarter kernels, every layout and grid storage; other channel counts with bf16 operands and 3 layers
+        if (!cp_default(d) && (n != 3 || (f & NIC_FLAG_FP16))) return NIC_E_UNSUPPORTED;
+        k = find(FAM_Q16, layout, d->channels, d->pe_channels, n);
+        return NIC_OK;
+    }
+    // the depth-generic kernels serve n_linear = 5, n_linear = 3 on request (NIC_FLAG_MLPN), and the decode from 16-bit grids: 2D layouts,
+    // split-bf16 products
+    const bool split = (f & NIC_FLAG_SPLIT_BF16) != 0, grid16 = (f & (NIC_FLAG_GRID_BF16 | NIC_FLAG_GRID_FP16)) != 0;
+    const bool mlpn = n == 5 || (f & NIC_FLAG_MLPN) != 0 || (why == INFER && grid16);
+    if (grid16 && (!two_d || !split || (f & NIC_FLAG_SPLIT_TILE32))) return NIC_E_UNSUPPORTED;   // 16-bit grid storage: the quarter-layout 2D kernels only
+    if (mlpn && (!two_d || !split)) return NIC_E_UNSUPPORTED;
+    if (mlpn) k = find(FAM_MLPN, layout, kC, kP, n);
+    else if (why == TRAIN && use_t16(layout, d)) k = find(FAM_T16, layout, kC, kP, 3);
+    else k = find(FAM_FUSED, layout, kC, kP, 3);
+    return NIC_OK;
 }
 
 // ---- the optimiser tail of the call in progress (nic_path_desc.tail -> nic_adam.hpp::StepTail), parked around the reduce dispatch
@@ -93,6 +143,10 @@ thread_local hipEvent_t g_kernel_end = nullptr;               // nic_mark_kernel
 void mark_kernel_end(hipStream_t s) {
     if (g_kernel_end) { (void)hipEventRecord(g_kernel_end, s); g_kernel_end = nullptr; }
 }
+// a training entry point consumes the parked event on every return: recorded between its kernel and its reduction, or dropped
+struct KernelEndScope {
+    ~KernelEndScope() { g_kernel_end = nullptr; }
+};
 thread_local const StepTail* g_tail = nullptr;
 thread_local int64_t g_tail_blocks = 0;
 struct TailScope {
@@ -254,8 +308,9 @@ int grid_for(int64_t n_tiles, int per_cu, int waves_per_wg = 4, int max_wg = 0) 
     return (int)want;
 }
 
-void fill_encode(FusedParams& p, const nic_path_desc* d, const FusedInfo& fi, const float* g0, const float* g1, const int32_t* origins,
-                 const float* noise, bool allow_packed = false) {
+void fill_encode(FusedParams& p, const nic_path_desc* d, const FusedKernel& k, const float* g0, const float* g1, const int32_t* origins,
+                 const float* noise) {
+    const FusedInfo& fi = k.info;
     p.d = *d;
     p.g0.p = g0; p.g0.nx = d->g0_nodes[0]; p.g0.ny = d->g0_nodes[1]; p.g0.nz = d->dim == 3 ? d->g0_nodes[2] : 1;
     p.g0.plane = (int64_t)p.g0.nx * p.g0.ny * p.g0.nz;
@@ -300,14 +355,14 @@ void fill_encode(FusedParams& p, const nic_path_desc* d, const FusedInfo& fi, co
     p.tiles_y = ty; p.tiles_z = tz;
     p.tiles_main = (int64_t)p.full_x * ty * tz;
     p.tiles_per_crop = p.tiles_main + edge_tiles;
-    // packed tiling (the 32-sample kernels): 32 consecutive blocks of the crop's block list per macro-tile, when that needs at least
+    // packed tiling (fused_kernel, fused_q16_kernel): 32 (16) consecutive blocks of the crop's block list per macro-tile, when that needs at least
     // 15 % fewer macro-tiles than the 16 x 2 wave blocks (block counts far from multiples of 16 and 2: small unaligned crops)
     p.pk_nc = 0;
     {
         const int bz = d->dim == 3 ? blocks(ez) : 1;
         const int tsz = fi.tx * fi.ty * fi.tz;                                   // 32 blocks (fused_kernel) or 16 (fused_q16_kernel)
         const int64_t nc = (int64_t)bx * by * bz, pt = (nc + tsz - 1) / tsz;
-        if (allow_packed && (tsz == 32 || tsz == 16) && nc < ((int64_t)1 << 24) && pt * 115 <= p.tiles_per_crop * 100) {
+        if ((k.family == FAM_FUSED || k.family == FAM_Q16) && (tsz == 32 || tsz == 16) && nc < ((int64_t)1 << 24) && pt * 115 <= p.tiles_per_crop * 100) {
             p.pk_bx = bx; p.pk_by = by; p.pk_nc = (int)nc;
             p.edge_lw = -1;
             p.tiles_main = pt;
@@ -341,103 +396,11 @@ void set_f16(FusedParams& p, const nic_path_desc* d, bool auto_from_loss) {
     p.dz_scale = ldexpf(1.0f, k);
     p.dz_unscale = ldexpf(1.0f, -k);
 }
-int mlp_depth(const nic_mlp* m) { return m->n_linear == 0 ? 3 : m->n_linear; }
-bool depth_unsupported(const nic_mlp* m) { const int n = mlp_depth(m); return n != 3 && n != 5 && n >= 2 && n <= NIC_MAX_LINEAR; }
 void fill_mlp(FusedParams& p, const nic_mlp* m) {
     for (int i = 0; i < NIC_MAX_LINEAR; ++i) { p.W[i] = m->w[i]; p.b[i] = m->b[i]; }
     p.n_linear = mlp_depth(m);
 }
-bool mlp_ok(const nic_mlp* m) {
-    if (!m) return false;
-    const int n = mlp_depth(m);
-    if (n != 3 && n != 5) return false;
-    for (int i = 0; i < n; ++i) if (!m->w[i] || !m->b[i]) return false;
-    return true;
-}
 int grid_kind_of(const nic_path_desc* d) { return (d->flags & NIC_FLAG_GRID_BF16) ? 1 : ((d->flags & NIC_FLAG_GRID_FP16) ? 2 : 0); }
-// the depth-generic kernels serve n_linear = 5, n_linear = 3 on request (NIC_FLAG_MLPN), and the decode from 16-bit grids: 2D layouts,
-// split-bf16 products
-int use_mlpn(int layout, const nic_path_desc* d, const nic_mlp* m, bool grid_u8, bool& yes, bool inference = false) {
-    const int n = mlp_depth(m);
-    if ((d->flags & NIC_FLAG_GRID_BF16) && (d->flags & NIC_FLAG_GRID_FP16)) return NIC_E_ARG;
-    yes = n == 5 || (d->flags & NIC_FLAG_MLPN) != 0 || (inference && grid_kind_of(d) != 0);
-    if (grid_kind_of(d) != 0 && ((layout != 1 && layout != 2) || !(d->flags & NIC_FLAG_SPLIT_BF16) || (d->flags & NIC_FLAG_SPLIT_TILE32) || grid_u8))
-        return NIC_E_UNSUPPORTED;                                  // 16-bit grid storage: the quarter-layout 2D kernels only
-    if (!yes) return NIC_OK;
-    if ((layout != 1 && layout != 2) || !(d->flags & NIC_FLAG_SPLIT_BF16) || grid_u8) return NIC_E_UNSUPPORTED;
-    return NIC_OK;
-}
-FusedInfo info_mlpn(int n_linear) { return FusedInfo{0, mlpn_record_floats(n_linear), 16, 1, 1, 73, 4}; }
-// plain-bf16 kernels (fused_q16.hpp): every layout, 3 or 5 Linear layers
-int q16_rec(int layout, int n_linear) {
-    switch (layout) {
-        case 1: return q16_record_floats<1>(n_linear);
-        case 2: return q16_record_floats<2>(n_linear);
-        case 3: return q16_record_floats<3>(n_linear);
-        default: return q16_record_floats<4>(n_linear);
-    }
-}
-int q16_rec_cp(int layout, int c, int pch) {
-#define X(L, C, P) if (layout == L && c == C && pch == P) return q16_record_floats_cp<L, C, P>();
-    NIC_CP_LIST(X)
-#undef X
-    return 0;
-}
-FusedInfo info_q16(int layout, int n_linear, const nic_path_desc* d = nullptr) {
-    const int c = d ? d->channels : kC, pch = d ? d->pe_channels : kP;
-    const int cin = layout <= 2 ? 5 * c + 2 * pch + 1 : (layout == 3 ? 9 * c + 19 : 5 * c + 19);
-    const bool def = c == kC && pch == kP;
-    return FusedInfo{0, def ? q16_rec(layout, n_linear) : q16_rec_cp(layout, c, pch), 16, 1, 1, cin, 8};
-}
-int launch_q16_any(int layout, int n_linear, int mode, const FusedParams& p, int grid, hipStream_t s) {
-    if (!cp_default(&p.d)) {
-        if (n_linear != 3) return NIC_E_UNSUPPORTED;
-#define X(L, C, P) if (layout == L && p.d.channels == C && p.d.pe_channels == P) return launch_q16_cp<L, C, P>(mode, p, grid, s);
-        NIC_CP_LIST(X)
-#undef X
-        return NIC_E_UNSUPPORTED;
-    }
-    switch (layout) {
-        case 1: return launch_q16<1>(n_linear, mode, p, grid, s);
-        case 2: return launch_q16<2>(n_linear, mode, p, grid, s);
-        case 3: return launch_q16<3>(n_linear, mode, p, grid, s);
-        default: return launch_q16<4>(n_linear, mode, p, grid, s);
-    }
-}
-int reduce_q16_any(int layout, int n_linear, const nic_path_desc* d, const float* partials, int n_rec, nic_mlp_grads g, float* loss, float loss_scale, hipStream_t s) {
-    if (!cp_default(d)) {
-#define X(L, C, P) if (layout == L && d->channels == C && d->pe_channels == P) return reduce_q16_cp<L, C, P>(partials, n_rec, g, loss, loss_scale, s);
-        NIC_CP_LIST(X)
-#undef X
-        return NIC_E_UNSUPPORTED;
-    }
-    switch (layout) {
-        case 1: return reduce_q16<1>(n_linear, partials, n_rec, g, loss, loss_scale, s);
-        case 2: return reduce_q16<2>(n_linear, partials, n_rec, g, loss, loss_scale, s);
-        case 3: return reduce_q16<3>(n_linear, partials, n_rec, g, loss, loss_scale, s);
-        default: return reduce_q16<4>(n_linear, partials, n_rec, g, loss, loss_scale, s);
-    }
-}
-// multi-level layouts (fused_q16.hpp::QML): (levels, C, n_linear) with P = 6, one translation unit each (fused_ml_*.hip)
-#define NIC_ML_LIST(X) X(2, 4, 3) X(3, 4, 3) X(5, 4, 3) X(2, 4, 5) X(3, 4, 5) X(2, 12, 3) X(3, 12, 3)
-int ml_rec(int lv, int c, int nl) {
-#define X(L, C, N) if (lv == L && c == C && nl == N) return ml_record_floats<L, C, N>();
-    NIC_ML_LIST(X)
-#undef X
-    return 0;
-}
-int launch_ml_any(int lv, int c, int nl, int pe, int mode, const FusedParams& p, int grid, hipStream_t s) {
-#define X(L, C, N) if (lv == L && c == C && nl == N) return launch_ml<L, C, N>(pe, mode, p, grid, s);
-    NIC_ML_LIST(X)
-#undef X
-    return NIC_E_UNSUPPORTED;
-}
-int reduce_ml_any(int lv, int c, int nl, int pe, const float* partials, int n_rec, nic_mlp_grads g, float* loss, float loss_scale, hipStream_t s) {
-#define X(L, C, N) if (lv == L && c == C && nl == N) return reduce_ml<L, C, N>(pe, partials, n_rec, g, loss, loss_scale, s);
-    NIC_ML_LIST(X)
-#undef X
-    return NIC_E_UNSUPPORTED;
-}
 FusedParams zero_params() {
     FusedParams p;
     ::memset(static_cast<void*>(&p), 0, sizeof(p));
@@ -445,13 +408,40 @@ FusedParams zero_params() {
     return p;
 }
 
+// workgroups for `units` work units, or NIC_E_UNSUPPORTED: the kernels count work units in 32 bits
+int unit_grid(int64_t units, int per_cu, const FusedKernel& k, const FusedParams& p) {
+    if (units >= ((int64_t)1 << 30)) return NIC_E_UNSUPPORTED;
+    return grid_for(units, per_cu, k.info.waves, p.d.max_workgroups);
+}
+// the end of every fused launch on `grid` workgroups.  Training (grads set): one record per workgroup in p.partials, the optimiser tail of
+// p.d riding on the reduction, the parked kernel-end event recorded between the two launches
+int run(const FusedKernel& k, const FusedParams& p, int mode, int grid, void* stream, const nic_mlp_grads* grads = nullptr, float* loss = nullptr,
+        size_t workspace_bytes = 0) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!grads) return k.launch(mode, p, grid, s);
+    if (workspace_bytes < (size_t)grid * k.info.rec * sizeof(float)) return NIC_E_WORKSPACE;
+    TailScope tail;
+    int rc = tail.open(&p.d, grads, p.step_dev);
+    if (rc) return rc;
+    rc = k.launch(mode, p, grid, s);
+    if (rc) return rc;
+    mark_kernel_end(s);
+    return k.reduce(p, grid, *grads, loss, s);
+}
+// an inference launch: every macro-tile in 2^rg_log2 groups, one segment
+int infer(const FusedKernel& k, FusedParams& p, void* stream) {
+    const int per_cu = k.family == FAM_FUSED ? 2 : 1;                  // fused_kernel: two workgroups per CU (the others: 84 KB of weight images)
+    balance_units(p, per_cu, k.info.waves);
+    const int grid = unit_grid(p.n_tiles << p.rg_log2, per_cu, k, p);
+    return grid < 0 ? grid : run(k, p, MODE_INFER, grid, stream);
+}
+
 int fused_train(const nic_path_desc* d, const float* g0, const float* g1, const int32_t* origins, const nic_mlp* mlp, const float* noise,
                 const float* target, const float* dy, float* y, float* loss, float* g0_grad, float* g1_grad, const nic_mlp_grads* grads,
                 void* workspace, size_t workspace_bytes, void* stream, const nic_target_image* img = nullptr, const int64_t* step_dev = nullptr) {
-    const int layout = pick_layout(d);
-    if (layout < 0) return layout;
-    if (mlp && depth_unsupported(mlp)) return NIC_E_UNSUPPORTED;      // the fused kernels exist for 3 and 5 Linear layers
-    int rc = check_geometry(d, true);
+    int rc = refuse_early(d, mlp, TRAIN);
+    if (rc) return rc;
+    rc = check_geometry(d, true);
     if (rc) return rc;
     if (!g0 || !g1 || !origins || !mlp_ok(mlp) || !g0_grad || !g1_grad || !grads || !workspace) return NIC_E_NULL;
     if ((target != nullptr) + (dy != nullptr) + (img != nullptr) != 1) return NIC_E_ARG;
@@ -462,20 +452,11 @@ int fused_train(const nic_path_desc* d, const float* g0, const float* g1, const 
         if (img->is_u8 && !(img->den > 0.f)) return NIC_E_ARG;
     }
     if (d->noise_mode == NIC_NOISE_TENSOR && !noise) return NIC_E_NULL;
-    const bool f16 = (d->flags & NIC_FLAG_FP16) != 0;                  // .. on IEEE half operands
-    const bool q16 = (d->flags & NIC_FLAG_BF16) != 0 || f16;           // plain 16-bit products: every layout on the quarter kernels
-    if (q16 && (d->flags & NIC_FLAG_GRID_BF16) && (d->flags & NIC_FLAG_GRID_FP16)) return NIC_E_ARG;
-    if (f16 && !cp_default(d)) return NIC_E_UNSUPPORTED;
-    bool mlpn = false;
-    if (!q16) {
-        rc = use_mlpn(layout, d, mlp, false, mlpn);
-        if (rc) return rc;
-    }
-    const bool t16 = !q16 && !mlpn && use_t16(layout, d);
-    if (q16 && !cp_default(d) && mlp_depth(mlp) != 3) return NIC_E_UNSUPPORTED;
-    const FusedInfo fi = q16 ? info_q16(layout, mlp_depth(mlp), d) : (mlpn ? info_mlpn(mlp_depth(mlp)) : (t16 ? info_t16() : info_of(layout)));
+    const FusedKernel* k = nullptr;
+    rc = select_kernel(d, mlp, TRAIN, k);
+    if (rc) return rc;
     FusedParams p = zero_params();
-    fill_encode(p, d, fi, g0, g1, origins, noise, q16 || (!mlpn && !t16));
+    fill_encode(p, d, *k, g0, g1, origins, noise);
     fill_mlp(p, mlp);
     p.g0_grad = g0_grad; p.g1_grad = g1_grad;
     p.target = target; p.dy = dy; p.y = y;
@@ -494,68 +475,40 @@ int fused_train(const nic_path_desc* d, const float* g0, const float* g1, const 
         p.timg_rcp = 1.0f / p.timg_den;
     }
     p.grid_kind = grid_kind_of(d);
-    if (f16) set_f16(p, d, target != nullptr || img != nullptr);
-    if (p.grid_kind != 0 && !(mlpn || t16 || q16)) return NIC_E_UNSUPPORTED;
-    if (step_dev != nullptr && !(t16 || q16)) return NIC_E_UNSUPPORTED;                // the device-side step: the two-waves-per-SIMD kernels
+    if (d->flags & NIC_FLAG_FP16) set_f16(p, d, target != nullptr || img != nullptr);
+    const bool eight = k->family == FAM_T16 || k->family == FAM_Q16;           // the two-waves-per-SIMD kernels
+    if (p.grid_kind != 0 && k->family == FAM_FUSED) return NIC_E_UNSUPPORTED;
+    if (step_dev != nullptr && !eight) return NIC_E_UNSUPPORTED;                       // the device-side step: the two-waves-per-SIMD kernels
     if (step_dev != nullptr && (d->flags & NIC_FLAG_ORIGINS_HOST)) return NIC_E_ARG;     // .. reads the origins the device sampler wrote
     p.step_dev = step_dev;
     p.partials = (float*)workspace;
-    const int wpw = (t16 || q16) ? 8 : 4;                     // waves per workgroup = work units per workgroup round
+    const int wpw = k->info.waves;                            // waves per workgroup = work units per workgroup round
     static const bool two_seg = []() { const char* e = getenv("NIC_TWO_SEG"); return !(e && e[0] == '0'); }();   // NIC_TWO_SEG=0: one segment (A/B timing)
     // (8 groups in segment 0 - a macro-tile's groups in two workgroups, two flushes: the reference's 3D sweep shape 0.368 -> 0.332 ms with
     //  method 4; method 3, twice the sums per lane, lost 5 % until its flush pre-added neighbouring sums and gains 6 % since)
-    balance_units(p, 1, wpw, (t16 || q16) && two_seg, !t16 && !q16 && !mlpn && two_seg, NIC_RG_SEG0, q16 ? NIC_Q16_RG0 : 0);
+    balance_units(p, 1, wpw, eight && two_seg, k->family == FAM_FUSED && two_seg, NIC_RG_SEG0, k->family == FAM_Q16 ? NIC_Q16_RG0 : 0);
     p.preadd_y = p.n_tiles <= (int64_t)4 * wpw * cu_count() ? 1 : 0;
     const int64_t units0 = p.seg_split << p.rg0_log2, units1 = (p.n_tiles - p.seg_split) << p.rg_log2;
-    const int64_t units_max = units0 > units1 ? units0 : units1;
-    if (units_max >= ((int64_t)1 << 30)) return NIC_E_UNSUPPORTED;                    // the kernels count work units in 32 bits
-    const int grid = grid_for(units_max, 1, wpw, d->max_workgroups);
-    const int n_rec = grid;                                   // one record per workgroup
-    if (workspace_bytes < (size_t)n_rec * fi.rec * sizeof(float)) return NIC_E_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
+    const int grid = unit_grid(units0 > units1 ? units0 : units1, 1, *k, p);
+    if (grid < 0) return grid;
     const int mode = img ? MODE_TRAIN_IMG : (target ? MODE_TRAIN_MSE : MODE_TRAIN_DY);
-    TailScope tail;                                           // nic_path_desc.tail: Adam rides on the reduce launch below
-    rc = tail.open(d, grads, step_dev);
-    if (rc) return rc;
-    if (q16) {
-        rc = launch_q16_any(layout, p.n_linear, mode, p, grid, s);
-        if (rc) return rc;
-        mark_kernel_end(s);
-        return reduce_q16_any(layout, p.n_linear, d, p.partials, n_rec, *grads, (target || img) ? loss : nullptr, d->loss_scale, s);
-    }
-    if (mlpn) {
-        rc = launch_mlpn(layout, p.n_linear, mode, p, grid, s);
-        if (rc) return rc;
-        mark_kernel_end(s);
-        return launch_reducen(layout, p.n_linear, p.partials, n_rec, *grads, (target || img) ? loss : nullptr, d->loss_scale, s);
-    }
-    if (t16) {
-        rc = launch_train16(layout, mode, p, grid, s);
-        if (rc) return rc;
-        mark_kernel_end(s);
-        return launch_reduce16(layout, p.partials, n_rec, *grads, (target || img) ? loss : nullptr, d->loss_scale, s);
-    }
-    rc = launch(layout, SRC_ENCODE, mode, p, grid, s);
-    if (rc) return rc;
-    mark_kernel_end(s);
-    return reduce(layout, p.partials, n_rec, *grads, (target || img) ? loss : nullptr, d->loss_scale, s);
+    return run(*k, p, mode, grid, stream, grads, (target || img) ? loss : nullptr, workspace_bytes);
 }
 
 // geometry, pairs and decoder of a multi-level launch -> FusedParams (regular 16 x 1 cell tiles of pair 0, whole macro-tiles: the flush of the
 // multi-level kernels sums runs of lanes, which the edge-tile / packed / grouped schedules of the single-pair kernels would break up)
 int fill_ml(FusedParams& p, const nic_path_desc* d, const nic_ml_pairs* pr, const int32_t* origins, const nic_mlp* mlp, const float* noise, bool training,
-            int& rec) {
+            const FusedKernel*& k) {
     if (!d || !pr || !origins || !mlp) return NIC_E_NULL;
     if (d->dim != 2 || d->method != 1 || d->hidden != kH || d->pe_channels != kP) return NIC_E_UNSUPPORTED;
     if (d->pe_mode != NIC_PE_TRIANGULAR && d->pe_mode != NIC_PE_SINUSOIDAL) return NIC_E_UNSUPPORTED;
     if (pr->levels < 2 || pr->levels > NIC_ML_MAX_LEVELS) return NIC_E_UNSUPPORTED;
     if (!mlp_ok(mlp)) return depth_unsupported(mlp) ? NIC_E_UNSUPPORTED : NIC_E_NULL;
-    rec = ml_rec(pr->levels, d->channels, mlp_depth(mlp));
-    if (rec == 0) return NIC_E_UNSUPPORTED;
-    if (d->flags & (NIC_FLAG_GRID_BF16 | NIC_FLAG_GRID_FP16)) return NIC_E_UNSUPPORTED;       // fp32 grids
+    int rc = select_kernel(d, mlp, MULTI_LEVEL, k, pr->levels);
+    if (rc) return rc;
     nic_path_desc d2 = *d;
     for (int a = 0; a < 2; ++a) { d2.g0_nodes[a] = pr->g0_nodes[0][a]; d2.g1_nodes[a] = pr->g1_nodes[0][a]; }
-    int rc = check_geometry(&d2, training);
+    rc = check_geometry(&d2, training);
     if (rc) return rc;
     if (d->log2_step - 2 * (pr->levels - 1) < -16) return NIC_E_ARG;
     if (d->noise_mode == NIC_NOISE_TENSOR && !noise) return NIC_E_NULL;
@@ -566,8 +519,7 @@ int fill_ml(FusedParams& p, const nic_path_desc* d, const nic_ml_pairs* pr, cons
         if ((int64_t)pr->g0_nodes[l][0] * pr->g0_nodes[l][1] >= (int64_t)1 << 30 || 10 * (int64_t)pr->g1_nodes[l][0] * pr->g1_nodes[l][1] >= (int64_t)1 << 30)
             return NIC_E_UNSUPPORTED;
     }
-    const int cin = pr->levels * (5 * d->channels + 2 * d->pe_channels) + 1;
-    fill_encode(p, &d2, FusedInfo{0, rec, 16, 1, 1, cin, 8}, pr->g0[0], pr->g1[0], origins, noise, false);
+    fill_encode(p, &d2, *k, pr->g0[0], pr->g1[0], origins, noise);
     if (p.edge_lw >= 0) {                                              // the remainder column along x as one more column of regular tiles
         p.full_x += 1;
         p.edge_lw = -1;
@@ -600,58 +552,33 @@ int nic_mark_kernel_end(void* hip_event) {
 int nic_fused_ml_forward_backward(const nic_path_desc* d, const nic_ml_pairs* pairs, const int32_t* origins, const nic_mlp* mlp, const float* noise,
                                   const float* target, float* y, float* loss, const nic_mlp_grads* grads, void* workspace, size_t workspace_bytes,
                                   void* stream) {
+    const KernelEndScope end;
     if (!target || !loss || !grads || !workspace) return NIC_E_NULL;
     FusedParams p = zero_params();
-    int rec = 0;
-    int rc = fill_ml(p, d, pairs, origins, mlp, noise, true, rec);
+    const FusedKernel* k = nullptr;
+    int rc = fill_ml(p, d, pairs, origins, mlp, noise, true, k);
     if (rc) return rc;
     p.target = target; p.y = y;
-    p.partials = (float*)workspace;
-    p.rg_log2 = 0; p.rg0_log2 = 0; p.seg_split = 0; p.preadd_y = 0;    // whole macro-tiles, one segment
-    if (p.n_tiles >= ((int64_t)1 << 30)) return NIC_E_UNSUPPORTED;
-    const int grid = grid_for(p.n_tiles, 1, 8, d->max_workgroups);
-    if (workspace_bytes < (size_t)grid * rec * sizeof(float)) return NIC_E_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    TailScope tail;
-    rc = tail.open(d, grads, nullptr);
-    if (rc) return rc;
-    rc = launch_ml_any(pairs->levels, d->channels, p.n_linear, d->pe_mode, MODE_TRAIN_MSE, p, grid, s);
-    if (rc) return rc;
-    mark_kernel_end(s);
-    return reduce_ml_any(pairs->levels, d->channels, p.n_linear, d->pe_mode, p.partials, grid, *grads, loss, d->loss_scale, s);
+    p.partials = (float*)workspace;                                   // whole macro-tiles, one segment (rg_log2 = seg_split = 0), no y pre-add
+    const int grid = unit_grid(p.n_tiles, 1, *k, p);
+    return grid < 0 ? grid : run(*k, p, MODE_TRAIN_MSE, grid, stream, grads, loss, workspace_bytes);
 }
 
 int nic_fused_ml_forward(const nic_path_desc* d, const nic_ml_pairs* pairs, const int32_t* origins, const nic_mlp* mlp, float* y, void* stream) {
     if (!y) return NIC_E_NULL;
     if (d && d->noise_mode != NIC_NOISE_NONE) return NIC_E_ARG;        // decoding never adds noise (image_compression.py:307-346)
     FusedParams p = zero_params();
-    int rec = 0;
-    int rc = fill_ml(p, d, pairs, origins, mlp, nullptr, false, rec);
+    const FusedKernel* k = nullptr;
+    const int rc = fill_ml(p, d, pairs, origins, mlp, nullptr, false, k);
     if (rc) return rc;
     p.y = y;
-    balance_units(p, 1, 8);
-    if ((p.n_tiles << p.rg_log2) >= ((int64_t)1 << 30)) return NIC_E_UNSUPPORTED;
-    p.seg_split = 0;
-    return launch_ml_any(pairs->levels, d->channels, p.n_linear, d->pe_mode, MODE_INFER, p, grid_for(p.n_tiles << p.rg_log2, 1, 8, d->max_workgroups),
-                         (hipStream_t)stream);
+    return infer(*k, p, stream);
 }
 
-size_t nic_workspace_bytes(const nic_path_desc* d) {
-    int rec = fused_info<3>().rec;                                   // the largest record
-    if (d) {
-        const int layout = pick_layout(d);
-        if (layout > 0) rec = info_of(layout).rec;
-    }
-    if (train16_record_floats() > rec) rec = train16_record_floats();
-    if (mlpn_record_floats(5) > rec) rec = mlpn_record_floats(5);
-    for (int l = 1; l <= 4; ++l)
-        if (q16_rec(l, 5) > rec) rec = q16_rec(l, 5);
-#define X(L, C, P) if (q16_record_floats_cp<L, C, P>() > rec) rec = q16_record_floats_cp<L, C, P>();
-    NIC_CP_LIST(X)
-#undef X
-#define X(L, C, N) if (ml_record_floats<L, C, N>() > rec) rec = ml_record_floats<L, C, N>();
-    NIC_ML_LIST(X)
-#undef X
+size_t nic_workspace_bytes(const nic_path_desc*) {
+    int rec = 0;                                                      // the largest record
+    for (const FusedKernel& k : kernels())
+        if (k.info.rec > rec) rec = k.info.rec;
     const size_t fused = (size_t)(cu_count() / 8 * 8) * rec * sizeof(float) + (1u << 20);   // one record per workgroup, at most one workgroup per CU (+ 1 MiB: diagnostic builds)
     const size_t psnr = 1024 * sizeof(double);
     return fused > psnr ? fused : psnr;
@@ -659,85 +586,52 @@ size_t nic_workspace_bytes(const nic_path_desc* d) {
 
 int nic_fused_forward(const nic_path_desc* d, const float* g0, const float* g1, const int32_t* origins, const nic_mlp* mlp,
                       const float* noise, float* y, void* stream) {
-    const int layout = pick_layout(d);
-    if (layout < 0) return layout;
-    if (mlp && depth_unsupported(mlp)) return NIC_E_UNSUPPORTED;      // the fused kernels exist for 3 and 5 Linear layers
-    int rc = check_geometry(d);
+    int rc = refuse_early(d, mlp, INFER);
+    if (rc) return rc;
+    rc = check_geometry(d);
     if (rc) return rc;
     if (!g0 || !g1 || !origins || !mlp_ok(mlp) || !y) return NIC_E_NULL;
     if (d->noise_mode == NIC_NOISE_TENSOR && !noise) return NIC_E_NULL;
-    if (d->flags & (NIC_FLAG_BF16 | NIC_FLAG_FP16)) {
-        // plain 16-bit products: the forward pass of fused_q16_kernel (every layout and channel count those kernels serve, 16-bit grids included)
-        if ((d->flags & NIC_FLAG_GRID_BF16) && (d->flags & NIC_FLAG_GRID_FP16)) return NIC_E_ARG;
-        if (!cp_default(d) && (mlp_depth(mlp) != 3 || (d->flags & NIC_FLAG_FP16))) return NIC_E_UNSUPPORTED;
-        FusedParams p = zero_params();
-        fill_encode(p, d, info_q16(layout, mlp_depth(mlp), d), g0, g1, origins, noise, true);
-        if (d->flags & NIC_FLAG_FP16) set_f16(p, d, false);
-        fill_mlp(p, mlp);
-        p.y = y;
-        p.grid_kind = grid_kind_of(d);
-        balance_units(p, 1, 8);
-        if ((p.n_tiles << p.rg_log2) >= ((int64_t)1 << 30)) return NIC_E_UNSUPPORTED;
-        p.seg_split = 0;                                              // one segment: every macro-tile in 2^rg_log2 groups
-        return launch_q16_any(layout, p.n_linear, MODE_INFER, p, grid_for(p.n_tiles << p.rg_log2, 1, 8, d->max_workgroups), (hipStream_t)stream);
-    }
-    bool mlpn = false;
-    rc = use_mlpn(layout, d, mlp, false, mlpn, true);
+    const FusedKernel* k = nullptr;
+    rc = select_kernel(d, mlp, INFER, k);
     if (rc) return rc;
-    const FusedInfo fi = mlpn ? info_mlpn(mlp_depth(mlp)) : info_of(layout);
     FusedParams p = zero_params();
-    fill_encode(p, d, fi, g0, g1, origins, noise, !mlpn);
+    fill_encode(p, d, *k, g0, g1, origins, noise);
+    if (d->flags & NIC_FLAG_FP16) set_f16(p, d, false);
     fill_mlp(p, mlp);
     p.y = y;
     p.grid_kind = grid_kind_of(d);
-    if (mlpn) {                                                       // one workgroup per CU (84 KB of weight images)
-        balance_units(p, 1, 4);
-        if ((p.n_tiles << p.rg_log2) >= ((int64_t)1 << 30)) return NIC_E_UNSUPPORTED;     // the kernels count work units in 32 bits
-        return launch_mlpn(layout, p.n_linear, MODE_INFER, p, grid_for(p.n_tiles << p.rg_log2, 1, 4, d->max_workgroups), (hipStream_t)stream);
-    }
-    balance_units(p, 2);
-    if ((p.n_tiles << p.rg_log2) >= ((int64_t)1 << 30)) return NIC_E_UNSUPPORTED;
-    return launch(layout, SRC_ENCODE, MODE_INFER, p, grid_for(p.n_tiles << p.rg_log2, 2, 4, d->max_workgroups), (hipStream_t)stream);
+    return infer(*k, p, stream);
 }
 
 int nic_fused_forward_u8(const nic_path_desc* d, const uint8_t* g0_u8, const uint8_t* g1_u8, const int32_t* origins, const nic_mlp* mlp,
                          float* y, uint8_t* y_u8, void* stream) {
-    const int layout = pick_layout(d);
-    if (layout < 0) return layout;
-    // the stored-codec kernels are the 32-sample / depth-generic families, built for C = 12, P = 6 (with NIC_FLAG_BF16 pick_layout also answers for
-    // the plain-bf16 kernels' other widths, which have no uint8 grid kind): the caller decodes through fp_load + the layer-wise route instead
-    if (!cp_default(d)) return NIC_E_UNSUPPORTED;
-    if (mlp && depth_unsupported(mlp)) return NIC_E_UNSUPPORTED;      // the fused kernels exist for 3 and 5 Linear layers
-    int rc = check_geometry(d);
+    int rc = refuse_early(d, mlp, INFER_U8);
+    if (rc) return rc;
+    rc = check_geometry(d);
     if (rc) return rc;
     if (!g0_u8 || !g1_u8 || !origins || !mlp_ok(mlp) || (!y && !y_u8)) return NIC_E_NULL;
     if (d->noise_mode != NIC_NOISE_NONE) return NIC_E_ARG;            // decoding never adds noise (image_compression.py:307-346)
     if (d->num_bits < 1 || d->num_bits > 8) return NIC_E_ARG;
-    const bool deep = mlp_depth(mlp) != 3;                            // 5-layer decoders: the depth-generic kernel, 2D (grid kind 3 = the codec)
-    if (deep && layout != 1 && layout != 2) return NIC_E_UNSUPPORTED;
-    const FusedInfo fi = deep ? info_mlpn(mlp_depth(mlp)) : info_of(layout);
+    const FusedKernel* k = nullptr;
+    rc = select_kernel(d, mlp, INFER_U8, k);
+    if (rc) return rc;
     FusedParams p = zero_params();
-    fill_encode(p, d, fi, reinterpret_cast<const float*>(g0_u8), reinterpret_cast<const float*>(g1_u8), origins, nullptr, !deep);
+    fill_encode(p, d, *k, reinterpret_cast<const float*>(g0_u8), reinterpret_cast<const float*>(g1_u8), origins, nullptr);
     fill_mlp(p, mlp);
     p.dq_sub = (float)((1 << (d->num_bits - 1)) - 1);
     p.dq_den = (float)((1 << d->num_bits) - 1);
     p.dq_rcp = 1.0f / p.dq_den;
     p.y = y; p.y_u8 = y_u8;
-    if (deep) {
-        p.grid_kind = 3;
-        balance_units(p, 1, 4);
-        if ((p.n_tiles << p.rg_log2) >= ((int64_t)1 << 30)) return NIC_E_UNSUPPORTED;
-        return launch_mlpn(layout, p.n_linear, MODE_INFER, p, grid_for(p.n_tiles << p.rg_log2, 1, 4, d->max_workgroups), (hipStream_t)stream);
-    }
-    p.grid_u8 = 1;
-    balance_units(p, 2);
-    if ((p.n_tiles << p.rg_log2) >= ((int64_t)1 << 30)) return NIC_E_UNSUPPORTED;
-    return launch(layout, SRC_ENCODE, MODE_INFER, p, grid_for(p.n_tiles << p.rg_log2, 2, 4, d->max_workgroups), (hipStream_t)stream);
+    if (k->family == FAM_MLPN) p.grid_kind = 3;
+    else p.grid_u8 = 1;
+    return infer(*k, p, stream);
 }
 
 int nic_fused_forward_backward(const nic_path_desc* d, const float* g0, const float* g1, const int32_t* origins, const nic_mlp* mlp,
                                const float* noise, const float* target, float* y, float* loss, float* g0_grad, float* g1_grad,
                                const nic_mlp_grads* grads, void* workspace, size_t workspace_bytes, void* stream) {
+    const KernelEndScope end;
     if (!target || !loss) return NIC_E_NULL;
     return fused_train(d, g0, g1, origins, mlp, noise, target, nullptr, y, loss, g0_grad, g1_grad, grads, workspace, workspace_bytes, stream);
 }
@@ -745,6 +639,7 @@ int nic_fused_forward_backward(const nic_path_desc* d, const float* g0, const fl
 int nic_fused_forward_backward_img(const nic_path_desc* d, const float* g0, const float* g1, const int32_t* origins, const nic_mlp* mlp,
                                    const float* noise, const nic_target_image* image, float* y, float* loss, float* g0_grad,
                                    float* g1_grad, const nic_mlp_grads* grads, void* workspace, size_t workspace_bytes, void* stream) {
+    const KernelEndScope end;
     if (!image || !loss) return NIC_E_NULL;
     return fused_train(d, g0, g1, origins, mlp, noise, nullptr, nullptr, y, loss, g0_grad, g1_grad, grads, workspace, workspace_bytes, stream,
                        image);
@@ -753,6 +648,7 @@ int nic_fused_forward_backward_img(const nic_path_desc* d, const float* g0, cons
 int nic_fused_forward_backward_img_dev(const nic_path_desc* d, const float* g0, const float* g1, const int32_t* origins, const nic_mlp* mlp,
                                        const nic_target_image* image, float* loss, float* g0_grad, float* g1_grad, const nic_mlp_grads* grads,
                                        const int64_t* step_dev, void* workspace, size_t workspace_bytes, void* stream) {
+    const KernelEndScope end;
     if (!image || !loss || !step_dev) return NIC_E_NULL;
     if (d && d->noise_mode == NIC_NOISE_TENSOR) return NIC_E_ARG;                      // a captured step draws its noise in the kernel (or none)
     return fused_train(d, g0, g1, origins, mlp, nullptr, nullptr, nullptr, nullptr, loss, g0_grad, g1_grad, grads, workspace, workspace_bytes, stream,
@@ -762,6 +658,7 @@ int nic_fused_forward_backward_img_dev(const nic_path_desc* d, const float* g0, 
 int nic_fused_backward_dy(const nic_path_desc* d, const float* g0, const float* g1, const int32_t* origins, const nic_mlp* mlp,
                           const float* noise, const float* dy, float* g0_grad, float* g1_grad, const nic_mlp_grads* grads,
                           void* workspace, size_t workspace_bytes, void* stream) {
+    const KernelEndScope end;
     if (!dy) return NIC_E_NULL;
     return fused_train(d, g0, g1, origins, mlp, noise, nullptr, dy, nullptr, nullptr, g0_grad, g1_grad, grads, workspace, workspace_bytes, stream);
 }
@@ -776,28 +673,22 @@ int nic_decoder_forward(const nic_mlp* mlp, const float* x, int64_t n, int cin, 
     FusedParams p = zero_params();
     fill_mlp(p, mlp);
     p.x = x; p.y = y; p.n_total = n; p.n_tiles = (n + 31) / 32;
-    return launch(layout, SRC_MEMORY, MODE_INFER, p, grid_for(p.n_tiles, 2), (hipStream_t)stream);
+    return run(*find(FAM_DECODER, layout, kC, kP, 3), p, MODE_INFER, grid_for(p.n_tiles, 2), stream);
 }
 
 int nic_decoder_backward(const nic_mlp* mlp, const float* x, const float* dy, int64_t n, int cin, int hidden, float* dx,
                          const nic_mlp_grads* grads, void* workspace, size_t workspace_bytes, void* stream) {
+    const KernelEndScope end;
     if (!mlp_ok(mlp) || !x || !dy || !grads || !workspace) return NIC_E_NULL;
     if (hidden != kH || mlp_depth(mlp) != 3) return NIC_E_UNSUPPORTED;
     const int layout = layout_of_cin(cin);
     if (layout < 0) return layout;
     if (n <= 0) return NIC_E_ARG;
-    const FusedInfo fi = info_of(layout);
     FusedParams p = zero_params();
     fill_mlp(p, mlp);
     p.x = x; p.dy = dy; p.dx = dx; p.n_total = n; p.n_tiles = (n + 31) / 32;
     p.partials = (float*)workspace;
-    const int grid = grid_for(p.n_tiles, 1);
-    const int n_rec = grid * 4 / fi.waves_per_rec;
-    if (workspace_bytes < (size_t)n_rec * fi.rec * sizeof(float)) return NIC_E_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    const int rc = launch(layout, SRC_MEMORY, MODE_TRAIN_DY, p, grid, s);
-    if (rc) return rc;
-    return reduce(layout, p.partials, n_rec, *grads, nullptr, 0.f, s);
+    return run(*find(FAM_DECODER, layout, kC, kP, 3), p, MODE_TRAIN_DY, grid_for(p.n_tiles, 1), stream, grads, nullptr, workspace_bytes);
 }
 
 }  // extern "C"

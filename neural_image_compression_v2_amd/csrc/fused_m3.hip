@@ -1,5 +1,6 @@
 // fused kernels for Layout<3> (see nic_device.hpp)
 #include "fused_launch.hpp"
 namespace nic {
-NIC_INSTANTIATE_LAYOUT(3)
+template FusedKernel fused_kernels<3, SRC_ENCODE>();
+template FusedKernel fused_kernels<3, SRC_MEMORY>();
 }

@@ -1,5 +1,6 @@
 // fused kernels for Layout<4> (see nic_device.hpp)
 #include "fused_launch.hpp"
 namespace nic {
-NIC_INSTANTIATE_LAYOUT(4)
+template FusedKernel fused_kernels<4, SRC_ENCODE>();
+template FusedKernel fused_kernels<4, SRC_MEMORY>();
 }

@@ -1,7 +1,7 @@
 // depth-generic 2D fused kernels (fused_mlpn.hpp): NL = 5 (the "4 x 64" decoder) for training and decode; NL = 3 is instantiated too,
 // as the cross-check of the layer loop against the dedicated 3-layer kernels (NIC_FLAG_MLPN).
 #include "fused_mlpn.hpp"
-#include "fused_t16.hpp"
+#include "fused_dispatch.hpp"
 
 namespace nic {
 
@@ -16,24 +16,21 @@ static int launch_n(int mode, const FusedParams& p, int grid, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
-int launch_mlpn(int layout, int n_linear, int mode, const FusedParams& p, int grid, hipStream_t s) {
-    if (n_linear == 5) return layout == 1 ? launch_n<Layout<1>, 5>(mode, p, grid, s) : launch_n<Layout<2>, 5>(mode, p, grid, s);
-    if (n_linear == 3) return layout == 1 ? launch_n<Layout<1>, 3>(mode, p, grid, s) : launch_n<Layout<2>, 3>(mode, p, grid, s);
-    return NIC_E_UNSUPPORTED;
-}
-
-template <int NL>
-static int reduce_n(int layout, const float* partials, int n_rec, nic_mlp_grads g, float* loss, float loss_scale, hipStream_t s) {
+template <class L, int NL>
+static int reduce_n(const FusedParams& p, int n_rec, const nic_mlp_grads& g, float* loss, hipStream_t s) {
     constexpr int n_out = kH * 73 + kH + (NL - 2) * (kH * kH + kH) + 3 * kH + 3 + 1;
     const TailLaunch t = tail_for((n_out + 31) / 32);
-    const dim3 grid(t.blocks), block(256);
-    if (layout == 1) hipLaunchKernelGGL((reducen_kernel<Layout<1>, NL>), grid, block, 0, s, partials, n_rec, g, loss, loss_scale, t.tl);
-    else hipLaunchKernelGGL((reducen_kernel<Layout<2>, NL>), grid, block, 0, s, partials, n_rec, g, loss, loss_scale, t.tl);
+    hipLaunchKernelGGL((reducen_kernel<L, NL>), dim3(t.blocks), dim3(256), 0, s, p.partials, n_rec, g, loss, p.d.loss_scale, t.tl);
     return (int)hipGetLastError();
 }
-int launch_reducen(int layout, int n_linear, const float* partials, int n_rec, nic_mlp_grads g, float* loss, float loss_scale, hipStream_t s) {
-    return n_linear == 5 ? reduce_n<5>(layout, partials, n_rec, g, loss, loss_scale, s) : reduce_n<3>(layout, partials, n_rec, g, loss, loss_scale, s);
+
+template <int LAYOUT, int NL>
+FusedKernel mlpn_kernels() {
+    return {FAM_MLPN, LAYOUT, kC, kP, NL, {LdsN<NL>::REC, 16, 1, 1, 73, 4}, &launch_n<Layout<LAYOUT>, NL>, &reduce_n<Layout<LAYOUT>, NL>};
 }
-int mlpn_record_floats(int n_linear) { return n_linear == 5 ? LdsN<5>::REC : LdsN<3>::REC; }
+template FusedKernel mlpn_kernels<1, 3>();
+template FusedKernel mlpn_kernels<1, 5>();
+template FusedKernel mlpn_kernels<2, 3>();
+template FusedKernel mlpn_kernels<2, 5>();
 
 }  // namespace nic

@@ -1,5 +1,6 @@
-// plain-bf16 fused training kernels (fused_q16.hpp) for quarter layout QL<4>
+// plain 16-bit fused kernels (fused_q16.hpp) for quarter layout QL<4>, 3 and 5 Linear layers
 #include "fused_q16_launch.hpp"
 namespace nic {
-NIC_INSTANTIATE_Q16(4)
+template FusedKernel q16_kernels<4, 3>();
+template FusedKernel q16_kernels<4, 5>();
 }

@@ -1,6 +1,6 @@
 // the 8-wave / 16-sample 2D training kernels (fused_train16.hpp): Layout<1> (triangular PE) and Layout<2> (sinusoidal PE)
 #include "fused_train16.hpp"
-#include "fused_t16.hpp"
+#include "fused_dispatch.hpp"
 
 namespace nic {
 
@@ -15,19 +15,19 @@ static int launch_t16(int mode, const FusedParams& p, int grid, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
-int launch_train16(int layout, int mode, const FusedParams& p, int grid, hipStream_t s) {
-    return layout == 1 ? launch_t16<Layout<1>>(mode, p, grid, s) : launch_t16<Layout<2>>(mode, p, grid, s);
-}
-
-int launch_reduce16(int layout, const float* partials, int n_rec, nic_mlp_grads g, float* loss, float loss_scale, hipStream_t s) {
+template <class L>
+static int reduce_t16(const FusedParams& p, int n_rec, const nic_mlp_grads& g, float* loss, hipStream_t s) {
     constexpr int outs = 256 / NIC_R16_SLICES;
     const TailLaunch t = tail_for((kR16_SRC + outs - 1) / outs);
-    const dim3 grid(t.blocks), block(256);
-    if (layout == 1) hipLaunchKernelGGL((reduce16_kernel<Layout<1>>), grid, block, 0, s, partials, n_rec, g, loss, loss_scale, t.tl);
-    else hipLaunchKernelGGL((reduce16_kernel<Layout<2>>), grid, block, 0, s, partials, n_rec, g, loss, loss_scale, t.tl);
+    hipLaunchKernelGGL((reduce16_kernel<L>), dim3(t.blocks), dim3(256), 0, s, p.partials, n_rec, g, loss, p.d.loss_scale, t.tl);
     return (int)hipGetLastError();
 }
 
-int train16_record_floats() { return Lds16::REC; }
+template <int LAYOUT>
+FusedKernel train16_kernels() {
+    return {FAM_T16, LAYOUT, kC, kP, 3, {Lds16::REC, 16, 1, 1, 73, 8}, &launch_t16<Layout<LAYOUT>>, &reduce_t16<Layout<LAYOUT>>};
+}
+template FusedKernel train16_kernels<1>();
+template FusedKernel train16_kernels<2>();
 
 }  // namespace nic

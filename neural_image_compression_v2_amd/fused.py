@@ -15,7 +15,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 
-from . import _lib
+from . import _build, _lib
 from ._lib import (NIC_G1_REFERENCE, NIC_G1_TEXTBOOK, NIC_G1_UNWEIGHTED, NIC_NOISE_NONE, NIC_NOISE_KERNEL,
                    NIC_NOISE_TENSOR, NIC_PE_SINUSOIDAL, NIC_PE_TRIANGULAR)
 
@@ -690,7 +690,7 @@ class StepPlan:
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # multi-level fused step (nic_fused_ml_*: several level pairs per sample, csrc/fused_q16.hpp::QML)
 # ---------------------------------------------------------------------------------------------------------------------------------------
-ML_FUSED = {(2, 4, 3), (3, 4, 3), (5, 4, 3), (2, 4, 5), (3, 4, 5), (2, 12, 3), (3, 12, 3)}      # (levels, C, n_linear) with P = 6, H = 64: what fits the LDS
+ML_FUSED = set(_build.instance_list("NIC_ML_LIST"))      # (levels, C, n_linear) with P = 6, H = 64: what fits the LDS (csrc/fused_capi.hip)
 
 
 def ml_is_fused(levels: int, channels: int, pe_channels: int, hidden: int, n_linear: int) -> bool:

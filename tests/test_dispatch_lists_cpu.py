@@ -1,5 +1,6 @@
 """CPU-only checks (run with -m "not gpu") that tie the fused dispatch tables together: NIC_CP_LIST / NIC_ML_LIST in csrc/fused_capi.hip, the
-translation units _build.py compiles for them, fused.ML_FUSED, and the cell matrix of tests/test_gpu_dispatch_matrix.py.  Through the C ABI with
+objects _build.py compiles for them, the dispatch table of csrc/fused_capi.hip, fused.ML_FUSED, and the cell matrix of
+tests/test_gpu_dispatch_matrix.py.  Through the C ABI with
 fake pointers (never dereferenced: the checks decide first, as in test_host_cpu.py) every listed entry gets past dispatch and its unlisted
 neighbours are refused with NIC_E_UNSUPPORTED."""
 import ctypes
@@ -9,7 +10,7 @@ import re
 import pytest
 import torch
 
-from tests.test_gpu_dispatch_matrix import (CAPI, FAMILIES, LAYOUTS, MODES, REFUSED, Cell, cp_list, enumerate_cells, geometry,
+from tests.test_gpu_dispatch_matrix import (FAMILIES, LAYOUTS, MODES, REFUSED, Cell, cp_list, enumerate_cells, geometry,
                                             ml_list)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,13 +28,13 @@ def lib():
 
 
 def _launched_modes(path: str, start: str):
-    """the MODE_* of the hipLaunchKernelGGL lines in the block of ``path`` that begins at the line matching ``start``"""
+    """the MODE_* of the hipLaunchKernelGGL lines of the function template of ``path`` that begins at the line matching ``start``"""
     with open(path) as f:
         lines = f.read().splitlines()
     i = next(k for k, ln in enumerate(lines) if re.search(start, ln))
     modes = set()
     for ln in lines[i + 1:]:
-        if re.match(r"\s*(#define|template <class|}\s*//\s*namespace)", ln):
+        if re.match(r"\s*(#define|template <|}\s*//\s*namespace)", ln):
             break
         if "hipLaunchKernelGGL" in ln:
             modes |= {MODE_NAMES[m] for m in re.findall(r"MODE_(\w+)", ln.split("hipLaunchKernelGGL", 1)[1])}
@@ -41,29 +42,34 @@ def _launched_modes(path: str, start: str):
 
 
 def test_lists_match_the_build_and_the_translation_units():
+    """the lists live in fused_capi.hip alone; every entry has an object in the build and a record in the dispatch table"""
     from neural_image_compression_v2_amd import _build, fused
     cp = cp_list()
     ml = ml_list()
     assert len(cp) == len(set(cp)) >= 15 and len(ml) == len(set(ml)) >= 7
-    built_cp = [tuple(int(v) for v in m.groups()) for m in (re.fullmatch(r"fused_qc_(\d+)_(\d+)_(\d+)\.hip", s) for s in _build.SOURCES) if m]
-    assert sorted(cp) == sorted(built_cp), "NIC_CP_LIST and the fused_qc_* translation units of _build.SOURCES differ"
-    assert [tuple(e) for e in _build.ML_LIST] == ml, "NIC_ML_LIST and _build.ML_LIST differ"
-    built_ml = [tuple(int(v) for v in m.groups()) for m in (re.fullmatch(r"fused_ml_(\d+)_(\d+)_(\d+)\.hip", s) for s in _build.SOURCES) if m]
-    assert sorted(built_ml) == sorted(ml)
+    objs = [o for _, o, _ in _build.units()]
+    assert len(objs) == len(set(objs))
+    for e in cp:
+        assert "fused_qc_{}_{}_{}.o".format(*e) in objs, e
+    for e in ml:
+        assert "fused_ml_{}_{}_{}.o".format(*e) in objs, e
     assert set(fused.ML_FUSED) == set(ml), "fused.ML_FUSED (MultiLevelField's choice of route) and NIC_ML_LIST differ"
-    for (a, b, c), fmt, macro in [(e, "fused_qc_{}_{}_{}.hip", "NIC_INSTANTIATE_Q16_CP") for e in cp] + [(e, "fused_ml_{}_{}_{}.hip", "NIC_INSTANTIATE_ML") for e in ml]:
-        path = os.path.join(CSRC, fmt.format(a, b, c))
-        assert os.path.exists(path), path
-        with open(path) as f:
-            src = f.read()
-        assert re.search(rf"^\s*{macro}\(\s*{a}\s*,\s*{b}\s*,\s*{c}\s*\)\s*$", src, re.M), f"{path} lacks {macro}({a}, {b}, {c})"
+    with open(os.path.join(CSRC, "fused_capi.hip")) as f:
+        capi = f.read()
+    # the table holds one record per list entry (q16_cp_kernels / ml_kernels, expanded from the lists)
+    assert re.search(r"#define X\(L, C, P\) q16_cp_kernels<L, C, P>\(\),\s*NIC_CP_LIST\(X\)", capi)
+    assert re.search(r"#define X\(LV, C, NL\) ml_kernels<LV, C, NL>\(\),\s*NIC_ML_LIST\(X\)", capi)
+    for name in os.listdir(CSRC):                            # no other copy of the lists
+        if name != "fused_capi.hip" and name.endswith((".h", ".hpp", ".hip")):
+            with open(os.path.join(CSRC, name)) as f:
+                assert not re.search(r"#define\s+NIC_(CP|ML)_LIST", f.read()), name
 
 
 def test_the_enumerator_covers_every_entry_in_every_instantiated_mode():
     cells = enumerate_cells()
     assert len(cells) == len(set(cells))
     q16_modes = _launched_modes(os.path.join(CSRC, "fused_q16_launch.hpp"), r"static int launch_q16_nl\(")
-    ml_modes = _launched_modes(os.path.join(CSRC, "fused_q16_launch.hpp"), r"#define NIC_INSTANTIATE_ML\(")
+    ml_modes = _launched_modes(os.path.join(CSRC, "fused_q16_launch.hpp"), r"static int launch_ml\(")
     assert q16_modes == set(MODES) and ml_modes == {"mse", "infer"}
     for layout, C, P in cp_list():
         for grid in ("fp32", "bf16", "fp16"):

@@ -3,8 +3,8 @@
 The dispatcher picks a kernel from the layout (2D triangular / sinusoidal, 3D method 3 / 4), the decoder depth, the arithmetic (fp32,
 split-bf16, plain bf16, plain fp16), the grid storage (fp32, bf16, fp16), the channel counts (NIC_CP_LIST) and the level count (NIC_ML_LIST),
 and every kernel has up to four modes: inference, MSE on a target tensor, MSE on the resident image, incoming dY.  ``enumerate_cells`` lists
-every reachable combination: the fixed families are written down once from the routing of ``fused_train`` / ``use_mlpn`` / ``use_t16``, the
-channel-count and multi-level entries are parsed from the lists in fused_capi.hip, so a new entry there is a new case here.  What the C side
+every reachable combination: the fixed families are written down once from the routing of ``select_kernel`` (fused_capi.hip), the
+channel-count and multi-level entries are read from the lists in csrc/fused_capi.hip, so a new entry there is a new case here.  What the C side
 refuses with NIC_E_UNSUPPORTED is listed in ``REFUSED`` (tests/test_dispatch_lists_cpu.py asserts both lists through the C ABI).
 
 Each cell runs one small case: several unaligned crops with ragged extents, one touching the far edge, in-kernel noise with a non-zero
@@ -16,7 +16,6 @@ gradient against the oracle driven by the same dY (fp16: at three magnitudes, ea
 import ctypes
 import functools
 import os
-import re
 from collections import namedtuple
 
 import numpy as np
@@ -24,7 +23,6 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CAPI = os.path.join(ROOT, "neural_image_compression_v2_amd", "csrc", "fused_capi.hip")
 
 # layout id of pick_layout (fused_capi.hip) -> dim, method, triangular PE
 LAYOUTS = {1: (2, 1, True), 2: (2, 1, False), 3: (3, 3, True), 4: (3, 4, False)}
@@ -70,29 +68,16 @@ REFUSED = [
 ]
 
 
-def _parse_list(name: str):
-    """the (a, b, c) entries of ``#define NAME(X) X(a, b, c) ...`` in fused_capi.hip, in order"""
-    with open(CAPI) as f:
-        lines = f.read().splitlines()
-    start = [i for i, ln in enumerate(lines) if re.match(rf"\s*#define\s+{name}\(X\)", ln)]
-    assert len(start) == 1, f"{name} is defined {len(start)} times in {CAPI}"
-    body, i = [], start[0]
-    while True:
-        body.append(lines[i])
-        if not lines[i].rstrip().endswith("\\"):
-            break
-        i += 1
-    return [tuple(int(v) for v in m) for m in re.findall(r"X\(\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)\s*\)", "\n".join(body))]
-
-
 def cp_list():
     """NIC_CP_LIST: (layout, C, P)"""
-    return _parse_list("NIC_CP_LIST")
+    from neural_image_compression_v2_amd import _build
+    return _build.instance_list("NIC_CP_LIST")
 
 
 def ml_list():
     """NIC_ML_LIST: (levels, C, n_linear)"""
-    return _parse_list("NIC_ML_LIST")
+    from neural_image_compression_v2_amd import _build
+    return _build.instance_list("NIC_ML_LIST")
 
 
 def enumerate_cells():

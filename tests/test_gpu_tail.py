@@ -500,3 +500,38 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(dev):
     assert legs["stripes"]["value"] == d["value"] and legs["replicated"]["all_reduce_bytes_per_step"] > 30e6
     assert "stripes" in d["config"]["parallelism"] and np.isfinite(d["config"]["final_loss"]) and d["config"]["final_loss"] > 0
     assert d["config"]["psnr_db_after_these_steps"] > 5.0                       # the assembled stripes decode to an image
+
+
+def test_refused_training_call_drops_the_parked_kernel_end_event(dev):
+    """nic_mark_kernel_end parks a one-shot event for the next training call.  A training call that returns early (here NIC_E_WORKSPACE) must drop
+    it, so the next, unrelated successful call does not record it and a (start, end) pair as bench.py's KernelEvents builds it stays unrecorded"""
+    from neural_image_compression_v2_amd import _lib, fused
+    lib, hip = _lib.load(), ctypes.CDLL("libamdhip64.so")
+    fp, _ = _pyramid(2, 64, 12, seed=5, no_mip=True)
+    g0, g1 = fp[0].to(dev), fp[1].to(dev)
+    params = [q.to(dev) for q in O.init_mlp(73, 64, generator=torch.Generator().manual_seed(6)).tensors()]
+    geo = fused.PathGeometry(dim=2, method=1, step_number=0.25, mip_level=0, extent=(32, 32), num_crops=1, split_bf16=True)
+    target = torch.rand(32 * 32, 3).to(dev)
+    ev = [ctypes.c_void_p(), ctypes.c_void_p()]
+    for e in ev:
+        assert hip.hipEventCreate(ctypes.byref(e)) == 0
+    try:
+        stream = torch.cuda.current_stream(dev)
+        assert hip.hipEventRecord(ev[0], ctypes.c_void_p(stream.cuda_stream)) == 0
+        assert lib.nic_mark_kernel_end(ev[1]) == 0
+        d = geo.to_desc(g0, g1)
+        m, gs = fused._mlp_struct(params), _lib.NicMlpGrads()
+        fake = ctypes.c_void_p(16)                             # never dereferenced: the workspace check refuses first
+        org = (ctypes.c_int32 * 2)(0, 0)                       # (host memory either way: read on the host with NIC_FLAG_ORIGINS_HOST)
+        rc = lib.nic_fused_forward_backward(ctypes.byref(d), _lib.ptr(g0), _lib.ptr(g1), org, ctypes.byref(m), None, fake, None, fake, fake, fake,
+                                            ctypes.byref(gs), fake, 16, _lib.stream_ptr(dev))
+        assert rc == -4                                        # NIC_E_WORKSPACE
+        fused.fused_forward_backward(geo, g0, g1, [(0, 0)], params, target)
+        torch.cuda.synchronize()
+        ms = ctypes.c_float()
+        assert hip.hipEventElapsedTime(ctypes.byref(ms), ev[0], ev[1]) != 0, "the parked end event was recorded by a later call"
+        hip.hipGetLastError()                                  # (the expected failure would otherwise be the next launch check's error)
+    finally:
+        lib.nic_mark_kernel_end(None)
+        for e in ev:
+            hip.hipEventDestroy(e)
