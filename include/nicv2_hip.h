@@ -512,6 +512,32 @@ int nic_hash_encode_u8(const nic_hash_desc *desc, int num_bits, const uint8_t *s
 int nic_hash_pack_u8(const nic_hash_desc *desc, int num_bits, const float *table, uint8_t *stored, void *stream);   /* [L, T, F] fp32 -> compact */
 int64_t nic_hash_stored_bytes(const nic_hash_desc *desc);   /* F * sum_l E_l, or a negative NIC_E_* code */
 
+/* ---- hash-grid encoding + decoder in ONE kernel (hashgrid.py, HashGridField(fused=True)).  Nothing new is computed: the
+ *      encoding is nic_hash_encode's (nic_hash_encode_noisy's with `quant`, nic_hash_encode_u8's from the compact table), the decoder is
+ *      ColorDecoder(levels * features, 64, 3) with the GELU / sigmoid of the other kernels in fp32 MFMA arithmetic, the loss is
+ *      mean((y - target)^2) * loss_scale over the [N, 3] outputs of the launch, the backward is straight-through into the table - but the
+ *      [N, L F] row and its gradient stay on the chip.  Supported: dim 2 / 3, features 1 / 2 / 4 / 8, levels * features <= 64, hidden 64,
+ *      3 Linear layers (mlp->n_linear 3 or 0); everything else is NIC_E_UNSUPPORTED, and every argument error is returned on the host before any
+ *      GPU work.  nic_hash_fused_supported answers for a (desc, hidden, n_linear) without pointers: NIC_OK or the code the entry points return.
+ *      nic_hash_fused_forward_backward: two launches, the fused kernel and the fixed-order reduction of its per-workgroup decoder-gradient
+ *      records (workspace >= nic_hash_fused_workspace_bytes, else NIC_E_WORKSPACE).  table_grad: d loss / d table is ADDED with fp32 atomics
+ *      (the caller zeroes it; order not fixed); null = frozen table, no scatter.  quant: null or noise_mode NIC_NOISE_NONE = no noise.
+ *      flags: NIC_HASH_FUSED_ADD_GRADS - the decoder gradients are added to what mlp_grads holds (the later chunks of a chunked pass), else
+ *      overwritten; NIC_HASH_FUSED_ADD_LOSS - the same for *loss.  y: null or [N, 3].  tail: null, or the optimiser step riding on the
+ *      reduction exactly as nic_path_desc.tail does (the first n_stream tensors streamed - the table -, the rest the decoder's, their .grad
+ *      the mlp_grads buffers of this call, else NIC_E_ARG; no device schedule).  Honours nic_mark_kernel_end like every training entry point. */
+#define NIC_HASH_FUSED_ADD_GRADS 1
+#define NIC_HASH_FUSED_ADD_LOSS 2
+int nic_hash_fused_supported(const nic_hash_desc *desc, int hidden, int n_linear);
+size_t nic_hash_fused_workspace_bytes(const nic_hash_desc *desc, const nic_mlp *mlp);   /* 0: unsupported */
+int nic_hash_fused_forward(const nic_hash_desc *desc, const float *table, const int32_t *origins, const nic_mlp *mlp, float *y, void *stream);
+int nic_hash_fused_forward_u8(const nic_hash_desc *desc, int num_bits, const uint8_t *stored, const int32_t *origins, const nic_mlp *mlp,
+                              float *y, void *stream);
+int nic_hash_fused_forward_backward(const nic_hash_desc *desc, const nic_hash_quant *quant, const float *table, const int32_t *origins,
+                                    const nic_mlp *mlp, const float *target, float loss_scale, float *table_grad,
+                                    const nic_mlp_grads *mlp_grads, float *loss, float *y, int flags, void *workspace, size_t workspace_bytes,
+                                    const nic_step_tail *tail, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -181,6 +181,9 @@ TailLaunch tail_for(int reduce_blocks) {
     else { r.tl.t.count = 0; r.tl.t.sched = nullptr; r.tl.n_stream = 0; r.tl.reduce_blocks = 0x7fffffff; r.blocks = (unsigned)reduce_blocks; }
     return r;
 }
+// the parked nic_mark_kernel_end event for the training entry points of other translation units (hash_fused.hip)
+void kernel_end_mark(hipStream_t s) { mark_kernel_end(s); }
+void kernel_end_drop() { g_kernel_end = nullptr; }
 }  // namespace nic
 namespace {
 

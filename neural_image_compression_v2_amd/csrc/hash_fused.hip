@@ -1,0 +1,768 @@
+// Hash-grid encoding + ColorDecoder(L F, 64, 3) in ONE kernel (include/nicv2_hip.h: nic_hash_fused_*; hashgrid.py, HashGridField(fused=True);
+// DESIGN 4.7.2).  The [N, L F] encoding row and its gradient never reach global memory: a wave gathers the rows of its patch into an LDS tile,
+// runs the decoder forward and backward on the fp32 matrix pipe (v_mfma_f32_32x32x2_f32: an exact fmaf chain, the arithmetic of the general
+// decoder the layer-wise route uses), leaves d loss / d row in the same tile and scatters it into the table gradient with the run sums of
+// hash_encode_backward_kernel.  Semantics are those of hash_grid.hip, whose helpers are restated here unchanged (that file is pinned).
+//
+//   one wave per patch of 8 x 8 (2D) / 4 x 4 x 4 (3D) samples, x the fastest lane axis (the row numbering of nic_hash_encode: the noise keys
+//   and the run sums carry over); 4 waves per workgroup, one workgroup per CU, persistent, each XCD walks one contiguous range of patches.
+//   MLP: a wave's 64 samples in two halves of 32 (nt).  Z^T[h][n] = sum_k W[h][k] A[n][k]: the hidden unit is the MFMA row, the sample the
+//   column, so register r of lane (j, half) holds unit rho = 32 t + (r & 3) + 8 (r >> 2) + 4 half of sample 32 nt + j - and that register IS
+//   the B operand of k-step (t, r) of the next product (the reduction index may be walked in any order); only the weights come from LDS.
+//   Weight gradients reduce over the samples, which sit in the lanes: dZ and A go through two 16-sample LDS tiles per wave ([n][unit]) and
+//   come back as operands; their accumulators stay in registers for the whole launch and leave as one record per workgroup (summed over the
+//   four waves in wave order through LDS), which hash_fused_reduce_kernel adds up in a fixed order - with the optimiser tail riding on it.
+#include "nic_device.hpp"
+#include "nic_adam.hpp"
+
+namespace nic {
+namespace hfused {
+
+// ---- restated from hash_grid.hip ------------------------------------------------------------------------------------------------------
+__host__ __device__ inline bool hash_level_dense(int dim, int32_t R, int log2_table) {
+    uint64_t p = 1;
+    for (int a = 0; a < dim; ++a) {
+        p *= (uint64_t)R + 1;
+        if (p > (1ull << log2_table)) return false;
+    }
+    return true;
+}
+__host__ __device__ inline uint32_t hash_index(bool dense, uint32_t R, uint32_t mask, uint32_t vx, uint32_t vy, uint32_t vz) {
+    const uint32_t h = dense ? vx + (R + 1u) * (vy + (R + 1u) * vz) : (vx ^ (vy * 2654435761u) ^ (vz * 805459861u));
+    return h & mask;
+}
+__host__ __device__ inline int64_t hash_level_entries(int dim, int32_t R, int log2_table) {
+    if (!hash_level_dense(dim, R, log2_table)) return int64_t(1) << log2_table;
+    int64_t e = 1;
+    for (int a = 0; a < dim; ++a) e *= (int64_t)R + 1;
+    return e;
+}
+template <int F>
+__device__ __forceinline__ void load_row(const float* p, float (&v)[F]) {
+    if constexpr (F == 1) {
+        v[0] = *p;
+    } else if constexpr (F == 2) {
+        const float2 a = *reinterpret_cast<const float2*>(p);
+        v[0] = a.x; v[1] = a.y;
+    } else {
+#pragma unroll
+        for (int k = 0; k < F; k += 4) {
+            const float4 a = *reinterpret_cast<const float4*>(p + k);
+            v[k] = a.x; v[k + 1] = a.y; v[k + 2] = a.z; v[k + 3] = a.w;
+        }
+    }
+}
+template <int F>
+__device__ __forceinline__ void load_row_u8(const uint8_t* p, float scale, float bias, float (&v)[F]) {
+    uint32_t w[(F + 3) / 4];
+    if constexpr (F == 1) {
+        w[0] = *p;
+    } else if constexpr (F == 2) {
+        w[0] = *reinterpret_cast<const uint16_t*>(p);
+    } else if constexpr (F == 4) {
+        w[0] = *reinterpret_cast<const uint32_t*>(p);
+    } else {
+        const uint2 a = *reinterpret_cast<const uint2*>(p);
+        w[0] = a.x; w[1] = a.y;
+    }
+#pragma unroll
+    for (int f = 0; f < F; ++f) {
+        const float u = (float)((w[f >> 2] >> (8 * (f & 3))) & 0xFFu);
+        v[f] = __fdiv_rn(__fadd_rn(__fsub_rn(u, bias), 1.0f), scale);
+    }
+}
+template <int D>
+struct PatchSample {
+    int crop;
+    int idx[3];
+    bool live;
+    int64_t n;
+};
+template <int D>
+__device__ __forceinline__ PatchSample<D> patch_sample(const nic_hash_desc& d, int64_t wv, int64_t n_patches, int lane) {
+    constexpr int PS = D == 2 ? 8 : 4;
+    const int np1 = (d.extent[1] + PS - 1) / PS, np2 = D == 3 ? (d.extent[2] + PS - 1) / PS : 1;
+    const int64_t per_crop = (int64_t)((d.extent[0] + PS - 1) / PS) * np1 * np2;
+    const int64_t wc = wv < n_patches ? wv : n_patches - 1;
+    PatchSample<D> s;
+    s.crop = (int)(wc / per_crop);
+    int64_t pr = wc - (int64_t)s.crop * per_crop;
+    int pt[3] = {0, 0, 0};
+    if (D == 3) { pt[2] = (int)(pr % np2); pr /= np2; }
+    pt[1] = (int)(pr % np1);
+    pt[0] = (int)(pr / np1);
+    if (D == 2) {
+        s.idx[0] = PS * pt[0] + (lane & 7);
+        s.idx[1] = PS * pt[1] + (lane >> 3);
+        s.idx[2] = 0;
+    } else {
+        s.idx[0] = PS * pt[0] + (lane & 3);
+        s.idx[1] = PS * pt[1] + ((lane >> 2) & 3);
+        s.idx[2] = PS * pt[2] + (lane >> 4);
+    }
+    s.live = wv < n_patches;
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        s.live = s.live && s.idx[a] < d.extent[a];
+        s.idx[a] = s.idx[a] < d.extent[a] ? s.idx[a] : d.extent[a] - 1;
+    }
+    const int64_t n_per_crop = (int64_t)d.extent[0] * d.extent[1] * (D == 3 ? d.extent[2] : 1);
+    s.n = (int64_t)s.crop * n_per_crop + ((int64_t)s.idx[0] * d.extent[1] + s.idx[1]) * (D == 3 ? d.extent[2] : 1) + (D == 3 ? s.idx[2] : 0);
+    return s;
+}
+template <int D>
+__device__ __forceinline__ void level_cell(const uint32_t (&i)[3], uint32_t R, uint32_t S2, uint32_t (&v)[3], float (&w)[3]) {
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        const uint32_t q = (2u * i[a] + 1u) * R;
+        v[a] = q / S2;
+        w[a] = (float)(q - v[a] * S2) / (float)S2;
+    }
+    if (D == 2) { v[2] = 0; w[2] = 0.f; }
+}
+template <int D>
+__device__ __forceinline__ float corner_weight(const float (&w)[3], int c) {
+    float r = ((c & 1) ? w[0] : 1.0f - w[0]) * ((c & 2) ? w[1] : 1.0f - w[1]);
+    if (D == 3) r *= (c & 4) ? w[2] : 1.0f - w[2];
+    return r;
+}
+// ---- end of the restated helpers ------------------------------------------------------------------------------------------------------
+
+constexpr int XS = kH + 1;      // row stride of every LDS tile: lanes that walk rows hit 64 different banks
+constexpr int NQ = 16;          // samples per weight-gradient pass (the two transposed tiles of a wave)
+enum { HF_FWD = 0, HF_FWD_U8 = 1, HF_TRAIN = 2 };
+
+struct FParams {
+    nic_hash_desc d;
+    const float* table;
+    const uint8_t* stored;
+    const int32_t* origins;
+    const float *w1, *b1, *w2, *b2, *w3, *b3;
+    const float* target;
+    float* y;
+    float* grad;              // table gradient (null: frozen table, no scatter)
+    float* partials;          // one record per workgroup
+    NoiseSrc noise;           // mode NIC_NOISE_NONE / NIC_NOISE_KERNEL
+    uint64_t sample_base;
+    float q_scale, q_bias;
+    float dscale;             // 2 loss_scale / (3 N)
+    int64_t n_patches;
+};
+
+// the record of a workgroup, nn.Linear layouts back to back: dW1 [64, L F] | db1 | dW2 [64, 64] | db2 | dW3 [3, 64] | db3 | sum of squared errors
+struct RecLayout {
+    int w1, b1, w2, b2, w3, b3, loss, rec;
+    __host__ __device__ explicit RecLayout(int lf) {
+        w1 = 0; b1 = kH * lf; w2 = b1 + kH; b2 = w2 + kH * kH; w3 = b2 + kH; b3 = w3 + 3 * kH; loss = b3 + 3; rec = loss + 1;
+    }
+};
+
+struct Smem {
+    float w1[kH * XS], w2[kH * XS], w3[4 * kH], b1[kH], b2[kH], b3[4];
+    float x[4][kH * XS];        // per wave: the encoding rows [sample][column], later d loss / d row; at the end of the launch the workgroup's record
+    float p[4][NQ * XS], q[4][NQ * XS];
+};
+
+// LDS traffic between the lanes of ONE wave: its LDS instructions execute in order, the compiler must not move them across
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ int row_of(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+
+// integer sample coordinate per axis, clamped into the field
+template <int D>
+__device__ __forceinline__ void sample_coords(const FParams& p, const PatchSample<D>& s, uint32_t (&i)[3]) {
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        const int c = p.origins[s.crop * D + a] + s.idx[a];
+        i[a] = (uint32_t)(c < 0 ? 0 : (c >= p.d.S_max ? p.d.S_max - 1 : c));
+    }
+    if (D == 2) i[2] = 0;
+}
+
+// the level loop of hash_encode_kernel with the row going to LDS
+template <int D, int F, int MODE>
+__device__ __forceinline__ void encode_row(const FParams& p, const PatchSample<D>& s, const uint32_t (&i)[3], float* xrow) {
+    const nic_hash_desc& d = p.d;
+    const uint32_t S2 = 2u * (uint32_t)d.S_max, mask = (1u << d.log2_table) - 1u;
+    [[maybe_unused]] int64_t lev_off = 0;
+    [[maybe_unused]] U4 nblk{0u, 0u, 0u, 0u};
+    [[maybe_unused]] const bool noisy = MODE == HF_TRAIN && p.noise.mode == NIC_NOISE_KERNEL;
+#pragma unroll 2
+    for (int l = 0; l < d.levels; ++l) {
+        const uint32_t R = (uint32_t)d.resolution[l];
+        const bool dense = hash_level_dense(D, (int32_t)R, d.log2_table);
+        const float* tab = p.table + ((int64_t)l << d.log2_table) * F;
+        [[maybe_unused]] const uint8_t* stab = nullptr;
+        if constexpr (MODE == HF_FWD_U8) {
+            stab = p.stored + lev_off;
+            lev_off += (int64_t)F * hash_level_entries(D, (int32_t)R, d.log2_table);
+        }
+        uint32_t v[3];
+        float w[3];
+        level_cell<D>(i, R, S2, v, w);
+        float acc[F];
+#pragma unroll
+        for (int f = 0; f < F; ++f) acc[f] = 0.f;
+#pragma unroll
+        for (int c = 0; c < (1 << D); ++c) {
+            const uint32_t e = hash_index(dense, R, mask, v[0] + (c & 1), v[1] + ((c >> 1) & 1), D == 3 ? v[2] + ((c >> 2) & 1) : 0u);
+            float t[F];
+            if constexpr (MODE == HF_FWD_U8) load_row_u8<F>(stab + (int64_t)e * F, p.q_scale, p.q_bias, t);
+            else load_row<F>(tab + (int64_t)e * F, t);
+            const float cw = corner_weight<D>(w, c);
+#pragma unroll
+            for (int f = 0; f < F; ++f) acc[f] += cw * t[f];
+        }
+        if constexpr (MODE == HF_TRAIN) {
+            if (noisy) {
+                const int c0 = l * F;
+                if ((c0 & 15) == 0) nblk = noise_block(p.noise, p.sample_base + (uint64_t)s.n, c0 >> 4);
+#pragma unroll
+                for (int f = 0; f < F; ++f) acc[f] += noise_from_block(p.noise, nblk, (c0 + f) & 15);
+            }
+        }
+#pragma unroll
+        for (int f = 0; f < F; ++f) xrow[l * F + f] = acc[f];
+    }
+}
+
+// the level loop of hash_encode_backward_kernel with d loss / d row coming from LDS
+template <int D, int F>
+__device__ __forceinline__ void scatter_row(const FParams& p, const PatchSample<D>& s, const uint32_t (&i)[3], const float* xrow, int lane) {
+    const nic_hash_desc& d = p.d;
+    const uint32_t S2 = 2u * (uint32_t)d.S_max, mask = (1u << d.log2_table) - 1u;
+    for (int l = 0; l < d.levels; ++l) {
+        const uint32_t R = (uint32_t)d.resolution[l];
+        const bool dense = hash_level_dense(D, (int32_t)R, d.log2_table);
+        float* gtab = p.grad + ((int64_t)l << d.log2_table) * F;
+        uint32_t v[3];
+        float w[3];
+        level_cell<D>(i, R, S2, v, w);
+        float g[F];
+#pragma unroll
+        for (int f = 0; f < F; ++f) g[f] = s.live ? xrow[l * F + f] : 0.f;
+        const int64_t key = (int64_t)v[0] + ((int64_t)R + 1) * ((int64_t)v[1] + ((int64_t)R + 1) * (int64_t)v[2]);
+        const RunMasks m = run_masks(s.live ? key : -1 - (int64_t)lane, lane);
+        const bool issue = s.live && m.head;
+#pragma unroll
+        for (int c = 0; c < (1 << D); ++c) {
+            const uint32_t e = hash_index(dense, R, mask, v[0] + (c & 1), v[1] + ((c >> 1) & 1), D == 3 ? v[2] + ((c >> 2) & 1) : 0u);
+            const float cw = corner_weight<D>(w, c);
+#pragma unroll
+            for (int f = 0; f < F; ++f) {
+                float val = cw * g[f];
+                if (m.any_shared) val = run_sum(val, m);
+                if (issue) atomicAdd(gtab + (int64_t)e * F + f, val);
+            }
+        }
+    }
+}
+
+// acc[ta][tb] += sum over the NQ samples of a pass of P[n][32 ta + i] Q[n][32 tb + j]   (MASK4: P has 4 columns, one row tile)
+// side[ta] += every P operand of this lane: the bias gradient (column sums of dZ) of unit 32 ta + i over the samples of this half's parity
+template <int TA, int TB, bool MASK4>
+__device__ __forceinline__ void wgrad_mfma(const float* P, const float* Q, int j, int half, f32x16 (&acc)[TA][TB], float (&side)[TA]) {
+#pragma unroll
+    for (int s = 0; s < NQ / 2; ++s) {
+        float a[TA], b[TB];
+#pragma unroll
+        for (int ta = 0; ta < TA; ++ta) a[ta] = MASK4 ? (j < 4 ? P[(2 * s + half) * XS + j] : 0.f) : P[(2 * s + half) * XS + 32 * ta + j];
+#pragma unroll
+        for (int tb = 0; tb < TB; ++tb) b[tb] = Q[(2 * s + half) * XS + 32 * tb + j];
+#pragma unroll
+        for (int ta = 0; ta < TA; ++ta) {
+            side[ta] += a[ta];
+#pragma unroll
+            for (int tb = 0; tb < TB; ++tb) acc[ta][tb] = mfma(a[ta], b[tb], acc[ta][tb]);
+        }
+    }
+}
+// the [unit] values of this lane's sample -> row (j & 15) of a transposed tile
+template <int T>
+__device__ __forceinline__ void put_tile(float* P, int j, int half, const f32x16 (&u)[T]) {
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) P[(j & 15) * XS + 32 * t + row_of(r, half)] = u[t][r];
+}
+__device__ __forceinline__ float half_sum(float v) {      // over the 32 lanes of this lane's half, fixed order
+#pragma unroll
+    for (int m = 1; m < 32; m <<= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+template <int D, int F, int KT, int MODE>
+__global__ void __launch_bounds__(256) hash_fused_kernel(const FParams p) {
+    __shared__ Smem sm;
+    constexpr bool TRAIN = MODE == HF_TRAIN;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 31, half = lane >> 5;
+    const int LF = p.d.levels * F;
+    for (int e = tid; e < kH * XS; e += 256) {
+        const int h = e / XS, k = e - h * XS;
+        sm.w1[e] = k < LF ? p.w1[h * LF + k] : 0.f;
+        sm.w2[e] = k < kH ? p.w2[h * kH + k] : 0.f;
+    }
+    sm.w3[tid] = tid < 3 * kH ? p.w3[tid] : 0.f;
+    if (tid < kH) { sm.b1[tid] = p.b1[tid]; sm.b2[tid] = p.b2[tid]; }
+    if (tid < 4) sm.b3[tid] = tid < 3 ? p.b3[tid] : 0.f;
+    float* xs = sm.x[wave];
+    for (int e = lane; e < kH * XS; e += 64) xs[e] = 0.f;       // the columns past L F stay finite (their weights are zero)
+    __syncthreads();
+    float* xrow = xs + lane * XS;
+    [[maybe_unused]] float* P = sm.p[wave];
+    [[maybe_unused]] float* Q = sm.q[wave];
+
+    [[maybe_unused]] f32x16 gW1[2][KT], gW2[2][2], gW3[1][2];
+    [[maybe_unused]] float gb1[2] = {0.f, 0.f}, gb2[2] = {0.f, 0.f}, gb3[1] = {0.f}, sse = 0.f;
+    if constexpr (TRAIN) {
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+#pragma unroll
+            for (int b = 0; b < KT; ++b) gW1[a][b] = f32x16{};
+            gW2[a][0] = f32x16{}; gW2[a][1] = f32x16{};
+            gW3[0][a] = f32x16{};
+        }
+    }
+
+    // each XCD (blocks b, b + 8, ..) walks one contiguous range of groups of 4 patches
+    const int xcd = blockIdx.x & 7, nb8 = gridDim.x >> 3;
+    const int64_t n_groups = (p.n_patches + 3) >> 2, chunk = (n_groups + 7) >> 3;
+    const int64_t g_begin = xcd * chunk, g_end = g_begin + chunk < n_groups ? g_begin + chunk : n_groups;
+    const int ks1 = (LF + 1) >> 1;
+    for (int64_t g = g_begin + (blockIdx.x >> 3); g < g_end; g += nb8) {
+        const int64_t wv = 4 * g + wave;
+        if (wv >= p.n_patches) continue;                        // wave-uniform; nothing below synchronises the workgroup
+        const PatchSample<D> s = patch_sample<D>(p.d, wv, p.n_patches, lane);
+        uint32_t ci[3];
+        sample_coords<D>(p, s, ci);
+        encode_row<D, F, MODE>(p, s, ci, xrow);
+        wave_sync();
+        const unsigned long long live_mask = __ballot(s.live);
+#pragma unroll 1
+        for (int nt = 0; nt < 2; ++nt) {
+            const int src = 32 * nt + j;
+            const bool live = (live_mask >> src) & 1ull;
+            const int64_t n = (int64_t)(uint32_t)__shfl((int)(uint32_t)s.n, src) | ((int64_t)__shfl((int)(s.n >> 32), src) << 32);
+            const float* xb = xs + src * XS;
+            // ---- layer 1
+            f32x16 a1[2] = {f32x16{}, f32x16{}};
+            [[maybe_unused]] f32x16 d1[2];
+            for (int k = 0; k < ks1; ++k) {
+                const float b = xb[2 * k + half];
+                a1[0] = mfma(sm.w1[j * XS + 2 * k + half], b, a1[0]);
+                a1[1] = mfma(sm.w1[(32 + j) * XS + 2 * k + half], b, a1[1]);
+            }
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    float av, dv;
+                    gelu_and_grad(a1[t][r] + sm.b1[32 * t + row_of(r, half)], av, dv);
+                    a1[t][r] = av;
+                    if constexpr (TRAIN) d1[t][r] = dv;
+                }
+            // ---- layer 2
+            f32x16 a2[2] = {f32x16{}, f32x16{}};
+            [[maybe_unused]] f32x16 d2[2];
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int k = 32 * t + row_of(r, half);
+                    a2[0] = mfma(sm.w2[j * XS + k], a1[t][r], a2[0]);
+                    a2[1] = mfma(sm.w2[(32 + j) * XS + k], a1[t][r], a2[1]);
+                }
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    float av, dv;
+                    gelu_and_grad(a2[t][r] + sm.b2[32 * t + row_of(r, half)], av, dv);
+                    a2[t][r] = av;
+                    if constexpr (TRAIN) d2[t][r] = dv;
+                }
+            // ---- output layer: rows 0 .. 2 of one tile (registers 0 .. 2 of half 0)
+            f32x16 z3 = f32x16{};
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int k = 32 * t + row_of(r, half);
+                    z3 = mfma(j < 3 ? sm.w3[j * kH + k] : 0.f, a2[t][r], z3);
+                }
+            float yv[3];
+#pragma unroll
+            for (int o = 0; o < 3; ++o) yv[o] = sigmoid_f(z3[o] + sm.b3[o]);
+            const bool mine = half == 0 && live;
+            if (mine && p.y != nullptr) {
+#pragma unroll
+                for (int o = 0; o < 3; ++o) p.y[n * 3 + o] = yv[o];
+            }
+            if constexpr (TRAIN) {
+                // ---- dZ3 = dy y (1 - y), dy = 2 (y - t) loss_scale / (3 N)
+                float dz3[4] = {0.f, 0.f, 0.f, 0.f};
+                if (mine) {
+#pragma unroll
+                    for (int o = 0; o < 3; ++o) {
+                        const float e = yv[o] - p.target[n * 3 + o];
+                        sse += e * e;
+                        dz3[o] = p.dscale * e * yv[o] * (1.0f - yv[o]);
+                    }
+                }
+                // dW3 [o][h] += dZ3^T A2
+#pragma unroll 1
+                for (int q = 0; q < 2; ++q) {
+                    if ((j >> 4) == q) {
+                        put_tile<2>(Q, j, half, a2);
+                        if (half == 0) {
+#pragma unroll
+                            for (int o = 0; o < 4; ++o) P[(j & 15) * XS + o] = dz3[o];
+                        }
+                    }
+                    wave_sync();
+                    wgrad_mfma<1, 2, true>(P, Q, j, half, gW3, gb3);
+                    wave_sync();
+                }
+                // dA2 = W3^T dZ3 (k-steps: o = s of half 0; half 1 carries zeros), dZ2 = dA2 gelu'
+                f32x16 dz2[2] = {f32x16{}, f32x16{}};
+#pragma unroll
+                for (int o = 0; o < 3; ++o) {
+                    const float b = half == 0 ? dz3[o] : 0.f;
+                    dz2[0] = mfma(half == 0 ? sm.w3[o * kH + j] : 0.f, b, dz2[0]);
+                    dz2[1] = mfma(half == 0 ? sm.w3[o * kH + 32 + j] : 0.f, b, dz2[1]);
+                }
+#pragma unroll
+                for (int t = 0; t < 2; ++t) dz2[t] *= d2[t];
+                // dW2 [h2][h] += dZ2^T A1
+#pragma unroll 1
+                for (int q = 0; q < 2; ++q) {
+                    if ((j >> 4) == q) {
+                        put_tile<2>(P, j, half, dz2);
+                        put_tile<2>(Q, j, half, a1);
+                    }
+                    wave_sync();
+                    wgrad_mfma<2, 2, false>(P, Q, j, half, gW2, gb2);
+                    wave_sync();
+                }
+                // dA1 = W2^T dZ2, dZ1 = dA1 gelu'
+                f32x16 dz1[2] = {f32x16{}, f32x16{}};
+#pragma unroll
+                for (int t = 0; t < 2; ++t)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int k = 32 * t + row_of(r, half);
+                        dz1[0] = mfma(sm.w2[k * XS + j], dz2[t][r], dz1[0]);
+                        dz1[1] = mfma(sm.w2[k * XS + 32 + j], dz2[t][r], dz1[1]);
+                    }
+#pragma unroll
+                for (int t = 0; t < 2; ++t) dz1[t] *= d1[t];
+                // dW1 [h][k] += dZ1^T X (X: the rows of this half, in place)
+#pragma unroll 1
+                for (int q = 0; q < 2; ++q) {
+                    if ((j >> 4) == q) put_tile<2>(P, j, half, dz1);
+                    wave_sync();
+                    wgrad_mfma<2, KT, false>(P, xs + (32 * nt + 16 * q) * XS, j, half, gW1, gb1);
+                    wave_sync();
+                }
+                // dX = W1^T dZ1 over the rows of this half (their X is spent)
+                if (p.grad != nullptr) {
+                    f32x16 dx[KT];
+#pragma unroll
+                    for (int kt = 0; kt < KT; ++kt) dx[kt] = f32x16{};
+#pragma unroll
+                    for (int t = 0; t < 2; ++t)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const int h = 32 * t + row_of(r, half);
+#pragma unroll
+                            for (int kt = 0; kt < KT; ++kt) dx[kt] = mfma(sm.w1[h * XS + 32 * kt + j], dz1[t][r], dx[kt]);
+                        }
+                    float* xw = xs + src * XS;
+#pragma unroll
+                    for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) xw[32 * kt + row_of(r, half)] = dx[kt][r];
+                }
+            }
+        }
+        if constexpr (TRAIN) {
+            wave_sync();
+            if (p.grad != nullptr) scatter_row<D, F>(p, s, ci, xrow, lane);
+            wave_sync();
+        } else {
+            wave_sync();
+        }
+    }
+
+    if constexpr (TRAIN) {
+        // ---- the workgroup's record: the four waves add their accumulators in wave order into the (now free) row tiles
+        const RecLayout rl(LF);
+        float* R = &sm.x[0][0];
+        __syncthreads();
+        for (int w = 0; w < 4; ++w) {
+            if (wave == w) {
+                const bool first = w == 0;
+                auto put = [&](int at, float v) { R[at] = first ? v : R[at] + v; };
+#pragma unroll
+                for (int ta = 0; ta < 2; ++ta)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int h = 32 * ta + row_of(r, half);
+#pragma unroll
+                        for (int tb = 0; tb < KT; ++tb)
+                            if (32 * tb + j < LF) put(rl.w1 + h * LF + 32 * tb + j, gW1[ta][tb][r]);
+#pragma unroll
+                        for (int tb = 0; tb < 2; ++tb) put(rl.w2 + h * kH + 32 * tb + j, gW2[ta][tb][r]);
+                    }
+#pragma unroll
+                for (int ta = 0; ta < 2; ++ta) {                 // lane (i, half) summed the samples of parity `half`
+                    const float s1 = gb1[ta] + __shfl_xor(gb1[ta], 32), s2 = gb2[ta] + __shfl_xor(gb2[ta], 32);
+                    if (half == 0) { put(rl.b1 + 32 * ta + j, s1); put(rl.b2 + 32 * ta + j, s2); }
+                }
+                const float s3 = gb3[0] + __shfl_xor(gb3[0], 32);
+                if (lane < 3) put(rl.b3 + lane, s3);
+#pragma unroll
+                for (int o = 0; o < 3; ++o) {
+                    if (half == 0) { put(rl.w3 + o * kH + j, gW3[0][0][o]); put(rl.w3 + o * kH + 32 + j, gW3[0][1][o]); }
+                }
+                const float sl = half_sum(sse);
+                if (lane == 0) put(rl.loss, sl);
+            }
+            __syncthreads();
+        }
+        float* rec = p.partials + (int64_t)blockIdx.x * rl.rec;
+        for (int e = tid; e < rl.rec; e += 256) rec[e] = R[e];
+    }
+}
+
+// Fixed-order sum of the records: a block = 32 outputs x 8 slices of the record list, the slices combined through LDS in slice order
+// (reduce_partials_kernel's shape).  add_grads / add_loss: the result is added to what the buffers hold (a chunked pass).
+__global__ void __launch_bounds__(256) hash_fused_reduce_kernel(const float* partials, int n_rec, int lf, nic_mlp_grads g, float* loss, float loss_mul,
+                                                                int add_grads, int add_loss, const StepTail tl) {
+    if (tail_block(tl)) return;
+    __shared__ float red[8][32];
+    const RecLayout rl(lf);
+    const int slice = threadIdx.x >> 5, e = blockIdx.x * 32 + (threadIdx.x & 31);
+    float part[4] = {0.f, 0.f, 0.f, 0.f};
+    const int per = (n_rec + 7) >> 3, w_lo = slice * per, w_hi = w_lo + per < n_rec ? w_lo + per : n_rec;
+    if (e < rl.rec) {
+        const float* src = partials + e;
+        int w = w_lo;
+        for (; w + 4 <= w_hi; w += 4) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) part[k] += src[(int64_t)(w + k) * rl.rec];
+        }
+        for (; w < w_hi; ++w) part[0] += src[(int64_t)w * rl.rec];
+    }
+    red[slice][threadIdx.x & 31] = (part[0] + part[1]) + (part[2] + part[3]);
+    __syncthreads();
+    if (slice != 0 || e >= rl.rec) return;
+    float acc = red[0][threadIdx.x];
+#pragma unroll
+    for (int k = 1; k < 8; ++k) acc += red[k][threadIdx.x];
+    if (e == rl.loss) {
+        if (loss) *loss = add_loss ? *loss + acc * loss_mul : acc * loss_mul;
+        return;
+    }
+    float* dst = e < rl.b1 ? (g.w[0] ? g.w[0] + e : nullptr) : e < rl.w2 ? (g.b[0] ? g.b[0] + (e - rl.b1) : nullptr)
+               : e < rl.b2 ? (g.w[1] ? g.w[1] + (e - rl.w2) : nullptr) : e < rl.w3 ? (g.b[1] ? g.b[1] + (e - rl.b2) : nullptr)
+               : e < rl.b3 ? (g.w[2] ? g.w[2] + (e - rl.w3) : nullptr) : (g.b[2] ? g.b[2] + (e - rl.b3) : nullptr);
+    if (!dst) return;
+    if (add_grads) acc += *dst;
+    if (tl.t.count > 0) tail_store(tl, dst, acc);
+    else *dst = acc;
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------------
+static int device_cus() {
+    static int n = 0;
+    if (n == 0) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
+        else n = 256;
+    }
+    return n;
+}
+// workgroups a launch may use: one per CU, a multiple of 8 (one slice of the patch range per XCD)
+static int wg_cap() {
+    const int c = device_cus() / 8 * 8;
+    return c < 8 ? 8 : c;
+}
+static int64_t count_patches(const nic_hash_desc* d) {
+    const int PS = d->dim == 2 ? 8 : 4;
+    int64_t patches = d->num_crops;
+    for (int a = 0; a < d->dim; ++a) patches *= (d->extent[a] + PS - 1) / PS;
+    return patches;
+}
+static int grid_of(int64_t patches) {
+    const int64_t groups = (patches + 3) / 4, want = (groups + 7) / 8 * 8;
+    return (int)(want < wg_cap() ? want : wg_cap());
+}
+
+static int check_desc(const nic_hash_desc* d) {       // check_hash_desc of hash_grid.hip
+    if (!d) return NIC_E_NULL;
+    if (d->dim != 2 && d->dim != 3) return NIC_E_UNSUPPORTED;
+    if (d->features != 1 && d->features != 2 && d->features != 4 && d->features != 8) return NIC_E_UNSUPPORTED;
+    if (d->levels < 1 || d->levels > NIC_HASH_MAX_LEVELS) return NIC_E_ARG;
+    if (d->log2_table < 10 || d->log2_table > 24) return NIC_E_ARG;
+    if (d->S_max < 1 || d->flags != 0) return NIC_E_ARG;
+    for (int l = 0; l < d->levels; ++l)
+        if (d->resolution[l] < 1 || 2 * (int64_t)d->S_max * d->resolution[l] >= (int64_t(1) << 31)) return NIC_E_ARG;
+    if (d->num_crops < 1) return NIC_E_SHAPE;
+    for (int a = 0; a < d->dim; ++a)
+        if (d->extent[a] < 1 || d->extent[a] > d->S_max) return NIC_E_SHAPE;
+    return NIC_OK;
+}
+// the supported set, the only copy: dim 2 / 3, F in {1, 2, 4, 8}, L F <= 64, hidden 64, 3 Linear layers
+static int supported(const nic_hash_desc* d, int hidden, int n_linear) {
+    const int rc = check_desc(d);
+    if (rc) return rc;
+    if (d->levels * d->features > kH) return NIC_E_UNSUPPORTED;
+    if (hidden != kH || (n_linear != 3 && n_linear != 0)) return NIC_E_UNSUPPORTED;
+    return NIC_OK;
+}
+static bool mlp3_ok(const nic_mlp* m) {
+    for (int i = 0; i < 3; ++i)
+        if (!m->w[i] || !m->b[i]) return false;
+    return true;
+}
+
+template <int MODE, int D, int F>
+static void launch_kt(const FParams& p, int grid, hipStream_t s) {
+    if (p.d.levels * F > 32) hipLaunchKernelGGL((hash_fused_kernel<D, F, 2, MODE>), dim3(grid), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((hash_fused_kernel<D, F, 1, MODE>), dim3(grid), dim3(256), 0, s, p);
+}
+template <int MODE, int D>
+static void launch_f(const FParams& p, int grid, hipStream_t s) {
+    switch (p.d.features) {
+        case 1: launch_kt<MODE, D, 1>(p, grid, s); break;
+        case 2: launch_kt<MODE, D, 2>(p, grid, s); break;
+        case 4: launch_kt<MODE, D, 4>(p, grid, s); break;
+        default: launch_kt<MODE, D, 8>(p, grid, s); break;
+    }
+}
+template <int MODE>
+static int launch(const FParams& p, int grid, void* stream) {
+    if (p.d.dim == 2) launch_f<MODE, 2>(p, grid, (hipStream_t)stream);
+    else launch_f<MODE, 3>(p, grid, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+
+static void fill_common(FParams& p, const nic_hash_desc* d, const int32_t* origins, const nic_mlp* mlp, float* y) {
+    p.d = *d; p.origins = origins; p.y = y;
+    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
+    p.n_patches = count_patches(d);
+    p.noise.mode = NIC_NOISE_NONE;
+}
+
+struct KernelEndDrop {        // a training entry point consumes the parked nic_mark_kernel_end event on every return
+    ~KernelEndDrop() { kernel_end_drop(); }
+};
+
+}  // namespace hfused
+}  // namespace nic
+
+using namespace nic;
+using namespace nic::hfused;
+
+extern "C" {
+
+int nic_hash_fused_supported(const nic_hash_desc* desc, int hidden, int n_linear) { return supported(desc, hidden, n_linear); }
+
+size_t nic_hash_fused_workspace_bytes(const nic_hash_desc* desc, const nic_mlp* mlp) {
+    if (!desc || !mlp || supported(desc, kH, mlp->n_linear) != NIC_OK) return 0;
+    return (size_t)wg_cap() * RecLayout(desc->levels * desc->features).rec * sizeof(float);
+}
+
+int nic_hash_fused_forward(const nic_hash_desc* desc, const float* table, const int32_t* origins, const nic_mlp* mlp, float* y, void* stream) {
+    if (!desc || !mlp) return NIC_E_NULL;
+    const int rc = supported(desc, kH, mlp->n_linear);
+    if (rc) return rc;
+    if (!table || !origins || !mlp3_ok(mlp) || !y) return NIC_E_NULL;
+    FParams p{};
+    fill_common(p, desc, origins, mlp, y);
+    p.table = table;
+    return launch<HF_FWD>(p, grid_of(p.n_patches), stream);
+}
+
+int nic_hash_fused_forward_u8(const nic_hash_desc* desc, int num_bits, const uint8_t* stored, const int32_t* origins, const nic_mlp* mlp, float* y,
+                              void* stream) {
+    if (!desc || !mlp) return NIC_E_NULL;
+    const int rc = supported(desc, kH, mlp->n_linear);
+    if (rc) return rc;
+    if (!stored || !origins || !mlp3_ok(mlp) || !y) return NIC_E_NULL;
+    if (num_bits < 1 || num_bits > 8) return NIC_E_ARG;
+    FParams p{};
+    fill_common(p, desc, origins, mlp, y);
+    p.stored = stored;
+    p.q_scale = (float)((1 << num_bits) - 1);
+    p.q_bias = (float)(1 << (num_bits - 1));
+    return launch<HF_FWD_U8>(p, grid_of(p.n_patches), stream);
+}
+
+int nic_hash_fused_forward_backward(const nic_hash_desc* desc, const nic_hash_quant* quant, const float* table, const int32_t* origins,
+                                    const nic_mlp* mlp, const float* target, float loss_scale, float* table_grad, const nic_mlp_grads* mlp_grads,
+                                    float* loss, float* y, int flags, void* workspace, size_t workspace_bytes, const nic_step_tail* tail,
+                                    void* stream) {
+    const KernelEndDrop end;
+    if (!desc || !mlp) return NIC_E_NULL;
+    int rc = supported(desc, kH, mlp->n_linear);
+    if (rc) return rc;
+    if (!table || !origins || !mlp3_ok(mlp) || !target || !mlp_grads || !loss || !workspace) return NIC_E_NULL;
+    if (flags & ~(NIC_HASH_FUSED_ADD_GRADS | NIC_HASH_FUSED_ADD_LOSS)) return NIC_E_ARG;
+    FParams p{};
+    fill_common(p, desc, origins, mlp, y);
+    p.table = table; p.target = target; p.grad = table_grad;
+    if (quant) {
+        if (quant->num_bits < 1 || quant->num_bits > 8 || quant->sample_base < 0) return NIC_E_ARG;
+        if (quant->noise_mode == NIC_NOISE_TENSOR) return NIC_E_UNSUPPORTED;
+        if (quant->noise_mode != NIC_NOISE_NONE && quant->noise_mode != NIC_NOISE_KERNEL) return NIC_E_ARG;
+        if (quant->noise_mode == NIC_NOISE_KERNEL) {
+            p.noise.mode = NIC_NOISE_KERNEL;
+            p.noise.k0 = (uint32_t)quant->noise_seed; p.noise.k1 = (uint32_t)(quant->noise_seed >> 32);
+            p.noise.off_lo = (uint32_t)quant->noise_offset; p.noise.off_hi = (uint32_t)(quant->noise_offset >> 32);
+            p.noise.scale = ldexpf(1.0f, -quant->num_bits);
+            p.sample_base = (uint64_t)quant->sample_base;
+        }
+    }
+    const int lf = desc->levels * desc->features, grid = grid_of(p.n_patches);
+    const RecLayout rl(lf);
+    if (workspace_bytes < (size_t)grid * rl.rec * sizeof(float)) return NIC_E_WORKSPACE;
+    // the optimiser tail (fused_capi.hip, TailScope::open): a decoder entry's gradient is one of the buffers this call's reduction writes
+    const int reduce_blocks = (rl.rec + 31) / 32;
+    StepTail tl;
+    tl.t.count = 0; tl.t.sched = nullptr; tl.n_stream = 0; tl.reduce_blocks = 0x7fffffff;
+    int64_t tail_blocks = 0;
+    if (tail) {
+        if (!tail->tensors) return NIC_E_NULL;
+        if (tail->count < 1 || tail->count > NIC_ADAM_MAX_TENSORS || tail->n_stream < 0 || tail->n_stream > tail->count) return NIC_E_ARG;
+        if (tail->sched != nullptr) return NIC_E_ARG;                 // the device schedule belongs to the captured dense step
+        for (int i = tail->n_stream; i < tail->count; ++i) {
+            bool found = false;
+            for (int k = 0; k < 3; ++k)
+                found = found || (tail->tensors[i].grad != nullptr && (tail->tensors[i].grad == mlp_grads->w[k] || tail->tensors[i].grad == mlp_grads->b[k]));
+            if (!found) return NIC_E_ARG;
+        }
+        rc = adam_build_table(tail->tensors, tail->count, tail->n_stream, tail->beta1, tail->beta2, tail->eps, nullptr, 0, nullptr, tl.t, tl.n_stream,
+                              tail_blocks);
+        if (rc) return rc;
+        tl.reduce_blocks = reduce_blocks;
+    }
+    const double n_samples = (double)desc->num_crops * desc->extent[0] * desc->extent[1] * (desc->dim == 3 ? desc->extent[2] : 1);
+    const float loss_mul = (float)((double)loss_scale / (3.0 * n_samples));
+    p.dscale = 2.0f * loss_mul;
+    p.partials = (float*)workspace;
+    rc = launch<HF_TRAIN>(p, grid, stream);
+    if (rc) return rc;
+    kernel_end_mark((hipStream_t)stream);
+    hipLaunchKernelGGL(hash_fused_reduce_kernel, dim3((unsigned)(reduce_blocks + tail_blocks)), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)p.partials, grid, lf, *mlp_grads, loss, loss_mul, (flags & NIC_HASH_FUSED_ADD_GRADS) ? 1 : 0,
+                       (flags & NIC_HASH_FUSED_ADD_LOSS) ? 1 : 0, tl);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -145,6 +145,9 @@ struct TailLaunch {
     unsigned blocks;
 };
 TailLaunch tail_for(int reduce_blocks);
+// nic_mark_kernel_end's one-shot event (fused_capi.hip): recorded between a training entry point's kernel and its reduction, dropped on every other return
+void kernel_end_mark(hipStream_t s);
+void kernel_end_drop();
 
 // ---- host side: nic_adam_tensor list -> AdamTable.  Entries [0, n_stream) get chunk blocks (returned in `blocks`), the rest none.
 inline int adam_build_table(const nic_adam_tensor* tensors, int count, int n_stream, double beta1, double beta2, double eps, const float* sched,

@@ -21,7 +21,12 @@ every column of the encoding (``nic_hash_encode_noisy``: in-kernel Threefry keye
 ``freeze()`` quantises the table in place and only the decoder trains on; ``save_compressed`` stores the compact uint8 table (``nic_hash_pack_u8``:
 a dense level keeps only the (R + 1)^d vertices it can address) with the decoder, and ``load_compressed(...).decode()`` decodes straight from
 those bytes (``nic_hash_encode_u8``).  The schedule is the dense one (image_compression.py:237,385): noise while the epoch is below 0.95 N, then
-freeze - ``fit`` runs it."""
+freeze - ``fit`` runs it.
+
+``HashGridField(..., fused=True)`` runs the same step as TWO launches: one kernel gathers, decodes, forms the loss, back-propagates
+and scatters (``nic_hash_fused_forward_backward``; the [N, L F] row never reaches memory), the reduction of its decoder-gradient records carries
+the optimiser.  ``decode`` is one launch per tile.  Shapes outside the kernel's set (``nic_hash_fused_supported``) take the layer-wise route by
+themselves; ``field.route`` says which one runs."""
 from __future__ import annotations
 
 import ctypes
@@ -217,6 +222,92 @@ def hash_encode_u8(geo: HashGeometry, stored: torch.Tensor, coord, extent: Seque
     return out
 
 
+def hash_fused_supported(geo: HashGeometry, hidden: int = 64, n_linear: int = 3) -> bool:
+    """whether the fused encode + decoder kernels exist for this geometry and decoder (nic_hash_fused_supported: the only copy of the set)"""
+    return _lib.load().nic_hash_fused_supported(ctypes.byref(geo.to_desc(1, [1] * geo.dim)), int(hidden), int(n_linear)) == 0
+
+
+def _check_fused_decoder(geo: HashGeometry, params: Sequence[torch.Tensor]) -> List[torch.Tensor]:
+    if len(params) != 6:
+        raise _lib.Unsupported("the fused hash-grid kernels decode with 3 Linear layers")
+    params = fused.check_mlp(params, geo.width, params[0].shape[0])
+    if params[0].shape[0] != 64:
+        raise _lib.Unsupported("the fused hash-grid kernels decode with 64 hidden units")
+    return params
+
+
+@fused._on_tensor_device
+def hash_fused_forward(geo: HashGeometry, table: torch.Tensor, coord, extent: Sequence[int], params: Sequence[torch.Tensor],
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[N, 3] = ColorDecoder(hash_encode(table)) in one launch (nic_hash_fused_forward); ``params`` = W1, b1, W2, b2, W3, b3"""
+    t = _check_table(geo, table.detach())
+    params = _check_fused_decoder(geo, [q.detach() for q in params])
+    org = geo.upload_origins(coord, extent, t.device)
+    y = torch.empty(_n_samples(org.shape[0], extent), 3, dtype=torch.float32, device=t.device) if out is None else out
+    d, m = geo.to_desc(org.shape[0], extent), fused._mlp_struct(params)
+    _lib.check(_lib.load().nic_hash_fused_forward(ctypes.byref(d), _lib.ptr(t), _lib.ptr(org), ctypes.byref(m), _lib.ptr(y), _lib.stream_ptr(t.device)),
+               "nic_hash_fused_forward")
+    return y
+
+
+@fused._on_tensor_device
+def hash_fused_forward_u8(geo: HashGeometry, stored: torch.Tensor, coord, extent: Sequence[int], num_bits: int,
+                          params: Sequence[torch.Tensor]) -> torch.Tensor:
+    """``hash_fused_forward`` from the compact uint8 table (nic_hash_fused_forward_u8): the rows of ``hash_encode_u8`` into the same decoder code"""
+    if stored.dtype != torch.uint8 or not stored.is_cuda or stored.dim() != 1 or not stored.is_contiguous():
+        raise ValueError("stored must be a contiguous 1-D uint8 tensor on a HIP device")
+    if stored.numel() != hash_stored_bytes(geo):
+        raise ValueError(f"stored holds {stored.numel()} bytes, the geometry needs {hash_stored_bytes(geo)}")
+    params = _check_fused_decoder(geo, [q.detach() for q in params])
+    org = geo.upload_origins(coord, extent, stored.device)
+    y = torch.empty(_n_samples(org.shape[0], extent), 3, dtype=torch.float32, device=stored.device)
+    d, m = geo.to_desc(org.shape[0], extent), fused._mlp_struct(params)
+    _lib.check(_lib.load().nic_hash_fused_forward_u8(ctypes.byref(d), int(num_bits), _lib.ptr(stored), _lib.ptr(org), ctypes.byref(m), _lib.ptr(y),
+                                                     _lib.stream_ptr(stored.device)), "nic_hash_fused_forward_u8")
+    return y
+
+
+@fused._on_tensor_device
+def hash_fused_forward_backward(geo: HashGeometry, table: torch.Tensor, coord, extent: Sequence[int], params: Sequence[torch.Tensor],
+                                target: torch.Tensor, mlp_grads: Sequence[torch.Tensor], table_grad: Optional[torch.Tensor] = None,
+                                loss: Optional[torch.Tensor] = None, loss_scale: float = 1.0, want_y: bool = False, quant=None,
+                                add_grads: bool = False, add_loss: bool = False, tail=None):
+    """the whole training step of a hash-grid field in two launches (nic_hash_fused_forward_backward): loss = mean((y - target)^2) * loss_scale.
+    ``table_grad``: d loss / d table is ADDED into it (None: frozen table, no scatter).  ``mlp_grads``: six buffers like ``params``, overwritten
+    (``add_grads``: added to).  ``quant``: None or (num_bits, seed, offset, sample_base) for ``hash_encode_noisy``'s noise.  ``tail``: an
+    ``optim.StepTail`` on ``table_grad`` / ``mlp_grads`` - committed once the launch is queued.  Returns (loss [1], y or None)."""
+    t = _check_table(geo, table.detach())
+    params = _check_fused_decoder(geo, [q.detach() for q in params])
+    org = geo.upload_origins(coord, extent, t.device)
+    n = _n_samples(org.shape[0], extent)
+    target = _lib.require_cuda_f32(target, "target")
+    if tuple(target.shape) != (n, 3):
+        raise ValueError(f"target must be [{n}, 3], got {tuple(target.shape)}")
+    if table_grad is not None:
+        g = _check_table(geo, table_grad, "table_grad")
+        if g is not table_grad:
+            raise ValueError("table_grad must be contiguous: the kernel adds into it in place")
+    if len(mlp_grads) != 6 or any(not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.shape == q.shape) for g, q in zip(mlp_grads, params)):
+        raise ValueError("mlp_grads: six contiguous fp32 device buffers shaped like the decoder's parameters")
+    loss = torch.empty(1, dtype=torch.float32, device=t.device) if loss is None else loss
+    y = torch.empty(n, 3, dtype=torch.float32, device=t.device) if want_y else None
+    lib = _lib.load()
+    d, m, gs = geo.to_desc(org.shape[0], extent), fused._mlp_struct(params), fused._grads_struct(list(mlp_grads))
+    q = None
+    if quant is not None:
+        bits, seed, offset, base = quant
+        q = _lib.NicHashQuant(int(bits), _lib.NIC_NOISE_KERNEL, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(base))
+    ws = _lib.workspace(t.device, int(lib.nic_hash_fused_workspace_bytes(ctypes.byref(d), ctypes.byref(m))))
+    flags = (_lib.NIC_HASH_FUSED_ADD_GRADS if add_grads else 0) | (_lib.NIC_HASH_FUSED_ADD_LOSS if add_loss else 0)
+    _lib.check(lib.nic_hash_fused_forward_backward(ctypes.byref(d), None if q is None else ctypes.byref(q), _lib.ptr(t), _lib.ptr(org), ctypes.byref(m),
+                                                   _lib.ptr(target), float(loss_scale), _lib.ptr(table_grad), ctypes.byref(gs), _lib.ptr(loss), _lib.ptr(y),
+                                                   flags, _lib.ptr(ws), ws.numel(), None if tail is None else ctypes.byref(tail.struct),
+                                                   _lib.stream_ptr(t.device)), "nic_hash_fused_forward_backward")
+    if tail is not None:
+        tail.commit()
+    return loss, y
+
+
 class HashEncodeFunction(torch.autograd.Function):
     """``hash_encode`` as a differentiable op of the table: backward = ``nic_hash_encode_backward`` into a fresh zero [L, T, F] (what autograd
     through ``index_add`` of the corner entries would give, collisions summed)"""
@@ -247,11 +338,11 @@ class HashGridField:
     """a hash-grid table + one decoder over its [N, L F] encoding, trained like ``MultiLevelField`` (module docstring).  ``field_size``:
     (S_x, S_y) or (S_x, S_y, S_z), x = the image tensor's first spatial axis like everywhere in this package.  ``num_bits``: None = no codec
     (no noise, no clamp); b in 1..8 = quantisation-aware training for a uint8 table of b-bit values (module docstring), noise keyed by
-    ``noise_seed``."""
+    ``noise_seed``.  ``fused``: ``train_step`` / ``fit`` / ``decode`` on the fused encode + decoder kernels where they exist (``route``)."""
 
     def __init__(self, field_size: Union[int, Sequence[int]], levels: int = 16, features: int = 2, log2_table: int = 19, base_resolution: float = 16,
                  finest_resolution: Optional[float] = None, hidden: int = 64, n_linear: int = 3, device=None, seed: Optional[int] = None,
-                 num_bits: Optional[int] = None, noise_seed: int = 7):
+                 num_bits: Optional[int] = None, noise_seed: int = 7, fused: bool = False):
         if num_bits is not None and not 1 <= int(num_bits) <= 8:
             raise ValueError("num_bits in 1 .. 8 (the stored table is uint8), or None")
         self.field_size = (int(field_size),) * 2 if isinstance(field_size, int) else tuple(int(v) for v in field_size)
@@ -274,8 +365,14 @@ class HashGridField:
         self.num_bits = None if num_bits is None else int(num_bits)
         self.noise_seed, self.steps, self.frozen, self.stored = int(noise_seed), 0, False, None
         self._pass_samples = 0                       # samples of the current accumulate pass so far: the next chunk's sample_base
+        self._set_route(fused)
         if self.num_bits is not None:
             self.optimizer.set_clamp([self.table], *models._q_range(self.num_bits))
+
+    def _set_route(self, want_fused: bool) -> None:
+        """"fused" when asked for and the kernels exist for this shape, else "layerwise" (a field built without ``fused`` never asks the library)"""
+        self.route = "fused" if want_fused and hash_fused_supported(self.geo, self.hidden, self.n_linear) else "layerwise"
+        self._fused_gm = None                        # the decoder-gradient buffers of the fused step: persistent, so the optimiser's table stays valid
 
     @property
     def resolutions(self) -> Tuple[int, ...]:
@@ -299,6 +396,8 @@ class HashGridField:
         chunks of a pass share noise).  After ``freeze()`` only the decoder trains: no table gradient is formed."""
         if self.table is None:
             raise RuntimeError("a field from load_compressed decodes only")
+        if self.route == "fused":
+            return self._fused_train_step(coord, extent, target, accumulate, scale, step, noise)
         params = self.decoder.linear_params()
         grad = self.table.grad
         frozen = self.frozen
@@ -337,6 +436,47 @@ class HashGridField:
                 self.scheduler.step()
             self.steps += 1
         return loss.detach()
+
+    @torch.no_grad()
+    def _fused_train_step(self, coord, extent, target, accumulate, scale, step, noise) -> torch.Tensor:
+        """``train_step`` as two launches: the fused kernel, then the reduction of its decoder-gradient records with the optimiser riding on it
+        (``FusedAdam.step_tail``).  The decoder gradients live in persistent buffers; the chunks of a pass add into them and into the table
+        gradient, and only the last chunk carries the optimiser."""
+        params = self.decoder.linear_params()
+        frozen = self.frozen
+        grad = None if frozen else self.table.grad
+        if self._fused_gm is None:
+            self._fused_gm = [torch.zeros_like(p) for p in params]
+        gm = self._fused_gm
+        for p, g in zip(params, gm):
+            p.grad = g
+        if not accumulate:
+            if not frozen and not self._grad_clean:
+                grad.zero_()
+            self._pass_samples = 0
+        org = self.geo.upload_origins(coord, extent, self.device)
+        n = _n_samples(org.shape[0], extent)
+        if noise is None:
+            noise = self.num_bits is not None and not frozen
+        if noise and self.num_bits is None:
+            raise ValueError("noise needs num_bits: its amplitude is one quantisation step")
+        quant = (self.num_bits, self.noise_seed, self.steps, self._pass_samples) if noise else None
+        tail = None
+        if step:
+            tail = self.optimizer.step_tail([] if frozen else [(self.table, grad)], list(zip(params, gm)))
+        loss, _ = hash_fused_forward_backward(self.geo, self.table, org, extent, params, target, gm, table_grad=grad, loss_scale=float(scale), quant=quant,
+                                              add_grads=accumulate, tail=tail)
+        self._pass_samples += n
+        if not frozen:
+            self._grad_clean = False
+        if step:
+            self.optimizer.step()                    # nothing to launch after a committed tail
+            if not frozen:
+                self._grad_clean = self.optimizer.zeroed_in_last_step(grad)
+            if self.scheduler is not None:
+                self.scheduler.step()
+            self.steps += 1
+        return loss
 
     @torch.no_grad()
     def freeze(self) -> None:
@@ -394,8 +534,9 @@ class HashGridField:
                     "n_linear": self.n_linear, "table": stored.cpu(), "decoder": {k: v.detach().cpu() for k, v in self.decoder.state_dict().items()}}, path)
 
     @classmethod
-    def load_compressed(cls, path, device=None) -> "HashGridField":
-        """a decode-only field from ``save_compressed``'s file: ``decode()`` gathers from the uint8 table (nic_hash_encode_u8), no fp32 table"""
+    def load_compressed(cls, path, device=None, fused: bool = False) -> "HashGridField":
+        """a decode-only field from ``save_compressed``'s file: ``decode()`` gathers from the uint8 table (nic_hash_encode_u8; ``fused``:
+        nic_hash_fused_forward_u8), no fp32 table"""
         d = torch.load(path, map_location="cpu", weights_only=True)
         if not isinstance(d, dict) or d.get("format") != COMPRESSED_FORMAT:
             raise ValueError(f"{path}: not a {COMPRESSED_FORMAT} file")
@@ -415,6 +556,7 @@ class HashGridField:
         self.decoder.load_state_dict(d["decoder"])
         self.optimizer = self.scheduler = None
         self.noise_seed, self.steps, self.frozen, self._pass_samples, self._grad_clean = 0, 0, True, 0, True
+        self._set_route(fused)
         return self
 
     @torch.no_grad()
@@ -426,7 +568,12 @@ class HashGridField:
         table = None if self.table is None else self.table.detach()
         for o in itertools.product(*[range(0, s, tile) for s in size]):
             ext = [min(tile, s - a) for s, a in zip(size, o)]
-            x = hash_encode_u8(self.geo, self.stored, [o], ext, self.num_bits) if table is None else hash_encode(self.geo, table, [o], ext)
             sl = tuple(slice(a, a + e) for a, e in zip(o, ext))
+            if self.route == "fused":
+                y = hash_fused_forward_u8(self.geo, self.stored, [o], ext, self.num_bits, params) if table is None \
+                    else hash_fused_forward(self.geo, table, [o], ext, params)
+                out[sl] = y.reshape(*ext, 3)
+                continue
+            x = hash_encode_u8(self.geo, self.stored, [o], ext, self.num_bits) if table is None else hash_encode(self.geo, table, [o], ext)
             out[sl] = fused.DecoderFunction.apply(x, *params).reshape(*ext, 3)
         return out
