@@ -512,6 +512,22 @@ int nic_hash_encode_u8(const nic_hash_desc *desc, int num_bits, const uint8_t *s
 int nic_hash_pack_u8(const nic_hash_desc *desc, int num_bits, const float *table, uint8_t *stored, void *stream);   /* [L, T, F] fp32 -> compact */
 int64_t nic_hash_stored_bytes(const nic_hash_desc *desc);   /* F * sum_l E_l, or a negative NIC_E_* code */
 
+/* ---- hash-grid codec: the bit-packed stored table, b bits per value (hashgrid.py, save_compressed(packed=True)).
+ *      With E_l as above and u the byte nic_hash_pack_u8 writes for a table value (0 <= u <= 2^b - 1 inside the clamp range):
+ *      level l is a little-endian bit stream; value f of entry e occupies bits [(e F + f) b, (e F + f + 1) b), least significant bit first;
+ *      bit k of the stream is bit k & 7 of byte k >> 3; the stored value is u & (2^b - 1).  Each level's stream is padded with zero bits to a
+ *      multiple of 4 bytes, so level l starts at byte 4 sum_{k<l} ceil(E_k F b / 32).  After the last level come 8 zero bytes: a gather reads a
+ *      window of up to three aligned dwords from the dword an entry starts in (F b <= 64, start bit <= 31) and never leaves the buffer.
+ *      nic_hash_packed_bytes = 4 sum_l ceil(E_l F b / 32) + 8 (or a negative NIC_E_* code); at b = 8 each level's bytes are the uint8 format's.
+ *      nic_hash_pack_bits writes the whole buffer from the fp32 [L, T, F] table (padding and tail as zeros; nic_hash_pack_u8's arithmetic per
+ *      value), nic_hash_unpack_bits turns it back into the compact uint8 table, nic_hash_encode_bits is nic_hash_encode_u8 from the packed
+ *      table, bit for bit (the masked value takes the same dequantisation and blend).  `packed` must be 4-byte aligned (else NIC_E_ARG, after
+ *      the checks the _u8 siblings make, which come in the same order with the same codes, all before any GPU work). */
+int64_t nic_hash_packed_bytes(const nic_hash_desc *desc, int num_bits);
+int nic_hash_pack_bits(const nic_hash_desc *desc, int num_bits, const float *table, uint8_t *packed, void *stream);
+int nic_hash_unpack_bits(const nic_hash_desc *desc, int num_bits, const uint8_t *packed, uint8_t *stored, void *stream);
+int nic_hash_encode_bits(const nic_hash_desc *desc, int num_bits, const uint8_t *packed, const int32_t *origins, float *out, void *stream);
+
 /* ---- hash-grid encoding + decoder in ONE kernel (hashgrid.py, HashGridField(fused=True)).  Nothing new is computed: the
  *      encoding is nic_hash_encode's (nic_hash_encode_noisy's with `quant`, nic_hash_encode_u8's from the compact table), the decoder is
  *      ColorDecoder(levels * features, 64, 3) with the GELU / sigmoid of the other kernels in fp32 MFMA arithmetic, the loss is
@@ -533,6 +549,9 @@ size_t nic_hash_fused_workspace_bytes(const nic_hash_desc *desc, const nic_mlp *
 int nic_hash_fused_forward(const nic_hash_desc *desc, const float *table, const int32_t *origins, const nic_mlp *mlp, float *y, void *stream);
 int nic_hash_fused_forward_u8(const nic_hash_desc *desc, int num_bits, const uint8_t *stored, const int32_t *origins, const nic_mlp *mlp,
                               float *y, void *stream);
+/* nic_hash_fused_forward_u8 from the bit-packed table (format above; `packed` 4-byte aligned); nic_hash_fused_supported answers for it too */
+int nic_hash_fused_forward_bits(const nic_hash_desc *desc, int num_bits, const uint8_t *packed, const int32_t *origins, const nic_mlp *mlp,
+                                float *y, void *stream);
 int nic_hash_fused_forward_backward(const nic_hash_desc *desc, const nic_hash_quant *quant, const float *table, const int32_t *origins,
                                     const nic_mlp *mlp, const float *target, float loss_scale, float *table_grad,
                                     const nic_mlp_grads *mlp_grads, float *loss, float *y, int flags, void *workspace, size_t workspace_bytes,

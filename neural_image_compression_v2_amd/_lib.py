@@ -175,10 +175,15 @@ SIGNATURES = {
     "nic_hash_encode_u8": (_I, [ctypes.POINTER(NicHashDesc), _I, _P, _P, _P, _P]),
     "nic_hash_pack_u8": (_I, [ctypes.POINTER(NicHashDesc), _I, _P, _P, _P]),
     "nic_hash_stored_bytes": (_L, [ctypes.POINTER(NicHashDesc)]),
+    "nic_hash_packed_bytes": (_L, [ctypes.POINTER(NicHashDesc), _I]),
+    "nic_hash_pack_bits": (_I, [ctypes.POINTER(NicHashDesc), _I, _P, _P, _P]),
+    "nic_hash_unpack_bits": (_I, [ctypes.POINTER(NicHashDesc), _I, _P, _P, _P]),
+    "nic_hash_encode_bits": (_I, [ctypes.POINTER(NicHashDesc), _I, _P, _P, _P, _P]),
     "nic_hash_fused_supported": (_I, [ctypes.POINTER(NicHashDesc), _I, _I]),
     "nic_hash_fused_workspace_bytes": (_SZ, [ctypes.POINTER(NicHashDesc), _M]),
     "nic_hash_fused_forward": (_I, [ctypes.POINTER(NicHashDesc), _P, _P, _M, _P, _P]),
     "nic_hash_fused_forward_u8": (_I, [ctypes.POINTER(NicHashDesc), _I, _P, _P, _M, _P, _P]),
+    "nic_hash_fused_forward_bits": (_I, [ctypes.POINTER(NicHashDesc), _I, _P, _P, _M, _P, _P]),
     "nic_hash_fused_forward_backward": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashQuant), _P, _P, _M, _P, _F, _P, _G, _P, _P, _I, _P, _SZ,
                                              ctypes.POINTER(NicStepTail), _P]),
 }

@@ -71,6 +71,38 @@ __device__ __forceinline__ void load_row_u8(const uint8_t* p, float scale, float
         v[f] = __fdiv_rn(__fadd_rn(__fsub_rn(u, bias), 1.0f), scale);
     }
 }
+__host__ __device__ inline int64_t hash_level_dwords(int dim, int32_t R, int log2_table, int F, int bits) {
+    return (hash_level_entries(dim, R, log2_table) * (F * bits) + 31) >> 5;
+}
+__host__ __device__ inline bool hash_bits_tight(int F, int bits) { return 32 % (F * bits) == 0 || F * bits == 64; }
+template <int F, bool TIGHT>
+__device__ __forceinline__ void load_row_bits(const uint32_t* lev, uint32_t e, int bits, float scale, float bias, float (&v)[F]) {
+    const uint32_t bit = e * (uint32_t)(F * bits), sh = bit & 31u;
+    const uint32_t* q = lev + (bit >> 5);
+    uint32_t x0, x1 = 0u;
+    const uint32_t w0 = q[0];
+    if constexpr (F <= 4) {
+        if constexpr (TIGHT) x0 = w0 >> sh;
+        else x0 = __builtin_amdgcn_alignbit(q[1], w0, sh);
+    } else {
+        if constexpr (TIGHT) {
+            x0 = w0 >> sh;
+            if (bits == 8) x1 = q[1];                                // F b = 64 starts on a dword
+        } else {
+            const uint32_t w1 = q[1], w2 = q[2];
+            x0 = __builtin_amdgcn_alignbit(w1, w0, sh);
+            x1 = __builtin_amdgcn_alignbit(w2, w1, sh);
+        }
+    }
+#pragma unroll
+    for (int f = 0; f < F; ++f) {
+        uint32_t uv;
+        if constexpr (F <= 4) uv = __builtin_amdgcn_ubfe(x0, (uint32_t)(f * bits), (uint32_t)bits);      // f b + b <= 32
+        else uv = __builtin_amdgcn_ubfe((uint32_t)((((uint64_t)x1 << 32) | x0) >> (f * bits)), 0u, (uint32_t)bits);
+        const float u = (float)uv;
+        v[f] = __fdiv_rn(__fadd_rn(__fsub_rn(u, bias), 1.0f), scale);
+    }
+}
 template <int D>
 struct PatchSample {
     int crop;
@@ -130,7 +162,7 @@ __device__ __forceinline__ float corner_weight(const float (&w)[3], int c) {
 
 constexpr int XS = kH + 1;      // row stride of every LDS tile: lanes that walk rows hit 64 different banks
 constexpr int NQ = 16;          // samples per weight-gradient pass (the two transposed tiles of a wave)
-enum { HF_FWD = 0, HF_FWD_U8 = 1, HF_TRAIN = 2 };
+enum { HF_FWD = 0, HF_FWD_U8 = 1, HF_TRAIN = 2, HF_FWD_BITS = 3 };
 
 struct FParams {
     nic_hash_desc d;
@@ -147,6 +179,9 @@ struct FParams {
     float q_scale, q_bias;
     float dscale;             // 2 loss_scale / (3 N)
     int64_t n_patches;
+    // HF_FWD_BITS only (appended: the other modes read the fields above at the offsets they always had)
+    const uint32_t* packed;   // bit-packed table, 4-byte aligned
+    int32_t q_bits, q_tight;  // b; F b divides 32 or is 64 (hash_grid.hip, load_row_bits)
 };
 
 // the record of a workgroup, nn.Linear layouts back to back: dW1 [64, L F] | db1 | dW2 [64, 64] | db2 | dW3 [3, 64] | db3 | sum of squared errors
@@ -184,11 +219,12 @@ __device__ __forceinline__ void sample_coords(const FParams& p, const PatchSampl
 }
 
 // the level loop of hash_encode_kernel with the row going to LDS
-template <int D, int F, int MODE>
+template <int D, int F, int MODE, bool TIGHT = false>
 __device__ __forceinline__ void encode_row(const FParams& p, const PatchSample<D>& s, const uint32_t (&i)[3], float* xrow) {
     const nic_hash_desc& d = p.d;
     const uint32_t S2 = 2u * (uint32_t)d.S_max, mask = (1u << d.log2_table) - 1u;
     [[maybe_unused]] int64_t lev_off = 0;
+    [[maybe_unused]] int64_t lev_dw = 0;
     [[maybe_unused]] U4 nblk{0u, 0u, 0u, 0u};
     [[maybe_unused]] const bool noisy = MODE == HF_TRAIN && p.noise.mode == NIC_NOISE_KERNEL;
 #pragma unroll 2
@@ -201,6 +237,11 @@ __device__ __forceinline__ void encode_row(const FParams& p, const PatchSample<D
             stab = p.stored + lev_off;
             lev_off += (int64_t)F * hash_level_entries(D, (int32_t)R, d.log2_table);
         }
+        [[maybe_unused]] const uint32_t* btab = nullptr;
+        if constexpr (MODE == HF_FWD_BITS) {
+            btab = p.packed + lev_dw;
+            lev_dw += hash_level_dwords(D, (int32_t)R, d.log2_table, F, p.q_bits);
+        }
         uint32_t v[3];
         float w[3];
         level_cell<D>(i, R, S2, v, w);
@@ -212,6 +253,7 @@ __device__ __forceinline__ void encode_row(const FParams& p, const PatchSample<D
             const uint32_t e = hash_index(dense, R, mask, v[0] + (c & 1), v[1] + ((c >> 1) & 1), D == 3 ? v[2] + ((c >> 2) & 1) : 0u);
             float t[F];
             if constexpr (MODE == HF_FWD_U8) load_row_u8<F>(stab + (int64_t)e * F, p.q_scale, p.q_bias, t);
+            else if constexpr (MODE == HF_FWD_BITS) load_row_bits<F, TIGHT>(btab, e, p.q_bits, p.q_scale, p.q_bias, t);
             else load_row<F>(tab + (int64_t)e * F, t);
             const float cw = corner_weight<D>(w, c);
 #pragma unroll
@@ -339,7 +381,12 @@ __global__ void __launch_bounds__(256) hash_fused_kernel(const FParams p) {
         const PatchSample<D> s = patch_sample<D>(p.d, wv, p.n_patches, lane);
         uint32_t ci[3];
         sample_coords<D>(p, s, ci);
-        encode_row<D, F, MODE>(p, s, ci, xrow);
+        if constexpr (MODE == HF_FWD_BITS) {                     // b is uniform over the launch: the window's width is decided once per row
+            if (p.q_tight) encode_row<D, F, MODE, true>(p, s, ci, xrow);
+            else encode_row<D, F, MODE, false>(p, s, ci, xrow);
+        } else {
+            encode_row<D, F, MODE>(p, s, ci, xrow);
+        }
         wave_sync();
         const unsigned long long live_mask = __ballot(s.live);
 #pragma unroll 1
@@ -702,6 +749,23 @@ int nic_hash_fused_forward_u8(const nic_hash_desc* desc, int num_bits, const uin
     p.q_scale = (float)((1 << num_bits) - 1);
     p.q_bias = (float)(1 << (num_bits - 1));
     return launch<HF_FWD_U8>(p, grid_of(p.n_patches), stream);
+}
+
+int nic_hash_fused_forward_bits(const nic_hash_desc* desc, int num_bits, const uint8_t* packed, const int32_t* origins, const nic_mlp* mlp, float* y,
+                                void* stream) {
+    if (!desc || !mlp) return NIC_E_NULL;
+    const int rc = supported(desc, kH, mlp->n_linear);
+    if (rc) return rc;
+    if (!packed || !origins || !mlp3_ok(mlp) || !y) return NIC_E_NULL;
+    if (num_bits < 1 || num_bits > 8) return NIC_E_ARG;
+    if ((uintptr_t)packed & 3u) return NIC_E_ARG;                    // the gather reads aligned dwords
+    FParams p{};
+    fill_common(p, desc, origins, mlp, y);
+    p.packed = (const uint32_t*)packed;
+    p.q_bits = num_bits; p.q_tight = hash_bits_tight(desc->features, num_bits) ? 1 : 0;
+    p.q_scale = (float)((1 << num_bits) - 1);
+    p.q_bias = (float)(1 << (num_bits - 1));
+    return launch<HF_FWD_BITS>(p, grid_of(p.n_patches), stream);
 }
 
 int nic_hash_fused_forward_backward(const nic_hash_desc* desc, const nic_hash_quant* quant, const float* table, const int32_t* origins,

@@ -8,6 +8,10 @@
 //
 // The codec (nic_hash_encode_noisy / _u8 / nic_hash_pack_u8): the same forward kernel with a table source (fp32 [L, T, F] or the compact uint8
 // table, dequantised per corner with load4fp's arithmetic) and optional in-kernel noise on every column, one generator block per 16 columns.
+//
+// The bit-packed table (nic_hash_encode_bits / nic_hash_pack_bits / nic_hash_unpack_bits; the format is spelled out in the header): a third
+// table source, b bits per value in one little-endian bit stream per level.  An entry is read as a window of aligned dwords from the dword it
+// starts in, funnel-shifted to bit 0 and masked into the uint8 value, which then takes load_row_u8's dequantisation and the same blend.
 #include "nic_device.hpp"
 
 namespace nic {
@@ -39,9 +43,13 @@ struct HashParams {
     NoiseSrc noise;          // in-kernel noise (NOISE)
     uint64_t sample_base;
     float q_scale, q_bias;   // load4fp: (u - q_bias + 1) / q_scale, q_scale = 2^b - 1, q_bias = 2^(b-1)
+    // bit-packed launches only (appended likewise)
+    const uint32_t* packed;  // bit-packed table (HSRC_BITS), 4-byte aligned
+    int32_t q_bits;          // b
+    int32_t q_tight;         // F b divides 32, or is 64: no entry leaves the dword(s) it starts in, so the window shrinks to them
 };
 
-enum HashSrc { HSRC_F32 = 0, HSRC_U8 = 1 };
+enum HashSrc { HSRC_F32 = 0, HSRC_U8 = 1, HSRC_BITS = 2 };
 
 template <int F>
 __device__ __forceinline__ void load_row(const float* p, float (&v)[F]) {
@@ -98,6 +106,45 @@ __host__ __device__ inline int64_t hash_level_entries(int dim, int32_t R, int lo
     int64_t e = 1;
     for (int a = 0; a < dim; ++a) e *= (int64_t)R + 1;
     return e;
+}
+
+// dwords of a level's bit stream: E F b bits (<= 2^30), padded with zero bits to whole dwords
+__host__ __device__ inline int64_t hash_level_dwords(int dim, int32_t R, int log2_table, int F, int bits) {
+    return (hash_level_entries(dim, R, log2_table) * (F * bits) + 31) >> 5;
+}
+__host__ __device__ inline bool hash_bits_tight(int F, int bits) { return 32 % (F * bits) == 0 || F * bits == 64; }
+
+// one bit-packed entry of F b bits at bit e F b of its level's stream `lev`: aligned dword loads only - the dword the entry starts in and the
+// next one (F <= 4: F b <= 32) or two (F = 8: F b <= 64; the 8 zero bytes after the last level keep that window inside the buffer), funnel-
+// shifted so that the entry starts at bit 0.  TIGHT (HashParams::q_tight, uniform over the launch): no entry straddles, the extra dword is not read.
+// The value then takes load_row_u8's dequantisation, expression for expression.
+template <int F, bool TIGHT>
+__device__ __forceinline__ void load_row_bits(const uint32_t* lev, uint32_t e, int bits, float scale, float bias, float (&v)[F]) {
+    const uint32_t bit = e * (uint32_t)(F * bits), sh = bit & 31u;
+    const uint32_t* q = lev + (bit >> 5);
+    uint32_t x0, x1 = 0u;
+    const uint32_t w0 = q[0];
+    if constexpr (F <= 4) {
+        if constexpr (TIGHT) x0 = w0 >> sh;
+        else x0 = __builtin_amdgcn_alignbit(q[1], w0, sh);
+    } else {
+        if constexpr (TIGHT) {
+            x0 = w0 >> sh;
+            if (bits == 8) x1 = q[1];                                // F b = 64 starts on a dword
+        } else {
+            const uint32_t w1 = q[1], w2 = q[2];
+            x0 = __builtin_amdgcn_alignbit(w1, w0, sh);
+            x1 = __builtin_amdgcn_alignbit(w2, w1, sh);
+        }
+    }
+#pragma unroll
+    for (int f = 0; f < F; ++f) {
+        uint32_t uv;
+        if constexpr (F <= 4) uv = __builtin_amdgcn_ubfe(x0, (uint32_t)(f * bits), (uint32_t)bits);      // f b + b <= 32
+        else uv = __builtin_amdgcn_ubfe((uint32_t)((((uint64_t)x1 << 32) | x0) >> (f * bits)), 0u, (uint32_t)bits);
+        const float u = (float)uv;
+        v[f] = __fdiv_rn(__fadd_rn(__fsub_rn(u, bias), 1.0f), scale);
+    }
 }
 
 // the sample of this lane in patch `wv` (clamped to the last patch; `live` = a real sample of a real patch)
@@ -188,6 +235,7 @@ __global__ void __launch_bounds__(256) hash_encode_kernel(HashParams p) {
         sample_coords<D>(p, s, i);
         float* orow = p.out + s.n * LF;
         [[maybe_unused]] int64_t lev_off = 0;              // HSRC_U8: byte offset of level l = F * sum_{k<l} E_k
+        [[maybe_unused]] int64_t lev_dw = 0;               // HSRC_BITS: dword offset of level l = sum_{k<l} ceil(E_k F b / 32)
         [[maybe_unused]] U4 nblk{0u, 0u, 0u, 0u};          // NOISE: the generator block of columns (l F) & ~15 ..
         for (int l = 0; l < d.levels; ++l) {
             const uint32_t R = (uint32_t)d.resolution[l];
@@ -197,6 +245,11 @@ __global__ void __launch_bounds__(256) hash_encode_kernel(HashParams p) {
             if constexpr (SRC == HSRC_U8) {
                 stab = p.stored + lev_off;
                 lev_off += (int64_t)F * hash_level_entries(D, (int32_t)R, d.log2_table);
+            }
+            [[maybe_unused]] const uint32_t* btab = nullptr;
+            if constexpr (SRC == HSRC_BITS) {
+                btab = p.packed + lev_dw;
+                lev_dw += hash_level_dwords(D, (int32_t)R, d.log2_table, F, p.q_bits);
             }
             uint32_t v[3];
             float w[3];
@@ -209,6 +262,10 @@ __global__ void __launch_bounds__(256) hash_encode_kernel(HashParams p) {
                 const uint32_t e = hash_index(dense, R, mask, v[0] + (c & 1), v[1] + ((c >> 1) & 1), D == 3 ? v[2] + ((c >> 2) & 1) : 0u);
                 float t[F];
                 if constexpr (SRC == HSRC_U8) load_row_u8<F>(stab + (int64_t)e * F, p.q_scale, p.q_bias, t);
+                else if constexpr (SRC == HSRC_BITS) {
+                    if (p.q_tight) load_row_bits<F, true>(btab, e, p.q_bits, p.q_scale, p.q_bias, t);
+                    else load_row_bits<F, false>(btab, e, p.q_bits, p.q_scale, p.q_bias, t);
+                }
                 else load_row<F>(tab + (int64_t)e * F, t);
                 const float cw = corner_weight<D>(w, c);
 #pragma unroll
@@ -306,6 +363,63 @@ __global__ void __launch_bounds__(256) hash_pack_u8_kernel(HashPackParams p) {
     }
 }
 
+// fp32 [L, T, F] -> bit-packed: one output dword per thread, assembled in registers from the values whose bits fall into it (hash_pack_u8_kernel's
+// arithmetic per value, & (2^b - 1)); the level comes from the dword prefix pre[].  The padding bits and the two tail dwords come out zero.
+struct HashBitsParams {
+    const float* src;
+    uint32_t* packed;                            // pack: destination
+    const uint32_t* packed_in;                   // unpack: source
+    uint8_t* dst_u8;                             // unpack: the compact uint8 table
+    int64_t pre[NIC_HASH_MAX_LEVELS + 1];        // dword offset of level l in the packed table; pre[levels] = the first tail dword
+    int64_t pre_u8[NIC_HASH_MAX_LEVELS + 1];     // byte offset of level l in the compact uint8 table (= F * sum E_k: values before level l)
+    int levels, log2_table, features, bits;
+    float scale, bias;
+};
+__global__ void __launch_bounds__(256) hash_pack_bits_kernel(HashBitsParams p) {
+    const int64_t n = p.pre[p.levels] + 2;
+    const uint32_t vmask = (1u << p.bits) - 1u;
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+        int l = 0;
+        int64_t base = 0, vals = p.pre_u8[1];
+#pragma unroll
+        for (int j = 1; j < NIC_HASH_MAX_LEVELS; ++j) {
+            const bool past = j < p.levels && k >= p.pre[j];
+            l = past ? j : l;
+            base = past ? p.pre[j] : base;
+            vals = past ? p.pre_u8[j + 1] - p.pre_u8[j] : vals;
+        }
+        uint32_t w = 0u;
+        if (k < p.pre[p.levels]) {
+            const int64_t bit0 = (k - base) << 5;                       // first stream bit of this dword
+            const float* src = p.src + ((int64_t)l << p.log2_table) * p.features;
+            for (int64_t i = bit0 / p.bits; i < vals && i * p.bits < bit0 + 32; ++i) {
+                const float v = __fadd_rn(floorf(__fadd_rn(__fmul_rn(src[i], p.scale), 0.5f)), p.bias);
+                const uint32_t u = (uint32_t)(uint8_t)(int)v & vmask;
+                const int at = (int)(i * p.bits - bit0);                // -7 .. 31: a value may begin in the dword before
+                w |= at >= 0 ? u << at : u >> -at;
+            }
+        }
+        p.packed[k] = w;
+    }
+}
+// bit-packed -> compact uint8: one byte per thread (hash_pack_u8_kernel's shape), the value's two-dword window funnel-shifted and masked
+__global__ void __launch_bounds__(256) hash_unpack_bits_kernel(HashBitsParams p) {
+    const int64_t n = p.pre_u8[p.levels];
+    const uint32_t vmask = (1u << p.bits) - 1u;
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+        int64_t base = 0, dw = 0;
+#pragma unroll
+        for (int j = 1; j < NIC_HASH_MAX_LEVELS; ++j) {
+            const bool past = j < p.levels && k >= p.pre_u8[j];
+            base = past ? p.pre_u8[j] : base;
+            dw = past ? p.pre[j] : dw;
+        }
+        const int64_t bit = (k - base) * p.bits;
+        const uint32_t* q = p.packed_in + dw + (bit >> 5);
+        p.dst_u8[k] = (uint8_t)(__builtin_amdgcn_alignbit(q[1], q[0], (uint32_t)bit & 31u) & vmask);
+    }
+}
+
 static inline int hash_blocks(const nic_hash_desc* d) {
     const int PS = d->dim == 2 ? 8 : 4;
     int64_t patches = d->num_crops;
@@ -333,13 +447,14 @@ static int check_hash_desc(const nic_hash_desc* d) {
     return NIC_OK;
 }
 
-enum HashKernel { HK_FWD, HK_BWD, HK_FWD_NOISY, HK_FWD_U8 };
+enum HashKernel { HK_FWD, HK_BWD, HK_FWD_NOISY, HK_FWD_U8, HK_FWD_BITS };
 
 template <int K, int D, int F>
 static void launch_k(const HashParams& p, int nb, hipStream_t s) {
     if constexpr (K == HK_BWD) hipLaunchKernelGGL((hash_encode_backward_kernel<D, F>), dim3(nb), dim3(256), 0, s, p);
     else if constexpr (K == HK_FWD_NOISY) hipLaunchKernelGGL((hash_encode_kernel<D, F, HSRC_F32, true>), dim3(nb), dim3(256), 0, s, p);
     else if constexpr (K == HK_FWD_U8) hipLaunchKernelGGL((hash_encode_kernel<D, F, HSRC_U8, false>), dim3(nb), dim3(256), 0, s, p);
+    else if constexpr (K == HK_FWD_BITS) hipLaunchKernelGGL((hash_encode_kernel<D, F, HSRC_BITS, false>), dim3(nb), dim3(256), 0, s, p);
     else hipLaunchKernelGGL((hash_encode_kernel<D, F>), dim3(nb), dim3(256), 0, s, p);
 }
 
@@ -367,6 +482,17 @@ static int64_t hash_stored_prefix(const nic_hash_desc* d, int64_t* pre) {
     for (int l = 0; l < d->levels; ++l) {
         if (pre) pre[l] = off;
         off += (int64_t)d->features * hash_level_entries(d->dim, d->resolution[l], d->log2_table);
+    }
+    if (pre) pre[d->levels] = off;
+    return off;
+}
+
+// sum_l ceil(E_l F b / 32); pre (optional) gets the dword offset of every level and the first tail dword at [levels]
+static int64_t hash_packed_prefix(const nic_hash_desc* d, int num_bits, int64_t* pre) {
+    int64_t off = 0;
+    for (int l = 0; l < d->levels; ++l) {
+        if (pre) pre[l] = off;
+        off += hash_level_dwords(d->dim, d->resolution[l], d->log2_table, d->features, num_bits);
     }
     if (pre) pre[d->levels] = off;
     return off;
@@ -456,6 +582,63 @@ int64_t nic_hash_stored_bytes(const nic_hash_desc* desc) {
     const int rc = check_hash_desc(desc);
     if (rc) return rc;
     return hash_stored_prefix(desc, nullptr);
+}
+
+int64_t nic_hash_packed_bytes(const nic_hash_desc* desc, int num_bits) {
+    const int rc = check_hash_desc(desc);
+    if (rc) return rc;
+    if (num_bits < 1 || num_bits > 8) return NIC_E_ARG;
+    return 4 * hash_packed_prefix(desc, num_bits, nullptr) + 8;
+}
+
+int nic_hash_encode_bits(const nic_hash_desc* desc, int num_bits, const uint8_t* packed, const int32_t* origins, float* out, void* stream) {
+    const int rc = check_hash_desc(desc);
+    if (rc) return rc;
+    if (!packed || !origins || !out) return NIC_E_NULL;
+    if (num_bits < 1 || num_bits > 8) return NIC_E_ARG;
+    if ((uintptr_t)packed & 3u) return NIC_E_ARG;                    // the gather reads aligned dwords
+    HashParams p{};
+    p.d = *desc; p.packed = (const uint32_t*)packed; p.origins = origins; p.out = out;
+    p.q_bits = num_bits; p.q_tight = hash_bits_tight(desc->features, num_bits) ? 1 : 0;
+    set_dequant(p, num_bits);
+    return hash_launch<HK_FWD_BITS>(p, stream);
+}
+
+static int hash_bits_params(HashBitsParams& p, const nic_hash_desc* desc, int num_bits) {
+    p.levels = desc->levels; p.log2_table = desc->log2_table; p.features = desc->features; p.bits = num_bits;
+    p.scale = (float)((1 << num_bits) - 1);
+    p.bias = (float)((1 << (num_bits - 1)) - 1);
+    hash_stored_prefix(desc, p.pre_u8);
+    hash_packed_prefix(desc, num_bits, p.pre);
+    return 0;
+}
+
+int nic_hash_pack_bits(const nic_hash_desc* desc, int num_bits, const float* table, uint8_t* packed, void* stream) {
+    const int rc = check_hash_desc(desc);
+    if (rc) return rc;
+    if (!table || !packed) return NIC_E_NULL;
+    if (num_bits < 1 || num_bits > 8) return NIC_E_ARG;
+    if ((uintptr_t)packed & 3u) return NIC_E_ARG;
+    HashBitsParams p{};
+    hash_bits_params(p, desc, num_bits);
+    p.src = table; p.packed = (uint32_t*)packed;
+    const int64_t b = (p.pre[p.levels] + 2 + 255) / 256;
+    hipLaunchKernelGGL(hash_pack_bits_kernel, dim3((unsigned)(b > 4096 ? 4096 : b)), dim3(256), 0, (hipStream_t)stream, p);
+    return (int)hipGetLastError();
+}
+
+int nic_hash_unpack_bits(const nic_hash_desc* desc, int num_bits, const uint8_t* packed, uint8_t* stored, void* stream) {
+    const int rc = check_hash_desc(desc);
+    if (rc) return rc;
+    if (!packed || !stored) return NIC_E_NULL;
+    if (num_bits < 1 || num_bits > 8) return NIC_E_ARG;
+    if ((uintptr_t)packed & 3u) return NIC_E_ARG;
+    HashBitsParams p{};
+    hash_bits_params(p, desc, num_bits);
+    p.packed_in = (const uint32_t*)packed; p.dst_u8 = stored;
+    const int64_t b = (p.pre_u8[p.levels] + 255) / 256;
+    hipLaunchKernelGGL(hash_unpack_bits_kernel, dim3((unsigned)(b > 4096 ? 4096 : b)), dim3(256), 0, (hipStream_t)stream, p);
+    return (int)hipGetLastError();
 }
 
 }  // extern "C"

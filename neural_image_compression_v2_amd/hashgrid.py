@@ -23,6 +23,10 @@ a dense level keeps only the (R + 1)^d vertices it can address) with the decoder
 those bytes (``nic_hash_encode_u8``).  The schedule is the dense one (image_compression.py:237,385): noise while the epoch is below 0.95 N, then
 freeze - ``fit`` runs it.
 
+``save_compressed(path, packed=True)`` stores the table bit-packed instead, b bits per value (``nic_hash_pack_bits``; format tag
+``nicv2-hashgrid-bits/1``, layout in include/nicv2_hip.h); ``load_compressed`` reads either form and ``decode()`` of a packed field gathers from
+the packed bits (``nic_hash_encode_bits`` / ``nic_hash_fused_forward_bits``) without ever unpacking the table.
+
 ``HashGridField(..., fused=True)`` runs the same step as TWO launches: one kernel gathers, decodes, forms the loss, back-propagates
 and scatters (``nic_hash_fused_forward_backward``; the [N, L F] row never reaches memory), the reduction of its decoder-gradient records carries
 the optimiser.  ``decode`` is one launch per tile.  Shapes outside the kernel's set (``nic_hash_fused_supported``) take the layer-wise route by
@@ -222,6 +226,58 @@ def hash_encode_u8(geo: HashGeometry, stored: torch.Tensor, coord, extent: Seque
     return out
 
 
+def hash_packed_bytes(geo: HashGeometry, num_bits: int) -> int:
+    """bytes of the bit-packed table: 4 * sum_l ceil(E_l F b / 32) + 8 (nic_hash_packed_bytes)"""
+    n = _lib.load().nic_hash_packed_bytes(ctypes.byref(geo.to_desc(1, [1] * geo.dim)), int(num_bits))
+    _lib.check(n if n < 0 else 0, "nic_hash_packed_bytes")
+    return int(n)
+
+
+def _check_packed(geo: HashGeometry, packed: torch.Tensor, num_bits: int) -> None:
+    if not isinstance(packed, torch.Tensor) or packed.dtype != torch.uint8 or not packed.is_cuda or packed.dim() != 1 or not packed.is_contiguous():
+        raise ValueError("packed must be a contiguous 1-D uint8 tensor on a HIP device")
+    if packed.numel() != hash_packed_bytes(geo, num_bits):
+        raise ValueError(f"packed holds {packed.numel()} bytes, the geometry needs {hash_packed_bytes(geo, num_bits)} at {int(num_bits)} bits")
+    if packed.data_ptr() % 4:
+        raise ValueError("packed must start on a 4-byte boundary: the gather reads aligned dwords")
+
+
+@fused._on_tensor_device
+def hash_pack_bits(geo: HashGeometry, table: torch.Tensor, num_bits: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the bit-packed table of an fp32 [L, T, F] one (nic_hash_pack_bits): ``hash_pack_u8``'s value & (2^b - 1) in b bits, each level's stream
+    padded to whole dwords, 8 zero bytes at the end.  ``out``: a buffer of ``hash_packed_bytes`` to fill (every byte is written)."""
+    t = _check_table(geo, table.detach())
+    if out is None:
+        out = torch.empty(hash_packed_bytes(geo, num_bits), dtype=torch.uint8, device=t.device)
+    _check_packed(geo, out, num_bits)
+    _lib.check(_lib.load().nic_hash_pack_bits(ctypes.byref(geo.to_desc(1, [1] * geo.dim)), int(num_bits), _lib.ptr(t), _lib.ptr(out), _lib.stream_ptr(t.device)),
+               "nic_hash_pack_bits")
+    return out
+
+
+@fused._on_tensor_device
+def hash_unpack_bits(geo: HashGeometry, packed: torch.Tensor, num_bits: int) -> torch.Tensor:
+    """the compact uint8 table (``hash_pack_u8``'s layout) a bit-packed one stores (nic_hash_unpack_bits)"""
+    _check_packed(geo, packed, num_bits)
+    out = torch.empty(hash_stored_bytes(geo), dtype=torch.uint8, device=packed.device)
+    _lib.check(_lib.load().nic_hash_unpack_bits(ctypes.byref(geo.to_desc(1, [1] * geo.dim)), int(num_bits), _lib.ptr(packed), _lib.ptr(out),
+                                                _lib.stream_ptr(packed.device)), "nic_hash_unpack_bits")
+    return out
+
+
+@fused._on_tensor_device
+def hash_encode_bits(geo: HashGeometry, packed: torch.Tensor, coord, extent: Sequence[int], num_bits: int) -> torch.Tensor:
+    """``hash_encode_u8`` from the bit-packed table (nic_hash_encode_bits): the same rows, bit for bit"""
+    _check_packed(geo, packed, num_bits)
+    org = geo.upload_origins(coord, extent, packed.device)
+    num_crops = org.shape[0]
+    out = torch.empty(_n_samples(num_crops, extent), geo.width, dtype=torch.float32, device=packed.device)
+    d = geo.to_desc(num_crops, extent)
+    _lib.check(_lib.load().nic_hash_encode_bits(ctypes.byref(d), int(num_bits), _lib.ptr(packed), _lib.ptr(org), _lib.ptr(out), _lib.stream_ptr(packed.device)),
+               "nic_hash_encode_bits")
+    return out
+
+
 def hash_fused_supported(geo: HashGeometry, hidden: int = 64, n_linear: int = 3) -> bool:
     """whether the fused encode + decoder kernels exist for this geometry and decoder (nic_hash_fused_supported: the only copy of the set)"""
     return _lib.load().nic_hash_fused_supported(ctypes.byref(geo.to_desc(1, [1] * geo.dim)), int(hidden), int(n_linear)) == 0
@@ -264,6 +320,20 @@ def hash_fused_forward_u8(geo: HashGeometry, stored: torch.Tensor, coord, extent
     d, m = geo.to_desc(org.shape[0], extent), fused._mlp_struct(params)
     _lib.check(_lib.load().nic_hash_fused_forward_u8(ctypes.byref(d), int(num_bits), _lib.ptr(stored), _lib.ptr(org), ctypes.byref(m), _lib.ptr(y),
                                                      _lib.stream_ptr(stored.device)), "nic_hash_fused_forward_u8")
+    return y
+
+
+@fused._on_tensor_device
+def hash_fused_forward_bits(geo: HashGeometry, packed: torch.Tensor, coord, extent: Sequence[int], num_bits: int,
+                            params: Sequence[torch.Tensor]) -> torch.Tensor:
+    """``hash_fused_forward_u8`` from the bit-packed table (nic_hash_fused_forward_bits)"""
+    _check_packed(geo, packed, num_bits)
+    params = _check_fused_decoder(geo, [q.detach() for q in params])
+    org = geo.upload_origins(coord, extent, packed.device)
+    y = torch.empty(_n_samples(org.shape[0], extent), 3, dtype=torch.float32, device=packed.device)
+    d, m = geo.to_desc(org.shape[0], extent), fused._mlp_struct(params)
+    _lib.check(_lib.load().nic_hash_fused_forward_bits(ctypes.byref(d), int(num_bits), _lib.ptr(packed), _lib.ptr(org), ctypes.byref(m), _lib.ptr(y),
+                                                       _lib.stream_ptr(packed.device)), "nic_hash_fused_forward_bits")
     return y
 
 
@@ -331,7 +401,20 @@ def hash_encode_differentiable(geo: HashGeometry, table: torch.Tensor, coord, ex
     return HashEncodeFunction.apply(table, geo, org, tuple(int(e) for e in extent))
 
 
+def _table_of_u8(geo: HashGeometry, stored: torch.Tensor, num_bits: int) -> torch.Tensor:
+    """the fp32 [L, T, F] table a compact uint8 one stores (load4fp per level; the entries a dense level cannot address stay zero) - the input
+    ``hash_pack_bits`` takes when a uint8 file is re-saved packed; save4fp of these values gives the bytes back"""
+    table = torch.zeros(geo.table_shape(), dtype=torch.float32, device=stored.device)
+    off = 0
+    for l, r in enumerate(geo.resolutions):
+        e = min((int(r) + 1) ** geo.dim, geo.table_size)
+        table[l, :e] = models.load4fp(stored[off:off + e * geo.features], num_bits).reshape(e, geo.features)
+        off += e * geo.features
+    return table
+
+
 COMPRESSED_FORMAT = "nicv2-hashgrid-u8/1"
+PACKED_FORMAT = "nicv2-hashgrid-bits/1"          # the same dict with the bit-packed table (include/nicv2_hip.h, nic_hash_pack_bits)
 
 
 class HashGridField:
@@ -363,7 +446,7 @@ class HashGridField:
         self.scheduler = None
         self.hidden, self.n_linear = int(hidden), int(n_linear)
         self.num_bits = None if num_bits is None else int(num_bits)
-        self.noise_seed, self.steps, self.frozen, self.stored = int(noise_seed), 0, False, None
+        self.noise_seed, self.steps, self.frozen, self.stored, self.packed = int(noise_seed), 0, False, None, None
         self._pass_samples = 0                       # samples of the current accumulate pass so far: the next chunk's sample_base
         self._set_route(fused)
         if self.num_bits is not None:
@@ -516,41 +599,55 @@ class HashGridField:
             hist.append(tot)
         return [float(h) for h in hist]
 
-    def stored_bytes(self) -> dict:
-        """bytes ``save_compressed`` stores: the compact uint8 table and the fp32 decoder"""
-        return {"table": hash_stored_bytes(self.geo), "decoder": sum(v.numel() * v.element_size() for v in self.decoder.state_dict().values())}
+    def stored_bytes(self, packed: bool = False) -> dict:
+        """bytes ``save_compressed`` stores: the compact uint8 table (``packed``: the bit-packed one) and the fp32 decoder"""
+        if packed and self.num_bits is None:
+            raise RuntimeError("the packed size needs num_bits")
+        table = hash_packed_bytes(self.geo, self.num_bits) if packed else hash_stored_bytes(self.geo)
+        return {"table": table, "decoder": sum(v.numel() * v.element_size() for v in self.decoder.state_dict().values())}
 
     @torch.no_grad()
-    def save_compressed(self, path) -> None:
-        """one ``torch.save`` dict: format tag, geometry, num_bits, the compact uint8 table of a clamped copy of the table, the decoder"""
+    def save_compressed(self, path, packed: bool = False) -> None:
+        """one ``torch.save`` dict: format tag, geometry, num_bits, the compact uint8 table of a clamped copy of the table (``packed``: the
+        bit-packed table, num_bits bits per value, under the tag ``nicv2-hashgrid-bits/1``), the decoder.  A decode-only field re-saves the table
+        it holds, converted on the device when the other form is asked for."""
         if self.num_bits is None:
             raise RuntimeError("save_compressed needs num_bits")
-        if self.table is None:
-            stored = self.stored
+        if self.table is not None:
+            clamped = models.quantize_clamp(self.table, self.num_bits)
+            stored = hash_pack_bits(self.geo, clamped, self.num_bits) if packed else hash_pack_u8(self.geo, clamped, self.num_bits)
+        elif packed:
+            stored = self.packed if self.packed is not None else hash_pack_bits(self.geo, _table_of_u8(self.geo, self.stored, self.num_bits), self.num_bits)
         else:
-            stored = hash_pack_u8(self.geo, models.quantize_clamp(self.table, self.num_bits), self.num_bits)
-        torch.save({"format": COMPRESSED_FORMAT, "field_size": list(self.field_size), "resolutions": list(self.geo.resolutions),
+            stored = self.stored if self.stored is not None else hash_unpack_bits(self.geo, self.packed, self.num_bits)
+        torch.save({"format": PACKED_FORMAT if packed else COMPRESSED_FORMAT, "field_size": list(self.field_size), "resolutions": list(self.geo.resolutions),
                     "features": self.geo.features, "log2_table": self.geo.log2_table, "num_bits": self.num_bits, "hidden": self.hidden,
                     "n_linear": self.n_linear, "table": stored.cpu(), "decoder": {k: v.detach().cpu() for k, v in self.decoder.state_dict().items()}}, path)
 
     @classmethod
     def load_compressed(cls, path, device=None, fused: bool = False) -> "HashGridField":
-        """a decode-only field from ``save_compressed``'s file: ``decode()`` gathers from the uint8 table (nic_hash_encode_u8; ``fused``:
-        nic_hash_fused_forward_u8), no fp32 table"""
+        """a decode-only field from ``save_compressed``'s file, either format: ``decode()`` gathers from the table as stored - uint8
+        (nic_hash_encode_u8; ``fused``: nic_hash_fused_forward_u8) or bit-packed (nic_hash_encode_bits / nic_hash_fused_forward_bits) - with no
+        fp32 table and no conversion between the two"""
         d = torch.load(path, map_location="cpu", weights_only=True)
-        if not isinstance(d, dict) or d.get("format") != COMPRESSED_FORMAT:
-            raise ValueError(f"{path}: not a {COMPRESSED_FORMAT} file")
+        if not isinstance(d, dict) or d.get("format") not in (COMPRESSED_FORMAT, PACKED_FORMAT):
+            raise ValueError(f"{path}: not a {COMPRESSED_FORMAT} or {PACKED_FORMAT} file")
+        is_packed = d["format"] == PACKED_FORMAT
         self = cls.__new__(cls)
-        self.device = torch.device(device if device is not None else "cuda")
-        if self.device.type != "cuda":
-            raise RuntimeError("HashGridField needs a HIP device: there is no CPU implementation of this path")
         self.field_size = tuple(int(v) for v in d["field_size"])
         self.geo = HashGeometry(self.field_size, tuple(int(r) for r in d["resolutions"]), int(d["features"]), int(d["log2_table"]))
         self.num_bits, self.hidden, self.n_linear = int(d["num_bits"]), int(d["hidden"]), int(d["n_linear"])
+        if not 1 <= self.num_bits <= 8:
+            raise ValueError(f"{path}: num_bits {self.num_bits}")
         stored = d["table"]
-        if stored.dtype != torch.uint8 or stored.numel() != hash_stored_bytes(self.geo):
-            raise ValueError(f"{path}: the table holds {stored.numel()} {stored.dtype} values, the geometry needs {hash_stored_bytes(self.geo)} bytes")
-        self.stored = stored.to(self.device).contiguous()
+        need = hash_packed_bytes(self.geo, self.num_bits) if is_packed else hash_stored_bytes(self.geo)
+        if not isinstance(stored, torch.Tensor) or stored.dtype != torch.uint8 or stored.dim() != 1 or stored.numel() != need:
+            raise ValueError(f"{path}: the table holds {stored.numel()} {stored.dtype} values, a {d['format']} file of this geometry needs {need} bytes")
+        self.device = torch.device(device if device is not None else "cuda")
+        if self.device.type != "cuda":
+            raise RuntimeError("HashGridField needs a HIP device: there is no CPU implementation of this path")
+        stored = stored.to(self.device).contiguous()
+        self.stored, self.packed = (None, stored) if is_packed else (stored, None)
         self.table = None
         self.decoder = ColorDecoder(self.geo.width, self.hidden, self.n_linear).to(self.device)
         self.decoder.load_state_dict(d["decoder"])
@@ -561,7 +658,7 @@ class HashGridField:
 
     @torch.no_grad()
     def decode(self, tile: int = 1024) -> torch.Tensor:
-        """the whole field [S_x, S_y(, S_z), 3], in tiles of side <= ``tile`` (a field from ``load_compressed``: from its uint8 table)"""
+        """the whole field [S_x, S_y(, S_z), 3], in tiles of side <= ``tile`` (a field from ``load_compressed``: from its uint8 or bit-packed table)"""
         size = self.field_size
         out = torch.empty(*size, 3, dtype=torch.float32, device=self.device)
         params = [p.detach() for p in self.decoder.linear_params()]
@@ -570,10 +667,19 @@ class HashGridField:
             ext = [min(tile, s - a) for s, a in zip(size, o)]
             sl = tuple(slice(a, a + e) for a, e in zip(o, ext))
             if self.route == "fused":
-                y = hash_fused_forward_u8(self.geo, self.stored, [o], ext, self.num_bits, params) if table is None \
-                    else hash_fused_forward(self.geo, table, [o], ext, params)
+                if table is not None:
+                    y = hash_fused_forward(self.geo, table, [o], ext, params)
+                elif self.packed is not None:
+                    y = hash_fused_forward_bits(self.geo, self.packed, [o], ext, self.num_bits, params)
+                else:
+                    y = hash_fused_forward_u8(self.geo, self.stored, [o], ext, self.num_bits, params)
                 out[sl] = y.reshape(*ext, 3)
                 continue
-            x = hash_encode_u8(self.geo, self.stored, [o], ext, self.num_bits) if table is None else hash_encode(self.geo, table, [o], ext)
+            if table is not None:
+                x = hash_encode(self.geo, table, [o], ext)
+            elif self.packed is not None:
+                x = hash_encode_bits(self.geo, self.packed, [o], ext, self.num_bits)
+            else:
+                x = hash_encode_u8(self.geo, self.stored, [o], ext, self.num_bits)
             out[sl] = fused.DecoderFunction.apply(x, *params).reshape(*ext, 3)
         return out
