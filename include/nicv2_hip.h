@@ -557,6 +557,43 @@ int nic_hash_fused_forward_backward(const nic_hash_desc *desc, const nic_hash_qu
                                     const nic_mlp_grads *mlp_grads, float *loss, float *y, int flags, void *workspace, size_t workspace_bytes,
                                     const nic_step_tail *tail, void *stream);
 
+/* ---- the hash-grid field at arbitrary points (hashgrid.py, HashGridField.query / resample / train_points).
+ *      A point is `dim` fp32 coordinates in SAMPLE UNITS: p_a = i is the centre of integer sample i, the field spans [-1/2, S_a - 1/2].
+ *      points = [n_points, dim] fp32 (device; the host never reads it), row n of every output belongs to point n, in any order.
+ *      For these entry points desc->extent[a] is the field size S_a and desc->num_crops must be 1 (else NIC_E_SHAPE).
+ *      Fixed point with 8 fractional bits, so that the cell arithmetic stays exact integer:
+ *        p_a is first clamped in floating point to [-1/2, S_a - 1/2] (NaN -> the low edge, -inf / +inf -> the nearer edge);
+ *        t_a = rint(256 p_a) + 128 (round half to even; 256 p_a is exact), clamped to [0, 256 S_a - 1];
+ *        per level q = t_a R_l as an exact integer (< 2^38), v_a = q div (256 S_max), w_a = fp32(q mod 256 S_max) / fp32(256 S_max).
+ *      Entry index, corner weights, blend and column layout are nic_hash_encode's, unchanged.  Consequences:
+ *      - at a sample centre t = 128 (2 i + 1): q is 128 times the lattice route's q and the divisor 128 times its 2 S_max, so v is identical
+ *        and w is the same fp32 quotient (scaling both operands by a power of two is exact): the row equals nic_hash_encode's bit for bit
+ *        (and nic_hash_encode_noisy's / _u8's / _bits' for the other sources, the noise keyed by sample_base + n and the column);
+ *      - the upper clamp keeps v_a <= R_l - 1, corner v + 1 never exceeds R_l: a dense level of the compact uint8 or packed table is never
+ *        read past its E_l entries, and no input - out of range, NaN, infinite - can address outside a level; a point outside the field gives
+ *        exactly the row of the clamped point.
+ *      Host checks on top of nic_hash_encode's, all before any GPU work, codes in the order of the crop siblings (descriptor, null pointers,
+ *      arguments): 256 S_max < 2^30 (else NIC_E_ARG; every field the descriptor accepts at 4K or 256^3 passes); the source: kind one of
+ *      NIC_HASH_SRC_*, num_bits 0 for F32 and 1 .. 8 for U8 / BITS, a BITS table 4-byte aligned (else NIC_E_ARG); `quant` (null, or the
+ *      noise of nic_hash_encode_noisy) only with an F32 source (else NIC_E_ARG); n_points < 0 is NIC_E_ARG, n_points == 0 is NIC_OK with
+ *      no launch.  nic_hash_encode_points_backward is the straight-through scatter of nic_hash_encode_backward (ADDS into table_grad, fp32
+ *      atomics, order not fixed).  nic_hash_fused_forward_points is nic_hash_fused_forward / _u8 / _bits at points ([n_points, 3]; the set
+ *      nic_hash_fused_supported answers for).  There is no fused training at points. */
+#define NIC_HASH_SRC_F32 0   /* fp32 [levels, T, features] table */
+#define NIC_HASH_SRC_U8 1    /* compact uint8 table (nic_hash_pack_u8) */
+#define NIC_HASH_SRC_BITS 2  /* bit-packed table (nic_hash_pack_bits) */
+typedef struct nic_hash_source {
+    int32_t kind;            /* NIC_HASH_SRC_F32 / _U8 / _BITS */
+    int32_t num_bits;        /* 1 .. 8 for U8 / BITS, 0 for F32 */
+    const void *data;
+} nic_hash_source;
+int nic_hash_encode_points(const nic_hash_desc *desc, const nic_hash_source *src, const nic_hash_quant *quant, const float *points,
+                           int64_t n_points, float *out, void *stream);
+int nic_hash_encode_points_backward(const nic_hash_desc *desc, const float *points, int64_t n_points, const float *dx, float *table_grad,
+                                    void *stream);
+int nic_hash_fused_forward_points(const nic_hash_desc *desc, const nic_hash_source *src, const float *points, int64_t n_points,
+                                  const nic_mlp *mlp, float *y, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

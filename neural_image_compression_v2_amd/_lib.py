@@ -117,6 +117,14 @@ class NicHashQuant(ctypes.Structure):
                 ("sample_base", ctypes.c_int64)]
 
 
+NIC_HASH_SRC_F32, NIC_HASH_SRC_U8, NIC_HASH_SRC_BITS = 0, 1, 2
+
+
+class NicHashSource(ctypes.Structure):
+    """struct nic_hash_source (include/nicv2_hip.h): the table a point launch reads - fp32, compact uint8 or bit-packed (hashgrid.py)"""
+    _fields_ = [("kind", ctypes.c_int32), ("num_bits", ctypes.c_int32), ("data", ctypes.c_void_p)]
+
+
 _P, _I, _L, _F, _SZ, _DBL = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t, ctypes.c_double
 _D = ctypes.POINTER(NicPathDesc)
 _M = ctypes.POINTER(NicMlp)
@@ -186,6 +194,9 @@ SIGNATURES = {
     "nic_hash_fused_forward_bits": (_I, [ctypes.POINTER(NicHashDesc), _I, _P, _P, _M, _P, _P]),
     "nic_hash_fused_forward_backward": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashQuant), _P, _P, _M, _P, _F, _P, _G, _P, _P, _I, _P, _SZ,
                                              ctypes.POINTER(NicStepTail), _P]),
+    "nic_hash_encode_points": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashSource), ctypes.POINTER(NicHashQuant), _P, _L, _P, _P]),
+    "nic_hash_encode_points_backward": (_I, [ctypes.POINTER(NicHashDesc), _P, _L, _P, _P, _P]),
+    "nic_hash_fused_forward_points": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashSource), _P, _L, _M, _P, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -30,7 +30,14 @@ the packed bits (``nic_hash_encode_bits`` / ``nic_hash_fused_forward_bits``) wit
 ``HashGridField(..., fused=True)`` runs the same step as TWO launches: one kernel gathers, decodes, forms the loss, back-propagates
 and scatters (``nic_hash_fused_forward_backward``; the [N, L F] row never reaches memory), the reduction of its decoder-gradient records carries
 the optimiser.  ``decode`` is one launch per tile.  Shapes outside the kernel's set (``nic_hash_fused_supported``) take the layer-wise route by
-themselves; ``field.route`` says which one runs."""
+themselves; ``field.route`` says which one runs.
+
+Off the lattice (include/nicv2_hip.h, nic_hash_encode_points): a point is ``dim`` fp32 coordinates in sample units, p_a = i the
+centre of sample i, the field spanning [-1/2, S_a - 1/2]; t_a = rint(256 p_a) + 128 clamped to [0, 256 S_a - 1], q = t_a R_l, v_a = q div
+256 S_max, w_a = fp32(q mod 256 S_max) / fp32(256 S_max) - at a sample centre the lattice row, bit for bit.  ``hash_encode_points`` /
+``hash_encode_points_backward`` / ``hash_fused_forward_points`` (csrc/hash_points.hip) take a [N, dim] device tensor in any order;
+``HashGridField.query`` decodes at points from whichever table the field holds, ``resample`` on a regular grid of any size, ``train_points``
+is ``train_step`` on (point, colour) samples (layer-wise on either route: there is no fused training at points)."""
 from __future__ import annotations
 
 import ctypes
@@ -378,6 +385,101 @@ def hash_fused_forward_backward(geo: HashGeometry, table: torch.Tensor, coord, e
     return loss, y
 
 
+POINT_SOURCES = {"f32": _lib.NIC_HASH_SRC_F32, "u8": _lib.NIC_HASH_SRC_U8, "bits": _lib.NIC_HASH_SRC_BITS}
+
+
+def _check_points(geo: HashGeometry, points: torch.Tensor) -> torch.Tensor:
+    """[N, dim] fp32 on the device, contiguous; the values are the kernel's business (it clamps: the host never reads them)"""
+    pts = _lib.require_cuda_f32(points.detach() if isinstance(points, torch.Tensor) else points, "points")
+    if pts.dim() != 2 or pts.shape[1] != geo.dim:
+        raise ValueError(f"points must be [N, {geo.dim}] for a {geo.dim}D field, got {tuple(pts.shape)}")
+    return pts
+
+
+def _point_desc(geo: HashGeometry) -> "_lib.NicHashDesc":
+    if 256 * geo.s_max >= 2 ** 30:
+        raise ValueError(f"a field of {geo.s_max} samples per axis is too large for the point entry points: 256 * S_max < 2^30")
+    return geo.to_desc(1, geo.field_size)
+
+
+def _point_source(geo: HashGeometry, data: torch.Tensor, kind: str, num_bits: Optional[int]) -> Tuple["_lib.NicHashSource", torch.Tensor]:
+    """``nic_hash_source`` of a table: kind "f32" = the fp32 [L, T, F] table, "u8" = the compact uint8 one, "bits" = the bit-packed one"""
+    if kind not in POINT_SOURCES:
+        raise ValueError(f"table source {kind!r}: one of {sorted(POINT_SOURCES)}")
+    if kind == "f32":
+        if num_bits is not None:
+            raise ValueError("an fp32 table has no num_bits")
+        data = _check_table(geo, data.detach())
+        return _lib.NicHashSource(POINT_SOURCES[kind], 0, data.data_ptr()), data
+    if num_bits is None or not 1 <= int(num_bits) <= 8:
+        raise ValueError("a stored table needs its num_bits in 1 .. 8")
+    if kind == "bits":
+        _check_packed(geo, data, num_bits)
+    else:
+        if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or not data.is_cuda or data.dim() != 1 or not data.is_contiguous():
+            raise ValueError("stored must be a contiguous 1-D uint8 tensor on a HIP device")
+        if data.numel() != hash_stored_bytes(geo):
+            raise ValueError(f"stored holds {data.numel()} bytes, the geometry needs {hash_stored_bytes(geo)}")
+    return _lib.NicHashSource(POINT_SOURCES[kind], int(num_bits), data.data_ptr()), data
+
+
+@fused._on_tensor_device
+def hash_encode_points(geo: HashGeometry, data: torch.Tensor, points: torch.Tensor, kind: str = "f32", num_bits: Optional[int] = None,
+                       quant=None) -> torch.Tensor:
+    """[N, L F] encoding at ``points`` [N, dim] (fp32, sample units: p = i is the centre of sample i; anything outside [-1/2, S - 1/2] or not
+    finite is clamped by the kernel) from the table ``data`` of ``kind`` "f32" / "u8" / "bits" (nic_hash_encode_points).  ``quant``: None or
+    (num_bits, seed, offset, sample_base) for ``hash_encode_noisy``'s noise keyed by sample_base + row (fp32 table only)."""
+    src, data = _point_source(geo, data, kind, num_bits)
+    pts = _check_points(geo, points)
+    d = _point_desc(geo)
+    out = torch.empty(pts.shape[0], geo.width, dtype=torch.float32, device=data.device)
+    q = None
+    if quant is not None:
+        if kind != "f32":
+            raise ValueError("noise belongs to training, which reads the fp32 table")
+        bits, seed, offset, base = quant
+        q = _lib.NicHashQuant(int(bits), _lib.NIC_NOISE_KERNEL, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(base))
+    if pts.shape[0] == 0:
+        return out
+    _lib.check(_lib.load().nic_hash_encode_points(ctypes.byref(d), ctypes.byref(src), None if q is None else ctypes.byref(q), _lib.ptr(pts), pts.shape[0],
+                                                  _lib.ptr(out), _lib.stream_ptr(data.device)), "nic_hash_encode_points")
+    return out
+
+
+@fused._on_tensor_device
+def hash_encode_points_backward(geo: HashGeometry, points: torch.Tensor, dx: torch.Tensor, table_grad: torch.Tensor) -> None:
+    """ADDS d loss / d table for the [N, L F] gradient ``dx`` of ``hash_encode_points`` into ``table_grad`` (nic_hash_encode_points_backward;
+    fp32 atomics, neighbouring points of one cell summed first)"""
+    g = _check_table(geo, table_grad, "table_grad")
+    if g is not table_grad:
+        raise ValueError("table_grad must be contiguous: the kernel adds into it in place")
+    pts = _check_points(geo, points)
+    dx = _lib.require_cuda_f32(dx, "dx")
+    if tuple(dx.shape) != (pts.shape[0], geo.width):
+        raise ValueError(f"dx must be [{pts.shape[0]}, {geo.width}], got {tuple(dx.shape)}")
+    d = _point_desc(geo)
+    if pts.shape[0] == 0:
+        return
+    _lib.check(_lib.load().nic_hash_encode_points_backward(ctypes.byref(d), _lib.ptr(pts), pts.shape[0], _lib.ptr(dx), _lib.ptr(g), _lib.stream_ptr(g.device)),
+               "nic_hash_encode_points_backward")
+
+
+@fused._on_tensor_device
+def hash_fused_forward_points(geo: HashGeometry, data: torch.Tensor, points: torch.Tensor, params: Sequence[torch.Tensor], kind: str = "f32",
+                              num_bits: Optional[int] = None) -> torch.Tensor:
+    """[N, 3] = ColorDecoder(hash_encode_points(...)) in one launch (nic_hash_fused_forward_points); ``params`` = W1, b1, W2, b2, W3, b3"""
+    src, data = _point_source(geo, data, kind, num_bits)
+    params = _check_fused_decoder(geo, [q.detach() for q in params])
+    pts = _check_points(geo, points)
+    d, m = _point_desc(geo), fused._mlp_struct(params)
+    y = torch.empty(pts.shape[0], 3, dtype=torch.float32, device=data.device)
+    if pts.shape[0] == 0:
+        return y
+    _lib.check(_lib.load().nic_hash_fused_forward_points(ctypes.byref(d), ctypes.byref(src), _lib.ptr(pts), pts.shape[0], ctypes.byref(m), _lib.ptr(y),
+                                                         _lib.stream_ptr(data.device)), "nic_hash_fused_forward_points")
+    return y
+
+
 class HashEncodeFunction(torch.autograd.Function):
     """``hash_encode`` as a differentiable op of the table: backward = ``nic_hash_encode_backward`` into a fresh zero [L, T, F] (what autograd
     through ``index_add`` of the corner entries would give, collisions summed)"""
@@ -399,6 +501,31 @@ def hash_encode_differentiable(geo: HashGeometry, table: torch.Tensor, coord, ex
     if not table.requires_grad:
         return hash_encode(geo, table, org, extent)
     return HashEncodeFunction.apply(table, geo, org, tuple(int(e) for e in extent))
+
+
+class HashEncodePointsFunction(torch.autograd.Function):
+    """``hash_encode_points`` as a differentiable op of the fp32 table (not of the points): backward = ``nic_hash_encode_points_backward``
+    into a fresh zero [L, T, F]"""
+
+    @staticmethod
+    def forward(ctx, table, geo: HashGeometry, points: torch.Tensor):
+        ctx.geo, ctx.points = geo, points
+        return hash_encode_points(geo, table, points)
+
+    @staticmethod
+    def backward(ctx, dx):
+        g = torch.zeros(ctx.geo.table_shape(), dtype=torch.float32, device=dx.device)
+        hash_encode_points_backward(ctx.geo, ctx.points, dx, g)
+        return g, None, None
+
+
+def hash_encode_points_differentiable(geo: HashGeometry, table: torch.Tensor, points: torch.Tensor) -> torch.Tensor:
+    """[N, L F] at ``points``, differentiable w.r.t. the fp32 ``table`` when it requires a gradient (``HashEncodePointsFunction``): the point
+    counterpart of ``hash_encode_differentiable``, for callers that put their own decoder and loss behind the encoding"""
+    pts = _check_points(geo, points)
+    if not table.requires_grad:
+        return hash_encode_points(geo, table, pts)
+    return HashEncodePointsFunction.apply(table, geo, pts)
 
 
 def _table_of_u8(geo: HashGeometry, stored: torch.Tensor, num_bits: int) -> torch.Tensor:
@@ -510,6 +637,56 @@ class HashGridField:
         loss.backward()
         if not frozen:
             hash_encode_backward(self.geo, org, extent, x.grad, grad)
+            self._grad_clean = False
+        if step:
+            self.optimizer.step()
+            if not frozen:
+                self._grad_clean = self.optimizer.zeroed_in_last_step(grad)
+            if self.scheduler is not None:
+                self.scheduler.step()
+            self.steps += 1
+        return loss.detach()
+
+    def train_points(self, points: torch.Tensor, target: torch.Tensor, accumulate: bool = False, scale: float = 1.0, step: bool = True,
+                     noise: Optional[bool] = None) -> torch.Tensor:
+        """``train_step`` on samples that are no raster: ``points`` [N, dim] (fp32, sample units, any order) with their colours ``target``
+        [N, 3].  ``accumulate`` / ``scale`` / ``step`` / ``noise``, the noise keys (seed, optimiser step, samples of this pass before this
+        chunk + row), the freeze behaviour and the optimiser bookkeeping are ``train_step``'s on the layer-wise route, which a fused field
+        takes too for this call (there is no fused training at points): on a crop's sample centres in raster order the two calls differ in
+        the order of the gradient atomics only."""
+        if self.table is None:
+            raise RuntimeError("a field from load_compressed decodes only")
+        params = self.decoder.linear_params()
+        grad = self.table.grad
+        frozen = self.frozen
+        # every check comes before the first write: a refused call leaves an accumulate pass as it was
+        pts = _check_points(self.geo, points)
+        n = pts.shape[0]
+        if n < 1:
+            raise ValueError("no points")
+        if tuple(target.shape) != (n, 3):
+            raise ValueError(f"target must be [{n}, 3], got {tuple(target.shape)}")
+        if noise is None:
+            noise = self.num_bits is not None and not frozen
+        if noise and self.num_bits is None:
+            raise ValueError("noise needs num_bits: its amplitude is one quantisation step")
+        _point_desc(self.geo)
+        if not accumulate:
+            for p in params:
+                p.grad = None
+            if not frozen and not self._grad_clean:
+                grad.zero_()
+            self._pass_samples = 0
+        quant = (self.num_bits, self.noise_seed, self.steps, self._pass_samples) if noise else None
+        x = hash_encode_points(self.geo, self.table, pts, quant=quant)
+        self._pass_samples += n
+        if not frozen:
+            x.requires_grad_(True)
+        y = fused.DecoderFunction.apply(x, *params)
+        loss = ((y - target) ** 2).mean() * scale
+        loss.backward()
+        if not frozen:
+            hash_encode_points_backward(self.geo, pts, x.grad, grad)
             self._grad_clean = False
         if step:
             self.optimizer.step()
@@ -682,4 +859,48 @@ class HashGridField:
             else:
                 x = hash_encode_u8(self.geo, self.stored, [o], ext, self.num_bits)
             out[sl] = fused.DecoderFunction.apply(x, *params).reshape(*ext, 3)
+        return out
+
+    def _point_table(self) -> Tuple[torch.Tensor, str, Optional[int]]:
+        """the table this field holds as a point-launch source: (data, kind, num_bits) - never converted"""
+        if self.table is not None:
+            return self.table.detach(), "f32", None
+        if self.packed is not None:
+            return self.packed, "bits", self.num_bits
+        return self.stored, "u8", self.num_bits
+
+    @torch.no_grad()
+    def query(self, points: torch.Tensor) -> torch.Tensor:
+        """[N, 3] colours at ``points`` [N, dim] (fp32, sample units: p = i is the centre of sample i, the field spans [-1/2, S - 1/2] and
+        points outside it read its edge), from the fp32 table or - a field from ``load_compressed`` - straight from its uint8 or bit-packed
+        table.  One launch on the fused route (nic_hash_fused_forward_points), encode + general decoder on the layer-wise one."""
+        data, kind, bits = self._point_table()
+        params = [p.detach() for p in self.decoder.linear_params()]
+        if self.route == "fused":
+            return hash_fused_forward_points(self.geo, data, points, params, kind, bits)
+        pts = _check_points(self.geo, points)
+        if pts.shape[0] == 0:
+            return torch.empty(0, 3, dtype=torch.float32, device=self.device)
+        return fused.DecoderFunction.apply(hash_encode_points(self.geo, data, pts, kind, bits), *params)
+
+    def _resample_points(self, size: Sequence[int], origin: Sequence[int], extent: Sequence[int]) -> torch.Tensor:
+        """[prod(extent), dim] fp32 points of the block ``origin`` .. ``origin + extent`` of a regular grid of ``size`` samples over the field,
+        the last axis fastest: p_a = (j + 1/2) S_a / size_a - 1/2, evaluated in float64 on the device and rounded once to fp32"""
+        axes = [((torch.arange(o, o + e, dtype=torch.float64, device=self.device) + 0.5) * s / n - 0.5).to(torch.float32)
+                for o, e, s, n in zip(origin, extent, self.field_size, size)]
+        return torch.stack([g.reshape(-1) for g in torch.meshgrid(*axes, indexing="ij")], dim=1).contiguous()
+
+    @torch.no_grad()
+    def resample(self, size: Union[int, Sequence[int]], tile: int = 1024) -> torch.Tensor:
+        """the field decoded on a regular grid of ANY size, [*size, 3]: output sample j of axis a sits at p_a = (j + 1/2) S_a / size_a - 1/2
+        (``size`` = the field size gives ``decode()``'s sample centres).  Walked in tiles of side <= ``tile``; the points of a tile are
+        generated on the device."""
+        size = (int(size),) * self.geo.dim if isinstance(size, int) else tuple(int(v) for v in size)
+        if len(size) != self.geo.dim or any(v < 1 for v in size):
+            raise ValueError(f"size {size} for a {self.geo.dim}D field")
+        out = torch.empty(*size, 3, dtype=torch.float32, device=self.device)
+        for o in itertools.product(*[range(0, s, tile) for s in size]):
+            ext = [min(tile, s - a) for s, a in zip(size, o)]
+            sl = tuple(slice(a, a + e) for a, e in zip(o, ext))
+            out[sl] = self.query(self._resample_points(size, o, ext)).reshape(*ext, 3)
         return out
