@@ -578,7 +578,7 @@ int nic_hash_fused_forward_backward(const nic_hash_desc *desc, const nic_hash_qu
  *      noise of nic_hash_encode_noisy) only with an F32 source (else NIC_E_ARG); n_points < 0 is NIC_E_ARG, n_points == 0 is NIC_OK with
  *      no launch.  nic_hash_encode_points_backward is the straight-through scatter of nic_hash_encode_backward (ADDS into table_grad, fp32
  *      atomics, order not fixed).  nic_hash_fused_forward_points is nic_hash_fused_forward / _u8 / _bits at points ([n_points, 3]; the set
- *      nic_hash_fused_supported answers for).  There is no fused training at points. */
+ *      nic_hash_fused_supported answers for).  Training at points in cell order and in one fused kernel: the next section. */
 #define NIC_HASH_SRC_F32 0   /* fp32 [levels, T, features] table */
 #define NIC_HASH_SRC_U8 1    /* compact uint8 table (nic_hash_pack_u8) */
 #define NIC_HASH_SRC_BITS 2  /* bit-packed table (nic_hash_pack_bits) */
@@ -593,6 +593,37 @@ int nic_hash_encode_points_backward(const nic_hash_desc *desc, const float *poin
                                     void *stream);
 int nic_hash_fused_forward_points(const nic_hash_desc *desc, const nic_hash_source *src, const float *points, int64_t n_points,
                                   const nic_mlp *mlp, float *y, void *stream);
+
+/* ---- cell-ordered and fused training at points (hashgrid.py, HashGridField.train_points(order=, fused=) / fit_points).
+ *      nic_hash_point_keys: keys[n] = the Morton key of point n, a pure function of the clamped fixed-point position defined above:
+ *        t_a as above (p_a clamped in floating point - NaN to the low edge, -inf / +inf to the nearer one - then rint(256 p_a) + 128 clamped to
+ *        [0, 256 S_a - 1]); b = the bit length of 256 S_max - 1 (<= 30), k = 31 for dim 2 and 21 for dim 3, s = max(0, b - k), u_a = t_a >> s;
+ *        bit j of u_a goes to bit j dim + a of the key.  0 <= key < 2^63.  Z-order of position is hierarchical: neighbours in key order share
+ *        their cell at the coarse levels and mostly at the fine ones, so a launch that walks the points in key order (a stable sort of the keys,
+ *        the caller's) sums neighbouring lanes of one cell before the atomics.  One lane per point; keys = [n_points] int64 (device).
+ *      nic_hash_encode_points_backward_ordered: nic_hash_encode_points_backward with lane n of the launch on point order[n] - it reads
+ *        points[order[n]] and row order[n] of dx.  order = [n_points] int32 (device; the host never reads it); every index is clamped to
+ *        [0, n_points - 1] by the kernel, so a buffer that is no permutation gives the sum over the rows it names and never an access out of
+ *        range.  order == NULL is nic_hash_encode_points_backward itself; n_points >= 2^31 with an order is NIC_E_ARG.
+ *      nic_hash_fused_forward_backward_points: nic_hash_fused_forward_backward with the samples taken from `points` through the cell arithmetic
+ *        of nic_hash_encode_points - two launches (the fused kernel, then the fixed-order reduction of its per-workgroup records with `tail`
+ *        riding on it), loss = mean((y - target)^2) loss_scale over the [n_points, 3] outputs, table_grad ADDED into (null: frozen table, no
+ *        scatter), NIC_HASH_FUSED_ADD_GRADS / _ADD_LOSS, y null or [n_points, 3], nic_mark_kernel_end honoured.  With `order`, wave w handles
+ *        points order[64 w .. 64 w + 63]: target is read and y written at row order[n], the noise keyed by sample_base + order[n] and the
+ *        column - an ordered call computes the unordered call's function up to the order of the sums, with noise too.  Indices are clamped as
+ *        above.  Supported: what nic_hash_fused_supported answers for, plus num_crops == 1 and 256 S_max < 2^30 of the point entries.
+ *      Host checks, all before any GPU work, in the order of the siblings: descriptor (fused set first for the fused entry), null pointers,
+ *      flags / quant, n_points < 0 or n_points >= 2^31 with an order (NIC_E_ARG), workspace < nic_hash_fused_points_workspace_bytes
+ *      (NIC_E_WORKSPACE; the query returns 0 for what the entry refuses), the tail (its decoder gradients must be this call's mlp_grads, else
+ *      NIC_E_ARG).  n_points == 0 is NIC_OK with no launch and leaves *loss untouched. */
+int nic_hash_point_keys(const nic_hash_desc *desc, const float *points, int64_t n_points, int64_t *keys, void *stream);
+int nic_hash_encode_points_backward_ordered(const nic_hash_desc *desc, const float *points, int64_t n_points, const float *dx,
+                                            const int32_t *order, float *table_grad, void *stream);
+size_t nic_hash_fused_points_workspace_bytes(const nic_hash_desc *desc, const nic_mlp *mlp);   /* 0: unsupported */
+int nic_hash_fused_forward_backward_points(const nic_hash_desc *desc, const nic_hash_quant *quant, const float *table, const float *points,
+                                           int64_t n_points, const int32_t *order, const nic_mlp *mlp, const float *target, float loss_scale,
+                                           float *table_grad, const nic_mlp_grads *mlp_grads, float *loss, float *y, int flags, void *workspace,
+                                           size_t workspace_bytes, const nic_step_tail *tail, void *stream);
 
 #ifdef __cplusplus
 }

@@ -197,6 +197,11 @@ SIGNATURES = {
     "nic_hash_encode_points": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashSource), ctypes.POINTER(NicHashQuant), _P, _L, _P, _P]),
     "nic_hash_encode_points_backward": (_I, [ctypes.POINTER(NicHashDesc), _P, _L, _P, _P, _P]),
     "nic_hash_fused_forward_points": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashSource), _P, _L, _M, _P, _P]),
+    "nic_hash_point_keys": (_I, [ctypes.POINTER(NicHashDesc), _P, _L, _P, _P]),
+    "nic_hash_encode_points_backward_ordered": (_I, [ctypes.POINTER(NicHashDesc), _P, _L, _P, _P, _P, _P]),
+    "nic_hash_fused_points_workspace_bytes": (_SZ, [ctypes.POINTER(NicHashDesc), _M]),
+    "nic_hash_fused_forward_backward_points": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashQuant), _P, _P, _L, _P, _M, _P, _F, _P, _G, _P, _P,
+                                                    _I, _P, _SZ, ctypes.POINTER(NicStepTail), _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -1,0 +1,451 @@
+// What the hash-grid kernels share, for translation units written after hash_grid.hip / hash_fused.hip / hash_points.hip (those three are pinned
+// and keep their own restated copies): the index helpers, the fp32 row loader, the fixed-point position and cell of a point
+// (include/nicv2_hip.h, nic_hash_encode_points), the level loops of the encode (row into an LDS tile) and of the scatter (run sums keyed on the
+// base vertex), and the ColorDecoder(L F, 64, 3) forward + backward on v_mfma_f32_32x32x2_f32 with its register-resident weight-gradient
+// accumulators and per-workgroup record (hash_fused.hip's training mode, the same product order).  run_masks / run_sum, the noise generator and
+// the activations come from nic_device.hpp, the optimiser tail from nic_adam.hpp.
+#pragma once
+#include "nic_device.hpp"
+#include "nic_adam.hpp"
+
+namespace nic {
+namespace hcommon {
+
+// ---- index helpers and loaders (hash_grid.hip) -------------------------------------------------------------------------------------------
+__host__ __device__ inline bool hash_level_dense(int dim, int32_t R, int log2_table) {
+    uint64_t p = 1;
+    for (int a = 0; a < dim; ++a) {
+        p *= (uint64_t)R + 1;
+        if (p > (1ull << log2_table)) return false;
+    }
+    return true;
+}
+__host__ __device__ inline uint32_t hash_index(bool dense, uint32_t R, uint32_t mask, uint32_t vx, uint32_t vy, uint32_t vz) {
+    const uint32_t h = dense ? vx + (R + 1u) * (vy + (R + 1u) * vz) : (vx ^ (vy * 2654435761u) ^ (vz * 805459861u));
+    return h & mask;
+}
+template <int F>
+__device__ __forceinline__ void load_row(const float* p, float (&v)[F]) {
+    if constexpr (F == 1) {
+        v[0] = *p;
+    } else if constexpr (F == 2) {
+        const float2 a = *reinterpret_cast<const float2*>(p);
+        v[0] = a.x; v[1] = a.y;
+    } else {
+#pragma unroll
+        for (int k = 0; k < F; k += 4) {
+            const float4 a = *reinterpret_cast<const float4*>(p + k);
+            v[k] = a.x; v[k + 1] = a.y; v[k + 2] = a.z; v[k + 3] = a.w;
+        }
+    }
+}
+template <int D>
+__device__ __forceinline__ float corner_weight(const float (&w)[3], int c) {
+    float r = ((c & 1) ? w[0] : 1.0f - w[0]) * ((c & 2) ? w[1] : 1.0f - w[1]);
+    if (D == 3) r *= (c & 4) ? w[2] : 1.0f - w[2];
+    return r;
+}
+
+// ---- the fixed-point split of a point (hash_points.hip) ------------------------------------------------------------------------------------
+// clamped in floating point first (NaN fails both comparisons' "keep" side and lands on the low edge, -inf / +inf on the nearer one), then
+// t = rint(256 p) + 128 (half to even; 256 p is exact) clamped to [0, 256 S - 1]
+template <int D>
+__device__ __forceinline__ void point_fixed(const nic_hash_desc& d, const float* points, int64_t n, uint32_t (&t)[3]) {
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        const float x = points[n * D + a], lo = -0.5f, hi = (float)d.extent[a] - 0.5f;
+        float c = x >= lo ? x : lo;
+        c = c <= hi ? c : hi;
+        const int ti = (int)rintf(256.0f * c) + 128, tmax = 256 * d.extent[a] - 1;
+        t[a] = (uint32_t)(ti < 0 ? 0 : (ti > tmax ? tmax : ti));
+    }
+    if (D == 2) t[2] = 0;
+}
+// q = t R (< 2^38), v = q div 256 S_max, w = fp32(q mod 256 S_max) / fp32(256 S_max), through q >> 8 (< 2^30) div / mod S_max in 32 bits
+template <int D>
+__device__ __forceinline__ void point_cell(const uint32_t (&t)[3], uint32_t R, uint32_t S, float fdiv, uint32_t (&v)[3], float (&w)[3]) {
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        const uint64_t q = (uint64_t)t[a] * R;
+        const uint32_t qh = (uint32_t)(q >> 8), ql = (uint32_t)q & 255u;
+        v[a] = qh / S;
+        w[a] = (float)(((qh - v[a] * S) << 8) | ql) / fdiv;
+    }
+    if (D == 2) { v[2] = 0; w[2] = 0.f; }
+}
+
+// the level loop of hash_points_encode_kernel from the fp32 table, the row going value by value into `row` (an LDS tile); NOISE: the noise of
+// nic_hash_encode_noisy keyed by `sample` and the column
+template <int D, int F, bool NOISE>
+__device__ __forceinline__ void encode_point_f32(const nic_hash_desc& d, const float* table, const uint32_t (&t)[3], const NoiseSrc& noise,
+                                                 uint64_t sample, float* row) {
+    const uint32_t S = (uint32_t)d.S_max, mask = (1u << d.log2_table) - 1u;
+    const float fdiv = (float)(256u * S);
+    [[maybe_unused]] U4 nblk{0u, 0u, 0u, 0u};
+#pragma unroll 2
+    for (int l = 0; l < d.levels; ++l) {
+        const uint32_t R = (uint32_t)d.resolution[l];
+        const bool dense = hash_level_dense(D, (int32_t)R, d.log2_table);
+        const float* tab = table + ((int64_t)l << d.log2_table) * F;
+        uint32_t v[3];
+        float w[3];
+        point_cell<D>(t, R, S, fdiv, v, w);
+        float acc[F];
+#pragma unroll
+        for (int f = 0; f < F; ++f) acc[f] = 0.f;
+#pragma unroll
+        for (int c = 0; c < (1 << D); ++c) {
+            const uint32_t e = hash_index(dense, R, mask, v[0] + (c & 1), v[1] + ((c >> 1) & 1), D == 3 ? v[2] + ((c >> 2) & 1) : 0u);
+            float tv[F];
+            load_row<F>(tab + (int64_t)e * F, tv);
+            const float cw = corner_weight<D>(w, c);
+#pragma unroll
+            for (int f = 0; f < F; ++f) acc[f] += cw * tv[f];
+        }
+        if constexpr (NOISE) {
+            // 16 % F == 0: a level's F columns lie in one generator block; it is generated at its first column and reused by the next levels
+            const int c0 = l * F;
+            if ((c0 & 15) == 0) nblk = noise_block(noise, sample, c0 >> 4);
+#pragma unroll
+            for (int f = 0; f < F; ++f) acc[f] += noise_from_block(noise, nblk, (c0 + f) & 15);
+        }
+#pragma unroll
+        for (int f = 0; f < F; ++f) row[l * F + f] = acc[f];
+    }
+}
+
+// the level loop of hash_points_backward_kernel for one lane's point: `grow(l, g)` hands over the F gradient values of level l (a dead lane
+// gets zeros without the call).  Runs are keyed on the base VERTEX; each lane weighs its own gradient before the sum and only NEIGHBOURING
+// lanes merge, so any point order is right - and cell order makes the runs long.  The whole wave must call this together (shuffles).
+template <int D, int F, class GRow>
+__device__ __forceinline__ void scatter_point(const nic_hash_desc& d, const uint32_t (&t)[3], float* grad, bool live, int lane, GRow grow) {
+    const uint32_t S = (uint32_t)d.S_max, mask = (1u << d.log2_table) - 1u;
+    const float fdiv = (float)(256u * S);
+    for (int l = 0; l < d.levels; ++l) {
+        const uint32_t R = (uint32_t)d.resolution[l];
+        const bool dense = hash_level_dense(D, (int32_t)R, d.log2_table);
+        float* gtab = grad + ((int64_t)l << d.log2_table) * F;
+        uint32_t v[3];
+        float w[3];
+        point_cell<D>(t, R, S, fdiv, v, w);
+        float g[F];
+#pragma unroll
+        for (int f = 0; f < F; ++f) g[f] = 0.f;
+        if (live) grow(l, g);
+        const int64_t key = (int64_t)v[0] + ((int64_t)R + 1) * ((int64_t)v[1] + ((int64_t)R + 1) * (int64_t)v[2]);
+        const RunMasks m = run_masks(live ? key : -1 - (int64_t)lane, lane);
+        const bool issue = live && m.head;
+#pragma unroll
+        for (int c = 0; c < (1 << D); ++c) {
+            const uint32_t e = hash_index(dense, R, mask, v[0] + (c & 1), v[1] + ((c >> 1) & 1), D == 3 ? v[2] + ((c >> 2) & 1) : 0u);
+            const float cw = corner_weight<D>(w, c);
+#pragma unroll
+            for (int f = 0; f < F; ++f) {
+                float val = cw * g[f];
+                if (m.any_shared) val = run_sum(val, m);
+                if (issue) atomicAdd(gtab + (int64_t)e * F + f, val);
+            }
+        }
+    }
+}
+
+// ---- the decoder on the fp32 matrix pipe (hash_fused.hip) ----------------------------------------------------------------------------------
+constexpr int XS = kH + 1;      // row stride of every LDS tile: lanes that walk rows hit 64 different banks
+constexpr int NQ = 16;          // samples per weight-gradient pass (the two transposed tiles of a wave)
+
+// the record of a workgroup, nn.Linear layouts back to back: dW1 [64, L F] | db1 | dW2 [64, 64] | db2 | dW3 [3, 64] | db3 | sum of squared errors
+// (hash_fused.hip's RecLayout: hash_fused_reduce_kernel reads records of this layout)
+struct RecLayout {
+    int w1, b1, w2, b2, w3, b3, loss, rec;
+    __host__ __device__ explicit RecLayout(int lf) {
+        w1 = 0; b1 = kH * lf; w2 = b1 + kH; b2 = w2 + kH * kH; w3 = b2 + kH; b3 = w3 + 3 * kH; loss = b3 + 3; rec = loss + 1;
+    }
+};
+
+struct TrainSmem {
+    float w1[kH * XS], w2[kH * XS], w3[4 * kH], b1[kH], b2[kH], b3[4];
+    float x[4][kH * XS];        // per wave: the encoding rows [sample][column], later d loss / d row; at the end of the launch the workgroup's record
+    float p[4][NQ * XS], q[4][NQ * XS];
+};
+
+// LDS traffic between the lanes of ONE wave: its LDS instructions execute in order, the compiler must not move them across
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ int row_of(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+
+// acc[ta][tb] += sum over the NQ samples of a pass of P[n][32 ta + i] Q[n][32 tb + j]   (MASK4: P has 4 columns, one row tile)
+// side[ta] += every P operand of this lane: the bias gradient (column sums of dZ) of unit 32 ta + i over the samples of this half's parity
+template <int TA, int TB, bool MASK4>
+__device__ __forceinline__ void wgrad_mfma(const float* P, const float* Q, int j, int half, f32x16 (&acc)[TA][TB], float (&side)[TA]) {
+#pragma unroll
+    for (int s = 0; s < NQ / 2; ++s) {
+        float a[TA], b[TB];
+#pragma unroll
+        for (int ta = 0; ta < TA; ++ta) a[ta] = MASK4 ? (j < 4 ? P[(2 * s + half) * XS + j] : 0.f) : P[(2 * s + half) * XS + 32 * ta + j];
+#pragma unroll
+        for (int tb = 0; tb < TB; ++tb) b[tb] = Q[(2 * s + half) * XS + 32 * tb + j];
+#pragma unroll
+        for (int ta = 0; ta < TA; ++ta) {
+            side[ta] += a[ta];
+#pragma unroll
+            for (int tb = 0; tb < TB; ++tb) acc[ta][tb] = mfma(a[ta], b[tb], acc[ta][tb]);
+        }
+    }
+}
+// the [unit] values of this lane's sample -> row (j & 15) of a transposed tile
+template <int T>
+__device__ __forceinline__ void put_tile(float* P, int j, int half, const f32x16 (&u)[T]) {
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) P[(j & 15) * XS + 32 * t + row_of(r, half)] = u[t][r];
+}
+__device__ __forceinline__ float half_sum(float v) {      // over the 32 lanes of this lane's half, fixed order
+#pragma unroll
+    for (int m = 1; m < 32; m <<= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+// the weight-gradient accumulators of one wave: in registers for the whole launch
+template <int KT>
+struct TrainAcc {
+    f32x16 gW1[2][KT], gW2[2][2], gW3[1][2];
+    float gb1[2], gb2[2], gb3[1], sse;
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+#pragma unroll
+            for (int b = 0; b < KT; ++b) gW1[a][b] = f32x16{};
+            gW2[a][0] = f32x16{}; gW2[a][1] = f32x16{};
+            gW3[0][a] = f32x16{};
+            gb1[a] = 0.f; gb2[a] = 0.f;
+        }
+        gb3[0] = 0.f; sse = 0.f;
+    }
+};
+
+// the decoder's weights into LDS (columns past L F are zero) and the wave's row tile cleared; the caller synchronises the workgroup after it
+__device__ __forceinline__ void load_decoder(TrainSmem& sm, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
+                                             const float* b3, int LF, int tid) {
+    for (int e = tid; e < kH * XS; e += 256) {
+        const int h = e / XS, k = e - h * XS;
+        sm.w1[e] = k < LF ? w1[h * LF + k] : 0.f;
+        sm.w2[e] = k < kH ? w2[h * kH + k] : 0.f;
+    }
+    sm.w3[tid] = tid < 3 * kH ? w3[tid] : 0.f;
+    if (tid < kH) { sm.b1[tid] = b1[tid]; sm.b2[tid] = b2[tid]; }
+    if (tid < 4) sm.b3[tid] = tid < 3 ? b3[tid] : 0.f;
+    float* xs = sm.x[tid >> 6];
+    for (int e = tid & 63; e < kH * XS; e += 64) xs[e] = 0.f;       // the columns past L F stay finite (their weights are zero)
+}
+
+// forward, loss and backward of the 32 samples `32 nt + j` of a wave's row tile `xs` (hash_fused_kernel's training mode, the same products in
+// the same order).  `mine`: this lane (half 0) owns a live sample; it reads its target at `trow`, writes y to `yrow` when that is not null.
+// The weight gradients go into `A`; with `want_dx`, d loss / d row replaces the rows of this half in `xs`.
+template <int KT>
+__device__ __forceinline__ void decoder_train_half(TrainSmem& sm, float* xs, float* P, float* Q, int nt, int j, int half, int ks1, bool mine,
+                                                   const float* trow, float* yrow, float dscale, bool want_dx, TrainAcc<KT>& A) {
+    const int src = 32 * nt + j;
+    const float* xb = xs + src * XS;
+    // ---- layer 1
+    f32x16 a1[2] = {f32x16{}, f32x16{}};
+    f32x16 d1[2];
+    for (int k = 0; k < ks1; ++k) {
+        const float b = xb[2 * k + half];
+        a1[0] = mfma(sm.w1[j * XS + 2 * k + half], b, a1[0]);
+        a1[1] = mfma(sm.w1[(32 + j) * XS + 2 * k + half], b, a1[1]);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float av, dv;
+            gelu_and_grad(a1[t][r] + sm.b1[32 * t + row_of(r, half)], av, dv);
+            a1[t][r] = av;
+            d1[t][r] = dv;
+        }
+    // ---- layer 2
+    f32x16 a2[2] = {f32x16{}, f32x16{}};
+    f32x16 d2[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int k = 32 * t + row_of(r, half);
+            a2[0] = mfma(sm.w2[j * XS + k], a1[t][r], a2[0]);
+            a2[1] = mfma(sm.w2[(32 + j) * XS + k], a1[t][r], a2[1]);
+        }
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float av, dv;
+            gelu_and_grad(a2[t][r] + sm.b2[32 * t + row_of(r, half)], av, dv);
+            a2[t][r] = av;
+            d2[t][r] = dv;
+        }
+    // ---- output layer: rows 0 .. 2 of one tile (registers 0 .. 2 of half 0)
+    f32x16 z3 = f32x16{};
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int k = 32 * t + row_of(r, half);
+            z3 = mfma(j < 3 ? sm.w3[j * kH + k] : 0.f, a2[t][r], z3);
+        }
+    float yv[3];
+#pragma unroll
+    for (int o = 0; o < 3; ++o) yv[o] = sigmoid_f(z3[o] + sm.b3[o]);
+    if (mine && yrow != nullptr) {
+#pragma unroll
+        for (int o = 0; o < 3; ++o) yrow[o] = yv[o];
+    }
+    // ---- dZ3 = dy y (1 - y), dy = 2 (y - t) loss_scale / (3 N)
+    float dz3[4] = {0.f, 0.f, 0.f, 0.f};
+    if (mine) {
+#pragma unroll
+        for (int o = 0; o < 3; ++o) {
+            const float e = yv[o] - trow[o];
+            A.sse += e * e;
+            dz3[o] = dscale * e * yv[o] * (1.0f - yv[o]);
+        }
+    }
+    // dW3 [o][h] += dZ3^T A2
+#pragma unroll 1
+    for (int q = 0; q < 2; ++q) {
+        if ((j >> 4) == q) {
+            put_tile<2>(Q, j, half, a2);
+            if (half == 0) {
+#pragma unroll
+                for (int o = 0; o < 4; ++o) P[(j & 15) * XS + o] = dz3[o];
+            }
+        }
+        wave_sync();
+        wgrad_mfma<1, 2, true>(P, Q, j, half, A.gW3, A.gb3);
+        wave_sync();
+    }
+    // dA2 = W3^T dZ3 (k-steps: o = s of half 0; half 1 carries zeros), dZ2 = dA2 gelu'
+    f32x16 dz2[2] = {f32x16{}, f32x16{}};
+#pragma unroll
+    for (int o = 0; o < 3; ++o) {
+        const float b = half == 0 ? dz3[o] : 0.f;
+        dz2[0] = mfma(half == 0 ? sm.w3[o * kH + j] : 0.f, b, dz2[0]);
+        dz2[1] = mfma(half == 0 ? sm.w3[o * kH + 32 + j] : 0.f, b, dz2[1]);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) dz2[t] *= d2[t];
+    // dW2 [h2][h] += dZ2^T A1
+#pragma unroll 1
+    for (int q = 0; q < 2; ++q) {
+        if ((j >> 4) == q) {
+            put_tile<2>(P, j, half, dz2);
+            put_tile<2>(Q, j, half, a1);
+        }
+        wave_sync();
+        wgrad_mfma<2, 2, false>(P, Q, j, half, A.gW2, A.gb2);
+        wave_sync();
+    }
+    // dA1 = W2^T dZ2, dZ1 = dA1 gelu'
+    f32x16 dz1[2] = {f32x16{}, f32x16{}};
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int k = 32 * t + row_of(r, half);
+            dz1[0] = mfma(sm.w2[k * XS + j], dz2[t][r], dz1[0]);
+            dz1[1] = mfma(sm.w2[k * XS + 32 + j], dz2[t][r], dz1[1]);
+        }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) dz1[t] *= d1[t];
+    // dW1 [h][k] += dZ1^T X (X: the rows of this half, in place)
+#pragma unroll 1
+    for (int q = 0; q < 2; ++q) {
+        if ((j >> 4) == q) put_tile<2>(P, j, half, dz1);
+        wave_sync();
+        wgrad_mfma<2, KT, false>(P, xs + (32 * nt + 16 * q) * XS, j, half, A.gW1, A.gb1);
+        wave_sync();
+    }
+    // dX = W1^T dZ1 over the rows of this half (their X is spent)
+    if (want_dx) {
+        f32x16 dx[KT];
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt) dx[kt] = f32x16{};
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int h = 32 * t + row_of(r, half);
+#pragma unroll
+                for (int kt = 0; kt < KT; ++kt) dx[kt] = mfma(sm.w1[h * XS + 32 * kt + j], dz1[t][r], dx[kt]);
+            }
+        float* xw = xs + src * XS;
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) xw[32 * kt + row_of(r, half)] = dx[kt][r];
+    }
+}
+
+// the workgroup's record: the four waves add their accumulators in wave order into the (now free) row tiles, then the record goes to `rec`
+template <int KT>
+__device__ __forceinline__ void write_record(TrainSmem& sm, const TrainAcc<KT>& A, int LF, float* rec, int tid) {
+    const int wave = tid >> 6, lane = tid & 63, j = lane & 31, half = lane >> 5;
+    const RecLayout rl(LF);
+    float* R = &sm.x[0][0];
+    __syncthreads();
+    for (int w = 0; w < 4; ++w) {
+        if (wave == w) {
+            const bool first = w == 0;
+            auto put = [&](int at, float v) { R[at] = first ? v : R[at] + v; };
+#pragma unroll
+            for (int ta = 0; ta < 2; ++ta)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int h = 32 * ta + row_of(r, half);
+#pragma unroll
+                    for (int tb = 0; tb < KT; ++tb)
+                        if (32 * tb + j < LF) put(rl.w1 + h * LF + 32 * tb + j, A.gW1[ta][tb][r]);
+#pragma unroll
+                    for (int tb = 0; tb < 2; ++tb) put(rl.w2 + h * kH + 32 * tb + j, A.gW2[ta][tb][r]);
+                }
+#pragma unroll
+            for (int ta = 0; ta < 2; ++ta) {                 // lane (i, half) summed the samples of parity `half`
+                const float s1 = A.gb1[ta] + __shfl_xor(A.gb1[ta], 32), s2 = A.gb2[ta] + __shfl_xor(A.gb2[ta], 32);
+                if (half == 0) { put(rl.b1 + 32 * ta + j, s1); put(rl.b2 + 32 * ta + j, s2); }
+            }
+            const float s3 = A.gb3[0] + __shfl_xor(A.gb3[0], 32);
+            if (lane < 3) put(rl.b3 + lane, s3);
+#pragma unroll
+            for (int o = 0; o < 3; ++o) {
+                if (half == 0) { put(rl.w3 + o * kH + j, A.gW3[0][0][o]); put(rl.w3 + o * kH + 32 + j, A.gW3[0][1][o]); }
+            }
+            const float sl = half_sum(A.sse);
+            if (lane == 0) put(rl.loss, sl);
+        }
+        __syncthreads();
+    }
+    for (int e = tid; e < rl.rec; e += 256) rec[e] = R[e];
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------------
+inline int device_cus() {
+    static int n = 0;
+    if (n == 0) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
+        else n = 256;
+    }
+    return n;
+}
+// workgroups a persistent launch may use: one per CU, a multiple of 8 (one slice of the range per XCD)
+inline int wg_cap() {
+    const int c = device_cus() / 8 * 8;
+    return c < 8 ? 8 : c;
+}
+
+}  // namespace hcommon
+}  // namespace nic

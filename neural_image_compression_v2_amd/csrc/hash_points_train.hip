@@ -1,0 +1,311 @@
+// Cell-ordered and fused training of the hash-grid field at ARBITRARY points (include/nicv2_hip.h: nic_hash_point_keys,
+// nic_hash_encode_points_backward_ordered, nic_hash_fused_points_workspace_bytes, nic_hash_fused_forward_backward_points; hashgrid.py,
+// HashGridField.train_points(order=, fused=) / fit_points).
+//
+//   keys      one Morton key per point from the clamped fixed-point position of nic_hash_encode_points: Z-order is hierarchical, so neighbours in
+//             key order share their cell at the coarse levels and mostly at the fine ones.  The sort is the caller's (a stable device sort).
+//   ordered   hash_points_backward_kernel with lane n on point order[n]: the run sums merge neighbouring lanes of one cell again, which random
+//             batches lost (124 ms against 14 ms for 8.3 M points).
+//   fused     hash_fused_kernel's training mode with hash_points_fused_kernel's sample source: a wave gathers the rows of 64 consecutive
+//             (ordered) points into its LDS tile, runs the decoder forward and backward on the fp32 matrix pipe, leaves d loss / d row in the
+//             tile and scatters it with the run sums keyed on the base vertex; one record per workgroup, reduced in a fixed order by
+//             hash_fused_reduce_kernel (linked from hash_fused.hip) with the optimiser tail riding on it.
+//
+// Every index read from `order` is clamped to [0, n_points - 1]: a buffer that is no permutation gives the sum over the rows it names.
+#include "hash_common.hpp"
+
+namespace nic {
+namespace hfused {
+// defined in hash_fused.hip; reads records of hcommon::RecLayout (the same layout as its own)
+__global__ void __launch_bounds__(256) hash_fused_reduce_kernel(const float* partials, int n_rec, int lf, nic_mlp_grads g, float* loss, float loss_mul,
+                                                                int add_grads, int add_loss, const StepTail tl);
+}  // namespace hfused
+
+namespace hptrain {
+using namespace hcommon;
+
+struct TParams {
+    nic_hash_desc d;          // extent[a] = S_a, num_crops = 1
+    const float* points;      // [n, dim]
+    int64_t n;
+    const int32_t* order;     // null, or [n] row indices (clamped)
+    const float* table;
+    const float* dx;          // ordered scatter: [n, L F]
+    float* grad;              // table gradient (fused: null = frozen table, no scatter)
+    int64_t* keys;
+    int32_t key_shift;        // s = max(0, b - k)
+    // fused only
+    const float *w1, *b1, *w2, *b2, *w3, *b3;
+    const float* target;
+    float* y;
+    float* partials;
+    NoiseSrc noise;
+    uint64_t sample_base;
+    float dscale;             // 2 loss_scale / (3 N)
+};
+
+// the row lane `pos` of the launch handles: order[pos] clamped into the point set, or pos itself
+__device__ __forceinline__ int64_t ordered_row(const TParams& p, int64_t pos) {
+    if (p.order == nullptr) return pos;
+    const int64_t i = p.order[pos];
+    return i < 0 ? 0 : (i >= p.n ? p.n - 1 : i);
+}
+
+// bit j of x -> bit 2 j (x < 2^31) / bit 3 j (x < 2^21)
+__device__ __forceinline__ uint64_t spread2(uint64_t x) {
+    x = (x | (x << 16)) & 0x0000FFFF0000FFFFull;
+    x = (x | (x << 8)) & 0x00FF00FF00FF00FFull;
+    x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0Full;
+    x = (x | (x << 2)) & 0x3333333333333333ull;
+    x = (x | (x << 1)) & 0x5555555555555555ull;
+    return x;
+}
+__device__ __forceinline__ uint64_t spread3(uint64_t x) {
+    x = (x | (x << 32)) & 0x001F00000000FFFFull;
+    x = (x | (x << 16)) & 0x001F0000FF0000FFull;
+    x = (x | (x << 8)) & 0x100F00F00F00F00Full;
+    x = (x | (x << 4)) & 0x10C30C30C30C30C3ull;
+    x = (x | (x << 2)) & 0x1249249249249249ull;
+    return x;
+}
+
+template <int D>
+__global__ void __launch_bounds__(256) hash_point_keys_kernel(const TParams p) {
+    for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < p.n; n += (int64_t)gridDim.x * 256) {
+        uint32_t t[3];
+        point_fixed<D>(p.d, p.points, n, t);
+        uint64_t key;
+        if (D == 2) key = spread2(t[0] >> p.key_shift) | (spread2(t[1] >> p.key_shift) << 1);
+        else key = spread3(t[0] >> p.key_shift) | (spread3(t[1] >> p.key_shift) << 1) | (spread3(t[2] >> p.key_shift) << 2);
+        p.keys[n] = (int64_t)key;
+    }
+}
+
+template <int D, int F>
+__global__ void __launch_bounds__(256) hash_points_backward_ordered_kernel(const TParams p) {
+    const int lane = threadIdx.x & 63;
+    const int LF = p.d.levels * F;
+    for (int64_t nb = (int64_t)blockIdx.x * 256; nb < p.n; nb += (int64_t)gridDim.x * 256) {      // block-uniform trip count: the shuffles see whole waves
+        const int64_t pos = nb + threadIdx.x;
+        const bool live = pos < p.n;
+        const int64_t n = ordered_row(p, live ? pos : p.n - 1);                                     // a dead lane reads the last point, adds nothing
+        uint32_t t[3];
+        point_fixed<D>(p.d, p.points, n, t);
+        const float* drow = p.dx + n * LF;
+        scatter_point<D, F>(p.d, t, p.grad, live, lane, [&](int l, float (&g)[F]) { load_row<F>(drow + l * F, g); });
+    }
+}
+
+template <int D, int F, int KT, bool NOISE>
+__global__ void __launch_bounds__(256) hash_points_fused_train_kernel(const TParams p) {
+    __shared__ TrainSmem sm;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 31, half = lane >> 5;
+    const int LF = p.d.levels * F;
+    load_decoder(sm, p.w1, p.b1, p.w2, p.b2, p.w3, p.b3, LF, tid);
+    __syncthreads();
+    float* xs = sm.x[wave];
+    float* xrow = xs + lane * XS;
+    float* P = sm.p[wave];
+    float* Q = sm.q[wave];
+    TrainAcc<KT> A;
+    A.clear();
+
+    // each XCD (blocks b, b + 8, ..) walks one contiguous range of groups of 4 waves of (ordered) points
+    const int64_t n_waves = (p.n + 63) >> 6;
+    const int xcd = blockIdx.x & 7, nb8 = gridDim.x >> 3;
+    const int64_t n_groups = (n_waves + 3) >> 2, chunk = (n_groups + 7) >> 3;
+    const int64_t g_begin = xcd * chunk, g_end = g_begin + chunk < n_groups ? g_begin + chunk : n_groups;
+    const int ks1 = (LF + 1) >> 1;
+    for (int64_t g = g_begin + (blockIdx.x >> 3); g < g_end; g += nb8) {
+        const int64_t wv = 4 * g + wave;
+        if (wv >= n_waves) continue;                            // wave-uniform; nothing below synchronises the workgroup
+        const int64_t pos = (wv << 6) + lane;
+        const bool live_lane = pos < p.n;
+        const int64_t row = ordered_row(p, live_lane ? pos : p.n - 1);       // a lane past the end takes the last point; it stores and adds nothing
+        uint32_t t[3];
+        point_fixed<D>(p.d, p.points, row, t);
+        encode_point_f32<D, F, NOISE>(p.d, p.table, t, p.noise, p.sample_base + (uint64_t)row, xrow);
+        wave_sync();
+        const unsigned long long live_mask = __ballot(live_lane);
+#pragma unroll 1
+        for (int nt = 0; nt < 2; ++nt) {
+            const int src = 32 * nt + j;
+            const bool mine = half == 0 && ((live_mask >> src) & 1ull);
+            const int64_t r = (int64_t)(uint32_t)__shfl((int)(uint32_t)row, src) | ((int64_t)__shfl((int)(row >> 32), src) << 32);
+            decoder_train_half<KT>(sm, xs, P, Q, nt, j, half, ks1, mine, p.target + r * 3, p.y != nullptr ? p.y + r * 3 : nullptr, p.dscale,
+                                   p.grad != nullptr, A);
+        }
+        wave_sync();
+        if (p.grad != nullptr)
+            scatter_point<D, F>(p.d, t, p.grad, live_lane, lane, [&](int l, float (&gv)[F]) {
+#pragma unroll
+                for (int f = 0; f < F; ++f) gv[f] = xrow[l * F + f];
+            });
+        wave_sync();
+    }
+    write_record<KT>(sm, A, LF, p.partials + (int64_t)blockIdx.x * RecLayout(LF).rec, tid);
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------------
+static int fused_grid(int64_t n_points) {
+    const int64_t groups = (n_points + 255) / 256, want = (groups + 7) / 8 * 8;
+    return (int)(want < wg_cap() ? want : wg_cap());
+}
+static int point_blocks(int64_t n_points) {
+    const int64_t b = (n_points + 255) / 256;
+    return (int)(b > 2048 ? 2048 : b);                     // the cap of the other point launches
+}
+
+// the descriptor checks of the point entries, their only copy (hash_points.hip): the unordered scatter with no points decides every descriptor
+// error on the host, in the siblings' order, and launches nothing
+static int check_point_desc(const nic_hash_desc* d) {
+    static float dummy;
+    return nic_hash_encode_points_backward(d, &dummy, 0, &dummy, &dummy, nullptr);
+}
+
+enum TKernel { TK_KEYS, TK_BWD, TK_TRAIN, TK_TRAIN_NOISY };
+
+template <int K, int D, int F>
+static void launch_k(const TParams& p, int nb, hipStream_t s) {
+    if constexpr (K == TK_BWD) {
+        hipLaunchKernelGGL((hash_points_backward_ordered_kernel<D, F>), dim3(nb), dim3(256), 0, s, p);
+    } else {
+        constexpr bool NOISE = K == TK_TRAIN_NOISY;
+        if (p.d.levels * F > 32) hipLaunchKernelGGL((hash_points_fused_train_kernel<D, F, 2, NOISE>), dim3(nb), dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((hash_points_fused_train_kernel<D, F, 1, NOISE>), dim3(nb), dim3(256), 0, s, p);
+    }
+}
+template <int K, int D>
+static void launch_f(const TParams& p, int nb, hipStream_t s) {
+    switch (p.d.features) {
+        case 1: launch_k<K, D, 1>(p, nb, s); break;
+        case 2: launch_k<K, D, 2>(p, nb, s); break;
+        case 4: launch_k<K, D, 4>(p, nb, s); break;
+        default: launch_k<K, D, 8>(p, nb, s); break;
+    }
+}
+template <int K>
+static int launch(const TParams& p, int nb, void* stream) {
+    if constexpr (K == TK_KEYS) {
+        if (p.d.dim == 2) hipLaunchKernelGGL(hash_point_keys_kernel<2>, dim3(nb), dim3(256), 0, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL(hash_point_keys_kernel<3>, dim3(nb), dim3(256), 0, (hipStream_t)stream, p);
+    } else {
+        if (p.d.dim == 2) launch_f<K, 2>(p, nb, (hipStream_t)stream);
+        else launch_f<K, 3>(p, nb, (hipStream_t)stream);
+    }
+    return (int)hipGetLastError();
+}
+
+struct KernelEndDrop {        // a training entry point consumes the parked nic_mark_kernel_end event on every return
+    ~KernelEndDrop() { kernel_end_drop(); }
+};
+
+}  // namespace hptrain
+}  // namespace nic
+
+using namespace nic;
+using namespace nic::hptrain;
+
+extern "C" {
+
+int nic_hash_point_keys(const nic_hash_desc* desc, const float* points, int64_t n_points, int64_t* keys, void* stream) {
+    const int rc = check_point_desc(desc);
+    if (rc) return rc;
+    if (!points || !keys) return NIC_E_NULL;
+    if (n_points < 0) return NIC_E_ARG;
+    if (n_points == 0) return NIC_OK;
+    TParams p{};
+    p.d = *desc; p.points = points; p.n = n_points; p.keys = keys;
+    int b = 0;                                                          // bit length of 256 S_max - 1 (<= 30)
+    for (uint32_t top = 256u * (uint32_t)desc->S_max - 1u; top; top >>= 1) ++b;
+    const int k = desc->dim == 2 ? 31 : 21;
+    p.key_shift = b > k ? b - k : 0;
+    return launch<TK_KEYS>(p, point_blocks(n_points), stream);
+}
+
+int nic_hash_encode_points_backward_ordered(const nic_hash_desc* desc, const float* points, int64_t n_points, const float* dx, const int32_t* order,
+                                            float* table_grad, void* stream) {
+    if (!order) return nic_hash_encode_points_backward(desc, points, n_points, dx, table_grad, stream);
+    const int rc = check_point_desc(desc);
+    if (rc) return rc;
+    if (!points || !dx || !table_grad) return NIC_E_NULL;
+    if (n_points < 0 || n_points >= (int64_t(1) << 31)) return NIC_E_ARG;
+    if (n_points == 0) return NIC_OK;
+    TParams p{};
+    p.d = *desc; p.points = points; p.n = n_points; p.dx = dx; p.order = order; p.grad = table_grad;
+    return launch<TK_BWD>(p, point_blocks(n_points), stream);
+}
+
+size_t nic_hash_fused_points_workspace_bytes(const nic_hash_desc* desc, const nic_mlp* mlp) {
+    if (!desc || !mlp || nic_hash_fused_supported(desc, kH, mlp->n_linear) != NIC_OK || check_point_desc(desc) != NIC_OK) return 0;
+    return (size_t)wg_cap() * RecLayout(desc->levels * desc->features).rec * sizeof(float);
+}
+
+int nic_hash_fused_forward_backward_points(const nic_hash_desc* desc, const nic_hash_quant* quant, const float* table, const float* points,
+                                           int64_t n_points, const int32_t* order, const nic_mlp* mlp, const float* target, float loss_scale,
+                                           float* table_grad, const nic_mlp_grads* mlp_grads, float* loss, float* y, int flags, void* workspace,
+                                           size_t workspace_bytes, const nic_step_tail* tail, void* stream) {
+    const KernelEndDrop end;
+    if (!desc || !mlp) return NIC_E_NULL;
+    int rc = nic_hash_fused_supported(desc, kH, mlp->n_linear);          // the only copy of the fused set (hash_fused.hip)
+    if (rc) return rc;
+    if ((rc = check_point_desc(desc)) != NIC_OK) return rc;
+    bool mlp_ok = true;
+    for (int i = 0; i < 3; ++i) mlp_ok = mlp_ok && mlp->w[i] && mlp->b[i];
+    if (!table || !points || !mlp_ok || !target || !mlp_grads || !loss || !workspace) return NIC_E_NULL;
+    if (flags & ~(NIC_HASH_FUSED_ADD_GRADS | NIC_HASH_FUSED_ADD_LOSS)) return NIC_E_ARG;
+    TParams p{};
+    p.d = *desc; p.points = points; p.n = n_points; p.order = order; p.table = table; p.target = target; p.grad = table_grad; p.y = y;
+    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
+    p.noise.mode = NIC_NOISE_NONE;
+    if (quant) {
+        if (quant->num_bits < 1 || quant->num_bits > 8 || quant->sample_base < 0) return NIC_E_ARG;
+        if (quant->noise_mode == NIC_NOISE_TENSOR) return NIC_E_UNSUPPORTED;
+        if (quant->noise_mode != NIC_NOISE_NONE && quant->noise_mode != NIC_NOISE_KERNEL) return NIC_E_ARG;
+        if (quant->noise_mode == NIC_NOISE_KERNEL) {
+            p.noise.mode = NIC_NOISE_KERNEL;
+            p.noise.k0 = (uint32_t)quant->noise_seed; p.noise.k1 = (uint32_t)(quant->noise_seed >> 32);
+            p.noise.off_lo = (uint32_t)quant->noise_offset; p.noise.off_hi = (uint32_t)(quant->noise_offset >> 32);
+            p.noise.scale = ldexpf(1.0f, -quant->num_bits);
+            p.sample_base = (uint64_t)quant->sample_base;
+        }
+    }
+    if (n_points < 0 || (order && n_points >= (int64_t(1) << 31))) return NIC_E_ARG;
+    const int lf = desc->levels * desc->features;
+    const RecLayout rl(lf);
+    if (workspace_bytes < (size_t)wg_cap() * rl.rec * sizeof(float)) return NIC_E_WORKSPACE;
+    // the optimiser tail (nic_hash_fused_forward_backward): a decoder entry's gradient is one of the buffers this call's reduction writes
+    const int reduce_blocks = (rl.rec + 31) / 32;
+    StepTail tl;
+    tl.t.count = 0; tl.t.sched = nullptr; tl.n_stream = 0; tl.reduce_blocks = 0x7fffffff;
+    int64_t tail_blocks = 0;
+    if (tail) {
+        if (!tail->tensors) return NIC_E_NULL;
+        if (tail->count < 1 || tail->count > NIC_ADAM_MAX_TENSORS || tail->n_stream < 0 || tail->n_stream > tail->count) return NIC_E_ARG;
+        if (tail->sched != nullptr) return NIC_E_ARG;                 // the device schedule belongs to the captured dense step
+        for (int i = tail->n_stream; i < tail->count; ++i) {
+            bool found = false;
+            for (int k = 0; k < 3; ++k)
+                found = found || (tail->tensors[i].grad != nullptr && (tail->tensors[i].grad == mlp_grads->w[k] || tail->tensors[i].grad == mlp_grads->b[k]));
+            if (!found) return NIC_E_ARG;
+        }
+        rc = adam_build_table(tail->tensors, tail->count, tail->n_stream, tail->beta1, tail->beta2, tail->eps, nullptr, 0, nullptr, tl.t, tl.n_stream,
+                              tail_blocks);
+        if (rc) return rc;
+        tl.reduce_blocks = reduce_blocks;
+    }
+    if (n_points == 0) return NIC_OK;                                 // nothing to launch: *loss and every gradient stay as they are
+    const int grid = fused_grid(n_points);
+    const float loss_mul = (float)((double)loss_scale / (3.0 * (double)n_points));
+    p.dscale = 2.0f * loss_mul;
+    p.partials = (float*)workspace;
+    rc = p.noise.mode == NIC_NOISE_KERNEL ? launch<TK_TRAIN_NOISY>(p, grid, stream) : launch<TK_TRAIN>(p, grid, stream);
+    if (rc) return rc;
+    kernel_end_mark((hipStream_t)stream);
+    hipLaunchKernelGGL(hfused::hash_fused_reduce_kernel, dim3((unsigned)(reduce_blocks + tail_blocks)), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)p.partials, grid, lf, *mlp_grads, loss, loss_mul, (flags & NIC_HASH_FUSED_ADD_GRADS) ? 1 : 0,
+                       (flags & NIC_HASH_FUSED_ADD_LOSS) ? 1 : 0, tl);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

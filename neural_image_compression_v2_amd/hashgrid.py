@@ -37,7 +37,14 @@ centre of sample i, the field spanning [-1/2, S_a - 1/2]; t_a = rint(256 p_a) + 
 256 S_max, w_a = fp32(q mod 256 S_max) / fp32(256 S_max) - at a sample centre the lattice row, bit for bit.  ``hash_encode_points`` /
 ``hash_encode_points_backward`` / ``hash_fused_forward_points`` (csrc/hash_points.hip) take a [N, dim] device tensor in any order;
 ``HashGridField.query`` decodes at points from whichever table the field holds, ``resample`` on a regular grid of any size, ``train_points``
-is ``train_step`` on (point, colour) samples (layer-wise on either route: there is no fused training at points)."""
+is ``train_step`` on (point, colour) samples.
+
+Training at points, cell-ordered and fused (csrc/hash_points_train.hip): ``hash_point_keys`` gives one Morton key per point from its
+clamped fixed-point position, ``hash_point_order`` the int32 permutation that sorts them (a stable device sort); a launch that walks the points in
+that order sums the neighbouring lanes of one cell before the gradient atomics, which random batches otherwise lose.
+``train_points(..., order="cell" | tensor, fused=True)`` opt into the ordered scatter (``nic_hash_encode_points_backward_ordered``) and the fused
+step at points (``nic_hash_fused_forward_backward_points``: two launches, the optimiser on the reduction); the defaults are the layer-wise,
+unordered call unchanged.  ``fit_points`` fits a fixed (point, colour) set: the order is computed once, every epoch walks it in compact chunks."""
 from __future__ import annotations
 
 import ctypes
@@ -49,6 +56,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 import torch
 
 from . import _lib, fused, models
+from .fused import DecoderFunction
 from .image_compression import ColorDecoder
 from .optim import CosineAnnealing, FusedAdam
 
@@ -446,10 +454,47 @@ def hash_encode_points(geo: HashGeometry, data: torch.Tensor, points: torch.Tens
     return out
 
 
+def _check_order(order, n: int, device) -> torch.Tensor:
+    """an int32 [N] device tensor of row indices (``hash_point_order``); its values are the kernel's business (it clamps them)"""
+    if not isinstance(order, torch.Tensor) or order.dtype != torch.int32 or not order.is_cuda or order.dim() != 1 or not order.is_contiguous():
+        raise ValueError("order must be a contiguous 1-D int32 tensor on a HIP device (hash_point_order)")
+    if order.shape[0] != n:
+        raise ValueError(f"order names {order.shape[0]} rows, there are {n} points")
+    if order.device != device:
+        raise ValueError(f"order lives on {order.device}, the points on {device}")
+    if n >= 2 ** 31:
+        raise ValueError("an order indexes fewer than 2^31 points")
+    return order
+
+
 @fused._on_tensor_device
-def hash_encode_points_backward(geo: HashGeometry, points: torch.Tensor, dx: torch.Tensor, table_grad: torch.Tensor) -> None:
+def hash_point_keys(geo: HashGeometry, points: torch.Tensor) -> torch.Tensor:
+    """int64 [N]: the Morton key of every point's clamped fixed-point position (nic_hash_point_keys; include/nicv2_hip.h states the bits)"""
+    pts = _check_points(geo, points)
+    d = _point_desc(geo)
+    keys = torch.empty(pts.shape[0], dtype=torch.int64, device=pts.device)
+    if pts.shape[0] == 0:
+        return keys
+    _lib.check(_lib.load().nic_hash_point_keys(ctypes.byref(d), _lib.ptr(pts), pts.shape[0], _lib.ptr(keys), _lib.stream_ptr(pts.device)),
+               "nic_hash_point_keys")
+    return keys
+
+
+def hash_point_order(geo: HashGeometry, points: torch.Tensor) -> torch.Tensor:
+    """int32 [N]: the permutation that walks ``points`` in cell (Z-) order - ``hash_point_keys`` through a stable device sort, so it is
+    deterministic.  For a fixed point set compute it once and pass it to every step."""
+    keys = hash_point_keys(geo, points)
+    if keys.shape[0] >= 2 ** 31:
+        raise ValueError("an order indexes fewer than 2^31 points")
+    return torch.sort(keys, stable=True).indices.to(torch.int32)
+
+
+@fused._on_tensor_device
+def hash_encode_points_backward(geo: HashGeometry, points: torch.Tensor, dx: torch.Tensor, table_grad: torch.Tensor,
+                                order: Optional[torch.Tensor] = None) -> None:
     """ADDS d loss / d table for the [N, L F] gradient ``dx`` of ``hash_encode_points`` into ``table_grad`` (nic_hash_encode_points_backward;
-    fp32 atomics, neighbouring points of one cell summed first)"""
+    fp32 atomics, neighbouring points of one cell summed first).  ``order``: an int32 [N] device tensor (``hash_point_order``) - lane n of the
+    launch takes point ``order[n]`` (nic_hash_encode_points_backward_ordered): the same sums, neighbours in cell order merged."""
     g = _check_table(geo, table_grad, "table_grad")
     if g is not table_grad:
         raise ValueError("table_grad must be contiguous: the kernel adds into it in place")
@@ -458,7 +503,13 @@ def hash_encode_points_backward(geo: HashGeometry, points: torch.Tensor, dx: tor
     if tuple(dx.shape) != (pts.shape[0], geo.width):
         raise ValueError(f"dx must be [{pts.shape[0]}, {geo.width}], got {tuple(dx.shape)}")
     d = _point_desc(geo)
+    if order is not None:
+        order = _check_order(order, pts.shape[0], pts.device)
     if pts.shape[0] == 0:
+        return
+    if order is not None:
+        _lib.check(_lib.load().nic_hash_encode_points_backward_ordered(ctypes.byref(d), _lib.ptr(pts), pts.shape[0], _lib.ptr(dx), _lib.ptr(order),
+                                                                       _lib.ptr(g), _lib.stream_ptr(g.device)), "nic_hash_encode_points_backward_ordered")
         return
     _lib.check(_lib.load().nic_hash_encode_points_backward(ctypes.byref(d), _lib.ptr(pts), pts.shape[0], _lib.ptr(dx), _lib.ptr(g), _lib.stream_ptr(g.device)),
                "nic_hash_encode_points_backward")
@@ -478,6 +529,53 @@ def hash_fused_forward_points(geo: HashGeometry, data: torch.Tensor, points: tor
     _lib.check(_lib.load().nic_hash_fused_forward_points(ctypes.byref(d), ctypes.byref(src), _lib.ptr(pts), pts.shape[0], ctypes.byref(m), _lib.ptr(y),
                                                          _lib.stream_ptr(data.device)), "nic_hash_fused_forward_points")
     return y
+
+
+@fused._on_tensor_device
+def hash_fused_forward_backward_points(geo: HashGeometry, table: torch.Tensor, points: torch.Tensor, params: Sequence[torch.Tensor],
+                                       target: torch.Tensor, mlp_grads: Sequence[torch.Tensor], table_grad: Optional[torch.Tensor] = None,
+                                       order: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None, loss_scale: float = 1.0,
+                                       want_y: bool = False, quant=None, add_grads: bool = False, add_loss: bool = False, tail=None):
+    """``hash_fused_forward_backward`` on (point, colour) samples (nic_hash_fused_forward_backward_points): loss = mean((y - target)^2) *
+    loss_scale over ``points`` [N, dim] with ``target`` [N, 3], in two launches.  ``order``: None or an int32 [N] device tensor
+    (``hash_point_order``) - wave w takes points order[64 w ..]; targets, outputs and noise keys stay at the caller's rows, so the result is the
+    unordered call's up to the order of the sums.  Everything else as there.  Returns (loss [1], y or None)."""
+    t = _check_table(geo, table.detach())
+    params = _check_fused_decoder(geo, [q.detach() for q in params])
+    pts = _check_points(geo, points)
+    n = pts.shape[0]
+    if n < 1:
+        raise ValueError("no points")
+    target = _lib.require_cuda_f32(target, "target")
+    if tuple(target.shape) != (n, 3):
+        raise ValueError(f"target must be [{n}, 3], got {tuple(target.shape)}")
+    if order is not None:
+        order = _check_order(order, n, pts.device)
+    if table_grad is not None:
+        g = _check_table(geo, table_grad, "table_grad")
+        if g is not table_grad:
+            raise ValueError("table_grad must be contiguous: the kernel adds into it in place")
+    if len(mlp_grads) != 6 or any(not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.shape == q.shape) for g, q in zip(mlp_grads, params)):
+        raise ValueError("mlp_grads: six contiguous fp32 device buffers shaped like the decoder's parameters")
+    d = _point_desc(geo)
+    loss = torch.empty(1, dtype=torch.float32, device=t.device) if loss is None else loss
+    y = torch.empty(n, 3, dtype=torch.float32, device=t.device) if want_y else None
+    lib = _lib.load()
+    m, gs = fused._mlp_struct(params), fused._grads_struct(list(mlp_grads))
+    q = None
+    if quant is not None:
+        bits, seed, offset, base = quant
+        q = _lib.NicHashQuant(int(bits), _lib.NIC_NOISE_KERNEL, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(base))
+    ws = _lib.workspace(t.device, int(lib.nic_hash_fused_points_workspace_bytes(ctypes.byref(d), ctypes.byref(m))))
+    flags = (_lib.NIC_HASH_FUSED_ADD_GRADS if add_grads else 0) | (_lib.NIC_HASH_FUSED_ADD_LOSS if add_loss else 0)
+    _lib.check(lib.nic_hash_fused_forward_backward_points(ctypes.byref(d), None if q is None else ctypes.byref(q), _lib.ptr(t), _lib.ptr(pts), n,
+                                                          _lib.ptr(order), ctypes.byref(m), _lib.ptr(target), float(loss_scale), _lib.ptr(table_grad),
+                                                          ctypes.byref(gs), _lib.ptr(loss), _lib.ptr(y), flags, _lib.ptr(ws), ws.numel(),
+                                                          None if tail is None else ctypes.byref(tail.struct), _lib.stream_ptr(t.device)),
+               "nic_hash_fused_forward_backward_points")
+    if tail is not None:
+        tail.commit()
+    return loss, y
 
 
 class HashEncodeFunction(torch.autograd.Function):
@@ -648,12 +746,15 @@ class HashGridField:
         return loss.detach()
 
     def train_points(self, points: torch.Tensor, target: torch.Tensor, accumulate: bool = False, scale: float = 1.0, step: bool = True,
-                     noise: Optional[bool] = None) -> torch.Tensor:
+                     noise: Optional[bool] = None, order=None, fused: bool = False) -> torch.Tensor:
         """``train_step`` on samples that are no raster: ``points`` [N, dim] (fp32, sample units, any order) with their colours ``target``
         [N, 3].  ``accumulate`` / ``scale`` / ``step`` / ``noise``, the noise keys (seed, optimiser step, samples of this pass before this
-        chunk + row), the freeze behaviour and the optimiser bookkeeping are ``train_step``'s on the layer-wise route, which a fused field
-        takes too for this call (there is no fused training at points): on a crop's sample centres in raster order the two calls differ in
-        the order of the gradient atomics only."""
+        chunk + row), the freeze behaviour and the optimiser bookkeeping are ``train_step``'s.  By default the call is layer-wise and unordered
+        on either route: on a crop's sample centres in raster order it differs from ``train_step`` in the order of the gradient atomics only.
+        ``order``: None, "cell" (``hash_point_order`` of these points, computed for this call) or an int32 [N] device tensor (a precomputed
+        ``hash_point_order``, reused across steps for a fixed point set) - the launch walks the points in that order so that neighbouring
+        lanes share their cells; rows, targets and noise keys stay the caller's.  ``fused``: the fused step at points (two launches,
+        ``nic_hash_fused_forward_backward_points``) - needs ``route == "fused"``."""
         if self.table is None:
             raise RuntimeError("a field from load_compressed decodes only")
         params = self.decoder.linear_params()
@@ -671,6 +772,16 @@ class HashGridField:
         if noise and self.num_bits is None:
             raise ValueError("noise needs num_bits: its amplitude is one quantisation step")
         _point_desc(self.geo)
+        if fused and self.route != "fused":
+            raise ValueError(f"fused=True on a field whose route is {self.route!r}: build it with fused=True (and a shape nic_hash_fused_supported takes)")
+        if order is not None and not (isinstance(order, str) and order == "cell"):
+            order = _check_order(order, n, pts.device)
+        if fused:
+            target = _lib.require_cuda_f32(target, "target")
+        if isinstance(order, str):
+            order = hash_point_order(self.geo, pts)
+        if fused:
+            return self._fused_train_points(pts, target, accumulate, scale, step, noise, order)
         if not accumulate:
             for p in params:
                 p.grad = None
@@ -682,11 +793,11 @@ class HashGridField:
         self._pass_samples += n
         if not frozen:
             x.requires_grad_(True)
-        y = fused.DecoderFunction.apply(x, *params)
+        y = DecoderFunction.apply(x, *params)          # `fused` is this call's argument here
         loss = ((y - target) ** 2).mean() * scale
         loss.backward()
         if not frozen:
-            hash_encode_points_backward(self.geo, pts, x.grad, grad)
+            hash_encode_points_backward(self.geo, pts, x.grad, grad, order=order)
             self._grad_clean = False
         if step:
             self.optimizer.step()
@@ -696,6 +807,77 @@ class HashGridField:
                 self.scheduler.step()
             self.steps += 1
         return loss.detach()
+
+    @torch.no_grad()
+    def _fused_train_points(self, pts, target, accumulate, scale, step, noise, order) -> torch.Tensor:
+        """``train_points`` as two launches, with ``_fused_train_step``'s bookkeeping: persistent decoder-gradient buffers, the chunks of a
+        pass adding into them and into the table gradient, the optimiser riding on the last chunk's reduction.  The arguments are checked."""
+        params = self.decoder.linear_params()
+        frozen = self.frozen
+        grad = None if frozen else self.table.grad
+        if self._fused_gm is None:
+            self._fused_gm = [torch.zeros_like(p) for p in params]
+        gm = self._fused_gm
+        for p, g in zip(params, gm):
+            p.grad = g
+        if not accumulate:
+            if not frozen and not self._grad_clean:
+                grad.zero_()
+            self._pass_samples = 0
+        quant = (self.num_bits, self.noise_seed, self.steps, self._pass_samples) if noise else None
+        tail = None
+        if step:
+            tail = self.optimizer.step_tail([] if frozen else [(self.table, grad)], list(zip(params, gm)))
+        loss, _ = hash_fused_forward_backward_points(self.geo, self.table, pts, params, target, gm, table_grad=grad, order=order,
+                                                     loss_scale=float(scale), quant=quant, add_grads=accumulate, tail=tail)
+        self._pass_samples += pts.shape[0]
+        if not frozen:
+            self._grad_clean = False
+        if step:
+            self.optimizer.step()                    # nothing to launch after a committed tail
+            if not frozen:
+                self._grad_clean = self.optimizer.zeroed_in_last_step(grad)
+            if self.scheduler is not None:
+                self.scheduler.step()
+            self.steps += 1
+        return loss
+
+    def fit_points(self, points: torch.Tensor, target: torch.Tensor, epochs: int, batch: Optional[int] = None, order="cell",
+                   fused: Optional[bool] = None, freeze_at: float = 0.95) -> List[float]:
+        """``fit`` for a fixed sample set: ``epochs`` passes over ``points`` [N, dim] with colours ``target`` [N, 3], one optimiser step per
+        pass.  ``order``: "cell" (default), None or an int32 [N] device tensor; it is computed once and the set is laid out in that order, so
+        every pass walks it in ``batch``-sized accumulate chunks that are contiguous ranges of the order - each chunk spatially compact (None:
+        the whole set in one call).  ``fused``: None = the field's route.  With ``num_bits``: noise while the epoch is below ``freeze_at`` *
+        epochs, then ``freeze()``.  Returns the per-pass losses."""
+        pts = _check_points(self.geo, points)
+        n = pts.shape[0]
+        if n < 1:
+            raise ValueError("no points")
+        target = _lib.require_cuda_f32(target, "target")
+        if tuple(target.shape) != (n, 3):
+            raise ValueError(f"target must be [{n}, 3], got {tuple(target.shape)}")
+        fused = self.route == "fused" if fused is None else bool(fused)
+        if fused and self.route != "fused":
+            raise ValueError(f"fused=True on a field whose route is {self.route!r}")
+        batch = n if batch is None else int(batch)
+        if batch < 1:
+            raise ValueError("batch >= 1")
+        if order is not None:
+            idx = hash_point_order(self.geo, pts) if isinstance(order, str) and order == "cell" else _check_order(order, n, pts.device)
+            idx = idx.to(torch.int64).clamp_(0, n - 1)
+            pts, target = pts[idx].contiguous(), target[idx].contiguous()       # laid out in the order once: a chunk is a slice
+        cuts = list(range(0, n, batch))
+        freeze_epoch = math.ceil(freeze_at * epochs) if self.num_bits is not None else None
+        hist = []
+        for ep in range(epochs):
+            if freeze_epoch is not None and ep >= freeze_epoch and not self.frozen:
+                self.freeze()
+            tot = 0.0
+            for k, c0 in enumerate(cuts):
+                c1 = min(c0 + batch, n)
+                tot = tot + self.train_points(pts[c0:c1], target[c0:c1], accumulate=k > 0, scale=(c1 - c0) / n, step=k == len(cuts) - 1, fused=fused)
+            hist.append(tot)
+        return [float(h) for h in hist]
 
     @torch.no_grad()
     def _fused_train_step(self, coord, extent, target, accumulate, scale, step, noise) -> torch.Tensor:
