@@ -625,6 +625,49 @@ int nic_hash_fused_forward_backward_points(const nic_hash_desc *desc, const nic_
                                            float *table_grad, const nic_mlp_grads *mlp_grads, float *loss, float *y, int flags, void *workspace,
                                            size_t workspace_bytes, const nic_step_tail *tail, void *stream);
 
+/* ---- hash-grid codec: a bit depth PER LEVEL (hashgrid.py, HashGridField(num_bits=[b_0, ..]); csrc/hash_mixed.hip).
+ *      level_bits->bits[l] = b_l in 1 .. 8 for each of desc->levels levels (entries past desc->levels are ignored); everything is the codec
+ *      above applied per level with b = b_l:
+ *      - clamp range of level l: [-(2^b_l - 1) / 2^(b_l + 1), 1/2] (nic_hash_clamp_levels, in place on the fp32 [L, T, F] table, NaN kept);
+ *      - noise: columns l F + f take nic_hash_encode_noisy's value with scale 2^-b_l.  Block numbering, the Threefry keys, the sample_base +
+ *        row keying and the value's expression are unchanged, only the power-of-two scale is the level's: equal depths give
+ *        nic_hash_encode_noisy's row bit for bit.  quant->num_bits is ignored by these entry points;
+ *      - stored format nicv2-hashgrid-bits/2 = format /1 with b replaced by b_l inside level l: value f of entry e of level l occupies bits
+ *        [(e F + f) b_l, (e F + f + 1) b_l) of that level's little-endian stream, each level is padded to whole dwords and starts at byte
+ *        4 sum_{k<l} ceil(E_k F b_k / 32), 8 zero bytes follow the last level; nic_hash_packed_bytes_levels = 4 sum_l ceil(E_l F b_l / 32) + 8
+ *        (host arithmetic; or a negative NIC_E_* code).  The stored value and its dequantisation are nic_hash_pack_u8's / nic_hash_encode_u8's
+ *        expressions with b_l: level l of a mixed table holds exactly the bytes level l of a /1 table of depth b_l holds and decodes to exactly
+ *        its columns.  nic_hash_pack_bits_levels writes the whole buffer (padding and tail as zeros, one dword per thread, no atomics).  There
+ *        is no uint8 form of a mixed table.
+ *      Positions: exactly one of `origins` / `points` is non-null (else NIC_E_ARG).  origins = the crop lattice of nic_hash_encode (rows,
+ *      noise keys and outputs in its sample order; n_points ignored); lattice sample i is taken as the point t = 256 i + 128, which gives the
+ *      crop route's row bit for bit (previous section), so the lattice route needs 256 S_max < 2^30 too.  points = as in
+ *      nic_hash_encode_points (desc->extent the field size, num_crops 1).
+ *      Source (src): NIC_HASH_SRC_F32, or NIC_HASH_SRC_BITS = a format /2 table, 4-byte aligned; NIC_HASH_SRC_U8 is NIC_E_ARG and
+ *      src->num_bits must be 0.  `quant` (null or kernel noise, then per-level noise) only with an F32 source.
+ *      nic_hash_encode_levels: the [N, L F] row.  nic_hash_fused_forward_levels: gather + decoder in one launch ([N, 3]; the set
+ *      nic_hash_fused_supported answers for).  nic_hash_fused_forward_backward_levels: nic_hash_fused_forward_backward_points' contract with
+ *      per-level noise and either position source - two launches, the second the fixed-order reduction with `tail` riding on it; `order` only
+ *      with `points` (else NIC_E_ARG); workspace >= nic_hash_fused_points_workspace_bytes (the size does not depend on the crops).
+ *      The straight-through scatter does not depend on the depth: nic_hash_encode_backward / nic_hash_encode_points_backward(_ordered) serve
+ *      the layer-wise backward as they are.  Every argument error is returned on the host before any GPU work, codes and order as in the
+ *      _points siblings (descriptor, the position pair, null pointers, depths outside 1 .. 8, source, quant, n_points, workspace, tail). */
+typedef struct nic_hash_level_bits {
+    int32_t bits[NIC_HASH_MAX_LEVELS];
+} nic_hash_level_bits;
+int64_t nic_hash_packed_bytes_levels(const nic_hash_desc *desc, const nic_hash_level_bits *level_bits);
+int nic_hash_pack_bits_levels(const nic_hash_desc *desc, const nic_hash_level_bits *level_bits, const float *table, uint8_t *packed, void *stream);
+int nic_hash_clamp_levels(const nic_hash_desc *desc, const nic_hash_level_bits *level_bits, float *table, void *stream);
+int nic_hash_encode_levels(const nic_hash_desc *desc, const nic_hash_level_bits *level_bits, const nic_hash_source *src,
+                           const nic_hash_quant *quant, const int32_t *origins, const float *points, int64_t n_points, float *out, void *stream);
+int nic_hash_fused_forward_levels(const nic_hash_desc *desc, const nic_hash_level_bits *level_bits, const nic_hash_source *src,
+                                  const int32_t *origins, const float *points, int64_t n_points, const nic_mlp *mlp, float *y, void *stream);
+int nic_hash_fused_forward_backward_levels(const nic_hash_desc *desc, const nic_hash_level_bits *level_bits, const nic_hash_quant *quant,
+                                           const float *table, const int32_t *origins, const float *points, int64_t n_points,
+                                           const int32_t *order, const nic_mlp *mlp, const float *target, float loss_scale, float *table_grad,
+                                           const nic_mlp_grads *mlp_grads, float *loss, float *y, int flags, void *workspace,
+                                           size_t workspace_bytes, const nic_step_tail *tail, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

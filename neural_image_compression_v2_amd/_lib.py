@@ -125,6 +125,11 @@ class NicHashSource(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("num_bits", ctypes.c_int32), ("data", ctypes.c_void_p)]
 
 
+class NicHashLevelBits(ctypes.Structure):
+    """struct nic_hash_level_bits (include/nicv2_hip.h): the bit depth of every level of a mixed-depth hash-grid codec launch (hashgrid.py)"""
+    _fields_ = [("bits", ctypes.c_int32 * NIC_HASH_MAX_LEVELS)]
+
+
 _P, _I, _L, _F, _SZ, _DBL = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t, ctypes.c_double
 _D = ctypes.POINTER(NicPathDesc)
 _M = ctypes.POINTER(NicMlp)
@@ -202,6 +207,15 @@ SIGNATURES = {
     "nic_hash_fused_points_workspace_bytes": (_SZ, [ctypes.POINTER(NicHashDesc), _M]),
     "nic_hash_fused_forward_backward_points": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashQuant), _P, _P, _L, _P, _M, _P, _F, _P, _G, _P, _P,
                                                     _I, _P, _SZ, ctypes.POINTER(NicStepTail), _P]),
+    "nic_hash_packed_bytes_levels": (_L, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashLevelBits)]),
+    "nic_hash_pack_bits_levels": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashLevelBits), _P, _P, _P]),
+    "nic_hash_clamp_levels": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashLevelBits), _P, _P]),
+    "nic_hash_encode_levels": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashLevelBits), ctypes.POINTER(NicHashSource),
+                                    ctypes.POINTER(NicHashQuant), _P, _P, _L, _P, _P]),
+    "nic_hash_fused_forward_levels": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashLevelBits), ctypes.POINTER(NicHashSource), _P, _P, _L, _M,
+                                           _P, _P]),
+    "nic_hash_fused_forward_backward_levels": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashLevelBits), ctypes.POINTER(NicHashQuant), _P, _P, _P,
+                                                    _L, _P, _M, _P, _F, _P, _G, _P, _P, _I, _P, _SZ, ctypes.POINTER(NicStepTail), _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -1,5 +1,6 @@
 // What the hash-grid kernels share, for translation units written after hash_grid.hip / hash_fused.hip / hash_points.hip (those three are pinned
-// and keep their own restated copies): the index helpers, the fp32 row loader, the fixed-point position and cell of a point
+// and keep their own restated copies): the index helpers, the fp32 and packed row loaders, the fixed-point position and cell of a point
+// or of a lattice sample
 // (include/nicv2_hip.h, nic_hash_encode_points), the level loops of the encode (row into an LDS tile) and of the scatter (run sums keyed on the
 // base vertex), and the ColorDecoder(L F, 64, 3) forward + backward on v_mfma_f32_32x32x2_f32 with its register-resident weight-gradient
 // accumulators and per-workgroup record (hash_fused.hip's training mode, the same product order).  run_masks / run_sum, the noise generator and
@@ -39,6 +40,58 @@ __device__ __forceinline__ void load_row(const float* p, float (&v)[F]) {
         }
     }
 }
+template <int F>
+__device__ __forceinline__ void store_row(float* p, const float (&v)[F]) {
+    if constexpr (F == 1) {
+        *p = v[0];
+    } else if constexpr (F == 2) {
+        *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < F; k += 4) *reinterpret_cast<float4*>(p + k) = make_float4(v[k], v[k + 1], v[k + 2], v[k + 3]);
+    }
+}
+// entries a level stores: the (R + 1)^dim vertices of a dense level, all T of a hashed one; dwords of its bit stream at `bits` bits per value
+__host__ __device__ inline int64_t hash_level_entries(int dim, int32_t R, int log2_table) {
+    if (!hash_level_dense(dim, R, log2_table)) return int64_t(1) << log2_table;
+    int64_t e = 1;
+    for (int a = 0; a < dim; ++a) e *= (int64_t)R + 1;
+    return e;
+}
+__host__ __device__ inline int64_t hash_level_dwords(int dim, int32_t R, int log2_table, int F, int bits) {
+    return (hash_level_entries(dim, R, log2_table) * (F * bits) + 31) >> 5;
+}
+__host__ __device__ inline bool hash_bits_tight(int F, int bits) { return 32 % (F * bits) == 0 || F * bits == 64; }
+// the packed-row loader (hash_grid.hip): entry e of F b bits at bit e F b of its level's stream, aligned dword loads only, funnel-shifted to
+// bit 0; TIGHT: no entry straddles, the extra dword is not read.  The value takes load_row_u8's dequantisation, expression for expression.
+template <int F, bool TIGHT>
+__device__ __forceinline__ void load_row_bits(const uint32_t* lev, uint32_t e, int bits, float scale, float bias, float (&v)[F]) {
+    const uint32_t bit = e * (uint32_t)(F * bits), sh = bit & 31u;
+    const uint32_t* q = lev + (bit >> 5);
+    uint32_t x0, x1 = 0u;
+    const uint32_t w0 = q[0];
+    if constexpr (F <= 4) {
+        if constexpr (TIGHT) x0 = w0 >> sh;
+        else x0 = __builtin_amdgcn_alignbit(q[1], w0, sh);
+    } else {
+        if constexpr (TIGHT) {
+            x0 = w0 >> sh;
+            if (bits == 8) x1 = q[1];                                // F b = 64 starts on a dword
+        } else {
+            const uint32_t w1 = q[1], w2 = q[2];
+            x0 = __builtin_amdgcn_alignbit(w1, w0, sh);
+            x1 = __builtin_amdgcn_alignbit(w2, w1, sh);
+        }
+    }
+#pragma unroll
+    for (int f = 0; f < F; ++f) {
+        uint32_t uv;
+        if constexpr (F <= 4) uv = __builtin_amdgcn_ubfe(x0, (uint32_t)(f * bits), (uint32_t)bits);      // f b + b <= 32
+        else uv = __builtin_amdgcn_ubfe((uint32_t)((((uint64_t)x1 << 32) | x0) >> (f * bits)), 0u, (uint32_t)bits);
+        const float u = (float)uv;
+        v[f] = __fdiv_rn(__fadd_rn(__fsub_rn(u, bias), 1.0f), scale);
+    }
+}
 template <int D>
 __device__ __forceinline__ float corner_weight(const float (&w)[3], int c) {
     float r = ((c & 1) ? w[0] : 1.0f - w[0]) * ((c & 2) ? w[1] : 1.0f - w[1]);
@@ -72,6 +125,60 @@ __device__ __forceinline__ void point_cell(const uint32_t (&t)[3], uint32_t R, u
         w[a] = (float)(((qh - v[a] * S) << 8) | ql) / fdiv;
     }
     if (D == 2) { v[2] = 0; w[2] = 0.f; }
+}
+
+// ---- the lattice as a position source (hash_grid.hip) -------------------------------------------------------------------------------------
+// the sample of this lane in patch `wv` of 8 x 8 / 4 x 4 x 4 samples, x the fastest lane axis (clamped to the last patch; `live` = a real
+// sample of a real patch); n = its row in nic_encode sample order
+template <int D>
+struct PatchSample {
+    int crop;
+    int idx[3];
+    bool live;
+    int64_t n;
+};
+template <int D>
+__device__ __forceinline__ PatchSample<D> patch_sample(const nic_hash_desc& d, int64_t wv, int64_t n_patches, int lane) {
+    constexpr int PS = D == 2 ? 8 : 4;
+    const int np1 = (d.extent[1] + PS - 1) / PS, np2 = D == 3 ? (d.extent[2] + PS - 1) / PS : 1;
+    const int64_t per_crop = (int64_t)((d.extent[0] + PS - 1) / PS) * np1 * np2;
+    const int64_t wc = wv < n_patches ? wv : n_patches - 1;
+    PatchSample<D> s;
+    s.crop = (int)(wc / per_crop);
+    int64_t pr = wc - (int64_t)s.crop * per_crop;
+    int pt[3] = {0, 0, 0};
+    if (D == 3) { pt[2] = (int)(pr % np2); pr /= np2; }
+    pt[1] = (int)(pr % np1);
+    pt[0] = (int)(pr / np1);
+    if (D == 2) {
+        s.idx[0] = PS * pt[0] + (lane & 7);
+        s.idx[1] = PS * pt[1] + (lane >> 3);
+        s.idx[2] = 0;
+    } else {
+        s.idx[0] = PS * pt[0] + (lane & 3);
+        s.idx[1] = PS * pt[1] + ((lane >> 2) & 3);
+        s.idx[2] = PS * pt[2] + (lane >> 4);
+    }
+    s.live = wv < n_patches;
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        s.live = s.live && s.idx[a] < d.extent[a];
+        s.idx[a] = s.idx[a] < d.extent[a] ? s.idx[a] : d.extent[a] - 1;
+    }
+    const int64_t n_per_crop = (int64_t)d.extent[0] * d.extent[1] * (D == 3 ? d.extent[2] : 1);
+    s.n = (int64_t)s.crop * n_per_crop + ((int64_t)s.idx[0] * d.extent[1] + s.idx[1]) * (D == 3 ? d.extent[2] : 1) + (D == 3 ? s.idx[2] : 0);
+    return s;
+}
+// lattice sample i (origin + index, clamped into the field like sample_coords) as the point t = 256 i + 128: both operands of the cell
+// quotient are 128 times the crop route's, so v, w and the row are nic_hash_encode's bit for bit (include/nicv2_hip.h)
+template <int D>
+__device__ __forceinline__ void lattice_fixed(const nic_hash_desc& d, const int32_t* origins, const PatchSample<D>& s, uint32_t (&t)[3]) {
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        const int c = origins[s.crop * D + a] + s.idx[a];
+        t[a] = 256u * (uint32_t)(c < 0 ? 0 : (c >= d.S_max ? d.S_max - 1 : c)) + 128u;
+    }
+    if (D == 2) t[2] = 0;
 }
 
 // the level loop of hash_points_encode_kernel from the fp32 table, the row going value by value into `row` (an LDS tile); NOISE: the noise of
@@ -162,9 +269,11 @@ struct RecLayout {
     }
 };
 
-struct TrainSmem {
+struct DecoderSmem {             // what a forward-only launch needs: the leading part of TrainSmem, member for member
     float w1[kH * XS], w2[kH * XS], w3[4 * kH], b1[kH], b2[kH], b3[4];
     float x[4][kH * XS];        // per wave: the encoding rows [sample][column], later d loss / d row; at the end of the launch the workgroup's record
+};
+struct TrainSmem : DecoderSmem {
     float p[4][NQ * XS], q[4][NQ * XS];
 };
 
@@ -229,7 +338,7 @@ struct TrainAcc {
 };
 
 // the decoder's weights into LDS (columns past L F are zero) and the wave's row tile cleared; the caller synchronises the workgroup after it
-__device__ __forceinline__ void load_decoder(TrainSmem& sm, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
+__device__ __forceinline__ void load_decoder(DecoderSmem& sm, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
                                              const float* b3, int LF, int tid) {
     for (int e = tid; e < kH * XS; e += 256) {
         const int h = e / XS, k = e - h * XS;
@@ -241,6 +350,53 @@ __device__ __forceinline__ void load_decoder(TrainSmem& sm, const float* w1, con
     if (tid < 4) sm.b3[tid] = tid < 3 ? b3[tid] : 0.f;
     float* xs = sm.x[tid >> 6];
     for (int e = tid & 63; e < kH * XS; e += 64) xs[e] = 0.f;       // the columns past L F stay finite (their weights are zero)
+}
+
+// the forward half of decoder_train_half alone (hash_fused_kernel's forward mode, the same products in the same order): y of sample
+// 32 nt + j of the row tile `xs` in registers 0 .. 2 of half 0
+__device__ __forceinline__ void decoder_forward_half(const DecoderSmem& sm, const float* xs, int nt, int j, int half, int ks1, float (&yv)[3]) {
+    const float* xb = xs + (32 * nt + j) * XS;
+    f32x16 a1[2] = {f32x16{}, f32x16{}};
+    for (int k = 0; k < ks1; ++k) {
+        const float b = xb[2 * k + half];
+        a1[0] = mfma(sm.w1[j * XS + 2 * k + half], b, a1[0]);
+        a1[1] = mfma(sm.w1[(32 + j) * XS + 2 * k + half], b, a1[1]);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float av, dv;
+            gelu_and_grad(a1[t][r] + sm.b1[32 * t + row_of(r, half)], av, dv);
+            a1[t][r] = av;
+        }
+    f32x16 a2[2] = {f32x16{}, f32x16{}};
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int k = 32 * t + row_of(r, half);
+            a2[0] = mfma(sm.w2[j * XS + k], a1[t][r], a2[0]);
+            a2[1] = mfma(sm.w2[(32 + j) * XS + k], a1[t][r], a2[1]);
+        }
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float av, dv;
+            gelu_and_grad(a2[t][r] + sm.b2[32 * t + row_of(r, half)], av, dv);
+            a2[t][r] = av;
+        }
+    f32x16 z3 = f32x16{};
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int k = 32 * t + row_of(r, half);
+            z3 = mfma(j < 3 ? sm.w3[j * kH + k] : 0.f, a2[t][r], z3);
+        }
+#pragma unroll
+    for (int o = 0; o < 3; ++o) yv[o] = sigmoid_f(z3[o] + sm.b3[o]);
 }
 
 // forward, loss and backward of the 32 samples `32 nt + j` of a wave's row tile `xs` (hash_fused_kernel's training mode, the same products in

@@ -32,6 +32,13 @@ and scatters (``nic_hash_fused_forward_backward``; the [N, L F] row never reache
 the optimiser.  ``decode`` is one launch per tile.  Shapes outside the kernel's set (``nic_hash_fused_supported``) take the layer-wise route by
 themselves; ``field.route`` says which one runs.
 
+A bit depth per level (include/nicv2_hip.h, nic_hash_level_bits; csrc/hash_mixed.hip): ``HashGridField(..., num_bits=[b_0, ..,
+b_{L-1}])`` applies the codec per level with b = b_l - level l is clamped to its own range (the optimiser clamps to the widest one,
+``nic_hash_clamp_levels`` tightens the rest after each step), its columns take noise of scale 2^-b_l, ``freeze()`` quantises it with b_l, and
+``save_compressed(path, packed=True)`` stores format ``nicv2-hashgrid-bits/2``: format /1 with b_l bits per value inside level l.  ``decode`` /
+``query`` / ``resample`` of a loaded mixed field read those bits through ``nic_hash_encode_levels`` / ``nic_hash_fused_forward_levels``.  A
+sequence always takes this path (equal depths give the uniform rows bit for bit); an int ``num_bits`` makes the calls it always made.
+
 Off the lattice (include/nicv2_hip.h, nic_hash_encode_points): a point is ``dim`` fp32 coordinates in sample units, p_a = i the
 centre of sample i, the field spanning [-1/2, S_a - 1/2]; t_a = rint(256 p_a) + 128 clamped to [0, 256 S_a - 1], q = t_a R_l, v_a = q div
 256 S_max, w_a = fp32(q mod 256 S_max) / fp32(256 S_max) - at a sample centre the lattice row, bit for bit.  ``hash_encode_points`` /
@@ -241,8 +248,40 @@ def hash_encode_u8(geo: HashGeometry, stored: torch.Tensor, coord, extent: Seque
     return out
 
 
-def hash_packed_bytes(geo: HashGeometry, num_bits: int) -> int:
-    """bytes of the bit-packed table: 4 * sum_l ceil(E_l F b / 32) + 8 (nic_hash_packed_bytes)"""
+def _check_level_bits(levels: int, bits) -> Tuple[int, ...]:
+    """a bit depth per level: a sequence of ``levels`` ints in 1 .. 8, as a tuple (anything else: ValueError)"""
+    if isinstance(bits, (str, bytes)) or not hasattr(bits, "__len__") or not hasattr(bits, "__iter__"):
+        raise ValueError(f"a bit depth per level is a sequence of {levels} ints in 1 .. 8, got {bits!r}")
+    out = []
+    for b in bits:
+        if isinstance(b, bool) or not isinstance(b, int) and not (hasattr(b, "__index__")):
+            raise ValueError(f"a bit depth per level is a sequence of ints in 1 .. 8, got {b!r}")
+        out.append(int(b))
+    if len(out) != int(levels):
+        raise ValueError(f"{len(out)} bit depths for {levels} levels")
+    if any(not 1 <= b <= 8 for b in out):
+        raise ValueError(f"bit depths {out}: each in 1 .. 8")
+    return tuple(out)
+
+
+def _level_bits_struct(geo: HashGeometry, bits) -> "_lib.NicHashLevelBits":
+    lb = _lib.NicHashLevelBits()
+    for l, b in enumerate(_check_level_bits(geo.levels, bits)):
+        lb.bits[l] = b
+    return lb
+
+
+def _is_level_bits(bits) -> bool:
+    return bits is not None and not isinstance(bits, (str, bytes)) and hasattr(bits, "__len__")
+
+
+def hash_packed_bytes(geo: HashGeometry, num_bits) -> int:
+    """bytes of the bit-packed table: 4 * sum_l ceil(E_l F b / 32) + 8 (nic_hash_packed_bytes); ``num_bits`` a sequence: a depth per level,
+    format /2 (nic_hash_packed_bytes_levels)"""
+    if _is_level_bits(num_bits):
+        n = _lib.load().nic_hash_packed_bytes_levels(ctypes.byref(geo.to_desc(1, [1] * geo.dim)), ctypes.byref(_level_bits_struct(geo, num_bits)))
+        _lib.check(n if n < 0 else 0, "nic_hash_packed_bytes_levels")
+        return int(n)
     n = _lib.load().nic_hash_packed_bytes(ctypes.byref(geo.to_desc(1, [1] * geo.dim)), int(num_bits))
     _lib.check(n if n < 0 else 0, "nic_hash_packed_bytes")
     return int(n)
@@ -252,7 +291,7 @@ def _check_packed(geo: HashGeometry, packed: torch.Tensor, num_bits: int) -> Non
     if not isinstance(packed, torch.Tensor) or packed.dtype != torch.uint8 or not packed.is_cuda or packed.dim() != 1 or not packed.is_contiguous():
         raise ValueError("packed must be a contiguous 1-D uint8 tensor on a HIP device")
     if packed.numel() != hash_packed_bytes(geo, num_bits):
-        raise ValueError(f"packed holds {packed.numel()} bytes, the geometry needs {hash_packed_bytes(geo, num_bits)} at {int(num_bits)} bits")
+        raise ValueError(f"packed holds {packed.numel()} bytes, the geometry needs {hash_packed_bytes(geo, num_bits)} at {num_bits} bits")
     if packed.data_ptr() % 4:
         raise ValueError("packed must start on a 4-byte boundary: the gather reads aligned dwords")
 
@@ -578,6 +617,149 @@ def hash_fused_forward_backward_points(geo: HashGeometry, table: torch.Tensor, p
     return loss, y
 
 
+@fused._on_tensor_device
+def hash_pack_bits_levels(geo: HashGeometry, table: torch.Tensor, level_bits, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """format /2 of an fp32 [L, T, F] table (nic_hash_pack_bits_levels): ``hash_pack_bits`` with ``level_bits[l]`` bits per value inside level
+    l.  Clamp each level to its range first.  ``out``: a buffer of ``hash_packed_bytes(geo, level_bits)`` to fill (every byte is written)."""
+    t = _check_table(geo, table.detach())
+    lb = _level_bits_struct(geo, level_bits)
+    if out is None:
+        out = torch.empty(hash_packed_bytes(geo, level_bits), dtype=torch.uint8, device=t.device)
+    _check_packed(geo, out, tuple(level_bits))
+    _lib.check(_lib.load().nic_hash_pack_bits_levels(ctypes.byref(geo.to_desc(1, [1] * geo.dim)), ctypes.byref(lb), _lib.ptr(t), _lib.ptr(out),
+                                                     _lib.stream_ptr(t.device)), "nic_hash_pack_bits_levels")
+    return out
+
+
+@fused._on_tensor_device
+def hash_clamp_levels(geo: HashGeometry, table: torch.Tensor, level_bits) -> torch.Tensor:
+    """clamps level l of the fp32 [L, T, F] ``table`` to ``models._q_range(level_bits[l])`` IN PLACE (nic_hash_clamp_levels; a NaN stays)"""
+    t = _check_table(geo, table.detach())
+    if t.data_ptr() != table.data_ptr():
+        raise ValueError("table must be contiguous: the kernel clamps it in place")
+    lb = _level_bits_struct(geo, level_bits)
+    _lib.check(_lib.load().nic_hash_clamp_levels(ctypes.byref(geo.to_desc(1, [1] * geo.dim)), ctypes.byref(lb), _lib.ptr(t), _lib.stream_ptr(t.device)),
+               "nic_hash_clamp_levels")
+    return table
+
+
+def _levels_source(geo: HashGeometry, data: torch.Tensor, kind: str, level_bits) -> Tuple["_lib.NicHashSource", torch.Tensor]:
+    """``nic_hash_source`` of a mixed-depth launch: "f32" = the fp32 [L, T, F] table, "bits" = a format /2 table (no uint8 form)"""
+    if kind == "f32":
+        data = _check_table(geo, data.detach())
+    elif kind == "bits":
+        _check_packed(geo, data, tuple(level_bits))
+    else:
+        raise ValueError(f"table source {kind!r} of a mixed-depth launch: 'f32' or 'bits'")
+    return _lib.NicHashSource(POINT_SOURCES[kind], 0, data.data_ptr()), data
+
+
+def _levels_positions(geo: HashGeometry, coord, extent, points, device):
+    """exactly one position source -> (desc, origins or None, points or None, N)"""
+    if (coord is None) == (points is None):
+        raise ValueError("exactly one of coord (with extent) and points")
+    if 256 * geo.s_max >= 2 ** 30:
+        raise ValueError(f"a field of {geo.s_max} samples per axis is too large for the mixed-depth entry points: 256 * S_max < 2^30")
+    if points is not None:
+        pts = _check_points(geo, points)
+        return _point_desc(geo), None, pts, pts.shape[0]
+    org = geo.upload_origins(coord, extent, device)
+    return geo.to_desc(org.shape[0], extent), org, None, _n_samples(org.shape[0], extent)
+
+
+def _levels_quant(quant) -> Optional["_lib.NicHashQuant"]:
+    """None or (seed, offset, sample_base): ``hash_encode_noisy``'s noise, its scale 2^-level_bits[l] on the columns of level l"""
+    if quant is None:
+        return None
+    seed, offset, base = quant
+    return _lib.NicHashQuant(0, _lib.NIC_NOISE_KERNEL, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(base))
+
+
+@fused._on_tensor_device
+def hash_encode_levels(geo: HashGeometry, data: torch.Tensor, level_bits, coord=None, extent: Optional[Sequence[int]] = None,
+                       points: Optional[torch.Tensor] = None, kind: str = "f32", quant=None) -> torch.Tensor:
+    """[N, L F] encoding with a bit depth per level (nic_hash_encode_levels) on the crops ``coord`` / ``extent`` or at ``points`` (exactly
+    one), from the fp32 table (``kind`` "f32"; ``quant`` = None or (seed, offset, sample_base): per-level noise) or from a format /2 table
+    (``kind`` "bits").  Columns l F .. of the result are those of the uniform-depth call at depth ``level_bits[l]``, bit for bit."""
+    lb = _level_bits_struct(geo, level_bits)
+    src, data = _levels_source(geo, data, kind, level_bits)
+    if quant is not None and kind != "f32":
+        raise ValueError("noise belongs to training, which reads the fp32 table")
+    d, org, pts, n = _levels_positions(geo, coord, extent, points, data.device)
+    out = torch.empty(n, geo.width, dtype=torch.float32, device=data.device)
+    if n == 0:
+        return out
+    q = _levels_quant(quant)
+    _lib.check(_lib.load().nic_hash_encode_levels(ctypes.byref(d), ctypes.byref(lb), ctypes.byref(src), None if q is None else ctypes.byref(q),
+                                                  _lib.ptr(org), _lib.ptr(pts), n if pts is not None else 0, _lib.ptr(out),
+                                                  _lib.stream_ptr(data.device)), "nic_hash_encode_levels")
+    return out
+
+
+@fused._on_tensor_device
+def hash_fused_forward_levels(geo: HashGeometry, data: torch.Tensor, level_bits, params: Sequence[torch.Tensor], coord=None,
+                              extent: Optional[Sequence[int]] = None, points: Optional[torch.Tensor] = None, kind: str = "f32") -> torch.Tensor:
+    """[N, 3] = ColorDecoder(hash_encode_levels(...)) in one launch (nic_hash_fused_forward_levels)"""
+    lb = _level_bits_struct(geo, level_bits)
+    src, data = _levels_source(geo, data, kind, level_bits)
+    params = _check_fused_decoder(geo, [q.detach() for q in params])
+    d, org, pts, n = _levels_positions(geo, coord, extent, points, data.device)
+    y = torch.empty(n, 3, dtype=torch.float32, device=data.device)
+    if n == 0:
+        return y
+    m = fused._mlp_struct(params)
+    _lib.check(_lib.load().nic_hash_fused_forward_levels(ctypes.byref(d), ctypes.byref(lb), ctypes.byref(src), _lib.ptr(org), _lib.ptr(pts),
+                                                         n if pts is not None else 0, ctypes.byref(m), _lib.ptr(y), _lib.stream_ptr(data.device)),
+               "nic_hash_fused_forward_levels")
+    return y
+
+
+@fused._on_tensor_device
+def hash_fused_forward_backward_levels(geo: HashGeometry, table: torch.Tensor, level_bits, params: Sequence[torch.Tensor], target: torch.Tensor,
+                                       mlp_grads: Sequence[torch.Tensor], coord=None, extent: Optional[Sequence[int]] = None,
+                                       points: Optional[torch.Tensor] = None, order: Optional[torch.Tensor] = None,
+                                       table_grad: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None, loss_scale: float = 1.0,
+                                       want_y: bool = False, quant=None, add_grads: bool = False, add_loss: bool = False, tail=None):
+    """``hash_fused_forward_backward`` (crops) / ``hash_fused_forward_backward_points`` (points, with ``order``) with a bit depth per level
+    (nic_hash_fused_forward_backward_levels): the same two launches, ``quant`` = None or (seed, offset, sample_base) for per-level noise.
+    Returns (loss [1], y or None)."""
+    t = _check_table(geo, table.detach())
+    lb = _level_bits_struct(geo, level_bits)
+    params = _check_fused_decoder(geo, [q.detach() for q in params])
+    d, org, pts, n = _levels_positions(geo, coord, extent, points, t.device)
+    if n < 1:
+        raise ValueError("no samples")
+    target = _lib.require_cuda_f32(target, "target")
+    if tuple(target.shape) != (n, 3):
+        raise ValueError(f"target must be [{n}, 3], got {tuple(target.shape)}")
+    if order is not None:
+        if pts is None:
+            raise ValueError("an order names points: it goes with points, not with crops")
+        order = _check_order(order, n, pts.device)
+    if table_grad is not None:
+        g = _check_table(geo, table_grad, "table_grad")
+        if g is not table_grad:
+            raise ValueError("table_grad must be contiguous: the kernel adds into it in place")
+    if len(mlp_grads) != 6 or any(not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.shape == q.shape) for g, q in zip(mlp_grads, params)):
+        raise ValueError("mlp_grads: six contiguous fp32 device buffers shaped like the decoder's parameters")
+    loss = torch.empty(1, dtype=torch.float32, device=t.device) if loss is None else loss
+    y = torch.empty(n, 3, dtype=torch.float32, device=t.device) if want_y else None
+    lib = _lib.load()
+    m, gs = fused._mlp_struct(params), fused._grads_struct(list(mlp_grads))
+    q = _levels_quant(quant)
+    ws = _lib.workspace(t.device, int(lib.nic_hash_fused_points_workspace_bytes(ctypes.byref(_point_desc(geo)), ctypes.byref(m))))
+    flags = (_lib.NIC_HASH_FUSED_ADD_GRADS if add_grads else 0) | (_lib.NIC_HASH_FUSED_ADD_LOSS if add_loss else 0)
+    _lib.check(lib.nic_hash_fused_forward_backward_levels(ctypes.byref(d), ctypes.byref(lb), None if q is None else ctypes.byref(q), _lib.ptr(t),
+                                                          _lib.ptr(org), _lib.ptr(pts), n if pts is not None else 0, _lib.ptr(order), ctypes.byref(m),
+                                                          _lib.ptr(target), float(loss_scale), _lib.ptr(table_grad), ctypes.byref(gs), _lib.ptr(loss),
+                                                          _lib.ptr(y), flags, _lib.ptr(ws), ws.numel(),
+                                                          None if tail is None else ctypes.byref(tail.struct), _lib.stream_ptr(t.device)),
+               "nic_hash_fused_forward_backward_levels")
+    if tail is not None:
+        tail.commit()
+    return loss, y
+
+
 class HashEncodeFunction(torch.autograd.Function):
     """``hash_encode`` as a differentiable op of the table: backward = ``nic_hash_encode_backward`` into a fresh zero [L, T, F] (what autograd
     through ``index_add`` of the corner entries would give, collisions summed)"""
@@ -640,17 +822,23 @@ def _table_of_u8(geo: HashGeometry, stored: torch.Tensor, num_bits: int) -> torc
 
 COMPRESSED_FORMAT = "nicv2-hashgrid-u8/1"
 PACKED_FORMAT = "nicv2-hashgrid-bits/1"          # the same dict with the bit-packed table (include/nicv2_hip.h, nic_hash_pack_bits)
+MIXED_FORMAT = "nicv2-hashgrid-bits/2"           # format /1 with "level_bits": a depth per level (nic_hash_pack_bits_levels); "num_bits" is None
 
 
 class HashGridField:
     """a hash-grid table + one decoder over its [N, L F] encoding, trained like ``MultiLevelField`` (module docstring).  ``field_size``:
     (S_x, S_y) or (S_x, S_y, S_z), x = the image tensor's first spatial axis like everywhere in this package.  ``num_bits``: None = no codec
     (no noise, no clamp); b in 1..8 = quantisation-aware training for a uint8 table of b-bit values (module docstring), noise keyed by
-    ``noise_seed``.  ``fused``: ``train_step`` / ``fit`` / ``decode`` on the fused encode + decoder kernels where they exist (``route``)."""
+    ``noise_seed``; a sequence of ``levels`` depths = a bit depth per level (``level_bits`` holds the tuple, ``num_bits`` stays None).  ``fused``: ``train_step`` / ``fit`` / ``decode`` on the fused encode + decoder kernels where they exist (``route``)."""
+
+    level_bits: Optional[Tuple[int, ...]] = None     # a bit depth per level (None: an int ``num_bits`` field, or no codec)
 
     def __init__(self, field_size: Union[int, Sequence[int]], levels: int = 16, features: int = 2, log2_table: int = 19, base_resolution: float = 16,
                  finest_resolution: Optional[float] = None, hidden: int = 64, n_linear: int = 3, device=None, seed: Optional[int] = None,
-                 num_bits: Optional[int] = None, noise_seed: int = 7, fused: bool = False):
+                 num_bits: Union[None, int, Sequence[int]] = None, noise_seed: int = 7, fused: bool = False):
+        level_bits = None
+        if _is_level_bits(num_bits):
+            level_bits, num_bits = _check_level_bits(levels, num_bits), None
         if num_bits is not None and not 1 <= int(num_bits) <= 8:
             raise ValueError("num_bits in 1 .. 8 (the stored table is uint8), or None")
         self.field_size = (int(field_size),) * 2 if isinstance(field_size, int) else tuple(int(v) for v in field_size)
@@ -671,11 +859,24 @@ class HashGridField:
         self.scheduler = None
         self.hidden, self.n_linear = int(hidden), int(n_linear)
         self.num_bits = None if num_bits is None else int(num_bits)
+        self.level_bits = level_bits
         self.noise_seed, self.steps, self.frozen, self.stored, self.packed = int(noise_seed), 0, False, None, None
         self._pass_samples = 0                       # samples of the current accumulate pass so far: the next chunk's sample_base
         self._set_route(fused)
         if self.num_bits is not None:
             self.optimizer.set_clamp([self.table], *models._q_range(self.num_bits))
+        if self.level_bits is not None:              # the optimiser's one clamp is the widest range; _clamp_levels tightens the rest
+            self.optimizer.set_clamp([self.table], *models._q_range(max(self.level_bits)))
+
+    @property
+    def _codec(self) -> bool:
+        return self.num_bits is not None or self.level_bits is not None
+
+    def _clamp_levels(self) -> None:
+        """after an optimiser step of a mixed-depth field: the levels below the widest depth into their own range (one launch; none when all
+        depths are equal)"""
+        if self.level_bits is not None and not self.frozen and len(set(self.level_bits)) > 1:
+            hash_clamp_levels(self.geo, self.table.detach(), self.level_bits)
 
     def _set_route(self, want_fused: bool) -> None:
         """"fused" when asked for and the kernels exist for this shape, else "layerwise" (a field built without ``fused`` never asks the library)"""
@@ -720,10 +921,12 @@ class HashGridField:
         if tuple(target.shape) != (n, 3):
             raise ValueError(f"target must be [{n}, 3], got {tuple(target.shape)}")
         if noise is None:
-            noise = self.num_bits is not None and not frozen
-        if noise and self.num_bits is None:
+            noise = self._codec and not frozen
+        if noise and not self._codec:
             raise ValueError("noise needs num_bits: its amplitude is one quantisation step")
-        if noise:
+        if noise and self.level_bits is not None:
+            x = hash_encode_levels(self.geo, self.table, self.level_bits, coord=org, extent=extent, quant=(self.noise_seed, self.steps, self._pass_samples))
+        elif noise:
             x = hash_encode_noisy(self.geo, self.table, org, extent, self.num_bits, self.noise_seed, self.steps, self._pass_samples)
         else:
             x = hash_encode(self.geo, self.table, org, extent)
@@ -738,6 +941,7 @@ class HashGridField:
             self._grad_clean = False
         if step:
             self.optimizer.step()
+            self._clamp_levels()
             if not frozen:
                 self._grad_clean = self.optimizer.zeroed_in_last_step(grad)
             if self.scheduler is not None:
@@ -768,8 +972,8 @@ class HashGridField:
         if tuple(target.shape) != (n, 3):
             raise ValueError(f"target must be [{n}, 3], got {tuple(target.shape)}")
         if noise is None:
-            noise = self.num_bits is not None and not frozen
-        if noise and self.num_bits is None:
+            noise = self._codec and not frozen
+        if noise and not self._codec:
             raise ValueError("noise needs num_bits: its amplitude is one quantisation step")
         _point_desc(self.geo)
         if fused and self.route != "fused":
@@ -789,7 +993,10 @@ class HashGridField:
                 grad.zero_()
             self._pass_samples = 0
         quant = (self.num_bits, self.noise_seed, self.steps, self._pass_samples) if noise else None
-        x = hash_encode_points(self.geo, self.table, pts, quant=quant)
+        if noise and self.level_bits is not None:
+            x = hash_encode_levels(self.geo, self.table, self.level_bits, points=pts, quant=quant[1:])
+        else:
+            x = hash_encode_points(self.geo, self.table, pts, quant=quant)
         self._pass_samples += n
         if not frozen:
             x.requires_grad_(True)
@@ -801,6 +1008,7 @@ class HashGridField:
             self._grad_clean = False
         if step:
             self.optimizer.step()
+            self._clamp_levels()
             if not frozen:
                 self._grad_clean = self.optimizer.zeroed_in_last_step(grad)
             if self.scheduler is not None:
@@ -828,13 +1036,19 @@ class HashGridField:
         tail = None
         if step:
             tail = self.optimizer.step_tail([] if frozen else [(self.table, grad)], list(zip(params, gm)))
-        loss, _ = hash_fused_forward_backward_points(self.geo, self.table, pts, params, target, gm, table_grad=grad, order=order,
-                                                     loss_scale=float(scale), quant=quant, add_grads=accumulate, tail=tail)
+        if self.level_bits is not None:
+            loss, _ = hash_fused_forward_backward_levels(self.geo, self.table, self.level_bits, params, target, gm, points=pts, order=order,
+                                                         table_grad=grad, loss_scale=float(scale), quant=None if quant is None else quant[1:],
+                                                         add_grads=accumulate, tail=tail)
+        else:
+            loss, _ = hash_fused_forward_backward_points(self.geo, self.table, pts, params, target, gm, table_grad=grad, order=order,
+                                                         loss_scale=float(scale), quant=quant, add_grads=accumulate, tail=tail)
         self._pass_samples += pts.shape[0]
         if not frozen:
             self._grad_clean = False
         if step:
             self.optimizer.step()                    # nothing to launch after a committed tail
+            self._clamp_levels()
             if not frozen:
                 self._grad_clean = self.optimizer.zeroed_in_last_step(grad)
             if self.scheduler is not None:
@@ -867,7 +1081,7 @@ class HashGridField:
             idx = idx.to(torch.int64).clamp_(0, n - 1)
             pts, target = pts[idx].contiguous(), target[idx].contiguous()       # laid out in the order once: a chunk is a slice
         cuts = list(range(0, n, batch))
-        freeze_epoch = math.ceil(freeze_at * epochs) if self.num_bits is not None else None
+        freeze_epoch = math.ceil(freeze_at * epochs) if self._codec else None
         hist = []
         for ep in range(epochs):
             if freeze_epoch is not None and ep >= freeze_epoch and not self.frozen:
@@ -899,20 +1113,26 @@ class HashGridField:
         org = self.geo.upload_origins(coord, extent, self.device)
         n = _n_samples(org.shape[0], extent)
         if noise is None:
-            noise = self.num_bits is not None and not frozen
-        if noise and self.num_bits is None:
+            noise = self._codec and not frozen
+        if noise and not self._codec:
             raise ValueError("noise needs num_bits: its amplitude is one quantisation step")
         quant = (self.num_bits, self.noise_seed, self.steps, self._pass_samples) if noise else None
         tail = None
         if step:
             tail = self.optimizer.step_tail([] if frozen else [(self.table, grad)], list(zip(params, gm)))
-        loss, _ = hash_fused_forward_backward(self.geo, self.table, org, extent, params, target, gm, table_grad=grad, loss_scale=float(scale), quant=quant,
-                                              add_grads=accumulate, tail=tail)
+        if self.level_bits is not None:
+            loss, _ = hash_fused_forward_backward_levels(self.geo, self.table, self.level_bits, params, target, gm, coord=org, extent=extent,
+                                                         table_grad=grad, loss_scale=float(scale), quant=None if quant is None else quant[1:],
+                                                         add_grads=accumulate, tail=tail)
+        else:
+            loss, _ = hash_fused_forward_backward(self.geo, self.table, org, extent, params, target, gm, table_grad=grad, loss_scale=float(scale),
+                                                  quant=quant, add_grads=accumulate, tail=tail)
         self._pass_samples += n
         if not frozen:
             self._grad_clean = False
         if step:
             self.optimizer.step()                    # nothing to launch after a committed tail
+            self._clamp_levels()
             if not frozen:
                 self._grad_clean = self.optimizer.zeroed_in_last_step(grad)
             if self.scheduler is not None:
@@ -924,12 +1144,17 @@ class HashGridField:
     def freeze(self) -> None:
         """quantise the table in place (nic_quantize) and stop updating it: ``train_step`` then trains the decoder alone, without noise
         (fp_freeze + fp_all_quantize of the dense codec)"""
-        if self.num_bits is None:
+        if not self._codec:
             raise RuntimeError("freeze() needs num_bits: there is no quantiser without it")
         if self.frozen:
             return
         t = self.table.detach()
-        _lib.check(_lib.load().nic_quantize(_lib.ptr(t), _lib.ptr(t), t.numel(), self.num_bits, _lib.stream_ptr(t.device)), "nic_quantize")
+        if self.level_bits is not None:              # each level's slice with its own depth
+            for l, b in enumerate(self.level_bits):
+                tl = t[l]
+                _lib.check(_lib.load().nic_quantize(_lib.ptr(tl), _lib.ptr(tl), tl.numel(), b, _lib.stream_ptr(t.device)), "nic_quantize")
+        else:
+            _lib.check(_lib.load().nic_quantize(_lib.ptr(t), _lib.ptr(t), t.numel(), self.num_bits, _lib.stream_ptr(t.device)), "nic_quantize")
         self.table.grad = None                       # FusedAdam skips a parameter without a gradient
         self.table.requires_grad_(False)
         self.frozen = True
@@ -945,7 +1170,7 @@ class HashGridField:
         starts = list(range(0, size[0], chunk))
         slabs = [target[x0:x0 + chunk].reshape(-1, 3).contiguous() for x0 in starts]
         total = sum(s.shape[0] for s in slabs)
-        freeze_epoch = math.ceil(freeze_at * epochs) if self.num_bits is not None else None
+        freeze_epoch = math.ceil(freeze_at * epochs) if self._codec else None
         hist = []
         for ep in range(epochs):
             if freeze_epoch is not None and ep >= freeze_epoch and not self.frozen:
@@ -960,9 +1185,11 @@ class HashGridField:
 
     def stored_bytes(self, packed: bool = False) -> dict:
         """bytes ``save_compressed`` stores: the compact uint8 table (``packed``: the bit-packed one) and the fp32 decoder"""
-        if packed and self.num_bits is None:
+        if packed and not self._codec:
             raise RuntimeError("the packed size needs num_bits")
-        table = hash_packed_bytes(self.geo, self.num_bits) if packed else hash_stored_bytes(self.geo)
+        if self.level_bits is not None and not packed:
+            raise ValueError("a mixed-depth table has no uint8 form: stored_bytes(packed=True)")
+        table = hash_packed_bytes(self.geo, self.level_bits if self.level_bits is not None else self.num_bits) if packed else hash_stored_bytes(self.geo)
         return {"table": table, "decoder": sum(v.numel() * v.element_size() for v in self.decoder.state_dict().values())}
 
     @torch.no_grad()
@@ -970,6 +1197,18 @@ class HashGridField:
         """one ``torch.save`` dict: format tag, geometry, num_bits, the compact uint8 table of a clamped copy of the table (``packed``: the
         bit-packed table, num_bits bits per value, under the tag ``nicv2-hashgrid-bits/1``), the decoder.  A decode-only field re-saves the table
         it holds, converted on the device when the other form is asked for."""
+        if self.level_bits is not None:
+            if not packed:
+                raise ValueError("a mixed-depth table has no uint8 form: save_compressed(path, packed=True)")
+            if self.table is not None:               # a per-level clamped copy; a decode-only field re-saves its buffer as it is
+                stored = hash_pack_bits_levels(self.geo, hash_clamp_levels(self.geo, self.table.detach().clone(), self.level_bits), self.level_bits)
+            else:
+                stored = self.packed
+            torch.save({"format": MIXED_FORMAT, "field_size": list(self.field_size), "resolutions": list(self.geo.resolutions),
+                        "features": self.geo.features, "log2_table": self.geo.log2_table, "num_bits": None, "level_bits": list(self.level_bits),
+                        "hidden": self.hidden, "n_linear": self.n_linear, "table": stored.cpu(),
+                        "decoder": {k: v.detach().cpu() for k, v in self.decoder.state_dict().items()}}, path)
+            return
         if self.num_bits is None:
             raise RuntimeError("save_compressed needs num_bits")
         if self.table is not None:
@@ -989,17 +1228,25 @@ class HashGridField:
         (nic_hash_encode_u8; ``fused``: nic_hash_fused_forward_u8) or bit-packed (nic_hash_encode_bits / nic_hash_fused_forward_bits) - with no
         fp32 table and no conversion between the two"""
         d = torch.load(path, map_location="cpu", weights_only=True)
-        if not isinstance(d, dict) or d.get("format") not in (COMPRESSED_FORMAT, PACKED_FORMAT):
-            raise ValueError(f"{path}: not a {COMPRESSED_FORMAT} or {PACKED_FORMAT} file")
-        is_packed = d["format"] == PACKED_FORMAT
+        if not isinstance(d, dict) or d.get("format") not in (COMPRESSED_FORMAT, PACKED_FORMAT, MIXED_FORMAT):
+            raise ValueError(f"{path}: not a {COMPRESSED_FORMAT}, {PACKED_FORMAT} or {MIXED_FORMAT} file")
+        is_mixed = d["format"] == MIXED_FORMAT
+        is_packed = is_mixed or d["format"] == PACKED_FORMAT
         self = cls.__new__(cls)
         self.field_size = tuple(int(v) for v in d["field_size"])
         self.geo = HashGeometry(self.field_size, tuple(int(r) for r in d["resolutions"]), int(d["features"]), int(d["log2_table"]))
-        self.num_bits, self.hidden, self.n_linear = int(d["num_bits"]), int(d["hidden"]), int(d["n_linear"])
-        if not 1 <= self.num_bits <= 8:
-            raise ValueError(f"{path}: num_bits {self.num_bits}")
+        self.hidden, self.n_linear = int(d["hidden"]), int(d["n_linear"])
+        if is_mixed:
+            try:
+                self.num_bits, self.level_bits = None, _check_level_bits(self.geo.levels, d.get("level_bits"))
+            except ValueError as e:
+                raise ValueError(f"{path}: level_bits: {e}") from None
+        else:
+            self.num_bits, self.level_bits = int(d["num_bits"]), None
+            if not 1 <= self.num_bits <= 8:
+                raise ValueError(f"{path}: num_bits {self.num_bits}")
         stored = d["table"]
-        need = hash_packed_bytes(self.geo, self.num_bits) if is_packed else hash_stored_bytes(self.geo)
+        need = hash_packed_bytes(self.geo, self.level_bits if is_mixed else self.num_bits) if is_packed else hash_stored_bytes(self.geo)
         if not isinstance(stored, torch.Tensor) or stored.dtype != torch.uint8 or stored.dim() != 1 or stored.numel() != need:
             raise ValueError(f"{path}: the table holds {stored.numel()} {stored.dtype} values, a {d['format']} file of this geometry needs {need} bytes")
         self.device = torch.device(device if device is not None else "cuda")
@@ -1028,6 +1275,8 @@ class HashGridField:
             if self.route == "fused":
                 if table is not None:
                     y = hash_fused_forward(self.geo, table, [o], ext, params)
+                elif self.level_bits is not None:
+                    y = hash_fused_forward_levels(self.geo, self.packed, self.level_bits, params, coord=[o], extent=ext, kind="bits")
                 elif self.packed is not None:
                     y = hash_fused_forward_bits(self.geo, self.packed, [o], ext, self.num_bits, params)
                 else:
@@ -1036,6 +1285,8 @@ class HashGridField:
                 continue
             if table is not None:
                 x = hash_encode(self.geo, table, [o], ext)
+            elif self.level_bits is not None:
+                x = hash_encode_levels(self.geo, self.packed, self.level_bits, coord=[o], extent=ext, kind="bits")
             elif self.packed is not None:
                 x = hash_encode_bits(self.geo, self.packed, [o], ext, self.num_bits)
             else:
@@ -1058,6 +1309,13 @@ class HashGridField:
         table.  One launch on the fused route (nic_hash_fused_forward_points), encode + general decoder on the layer-wise one."""
         data, kind, bits = self._point_table()
         params = [p.detach() for p in self.decoder.linear_params()]
+        if kind == "bits" and self.level_bits is not None:       # a loaded mixed-depth field: its format /2 table
+            if self.route == "fused":
+                return hash_fused_forward_levels(self.geo, data, self.level_bits, params, points=points, kind="bits")
+            pts = _check_points(self.geo, points)
+            if pts.shape[0] == 0:
+                return torch.empty(0, 3, dtype=torch.float32, device=self.device)
+            return fused.DecoderFunction.apply(hash_encode_levels(self.geo, data, self.level_bits, points=pts, kind="bits"), *params)
         if self.route == "fused":
             return hash_fused_forward_points(self.geo, data, points, params, kind, bits)
         pts = _check_points(self.geo, points)
