@@ -1,10 +1,12 @@
-// What the hash-grid kernels share, for translation units written after hash_grid.hip / hash_fused.hip / hash_points.hip (those three are pinned
-// and keep their own restated copies): the index helpers, the fp32 and packed row loaders, the fixed-point position and cell of a point
-// or of a lattice sample
-// (include/nicv2_hip.h, nic_hash_encode_points), the level loops of the encode (row into an LDS tile) and of the scatter (run sums keyed on the
-// base vertex), and the ColorDecoder(L F, 64, 3) forward + backward on v_mfma_f32_32x32x2_f32 with its register-resident weight-gradient
-// accumulators and per-workgroup record (hash_fused.hip's training mode, the same product order).  run_masks / run_sum, the noise generator and
-// the activations come from nic_device.hpp, the optimiser tail from nic_adam.hpp.
+// What the hash-grid kernels share, the one copy of it: all five translation units (hash_grid.hip, hash_fused.hip, hash_points.hip,
+// hash_points_train.hip, hash_mixed.hip) include this header and keep only their kernels, parameter structs and launch tables.
+// The index helpers, the fp32, uint8 and packed row loaders, the cell of a lattice sample (2 S_max arithmetic) and the fixed-point position and
+// cell of a point or of a lattice sample (include/nicv2_hip.h, nic_hash_encode_points), the level loops of the encode (row into an LDS tile) and
+// of the scatter (run sums keyed on the base vertex), the ColorDecoder(L F, 64, 3) forward + backward on v_mfma_f32_32x32x2_f32 with its
+// register-resident weight-gradient accumulators and per-workgroup record, and the host side of the entry points: descriptor checks, grid
+// rules, dequantisation constants, the noise source of a nic_hash_quant.  Everything on the device side is force-inlined, so a kernel's code
+// does not depend on where a helper is declared (profiles/hashgrid_common_disasm.txt).  run_masks / run_sum, the noise generator and the
+// activations come from nic_device.hpp, the optimiser tail from nic_adam.hpp.
 #pragma once
 #include "nic_device.hpp"
 #include "nic_adam.hpp"
@@ -12,7 +14,7 @@
 namespace nic {
 namespace hcommon {
 
-// ---- index helpers and loaders (hash_grid.hip) -------------------------------------------------------------------------------------------
+// ---- index helpers and loaders ---------------------------------------------------------------------------------------------------------
 __host__ __device__ inline bool hash_level_dense(int dim, int32_t R, int log2_table) {
     uint64_t p = 1;
     for (int a = 0; a < dim; ++a) {
@@ -21,6 +23,7 @@ __host__ __device__ inline bool hash_level_dense(int dim, int32_t R, int log2_ta
     }
     return true;
 }
+// the entry of vertex (vx, vy, vz) in a level of resolution R (vz = 0 in 2D); masked with T - 1: no input can leave a level
 __host__ __device__ inline uint32_t hash_index(bool dense, uint32_t R, uint32_t mask, uint32_t vx, uint32_t vy, uint32_t vz) {
     const uint32_t h = dense ? vx + (R + 1u) * (vy + (R + 1u) * vz) : (vx ^ (vy * 2654435761u) ^ (vz * 805459861u));
     return h & mask;
@@ -51,6 +54,26 @@ __device__ __forceinline__ void store_row(float* p, const float (&v)[F]) {
         for (int k = 0; k < F; k += 4) *reinterpret_cast<float4*>(p + k) = make_float4(v[k], v[k + 1], v[k + 2], v[k + 3]);
     }
 }
+// one compact uint8 entry of F bytes as ONE load (ubyte / ushort / dword / dwordx2), dequantised like load4fp_kernel (simple_kernels.hip)
+template <int F>
+__device__ __forceinline__ void load_row_u8(const uint8_t* p, float scale, float bias, float (&v)[F]) {
+    uint32_t w[(F + 3) / 4];
+    if constexpr (F == 1) {
+        w[0] = *p;
+    } else if constexpr (F == 2) {
+        w[0] = *reinterpret_cast<const uint16_t*>(p);
+    } else if constexpr (F == 4) {
+        w[0] = *reinterpret_cast<const uint32_t*>(p);
+    } else {
+        const uint2 a = *reinterpret_cast<const uint2*>(p);
+        w[0] = a.x; w[1] = a.y;
+    }
+#pragma unroll
+    for (int f = 0; f < F; ++f) {
+        const float u = (float)((w[f >> 2] >> (8 * (f & 3))) & 0xFFu);
+        v[f] = __fdiv_rn(__fadd_rn(__fsub_rn(u, bias), 1.0f), scale);
+    }
+}
 // entries a level stores: the (R + 1)^dim vertices of a dense level, all T of a hashed one; dwords of its bit stream at `bits` bits per value
 __host__ __device__ inline int64_t hash_level_entries(int dim, int32_t R, int log2_table) {
     if (!hash_level_dense(dim, R, log2_table)) return int64_t(1) << log2_table;
@@ -62,8 +85,10 @@ __host__ __device__ inline int64_t hash_level_dwords(int dim, int32_t R, int log
     return (hash_level_entries(dim, R, log2_table) * (F * bits) + 31) >> 5;
 }
 __host__ __device__ inline bool hash_bits_tight(int F, int bits) { return 32 % (F * bits) == 0 || F * bits == 64; }
-// the packed-row loader (hash_grid.hip): entry e of F b bits at bit e F b of its level's stream, aligned dword loads only, funnel-shifted to
-// bit 0; TIGHT: no entry straddles, the extra dword is not read.  The value takes load_row_u8's dequantisation, expression for expression.
+// one bit-packed entry of F b bits at bit e F b of its level's stream `lev`: aligned dword loads only - the dword the entry starts in and the
+// next one (F <= 4: F b <= 32) or two (F = 8: F b <= 64; the 8 zero bytes after the last level keep that window inside the buffer), funnel-
+// shifted so that the entry starts at bit 0.  TIGHT (uniform over the launch or the level): no entry straddles, the extra dword is not read.
+// The value then takes load_row_u8's dequantisation, expression for expression.
 template <int F, bool TIGHT>
 __device__ __forceinline__ void load_row_bits(const uint32_t* lev, uint32_t e, int bits, float scale, float bias, float (&v)[F]) {
     const uint32_t bit = e * (uint32_t)(F * bits), sh = bit & 31u;
@@ -99,9 +124,10 @@ __device__ __forceinline__ float corner_weight(const float (&w)[3], int c) {
     return r;
 }
 
-// ---- the fixed-point split of a point (hash_points.hip) ------------------------------------------------------------------------------------
-// clamped in floating point first (NaN fails both comparisons' "keep" side and lands on the low edge, -inf / +inf on the nearer one), then
-// t = rint(256 p) + 128 (half to even; 256 p is exact) clamped to [0, 256 S - 1]
+// ---- the fixed-point split of a point ------------------------------------------------------------------------------------------------------
+// the position of point n per axis: clamped in floating point first (NaN fails both comparisons' "keep" side and lands on the low edge,
+// -inf / +inf on the nearer one), so the conversion sees |256 p| < 2^30; then t = rint(256 p) + 128 (v_rndne: half to even; 256 p is exact)
+// clamped to [0, 256 S - 1] - the upper edge p = S - 1/2 gives 256 S and comes back into the last cell, so v <= R - 1 on every level
 template <int D>
 __device__ __forceinline__ void point_fixed(const nic_hash_desc& d, const float* points, int64_t n, uint32_t (&t)[3]) {
 #pragma unroll
@@ -127,7 +153,7 @@ __device__ __forceinline__ void point_cell(const uint32_t (&t)[3], uint32_t R, u
     if (D == 2) { v[2] = 0; w[2] = 0.f; }
 }
 
-// ---- the lattice as a position source (hash_grid.hip) -------------------------------------------------------------------------------------
+// ---- the lattice as a position source -------------------------------------------------------------------------------------------------------
 // the sample of this lane in patch `wv` of 8 x 8 / 4 x 4 x 4 samples, x the fastest lane axis (clamped to the last patch; `live` = a real
 // sample of a real patch); n = its row in nic_encode sample order
 template <int D>
@@ -168,6 +194,27 @@ __device__ __forceinline__ PatchSample<D> patch_sample(const nic_hash_desc& d, i
     const int64_t n_per_crop = (int64_t)d.extent[0] * d.extent[1] * (D == 3 ? d.extent[2] : 1);
     s.n = (int64_t)s.crop * n_per_crop + ((int64_t)s.idx[0] * d.extent[1] + s.idx[1]) * (D == 3 ? d.extent[2] : 1) + (D == 3 ? s.idx[2] : 0);
     return s;
+}
+// integer sample coordinate per axis, clamped into the field (an origin outside it is refused on the host; this keeps q < 2^31 regardless)
+template <int D>
+__device__ __forceinline__ void sample_coords(const nic_hash_desc& d, const int32_t* origins, const PatchSample<D>& s, uint32_t (&i)[3]) {
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        const int c = origins[s.crop * D + a] + s.idx[a];
+        i[a] = (uint32_t)(c < 0 ? 0 : (c >= d.S_max ? d.S_max - 1 : c));
+    }
+    if (D == 2) i[2] = 0;
+}
+// base vertex and fp32 weight per axis of one level on the crop route: q = (2 i + 1) R, v = q / 2 S_max, w = (q mod 2 S_max) / 2 S_max
+template <int D>
+__device__ __forceinline__ void level_cell(const uint32_t (&i)[3], uint32_t R, uint32_t S2, uint32_t (&v)[3], float (&w)[3]) {
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        const uint32_t q = (2u * i[a] + 1u) * R;
+        v[a] = q / S2;
+        w[a] = (float)(q - v[a] * S2) / (float)S2;
+    }
+    if (D == 2) { v[2] = 0; w[2] = 0.f; }
 }
 // lattice sample i (origin + index, clamped into the field like sample_coords) as the point t = 256 i + 128: both operands of the cell
 // quotient are 128 times the crop route's, so v, w and the row are nic_hash_encode's bit for bit (include/nicv2_hip.h)
@@ -256,12 +303,12 @@ __device__ __forceinline__ void scatter_point(const nic_hash_desc& d, const uint
     }
 }
 
-// ---- the decoder on the fp32 matrix pipe (hash_fused.hip) ----------------------------------------------------------------------------------
+// ---- the decoder on the fp32 matrix pipe ---------------------------------------------------------------------------------------------------
 constexpr int XS = kH + 1;      // row stride of every LDS tile: lanes that walk rows hit 64 different banks
 constexpr int NQ = 16;          // samples per weight-gradient pass (the two transposed tiles of a wave)
 
 // the record of a workgroup, nn.Linear layouts back to back: dW1 [64, L F] | db1 | dW2 [64, 64] | db2 | dW3 [3, 64] | db3 | sum of squared errors
-// (hash_fused.hip's RecLayout: hash_fused_reduce_kernel reads records of this layout)
+// (hash_fused_reduce_kernel reads records of this layout)
 struct RecLayout {
     int w1, b1, w2, b2, w3, b3, loss, rec;
     __host__ __device__ explicit RecLayout(int lf) {
@@ -588,6 +635,30 @@ __device__ __forceinline__ void write_record(TrainSmem& sm, const TrainAcc<KT>& 
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
+// what every entry point asks of a descriptor, in this order (tests/test_host_cpu.py and the *_cpu hash-grid tests pin it)
+inline int check_hash_desc(const nic_hash_desc* d) {
+    if (!d) return NIC_E_NULL;
+    if (d->dim != 2 && d->dim != 3) return NIC_E_UNSUPPORTED;
+    if (d->features != 1 && d->features != 2 && d->features != 4 && d->features != 8) return NIC_E_UNSUPPORTED;
+    if (d->levels < 1 || d->levels > NIC_HASH_MAX_LEVELS) return NIC_E_ARG;
+    if (d->log2_table < 10 || d->log2_table > 24) return NIC_E_ARG;
+    if (d->S_max < 1 || d->flags != 0) return NIC_E_ARG;
+    for (int l = 0; l < d->levels; ++l)      // q = (2 i + 1) R_l < 2 S_max R_l must stay below 2^31
+        if (d->resolution[l] < 1 || 2 * (int64_t)d->S_max * d->resolution[l] >= (int64_t(1) << 31)) return NIC_E_ARG;
+    if (d->num_crops < 1) return NIC_E_SHAPE;
+    for (int a = 0; a < d->dim; ++a)
+        if (d->extent[a] < 1 || d->extent[a] > d->S_max) return NIC_E_SHAPE;
+    return NIC_OK;
+}
+// then what the point entry points add: one field, 256 S_max < 2^30 (point_cell divides q >> 8 in 32 bits)
+inline int check_point_desc(const nic_hash_desc* d) {
+    const int rc = check_hash_desc(d);
+    if (rc) return rc;
+    if (d->num_crops != 1) return NIC_E_SHAPE;
+    if (256 * (int64_t)d->S_max >= (int64_t(1) << 30)) return NIC_E_ARG;
+    return NIC_OK;
+}
+
 inline int device_cus() {
     static int n = 0;
     if (n == 0) {
@@ -602,6 +673,56 @@ inline int wg_cap() {
     const int c = device_cus() / 8 * 8;
     return c < 8 ? 8 : c;
 }
+// patches of 8 x 8 / 4 x 4 x 4 samples in the crops of a lattice launch: one wave each
+inline int64_t count_patches(const nic_hash_desc* d) {
+    const int PS = d->dim == 2 ? 8 : 4;
+    int64_t patches = d->num_crops;
+    for (int a = 0; a < d->dim; ++a) patches *= (d->extent[a] + PS - 1) / PS;
+    return patches;
+}
+// workgroups of a persistent launch over `n_waves` wave items (patches, or groups of 64 points), four to a workgroup: a multiple of 8, capped
+inline int persistent_grid(int64_t n_waves) {
+    const int64_t groups = (n_waves + 3) / 4, want = (groups + 7) / 8 * 8;
+    return (int)(want < wg_cap() ? want : wg_cap());
+}
+// workgroups of a grid-strided launch over the same wave items, four to a workgroup: at least one, capped
+inline int strided_grid(int64_t n_waves) {
+    const int64_t b = (n_waves + 3) / 4;
+    return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
+}
+
+// load4fp's constants into a parameter struct: (u - q_bias + 1) / q_scale, q_scale = 2^b - 1, q_bias = 2^(b-1)
+template <class Params>
+inline void set_dequant(Params& p, int num_bits) {
+    p.q_scale = (float)((1 << num_bits) - 1);
+    p.q_bias = (float)(1 << (num_bits - 1));
+}
+// the noise source of a launch from a nic_hash_quant, with its argument checks; null, or noise_mode NIC_NOISE_NONE, leaves `noise` as it is.
+// uniform_depth: the scale is 2^-num_bits; without it num_bits is ignored and the scale is the kernel's to set (a depth per level)
+inline int set_noise(const nic_hash_quant* quant, bool uniform_depth, NoiseSrc& noise, uint64_t& sample_base) {
+    if (!quant) return NIC_OK;
+    if ((uniform_depth && (quant->num_bits < 1 || quant->num_bits > 8)) || quant->sample_base < 0) return NIC_E_ARG;
+    if (quant->noise_mode == NIC_NOISE_TENSOR) return NIC_E_UNSUPPORTED;
+    if (quant->noise_mode != NIC_NOISE_NONE && quant->noise_mode != NIC_NOISE_KERNEL) return NIC_E_ARG;
+    if (quant->noise_mode == NIC_NOISE_KERNEL) {
+        noise.mode = NIC_NOISE_KERNEL;
+        noise.k0 = (uint32_t)quant->noise_seed; noise.k1 = (uint32_t)(quant->noise_seed >> 32);
+        noise.off_lo = (uint32_t)quant->noise_offset; noise.off_hi = (uint32_t)(quant->noise_offset >> 32);
+        if (uniform_depth) noise.scale = ldexpf(1.0f, -quant->num_bits);
+        sample_base = (uint64_t)quant->sample_base;
+    }
+    return NIC_OK;
+}
+
+struct KernelEndDrop {        // a training entry point consumes the parked nic_mark_kernel_end event on every return
+    ~KernelEndDrop() { kernel_end_drop(); }
+};
 
 }  // namespace hcommon
+
+namespace hfused {
+// defined in hash_fused.hip; reads records of hcommon::RecLayout.  The fused training entry points of every translation unit launch it.
+__global__ void __launch_bounds__(256) hash_fused_reduce_kernel(const float* partials, int n_rec, int lf, nic_mlp_grads g, float* loss, float loss_mul,
+                                                                int add_grads, int add_loss, const StepTail tl);
+}  // namespace hfused
 }  // namespace nic

@@ -2,7 +2,7 @@
 // DESIGN 4.7.2).  The [N, L F] encoding row and its gradient never reach global memory: a wave gathers the rows of its patch into an LDS tile,
 // runs the decoder forward and backward on the fp32 matrix pipe (v_mfma_f32_32x32x2_f32: an exact fmaf chain, the arithmetic of the general
 // decoder the layer-wise route uses), leaves d loss / d row in the same tile and scatters it into the table gradient with the run sums of
-// hash_encode_backward_kernel.  Semantics are those of hash_grid.hip, whose helpers are restated here unchanged (that file is pinned).
+// hash_encode_backward_kernel.  Semantics are those of hash_grid.hip; the helpers, LDS layout and record layout are hash_common.hpp's.
 //
 //   one wave per patch of 8 x 8 (2D) / 4 x 4 x 4 (3D) samples, x the fastest lane axis (the row numbering of nic_hash_encode: the noise keys
 //   and the run sums carry over); 4 waves per workgroup, one workgroup per CU, persistent, each XCD walks one contiguous range of patches.
@@ -12,156 +12,12 @@
 //   Weight gradients reduce over the samples, which sit in the lanes: dZ and A go through two 16-sample LDS tiles per wave ([n][unit]) and
 //   come back as operands; their accumulators stay in registers for the whole launch and leave as one record per workgroup (summed over the
 //   four waves in wave order through LDS), which hash_fused_reduce_kernel adds up in a fixed order - with the optimiser tail riding on it.
-#include "nic_device.hpp"
-#include "nic_adam.hpp"
+#include "hash_common.hpp"
 
 namespace nic {
 namespace hfused {
+using namespace hcommon;
 
-// ---- restated from hash_grid.hip ------------------------------------------------------------------------------------------------------
-__host__ __device__ inline bool hash_level_dense(int dim, int32_t R, int log2_table) {
-    uint64_t p = 1;
-    for (int a = 0; a < dim; ++a) {
-        p *= (uint64_t)R + 1;
-        if (p > (1ull << log2_table)) return false;
-    }
-    return true;
-}
-__host__ __device__ inline uint32_t hash_index(bool dense, uint32_t R, uint32_t mask, uint32_t vx, uint32_t vy, uint32_t vz) {
-    const uint32_t h = dense ? vx + (R + 1u) * (vy + (R + 1u) * vz) : (vx ^ (vy * 2654435761u) ^ (vz * 805459861u));
-    return h & mask;
-}
-__host__ __device__ inline int64_t hash_level_entries(int dim, int32_t R, int log2_table) {
-    if (!hash_level_dense(dim, R, log2_table)) return int64_t(1) << log2_table;
-    int64_t e = 1;
-    for (int a = 0; a < dim; ++a) e *= (int64_t)R + 1;
-    return e;
-}
-template <int F>
-__device__ __forceinline__ void load_row(const float* p, float (&v)[F]) {
-    if constexpr (F == 1) {
-        v[0] = *p;
-    } else if constexpr (F == 2) {
-        const float2 a = *reinterpret_cast<const float2*>(p);
-        v[0] = a.x; v[1] = a.y;
-    } else {
-#pragma unroll
-        for (int k = 0; k < F; k += 4) {
-            const float4 a = *reinterpret_cast<const float4*>(p + k);
-            v[k] = a.x; v[k + 1] = a.y; v[k + 2] = a.z; v[k + 3] = a.w;
-        }
-    }
-}
-template <int F>
-__device__ __forceinline__ void load_row_u8(const uint8_t* p, float scale, float bias, float (&v)[F]) {
-    uint32_t w[(F + 3) / 4];
-    if constexpr (F == 1) {
-        w[0] = *p;
-    } else if constexpr (F == 2) {
-        w[0] = *reinterpret_cast<const uint16_t*>(p);
-    } else if constexpr (F == 4) {
-        w[0] = *reinterpret_cast<const uint32_t*>(p);
-    } else {
-        const uint2 a = *reinterpret_cast<const uint2*>(p);
-        w[0] = a.x; w[1] = a.y;
-    }
-#pragma unroll
-    for (int f = 0; f < F; ++f) {
-        const float u = (float)((w[f >> 2] >> (8 * (f & 3))) & 0xFFu);
-        v[f] = __fdiv_rn(__fadd_rn(__fsub_rn(u, bias), 1.0f), scale);
-    }
-}
-__host__ __device__ inline int64_t hash_level_dwords(int dim, int32_t R, int log2_table, int F, int bits) {
-    return (hash_level_entries(dim, R, log2_table) * (F * bits) + 31) >> 5;
-}
-__host__ __device__ inline bool hash_bits_tight(int F, int bits) { return 32 % (F * bits) == 0 || F * bits == 64; }
-template <int F, bool TIGHT>
-__device__ __forceinline__ void load_row_bits(const uint32_t* lev, uint32_t e, int bits, float scale, float bias, float (&v)[F]) {
-    const uint32_t bit = e * (uint32_t)(F * bits), sh = bit & 31u;
-    const uint32_t* q = lev + (bit >> 5);
-    uint32_t x0, x1 = 0u;
-    const uint32_t w0 = q[0];
-    if constexpr (F <= 4) {
-        if constexpr (TIGHT) x0 = w0 >> sh;
-        else x0 = __builtin_amdgcn_alignbit(q[1], w0, sh);
-    } else {
-        if constexpr (TIGHT) {
-            x0 = w0 >> sh;
-            if (bits == 8) x1 = q[1];                                // F b = 64 starts on a dword
-        } else {
-            const uint32_t w1 = q[1], w2 = q[2];
-            x0 = __builtin_amdgcn_alignbit(w1, w0, sh);
-            x1 = __builtin_amdgcn_alignbit(w2, w1, sh);
-        }
-    }
-#pragma unroll
-    for (int f = 0; f < F; ++f) {
-        uint32_t uv;
-        if constexpr (F <= 4) uv = __builtin_amdgcn_ubfe(x0, (uint32_t)(f * bits), (uint32_t)bits);      // f b + b <= 32
-        else uv = __builtin_amdgcn_ubfe((uint32_t)((((uint64_t)x1 << 32) | x0) >> (f * bits)), 0u, (uint32_t)bits);
-        const float u = (float)uv;
-        v[f] = __fdiv_rn(__fadd_rn(__fsub_rn(u, bias), 1.0f), scale);
-    }
-}
-template <int D>
-struct PatchSample {
-    int crop;
-    int idx[3];
-    bool live;
-    int64_t n;
-};
-template <int D>
-__device__ __forceinline__ PatchSample<D> patch_sample(const nic_hash_desc& d, int64_t wv, int64_t n_patches, int lane) {
-    constexpr int PS = D == 2 ? 8 : 4;
-    const int np1 = (d.extent[1] + PS - 1) / PS, np2 = D == 3 ? (d.extent[2] + PS - 1) / PS : 1;
-    const int64_t per_crop = (int64_t)((d.extent[0] + PS - 1) / PS) * np1 * np2;
-    const int64_t wc = wv < n_patches ? wv : n_patches - 1;
-    PatchSample<D> s;
-    s.crop = (int)(wc / per_crop);
-    int64_t pr = wc - (int64_t)s.crop * per_crop;
-    int pt[3] = {0, 0, 0};
-    if (D == 3) { pt[2] = (int)(pr % np2); pr /= np2; }
-    pt[1] = (int)(pr % np1);
-    pt[0] = (int)(pr / np1);
-    if (D == 2) {
-        s.idx[0] = PS * pt[0] + (lane & 7);
-        s.idx[1] = PS * pt[1] + (lane >> 3);
-        s.idx[2] = 0;
-    } else {
-        s.idx[0] = PS * pt[0] + (lane & 3);
-        s.idx[1] = PS * pt[1] + ((lane >> 2) & 3);
-        s.idx[2] = PS * pt[2] + (lane >> 4);
-    }
-    s.live = wv < n_patches;
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-        s.live = s.live && s.idx[a] < d.extent[a];
-        s.idx[a] = s.idx[a] < d.extent[a] ? s.idx[a] : d.extent[a] - 1;
-    }
-    const int64_t n_per_crop = (int64_t)d.extent[0] * d.extent[1] * (D == 3 ? d.extent[2] : 1);
-    s.n = (int64_t)s.crop * n_per_crop + ((int64_t)s.idx[0] * d.extent[1] + s.idx[1]) * (D == 3 ? d.extent[2] : 1) + (D == 3 ? s.idx[2] : 0);
-    return s;
-}
-template <int D>
-__device__ __forceinline__ void level_cell(const uint32_t (&i)[3], uint32_t R, uint32_t S2, uint32_t (&v)[3], float (&w)[3]) {
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-        const uint32_t q = (2u * i[a] + 1u) * R;
-        v[a] = q / S2;
-        w[a] = (float)(q - v[a] * S2) / (float)S2;
-    }
-    if (D == 2) { v[2] = 0; w[2] = 0.f; }
-}
-template <int D>
-__device__ __forceinline__ float corner_weight(const float (&w)[3], int c) {
-    float r = ((c & 1) ? w[0] : 1.0f - w[0]) * ((c & 2) ? w[1] : 1.0f - w[1]);
-    if (D == 3) r *= (c & 4) ? w[2] : 1.0f - w[2];
-    return r;
-}
-// ---- end of the restated helpers ------------------------------------------------------------------------------------------------------
-
-constexpr int XS = kH + 1;      // row stride of every LDS tile: lanes that walk rows hit 64 different banks
-constexpr int NQ = 16;          // samples per weight-gradient pass (the two transposed tiles of a wave)
 enum { HF_FWD = 0, HF_FWD_U8 = 1, HF_TRAIN = 2, HF_FWD_BITS = 3 };
 
 struct FParams {
@@ -183,40 +39,6 @@ struct FParams {
     const uint32_t* packed;   // bit-packed table, 4-byte aligned
     int32_t q_bits, q_tight;  // b; F b divides 32 or is 64 (hash_grid.hip, load_row_bits)
 };
-
-// the record of a workgroup, nn.Linear layouts back to back: dW1 [64, L F] | db1 | dW2 [64, 64] | db2 | dW3 [3, 64] | db3 | sum of squared errors
-struct RecLayout {
-    int w1, b1, w2, b2, w3, b3, loss, rec;
-    __host__ __device__ explicit RecLayout(int lf) {
-        w1 = 0; b1 = kH * lf; w2 = b1 + kH; b2 = w2 + kH * kH; w3 = b2 + kH; b3 = w3 + 3 * kH; loss = b3 + 3; rec = loss + 1;
-    }
-};
-
-struct Smem {
-    float w1[kH * XS], w2[kH * XS], w3[4 * kH], b1[kH], b2[kH], b3[4];
-    float x[4][kH * XS];        // per wave: the encoding rows [sample][column], later d loss / d row; at the end of the launch the workgroup's record
-    float p[4][NQ * XS], q[4][NQ * XS];
-};
-
-// LDS traffic between the lanes of ONE wave: its LDS instructions execute in order, the compiler must not move them across
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ int row_of(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
-// integer sample coordinate per axis, clamped into the field
-template <int D>
-__device__ __forceinline__ void sample_coords(const FParams& p, const PatchSample<D>& s, uint32_t (&i)[3]) {
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-        const int c = p.origins[s.crop * D + a] + s.idx[a];
-        i[a] = (uint32_t)(c < 0 ? 0 : (c >= p.d.S_max ? p.d.S_max - 1 : c));
-    }
-    if (D == 2) i[2] = 0;
-}
 
 // the level loop of hash_encode_kernel with the row going to LDS
 template <int D, int F, int MODE, bool TIGHT = false>
@@ -304,42 +126,11 @@ __device__ __forceinline__ void scatter_row(const FParams& p, const PatchSample<
     }
 }
 
-// acc[ta][tb] += sum over the NQ samples of a pass of P[n][32 ta + i] Q[n][32 tb + j]   (MASK4: P has 4 columns, one row tile)
-// side[ta] += every P operand of this lane: the bias gradient (column sums of dZ) of unit 32 ta + i over the samples of this half's parity
-template <int TA, int TB, bool MASK4>
-__device__ __forceinline__ void wgrad_mfma(const float* P, const float* Q, int j, int half, f32x16 (&acc)[TA][TB], float (&side)[TA]) {
-#pragma unroll
-    for (int s = 0; s < NQ / 2; ++s) {
-        float a[TA], b[TB];
-#pragma unroll
-        for (int ta = 0; ta < TA; ++ta) a[ta] = MASK4 ? (j < 4 ? P[(2 * s + half) * XS + j] : 0.f) : P[(2 * s + half) * XS + 32 * ta + j];
-#pragma unroll
-        for (int tb = 0; tb < TB; ++tb) b[tb] = Q[(2 * s + half) * XS + 32 * tb + j];
-#pragma unroll
-        for (int ta = 0; ta < TA; ++ta) {
-            side[ta] += a[ta];
-#pragma unroll
-            for (int tb = 0; tb < TB; ++tb) acc[ta][tb] = mfma(a[ta], b[tb], acc[ta][tb]);
-        }
-    }
-}
-// the [unit] values of this lane's sample -> row (j & 15) of a transposed tile
-template <int T>
-__device__ __forceinline__ void put_tile(float* P, int j, int half, const f32x16 (&u)[T]) {
-#pragma unroll
-    for (int t = 0; t < T; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) P[(j & 15) * XS + 32 * t + row_of(r, half)] = u[t][r];
-}
-__device__ __forceinline__ float half_sum(float v) {      // over the 32 lanes of this lane's half, fixed order
-#pragma unroll
-    for (int m = 1; m < 32; m <<= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
+// The decoder keeps its own body in every mode: hash_common.hpp's decoder_forward_half / decoder_train_half / write_record are the same products
+// in the same order but compile to other code, which has not been measured against this body on a GPU.
 template <int D, int F, int KT, int MODE>
 __global__ void __launch_bounds__(256) hash_fused_kernel(const FParams p) {
-    __shared__ Smem sm;
+    __shared__ TrainSmem sm;
     constexpr bool TRAIN = MODE == HF_TRAIN;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 31, half = lane >> 5;
     const int LF = p.d.levels * F;
@@ -380,7 +171,7 @@ __global__ void __launch_bounds__(256) hash_fused_kernel(const FParams p) {
         if (wv >= p.n_patches) continue;                        // wave-uniform; nothing below synchronises the workgroup
         const PatchSample<D> s = patch_sample<D>(p.d, wv, p.n_patches, lane);
         uint32_t ci[3];
-        sample_coords<D>(p, s, ci);
+        sample_coords<D>(p.d, p.origins, s, ci);
         if constexpr (MODE == HF_FWD_BITS) {                     // b is uniform over the launch: the window's width is decided once per row
             if (p.q_tight) encode_row<D, F, MODE, true>(p, s, ci, xrow);
             else encode_row<D, F, MODE, false>(p, s, ci, xrow);
@@ -625,48 +416,9 @@ __global__ void __launch_bounds__(256) hash_fused_reduce_kernel(const float* par
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
-static int device_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-        else n = 256;
-    }
-    return n;
-}
-// workgroups a launch may use: one per CU, a multiple of 8 (one slice of the patch range per XCD)
-static int wg_cap() {
-    const int c = device_cus() / 8 * 8;
-    return c < 8 ? 8 : c;
-}
-static int64_t count_patches(const nic_hash_desc* d) {
-    const int PS = d->dim == 2 ? 8 : 4;
-    int64_t patches = d->num_crops;
-    for (int a = 0; a < d->dim; ++a) patches *= (d->extent[a] + PS - 1) / PS;
-    return patches;
-}
-static int grid_of(int64_t patches) {
-    const int64_t groups = (patches + 3) / 4, want = (groups + 7) / 8 * 8;
-    return (int)(want < wg_cap() ? want : wg_cap());
-}
-
-static int check_desc(const nic_hash_desc* d) {       // check_hash_desc of hash_grid.hip
-    if (!d) return NIC_E_NULL;
-    if (d->dim != 2 && d->dim != 3) return NIC_E_UNSUPPORTED;
-    if (d->features != 1 && d->features != 2 && d->features != 4 && d->features != 8) return NIC_E_UNSUPPORTED;
-    if (d->levels < 1 || d->levels > NIC_HASH_MAX_LEVELS) return NIC_E_ARG;
-    if (d->log2_table < 10 || d->log2_table > 24) return NIC_E_ARG;
-    if (d->S_max < 1 || d->flags != 0) return NIC_E_ARG;
-    for (int l = 0; l < d->levels; ++l)
-        if (d->resolution[l] < 1 || 2 * (int64_t)d->S_max * d->resolution[l] >= (int64_t(1) << 31)) return NIC_E_ARG;
-    if (d->num_crops < 1) return NIC_E_SHAPE;
-    for (int a = 0; a < d->dim; ++a)
-        if (d->extent[a] < 1 || d->extent[a] > d->S_max) return NIC_E_SHAPE;
-    return NIC_OK;
-}
 // the supported set, the only copy: dim 2 / 3, F in {1, 2, 4, 8}, L F <= 64, hidden 64, 3 Linear layers
 static int supported(const nic_hash_desc* d, int hidden, int n_linear) {
-    const int rc = check_desc(d);
+    const int rc = check_hash_desc(d);
     if (rc) return rc;
     if (d->levels * d->features > kH) return NIC_E_UNSUPPORTED;
     if (hidden != kH || (n_linear != 3 && n_linear != 0)) return NIC_E_UNSUPPORTED;
@@ -706,10 +458,6 @@ static void fill_common(FParams& p, const nic_hash_desc* d, const int32_t* origi
     p.noise.mode = NIC_NOISE_NONE;
 }
 
-struct KernelEndDrop {        // a training entry point consumes the parked nic_mark_kernel_end event on every return
-    ~KernelEndDrop() { kernel_end_drop(); }
-};
-
 }  // namespace hfused
 }  // namespace nic
 
@@ -733,7 +481,7 @@ int nic_hash_fused_forward(const nic_hash_desc* desc, const float* table, const 
     FParams p{};
     fill_common(p, desc, origins, mlp, y);
     p.table = table;
-    return launch<HF_FWD>(p, grid_of(p.n_patches), stream);
+    return launch<HF_FWD>(p, persistent_grid(p.n_patches), stream);
 }
 
 int nic_hash_fused_forward_u8(const nic_hash_desc* desc, int num_bits, const uint8_t* stored, const int32_t* origins, const nic_mlp* mlp, float* y,
@@ -746,9 +494,8 @@ int nic_hash_fused_forward_u8(const nic_hash_desc* desc, int num_bits, const uin
     FParams p{};
     fill_common(p, desc, origins, mlp, y);
     p.stored = stored;
-    p.q_scale = (float)((1 << num_bits) - 1);
-    p.q_bias = (float)(1 << (num_bits - 1));
-    return launch<HF_FWD_U8>(p, grid_of(p.n_patches), stream);
+    set_dequant(p, num_bits);
+    return launch<HF_FWD_U8>(p, persistent_grid(p.n_patches), stream);
 }
 
 int nic_hash_fused_forward_bits(const nic_hash_desc* desc, int num_bits, const uint8_t* packed, const int32_t* origins, const nic_mlp* mlp, float* y,
@@ -763,9 +510,8 @@ int nic_hash_fused_forward_bits(const nic_hash_desc* desc, int num_bits, const u
     fill_common(p, desc, origins, mlp, y);
     p.packed = (const uint32_t*)packed;
     p.q_bits = num_bits; p.q_tight = hash_bits_tight(desc->features, num_bits) ? 1 : 0;
-    p.q_scale = (float)((1 << num_bits) - 1);
-    p.q_bias = (float)(1 << (num_bits - 1));
-    return launch<HF_FWD_BITS>(p, grid_of(p.n_patches), stream);
+    set_dequant(p, num_bits);
+    return launch<HF_FWD_BITS>(p, persistent_grid(p.n_patches), stream);
 }
 
 int nic_hash_fused_forward_backward(const nic_hash_desc* desc, const nic_hash_quant* quant, const float* table, const int32_t* origins,
@@ -781,19 +527,8 @@ int nic_hash_fused_forward_backward(const nic_hash_desc* desc, const nic_hash_qu
     FParams p{};
     fill_common(p, desc, origins, mlp, y);
     p.table = table; p.target = target; p.grad = table_grad;
-    if (quant) {
-        if (quant->num_bits < 1 || quant->num_bits > 8 || quant->sample_base < 0) return NIC_E_ARG;
-        if (quant->noise_mode == NIC_NOISE_TENSOR) return NIC_E_UNSUPPORTED;
-        if (quant->noise_mode != NIC_NOISE_NONE && quant->noise_mode != NIC_NOISE_KERNEL) return NIC_E_ARG;
-        if (quant->noise_mode == NIC_NOISE_KERNEL) {
-            p.noise.mode = NIC_NOISE_KERNEL;
-            p.noise.k0 = (uint32_t)quant->noise_seed; p.noise.k1 = (uint32_t)(quant->noise_seed >> 32);
-            p.noise.off_lo = (uint32_t)quant->noise_offset; p.noise.off_hi = (uint32_t)(quant->noise_offset >> 32);
-            p.noise.scale = ldexpf(1.0f, -quant->num_bits);
-            p.sample_base = (uint64_t)quant->sample_base;
-        }
-    }
-    const int lf = desc->levels * desc->features, grid = grid_of(p.n_patches);
+    if ((rc = set_noise(quant, true, p.noise, p.sample_base)) != NIC_OK) return rc;
+    const int lf = desc->levels * desc->features, grid = persistent_grid(p.n_patches);
     const RecLayout rl(lf);
     if (workspace_bytes < (size_t)grid * rl.rec * sizeof(float)) return NIC_E_WORKSPACE;
     // the optimiser tail (fused_capi.hip, TailScope::open): a decoder entry's gradient is one of the buffers this call's reduction writes

@@ -12,24 +12,10 @@
 // The bit-packed table (nic_hash_encode_bits / nic_hash_pack_bits / nic_hash_unpack_bits; the format is spelled out in the header): a third
 // table source, b bits per value in one little-endian bit stream per level.  An entry is read as a window of aligned dwords from the dword it
 // starts in, funnel-shifted to bit 0 and masked into the uint8 value, which then takes load_row_u8's dequantisation and the same blend.
-#include "nic_device.hpp"
+#include "hash_common.hpp"
 
 namespace nic {
-
-__host__ __device__ inline bool hash_level_dense(int dim, int32_t R, int log2_table) {
-    uint64_t p = 1;
-    for (int a = 0; a < dim; ++a) {
-        p *= (uint64_t)R + 1;
-        if (p > (1ull << log2_table)) return false;
-    }
-    return true;
-}
-
-// the entry of vertex (vx, vy, vz) in a level of resolution R (vz = 0 in 2D)
-__host__ __device__ inline uint32_t hash_index(bool dense, uint32_t R, uint32_t mask, uint32_t vx, uint32_t vy, uint32_t vz) {
-    const uint32_t h = dense ? vx + (R + 1u) * (vy + (R + 1u) * vz) : (vx ^ (vy * 2654435761u) ^ (vz * 805459861u));
-    return h & mask;
-}
+using namespace hcommon;
 
 struct HashParams {
     nic_hash_desc d;
@@ -51,173 +37,6 @@ struct HashParams {
 
 enum HashSrc { HSRC_F32 = 0, HSRC_U8 = 1, HSRC_BITS = 2 };
 
-template <int F>
-__device__ __forceinline__ void load_row(const float* p, float (&v)[F]) {
-    if constexpr (F == 1) {
-        v[0] = *p;
-    } else if constexpr (F == 2) {
-        const float2 a = *reinterpret_cast<const float2*>(p);
-        v[0] = a.x; v[1] = a.y;
-    } else {
-#pragma unroll
-        for (int k = 0; k < F; k += 4) {
-            const float4 a = *reinterpret_cast<const float4*>(p + k);
-            v[k] = a.x; v[k + 1] = a.y; v[k + 2] = a.z; v[k + 3] = a.w;
-        }
-    }
-}
-
-template <int F>
-__device__ __forceinline__ void store_row(float* p, const float (&v)[F]) {
-    if constexpr (F == 1) {
-        *p = v[0];
-    } else if constexpr (F == 2) {
-        *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < F; k += 4) *reinterpret_cast<float4*>(p + k) = make_float4(v[k], v[k + 1], v[k + 2], v[k + 3]);
-    }
-}
-
-// one compact uint8 entry of F bytes as ONE load (ubyte / ushort / dword / dwordx2), dequantised like load4fp_kernel (simple_kernels.hip)
-template <int F>
-__device__ __forceinline__ void load_row_u8(const uint8_t* p, float scale, float bias, float (&v)[F]) {
-    uint32_t w[(F + 3) / 4];
-    if constexpr (F == 1) {
-        w[0] = *p;
-    } else if constexpr (F == 2) {
-        w[0] = *reinterpret_cast<const uint16_t*>(p);
-    } else if constexpr (F == 4) {
-        w[0] = *reinterpret_cast<const uint32_t*>(p);
-    } else {
-        const uint2 a = *reinterpret_cast<const uint2*>(p);
-        w[0] = a.x; w[1] = a.y;
-    }
-#pragma unroll
-    for (int f = 0; f < F; ++f) {
-        const float u = (float)((w[f >> 2] >> (8 * (f & 3))) & 0xFFu);
-        v[f] = __fdiv_rn(__fadd_rn(__fsub_rn(u, bias), 1.0f), scale);
-    }
-}
-
-// entries a level stores in the compact table: the (R + 1)^dim vertices of a dense level, all T of a hashed one
-__host__ __device__ inline int64_t hash_level_entries(int dim, int32_t R, int log2_table) {
-    if (!hash_level_dense(dim, R, log2_table)) return int64_t(1) << log2_table;
-    int64_t e = 1;
-    for (int a = 0; a < dim; ++a) e *= (int64_t)R + 1;
-    return e;
-}
-
-// dwords of a level's bit stream: E F b bits (<= 2^30), padded with zero bits to whole dwords
-__host__ __device__ inline int64_t hash_level_dwords(int dim, int32_t R, int log2_table, int F, int bits) {
-    return (hash_level_entries(dim, R, log2_table) * (F * bits) + 31) >> 5;
-}
-__host__ __device__ inline bool hash_bits_tight(int F, int bits) { return 32 % (F * bits) == 0 || F * bits == 64; }
-
-// one bit-packed entry of F b bits at bit e F b of its level's stream `lev`: aligned dword loads only - the dword the entry starts in and the
-// next one (F <= 4: F b <= 32) or two (F = 8: F b <= 64; the 8 zero bytes after the last level keep that window inside the buffer), funnel-
-// shifted so that the entry starts at bit 0.  TIGHT (HashParams::q_tight, uniform over the launch): no entry straddles, the extra dword is not read.
-// The value then takes load_row_u8's dequantisation, expression for expression.
-template <int F, bool TIGHT>
-__device__ __forceinline__ void load_row_bits(const uint32_t* lev, uint32_t e, int bits, float scale, float bias, float (&v)[F]) {
-    const uint32_t bit = e * (uint32_t)(F * bits), sh = bit & 31u;
-    const uint32_t* q = lev + (bit >> 5);
-    uint32_t x0, x1 = 0u;
-    const uint32_t w0 = q[0];
-    if constexpr (F <= 4) {
-        if constexpr (TIGHT) x0 = w0 >> sh;
-        else x0 = __builtin_amdgcn_alignbit(q[1], w0, sh);
-    } else {
-        if constexpr (TIGHT) {
-            x0 = w0 >> sh;
-            if (bits == 8) x1 = q[1];                                // F b = 64 starts on a dword
-        } else {
-            const uint32_t w1 = q[1], w2 = q[2];
-            x0 = __builtin_amdgcn_alignbit(w1, w0, sh);
-            x1 = __builtin_amdgcn_alignbit(w2, w1, sh);
-        }
-    }
-#pragma unroll
-    for (int f = 0; f < F; ++f) {
-        uint32_t uv;
-        if constexpr (F <= 4) uv = __builtin_amdgcn_ubfe(x0, (uint32_t)(f * bits), (uint32_t)bits);      // f b + b <= 32
-        else uv = __builtin_amdgcn_ubfe((uint32_t)((((uint64_t)x1 << 32) | x0) >> (f * bits)), 0u, (uint32_t)bits);
-        const float u = (float)uv;
-        v[f] = __fdiv_rn(__fadd_rn(__fsub_rn(u, bias), 1.0f), scale);
-    }
-}
-
-// the sample of this lane in patch `wv` (clamped to the last patch; `live` = a real sample of a real patch)
-template <int D>
-struct PatchSample {
-    int crop;
-    int idx[3];
-    bool live;
-    int64_t n;
-};
-template <int D>
-__device__ __forceinline__ PatchSample<D> patch_sample(const nic_hash_desc& d, int64_t wv, int64_t n_patches, int lane) {
-    constexpr int PS = D == 2 ? 8 : 4;
-    const int np1 = (d.extent[1] + PS - 1) / PS, np2 = D == 3 ? (d.extent[2] + PS - 1) / PS : 1;
-    const int64_t per_crop = (int64_t)((d.extent[0] + PS - 1) / PS) * np1 * np2;
-    const int64_t wc = wv < n_patches ? wv : n_patches - 1;
-    PatchSample<D> s;
-    s.crop = (int)(wc / per_crop);
-    int64_t pr = wc - (int64_t)s.crop * per_crop;
-    int pt[3] = {0, 0, 0};
-    if (D == 3) { pt[2] = (int)(pr % np2); pr /= np2; }
-    pt[1] = (int)(pr % np1);
-    pt[0] = (int)(pr / np1);
-    if (D == 2) {
-        s.idx[0] = PS * pt[0] + (lane & 7);
-        s.idx[1] = PS * pt[1] + (lane >> 3);
-        s.idx[2] = 0;
-    } else {
-        s.idx[0] = PS * pt[0] + (lane & 3);
-        s.idx[1] = PS * pt[1] + ((lane >> 2) & 3);
-        s.idx[2] = PS * pt[2] + (lane >> 4);
-    }
-    s.live = wv < n_patches;
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-        s.live = s.live && s.idx[a] < d.extent[a];
-        s.idx[a] = s.idx[a] < d.extent[a] ? s.idx[a] : d.extent[a] - 1;
-    }
-    const int64_t n_per_crop = (int64_t)d.extent[0] * d.extent[1] * (D == 3 ? d.extent[2] : 1);
-    s.n = (int64_t)s.crop * n_per_crop + ((int64_t)s.idx[0] * d.extent[1] + s.idx[1]) * (D == 3 ? d.extent[2] : 1) + (D == 3 ? s.idx[2] : 0);
-    return s;
-}
-
-// integer sample coordinate per axis, clamped into the field (an origin outside it is refused on the host; this keeps q < 2^31 regardless)
-template <int D>
-__device__ __forceinline__ void sample_coords(const HashParams& p, const PatchSample<D>& s, uint32_t (&i)[3]) {
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-        const int c = p.origins[s.crop * D + a] + s.idx[a];
-        i[a] = (uint32_t)(c < 0 ? 0 : (c >= p.d.S_max ? p.d.S_max - 1 : c));
-    }
-    if (D == 2) i[2] = 0;
-}
-
-// base vertex and fp32 weight per axis of one level: q = (2 i + 1) R, v = q / 2 S_max, w = (q mod 2 S_max) / 2 S_max
-template <int D>
-__device__ __forceinline__ void level_cell(const uint32_t (&i)[3], uint32_t R, uint32_t S2, uint32_t (&v)[3], float (&w)[3]) {
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-        const uint32_t q = (2u * i[a] + 1u) * R;
-        v[a] = q / S2;
-        w[a] = (float)(q - v[a] * S2) / (float)S2;
-    }
-    if (D == 2) { v[2] = 0; w[2] = 0.f; }
-}
-
-template <int D>
-__device__ __forceinline__ float corner_weight(const float (&w)[3], int c) {
-    float r = ((c & 1) ? w[0] : 1.0f - w[0]) * ((c & 2) ? w[1] : 1.0f - w[1]);
-    if (D == 3) r *= (c & 4) ? w[2] : 1.0f - w[2];
-    return r;
-}
-
 template <int D, int F, int SRC = HSRC_F32, bool NOISE = false>
 __global__ void __launch_bounds__(256) hash_encode_kernel(HashParams p) {
     const nic_hash_desc& d = p.d;
@@ -232,7 +51,7 @@ __global__ void __launch_bounds__(256) hash_encode_kernel(HashParams p) {
         const PatchSample<D> s = patch_sample<D>(d, wb + (threadIdx.x >> 6), n_patches, lane);
         if (!s.live) continue;
         uint32_t i[3];
-        sample_coords<D>(p, s, i);
+        sample_coords<D>(d, p.origins, s, i);
         float* orow = p.out + s.n * LF;
         [[maybe_unused]] int64_t lev_off = 0;              // HSRC_U8: byte offset of level l = F * sum_{k<l} E_k
         [[maybe_unused]] int64_t lev_dw = 0;               // HSRC_BITS: dword offset of level l = sum_{k<l} ceil(E_k F b / 32)
@@ -296,7 +115,7 @@ __global__ void __launch_bounds__(256) hash_encode_backward_kernel(HashParams p)
     for (int64_t wb = (int64_t)blockIdx.x * 4; wb < n_patches; wb += (int64_t)gridDim.x * 4) {      // block-uniform trip count: the shuffles see whole waves
         const PatchSample<D> s = patch_sample<D>(d, wb + (threadIdx.x >> 6), n_patches, lane);
         uint32_t i[3];
-        sample_coords<D>(p, s, i);
+        sample_coords<D>(d, p.origins, s, i);
         const float* drow = p.dx + s.n * LF;
         for (int l = 0; l < d.levels; ++l) {
             const uint32_t R = (uint32_t)d.resolution[l];
@@ -420,32 +239,9 @@ __global__ void __launch_bounds__(256) hash_unpack_bits_kernel(HashBitsParams p)
     }
 }
 
-static inline int hash_blocks(const nic_hash_desc* d) {
-    const int PS = d->dim == 2 ? 8 : 4;
-    int64_t patches = d->num_crops;
-    for (int a = 0; a < d->dim; ++a) patches *= (d->extent[a] + PS - 1) / PS;
-    const int64_t b = (patches + 3) / 4;                 // one wave per patch, four waves per block
-    return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
-}
-
 }  // namespace nic
 
 using namespace nic;
-
-static int check_hash_desc(const nic_hash_desc* d) {
-    if (!d) return NIC_E_NULL;
-    if (d->dim != 2 && d->dim != 3) return NIC_E_UNSUPPORTED;
-    if (d->features != 1 && d->features != 2 && d->features != 4 && d->features != 8) return NIC_E_UNSUPPORTED;
-    if (d->levels < 1 || d->levels > NIC_HASH_MAX_LEVELS) return NIC_E_ARG;
-    if (d->log2_table < 10 || d->log2_table > 24) return NIC_E_ARG;
-    if (d->S_max < 1 || d->flags != 0) return NIC_E_ARG;
-    for (int l = 0; l < d->levels; ++l)      // q = (2 i + 1) R_l < 2 S_max R_l must stay below 2^31
-        if (d->resolution[l] < 1 || 2 * (int64_t)d->S_max * d->resolution[l] >= (int64_t(1) << 31)) return NIC_E_ARG;
-    if (d->num_crops < 1) return NIC_E_SHAPE;
-    for (int a = 0; a < d->dim; ++a)
-        if (d->extent[a] < 1 || d->extent[a] > d->S_max) return NIC_E_SHAPE;
-    return NIC_OK;
-}
 
 enum HashKernel { HK_FWD, HK_BWD, HK_FWD_NOISY, HK_FWD_U8, HK_FWD_BITS };
 
@@ -470,7 +266,7 @@ static void launch_f(const HashParams& p, int nb, hipStream_t s) {
 
 template <int K>
 static int hash_launch(const HashParams& p, void* stream) {
-    const int nb = hash_blocks(&p.d);
+    const int nb = strided_grid(count_patches(&p.d));         // one wave per patch, four waves per block
     if (p.d.dim == 2) launch_f<K, 2>(p, nb, (hipStream_t)stream);
     else launch_f<K, 3>(p, nb, (hipStream_t)stream);
     return (int)hipGetLastError();
@@ -496,11 +292,6 @@ static int64_t hash_packed_prefix(const nic_hash_desc* d, int num_bits, int64_t*
     }
     if (pre) pre[d->levels] = off;
     return off;
-}
-
-static void set_dequant(HashParams& p, int num_bits) {
-    p.q_scale = (float)((1 << num_bits) - 1);
-    p.q_bias = (float)(1 << (num_bits - 1));
 }
 
 extern "C" {
@@ -534,21 +325,13 @@ int nic_hash_index_host(const nic_hash_desc* desc, int level, int32_t vx, int32_
 
 int nic_hash_encode_noisy(const nic_hash_desc* desc, const nic_hash_quant* quant, const float* table, const int32_t* origins, float* out,
                           void* stream) {
-    const int rc = check_hash_desc(desc);
+    int rc = check_hash_desc(desc);
     if (rc) return rc;
     if (!quant || !table || !origins || !out) return NIC_E_NULL;
-    if (quant->num_bits < 1 || quant->num_bits > 8 || quant->sample_base < 0) return NIC_E_ARG;
-    if (quant->noise_mode == NIC_NOISE_TENSOR) return NIC_E_UNSUPPORTED;
-    if (quant->noise_mode != NIC_NOISE_NONE && quant->noise_mode != NIC_NOISE_KERNEL) return NIC_E_ARG;
     HashParams p{};
     p.d = *desc; p.table = table; p.origins = origins; p.out = out;
-    if (quant->noise_mode == NIC_NOISE_NONE) return hash_launch<HK_FWD>(p, stream);
-    p.noise.mode = NIC_NOISE_KERNEL;
-    p.noise.k0 = (uint32_t)quant->noise_seed; p.noise.k1 = (uint32_t)(quant->noise_seed >> 32);
-    p.noise.off_lo = (uint32_t)quant->noise_offset; p.noise.off_hi = (uint32_t)(quant->noise_offset >> 32);
-    p.noise.scale = ldexpf(1.0f, -quant->num_bits);
-    p.sample_base = (uint64_t)quant->sample_base;
-    return hash_launch<HK_FWD_NOISY>(p, stream);
+    if ((rc = set_noise(quant, true, p.noise, p.sample_base)) != NIC_OK) return rc;
+    return p.noise.mode == NIC_NOISE_KERNEL ? hash_launch<HK_FWD_NOISY>(p, stream) : hash_launch<HK_FWD>(p, stream);
 }
 
 int nic_hash_encode_u8(const nic_hash_desc* desc, int num_bits, const uint8_t* stored, const int32_t* origins, float* out, void* stream) {

@@ -11,16 +11,10 @@
 //   8 x 8 / 4 x 4 x 4 patch with x the fastest lane axis and number rows and noise keys in the crop's sample order; point launches give a
 //   wave 64 consecutive (ordered) points.
 //   fused training is hash_points_fused_train_kernel's body on those two pieces: encode -> decoder_train_half -> scatter_point ->
-//   write_record, then hash_fused_reduce_kernel (linked from hash_fused.hip) with the optimiser tail riding on it.
+//   write_record, then hash_fused_reduce_kernel (hash_fused.hip) with the optimiser tail riding on it.
 #include "hash_common.hpp"
 
 namespace nic {
-namespace hfused {
-// defined in hash_fused.hip; reads records of hcommon::RecLayout (the same layout as its own)
-__global__ void __launch_bounds__(256) hash_fused_reduce_kernel(const float* partials, int n_rec, int lf, nic_mlp_grads g, float* loss, float loss_mul,
-                                                                int add_grads, int add_loss, const StepTail tl);
-}  // namespace hfused
-
 namespace hmixed {
 using namespace hcommon;
 
@@ -85,7 +79,7 @@ __device__ __forceinline__ void blend_bits(const uint32_t* lev, bool dense, uint
     }
 }
 
-// THE level loop.  VEC: the row goes out in F-wide stores (global), else value by value (an LDS tile).  The blend is written as fmaf: the pinned
+// THE level loop.  VEC: the row goes out in F-wide stores (global), else value by value (an LDS tile).  The blend is written as fmaf: the uniform
 // kernels' `acc += cw * v` compiles to one fused multiply-add per corner, and bit equality with them must not hang on the vectoriser's choice
 // (left free, it split the F = 1 straddling blend into packed multiplies and separate adds: one ulp off)
 template <int D, int F, int SRC, bool NOISE, bool VEC>
@@ -303,31 +297,10 @@ __global__ void __launch_bounds__(256) hash_mixed_clamp_kernel(const MClampParam
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
-static int64_t count_patches(const nic_hash_desc* d) {
-    const int PS = d->dim == 2 ? 8 : 4;
-    int64_t patches = d->num_crops;
-    for (int a = 0; a < d->dim; ++a) patches *= (d->extent[a] + PS - 1) / PS;
-    return patches;
-}
-static int encode_grid(int64_t n_waves) {
-    const int64_t b = (n_waves + 3) / 4;
-    return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));       // the cap of the crop and point launches
-}
-static int fused_grid(int64_t n_waves) {
-    const int64_t groups = (n_waves + 3) / 4, want = (groups + 7) / 8 * 8;
-    return (int)(want < wg_cap() ? want : wg_cap());
-}
-
-// the descriptor checks are the siblings', their only copy: nic_hash_stored_bytes answers check_hash_desc (hash_grid.hip), the unordered point
-// scatter with no points what the point entries add (hash_points.hip).  The lattice route goes through the fixed-point cell too: 256 S_max < 2^30
-static int check_desc(const nic_hash_desc* d) {
-    const int64_t rc = nic_hash_stored_bytes(d);
-    return rc < 0 ? (int)rc : NIC_OK;
-}
+// the lattice route goes through the fixed-point cell too: 256 S_max < 2^30, as at points
 static int check_position_desc(const nic_hash_desc* d, bool at_points) {
-    static float dummy;
-    if (at_points) return nic_hash_encode_points_backward(d, &dummy, 0, &dummy, &dummy, nullptr);
-    const int rc = check_desc(d);
+    if (at_points) return check_point_desc(d);
+    const int rc = check_hash_desc(d);
     if (rc) return rc;
     return 256 * (int64_t)d->S_max >= (int64_t(1) << 30) ? NIC_E_ARG : NIC_OK;
 }
@@ -371,21 +344,6 @@ static int set_source(MParams& p, const nic_hash_source* src) {
     p.packed = (const uint32_t*)src->data;
     return NIC_OK;
 }
-// null, or kernel noise (nic_hash_encode_noisy's checks; quant->num_bits is ignored: the scale is the level's)
-static int set_noise(MParams& p, const nic_hash_quant* quant) {
-    if (!quant) return NIC_OK;
-    if (quant->sample_base < 0) return NIC_E_ARG;
-    if (quant->noise_mode == NIC_NOISE_TENSOR) return NIC_E_UNSUPPORTED;
-    if (quant->noise_mode != NIC_NOISE_NONE && quant->noise_mode != NIC_NOISE_KERNEL) return NIC_E_ARG;
-    if (quant->noise_mode == NIC_NOISE_KERNEL) {
-        p.noise.mode = NIC_NOISE_KERNEL;
-        p.noise.k0 = (uint32_t)quant->noise_seed; p.noise.k1 = (uint32_t)(quant->noise_seed >> 32);
-        p.noise.off_lo = (uint32_t)quant->noise_offset; p.noise.off_hi = (uint32_t)(quant->noise_offset >> 32);
-        p.sample_base = (uint64_t)quant->sample_base;
-    }
-    return NIC_OK;
-}
-
 enum MKernel { MK_ENC, MK_ENC_NOISY, MK_ENC_BITS, MK_FUSED, MK_FUSED_BITS, MK_TRAIN, MK_TRAIN_NOISY };
 
 template <int K, int D, int F>
@@ -417,10 +375,6 @@ static int launch(const MParams& p, int nb, void* stream) {
     return (int)hipGetLastError();
 }
 
-struct KernelEndDrop {        // a training entry point consumes the parked nic_mark_kernel_end event on every return
-    ~KernelEndDrop() { kernel_end_drop(); }
-};
-
 }  // namespace hmixed
 }  // namespace nic
 
@@ -430,7 +384,7 @@ using namespace nic::hmixed;
 extern "C" {
 
 int64_t nic_hash_packed_bytes_levels(const nic_hash_desc* desc, const nic_hash_level_bits* level_bits) {
-    int rc = check_desc(desc);
+    int rc = check_hash_desc(desc);
     if (rc) return rc;
     if (!level_bits) return NIC_E_NULL;
     if ((rc = check_bits(desc, level_bits)) != NIC_OK) return rc;
@@ -438,7 +392,7 @@ int64_t nic_hash_packed_bytes_levels(const nic_hash_desc* desc, const nic_hash_l
 }
 
 int nic_hash_pack_bits_levels(const nic_hash_desc* desc, const nic_hash_level_bits* level_bits, const float* table, uint8_t* packed, void* stream) {
-    int rc = check_desc(desc);
+    int rc = check_hash_desc(desc);
     if (rc) return rc;
     if (!level_bits || !table || !packed) return NIC_E_NULL;
     if ((rc = check_bits(desc, level_bits)) != NIC_OK) return rc;
@@ -457,7 +411,7 @@ int nic_hash_pack_bits_levels(const nic_hash_desc* desc, const nic_hash_level_bi
 }
 
 int nic_hash_clamp_levels(const nic_hash_desc* desc, const nic_hash_level_bits* level_bits, float* table, void* stream) {
-    int rc = check_desc(desc);
+    int rc = check_hash_desc(desc);
     if (rc) return rc;
     if (!level_bits || !table) return NIC_E_NULL;
     if ((rc = check_bits(desc, level_bits)) != NIC_OK) return rc;
@@ -473,7 +427,7 @@ int nic_hash_clamp_levels(const nic_hash_desc* desc, const nic_hash_level_bits* 
 
 int nic_hash_encode_levels(const nic_hash_desc* desc, const nic_hash_level_bits* level_bits, const nic_hash_source* src, const nic_hash_quant* quant,
                            const int32_t* origins, const float* points, int64_t n_points, float* out, void* stream) {
-    int rc = check_desc(desc);
+    int rc = check_hash_desc(desc);
     if (rc) return rc;
     if ((origins != nullptr) == (points != nullptr)) return NIC_E_ARG;
     if ((rc = check_position_desc(desc, points != nullptr)) != NIC_OK) return rc;
@@ -484,10 +438,10 @@ int nic_hash_encode_levels(const nic_hash_desc* desc, const nic_hash_level_bits*
     p.out = out;
     if ((rc = set_source(p, src)) != NIC_OK) return rc;
     if (quant && src->kind != NIC_HASH_SRC_F32) return NIC_E_ARG;        // noise belongs to training, which reads the fp32 table
-    if ((rc = set_noise(p, quant)) != NIC_OK) return rc;
+    if ((rc = set_noise(quant, false, p.noise, p.sample_base)) != NIC_OK) return rc;
     if (points && n_points < 0) return NIC_E_ARG;
     if (points && n_points == 0) return NIC_OK;
-    const int nb = encode_grid(p.n_waves);
+    const int nb = strided_grid(p.n_waves);
     if (src->kind == NIC_HASH_SRC_BITS) return launch<MK_ENC_BITS>(p, nb, stream);
     return p.noise.mode == NIC_NOISE_KERNEL ? launch<MK_ENC_NOISY>(p, nb, stream) : launch<MK_ENC>(p, nb, stream);
 }
@@ -510,7 +464,7 @@ int nic_hash_fused_forward_levels(const nic_hash_desc* desc, const nic_hash_leve
     if (points && n_points < 0) return NIC_E_ARG;
     if (points && n_points == 0) return NIC_OK;
     p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
-    const int grid = fused_grid(p.n_waves);
+    const int grid = persistent_grid(p.n_waves);
     return src->kind == NIC_HASH_SRC_BITS ? launch<MK_FUSED_BITS>(p, grid, stream) : launch<MK_FUSED>(p, grid, stream);
 }
 
@@ -535,7 +489,7 @@ int nic_hash_fused_forward_backward_levels(const nic_hash_desc* desc, const nic_
     fill_common(p, desc, level_bits, origins, points, n_points);
     p.order = order; p.table = table; p.target = target; p.grad = table_grad; p.y = y;
     p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
-    if ((rc = set_noise(p, quant)) != NIC_OK) return rc;
+    if ((rc = set_noise(quant, false, p.noise, p.sample_base)) != NIC_OK) return rc;
     if (points && (n_points < 0 || (order && n_points >= (int64_t(1) << 31)))) return NIC_E_ARG;
     const int lf = desc->levels * desc->features;
     const RecLayout rl(lf);
@@ -562,7 +516,7 @@ int nic_hash_fused_forward_backward_levels(const nic_hash_desc* desc, const nic_
     }
     if (points && n_points == 0) return NIC_OK;                       // nothing to launch: *loss and every gradient stay as they are
     const double n_samples = points ? (double)n_points : (double)desc->num_crops * desc->extent[0] * desc->extent[1] * (desc->dim == 3 ? desc->extent[2] : 1);
-    const int grid = fused_grid(p.n_waves);
+    const int grid = persistent_grid(p.n_waves);
     const float loss_mul = (float)((double)loss_scale / (3.0 * n_samples));
     p.dscale = 2.0f * loss_mul;
     p.partials = (float*)workspace;

@@ -9,115 +9,12 @@
 //
 // One lane per point, row n = point n, in any order: the run sums of the backward merge whichever NEIGHBOURING lanes share a base vertex (whole
 // runs in raster order, none for random points, the whole wave when all points coincide).  The fused decode is hash_fused.hip's forward mode
-// with the lane's coordinates taken from the point array; that file and hash_grid.hip are pinned, so their helpers are restated here unchanged.
-#include "nic_device.hpp"
+// with the lane's coordinates taken from the point array.  The helpers are hash_common.hpp's.
+#include "hash_common.hpp"
 
 namespace nic {
 namespace hpoints {
-
-// ---- restated from hash_grid.hip / hash_fused.hip -------------------------------------------------------------------------------------
-__host__ __device__ inline bool hash_level_dense(int dim, int32_t R, int log2_table) {
-    uint64_t p = 1;
-    for (int a = 0; a < dim; ++a) {
-        p *= (uint64_t)R + 1;
-        if (p > (1ull << log2_table)) return false;
-    }
-    return true;
-}
-__host__ __device__ inline uint32_t hash_index(bool dense, uint32_t R, uint32_t mask, uint32_t vx, uint32_t vy, uint32_t vz) {
-    const uint32_t h = dense ? vx + (R + 1u) * (vy + (R + 1u) * vz) : (vx ^ (vy * 2654435761u) ^ (vz * 805459861u));
-    return h & mask;
-}
-__host__ __device__ inline int64_t hash_level_entries(int dim, int32_t R, int log2_table) {
-    if (!hash_level_dense(dim, R, log2_table)) return int64_t(1) << log2_table;
-    int64_t e = 1;
-    for (int a = 0; a < dim; ++a) e *= (int64_t)R + 1;
-    return e;
-}
-__host__ __device__ inline int64_t hash_level_dwords(int dim, int32_t R, int log2_table, int F, int bits) {
-    return (hash_level_entries(dim, R, log2_table) * (F * bits) + 31) >> 5;
-}
-__host__ __device__ inline bool hash_bits_tight(int F, int bits) { return 32 % (F * bits) == 0 || F * bits == 64; }
-template <int F>
-__device__ __forceinline__ void load_row(const float* p, float (&v)[F]) {
-    if constexpr (F == 1) {
-        v[0] = *p;
-    } else if constexpr (F == 2) {
-        const float2 a = *reinterpret_cast<const float2*>(p);
-        v[0] = a.x; v[1] = a.y;
-    } else {
-#pragma unroll
-        for (int k = 0; k < F; k += 4) {
-            const float4 a = *reinterpret_cast<const float4*>(p + k);
-            v[k] = a.x; v[k + 1] = a.y; v[k + 2] = a.z; v[k + 3] = a.w;
-        }
-    }
-}
-template <int F>
-__device__ __forceinline__ void store_row(float* p, const float (&v)[F]) {
-    if constexpr (F == 1) {
-        *p = v[0];
-    } else if constexpr (F == 2) {
-        *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < F; k += 4) *reinterpret_cast<float4*>(p + k) = make_float4(v[k], v[k + 1], v[k + 2], v[k + 3]);
-    }
-}
-template <int F>
-__device__ __forceinline__ void load_row_u8(const uint8_t* p, float scale, float bias, float (&v)[F]) {
-    uint32_t w[(F + 3) / 4];
-    if constexpr (F == 1) {
-        w[0] = *p;
-    } else if constexpr (F == 2) {
-        w[0] = *reinterpret_cast<const uint16_t*>(p);
-    } else if constexpr (F == 4) {
-        w[0] = *reinterpret_cast<const uint32_t*>(p);
-    } else {
-        const uint2 a = *reinterpret_cast<const uint2*>(p);
-        w[0] = a.x; w[1] = a.y;
-    }
-#pragma unroll
-    for (int f = 0; f < F; ++f) {
-        const float u = (float)((w[f >> 2] >> (8 * (f & 3))) & 0xFFu);
-        v[f] = __fdiv_rn(__fadd_rn(__fsub_rn(u, bias), 1.0f), scale);
-    }
-}
-template <int F, bool TIGHT>
-__device__ __forceinline__ void load_row_bits(const uint32_t* lev, uint32_t e, int bits, float scale, float bias, float (&v)[F]) {
-    const uint32_t bit = e * (uint32_t)(F * bits), sh = bit & 31u;
-    const uint32_t* q = lev + (bit >> 5);
-    uint32_t x0, x1 = 0u;
-    const uint32_t w0 = q[0];
-    if constexpr (F <= 4) {
-        if constexpr (TIGHT) x0 = w0 >> sh;
-        else x0 = __builtin_amdgcn_alignbit(q[1], w0, sh);
-    } else {
-        if constexpr (TIGHT) {
-            x0 = w0 >> sh;
-            if (bits == 8) x1 = q[1];                                // F b = 64 starts on a dword
-        } else {
-            const uint32_t w1 = q[1], w2 = q[2];
-            x0 = __builtin_amdgcn_alignbit(w1, w0, sh);
-            x1 = __builtin_amdgcn_alignbit(w2, w1, sh);
-        }
-    }
-#pragma unroll
-    for (int f = 0; f < F; ++f) {
-        uint32_t uv;
-        if constexpr (F <= 4) uv = __builtin_amdgcn_ubfe(x0, (uint32_t)(f * bits), (uint32_t)bits);      // f b + b <= 32
-        else uv = __builtin_amdgcn_ubfe((uint32_t)((((uint64_t)x1 << 32) | x0) >> (f * bits)), 0u, (uint32_t)bits);
-        const float u = (float)uv;
-        v[f] = __fdiv_rn(__fadd_rn(__fsub_rn(u, bias), 1.0f), scale);
-    }
-}
-template <int D>
-__device__ __forceinline__ float corner_weight(const float (&w)[3], int c) {
-    float r = ((c & 1) ? w[0] : 1.0f - w[0]) * ((c & 2) ? w[1] : 1.0f - w[1]);
-    if (D == 3) r *= (c & 4) ? w[2] : 1.0f - w[2];
-    return r;
-}
-// ---- end of the restated helpers ------------------------------------------------------------------------------------------------------
+using namespace hcommon;
 
 enum PointSrc { PSRC_F32 = NIC_HASH_SRC_F32, PSRC_U8 = NIC_HASH_SRC_U8, PSRC_BITS = NIC_HASH_SRC_BITS };
 
@@ -139,36 +36,6 @@ struct PointParams {
     const float *w1, *b1, *w2, *b2, *w3, *b3;
     float* y;
 };
-
-// the fixed-point position of point n per axis: clamped in floating point first (NaN fails both comparisons' "keep" side and lands on the low
-// edge, -inf / +inf on the nearer one), so the conversion sees |256 p| < 2^30; then t = rint(256 p) + 128 (v_rndne: half to even; 256 p is exact)
-// clamped to [0, 256 S - 1] - the upper edge p = S - 1/2 gives 256 S and comes back into the last cell, so v <= R - 1 on every level
-template <int D>
-__device__ __forceinline__ void point_fixed(const PointParams& p, int64_t n, uint32_t (&t)[3]) {
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-        const float x = p.points[n * D + a], lo = -0.5f, hi = (float)p.d.extent[a] - 0.5f;
-        float c = x >= lo ? x : lo;
-        c = c <= hi ? c : hi;
-        const int ti = (int)rintf(256.0f * c) + 128, tmax = 256 * p.d.extent[a] - 1;
-        t[a] = (uint32_t)(ti < 0 ? 0 : (ti > tmax ? tmax : ti));
-    }
-    if (D == 2) t[2] = 0;
-}
-
-// base vertex and fp32 weight per axis of one level: q = t R (< 2^38), v = q div 256 S_max, w = fp32(q mod 256 S_max) / fp32(256 S_max),
-// through q >> 8 (< 2^30) div / mod S_max in 32 bits (file comment)
-template <int D>
-__device__ __forceinline__ void point_cell(const uint32_t (&t)[3], uint32_t R, uint32_t S, float fdiv, uint32_t (&v)[3], float (&w)[3]) {
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-        const uint64_t q = (uint64_t)t[a] * R;
-        const uint32_t qh = (uint32_t)(q >> 8), ql = (uint32_t)q & 255u;
-        v[a] = qh / S;
-        w[a] = (float)(((qh - v[a] * S) << 8) | ql) / fdiv;
-    }
-    if (D == 2) { v[2] = 0; w[2] = 0.f; }
-}
 
 // the level loop of hash_encode_kernel for one point; VEC: the row goes out in F-wide stores (global), else value by value (an LDS tile)
 template <int D, int F, int SRC, bool NOISE, bool TIGHT, bool VEC>
@@ -243,7 +110,7 @@ __global__ void __launch_bounds__(256) hash_points_encode_kernel(const PointPara
     const int LF = p.d.levels * F;
     for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < p.n; n += (int64_t)gridDim.x * 256) {
         uint32_t t[3];
-        point_fixed<D>(p, n, t);
+        point_fixed<D>(p.d, p.points, n, t);
         encode_point<D, F, SRC, NOISE, true>(p, t, n, p.out + n * LF);
     }
 }
@@ -260,7 +127,7 @@ __global__ void __launch_bounds__(256) hash_points_backward_kernel(const PointPa
         const bool live = n_raw < p.n;
         const int64_t n = live ? n_raw : p.n - 1;                                                   // a dead lane reads the last point, adds nothing
         uint32_t t[3];
-        point_fixed<D>(p, n, t);
+        point_fixed<D>(p.d, p.points, n, t);
         const float* drow = p.dx + n * LF;
         for (int l = 0; l < d.levels; ++l) {
             const uint32_t R = (uint32_t)d.resolution[l];
@@ -296,24 +163,11 @@ __global__ void __launch_bounds__(256) hash_points_backward_kernel(const PointPa
 }
 
 // ---- the fused decode at points: hash_fused_kernel's forward mode (hash_fused.hip), one wave per 64 consecutive points -------------------
-constexpr int XS = kH + 1;      // row stride of every LDS tile: lanes that walk rows hit 64 different banks
-
-struct Smem {
-    float w1[kH * XS], w2[kH * XS], w3[4 * kH], b1[kH], b2[kH], b3[4];
-    float x[4][kH * XS];        // per wave: the encoding rows [point][column]
-};
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ int row_of(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
+// The decoder keeps its own body: hash_common.hpp's load_decoder + decoder_forward_half compile to other code (registers and scratch no worse,
+// DESIGN 4.7.7), and that code's results and time against this body have not been measured on a GPU.
 template <int D, int F, int SRC>
 __global__ void __launch_bounds__(256) hash_points_fused_kernel(const PointParams p) {
-    __shared__ Smem sm;
+    __shared__ DecoderSmem sm;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 31, half = lane >> 5;
     const int LF = p.d.levels * F;
     for (int e = tid; e < kH * XS; e += 256) {
@@ -340,7 +194,7 @@ __global__ void __launch_bounds__(256) hash_points_fused_kernel(const PointParam
         if (wv >= n_waves) continue;                            // wave-uniform; nothing below synchronises the workgroup
         const int64_t n0 = wv << 6, n_raw = n0 + lane;
         uint32_t t[3];
-        point_fixed<D>(p, n_raw < p.n ? n_raw : p.n - 1, t);    // a lane past the end decodes the last point; its output is not stored
+        point_fixed<D>(p.d, p.points, n_raw < p.n ? n_raw : p.n - 1, t);    // a lane past the end decodes the last point; its output is not stored
         encode_point<D, F, SRC, false, false>(p, t, n_raw, xrow);
         wave_sync();
 #pragma unroll 1
@@ -399,45 +253,7 @@ __global__ void __launch_bounds__(256) hash_points_fused_kernel(const PointParam
     }
 }
 
-// ---- host side ------------------------------------------------------------------------------------------------------------------------
-static int device_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-        else n = 256;
-    }
-    return n;
-}
-// workgroups of a fused launch: one per CU, a multiple of 8 (one slice of the point range per XCD)
-static int fused_grid(int64_t n_points) {
-    const int cap = device_cus() / 8 * 8 < 8 ? 8 : device_cus() / 8 * 8;
-    const int64_t groups = (n_points + 255) / 256, want = (groups + 7) / 8 * 8;
-    return (int)(want < cap ? want : cap);
-}
-static int point_blocks(int64_t n_points) {
-    const int64_t b = (n_points + 255) / 256;
-    return (int)(b > 2048 ? 2048 : b);                     // the cap of the crop route (hash_blocks)
-}
-
-// check_hash_desc of hash_grid.hip, then what the point entry points add: one field, 256 S_max < 2^30
-static int check_point_desc(const nic_hash_desc* d) {
-    if (!d) return NIC_E_NULL;
-    if (d->dim != 2 && d->dim != 3) return NIC_E_UNSUPPORTED;
-    if (d->features != 1 && d->features != 2 && d->features != 4 && d->features != 8) return NIC_E_UNSUPPORTED;
-    if (d->levels < 1 || d->levels > NIC_HASH_MAX_LEVELS) return NIC_E_ARG;
-    if (d->log2_table < 10 || d->log2_table > 24) return NIC_E_ARG;
-    if (d->S_max < 1 || d->flags != 0) return NIC_E_ARG;
-    for (int l = 0; l < d->levels; ++l)
-        if (d->resolution[l] < 1 || 2 * (int64_t)d->S_max * d->resolution[l] >= (int64_t(1) << 31)) return NIC_E_ARG;
-    if (d->num_crops < 1) return NIC_E_SHAPE;
-    for (int a = 0; a < d->dim; ++a)
-        if (d->extent[a] < 1 || d->extent[a] > d->S_max) return NIC_E_SHAPE;
-    if (d->num_crops != 1) return NIC_E_SHAPE;
-    if (256 * (int64_t)d->S_max >= (int64_t(1) << 30)) return NIC_E_ARG;
-    return NIC_OK;
-}
-
+// ---- host side (the descriptor checks and grid rules are hash_common.hpp's) -------------------------------------------------------------
 // the table source into the parameters; NIC_E_NULL / NIC_E_ARG in the order of the _u8 / _bits siblings (null, bit depth, alignment)
 static int check_source(const nic_hash_source* src) {
     if (!src || !src->data) return NIC_E_NULL;
@@ -451,8 +267,7 @@ static int set_source(PointParams& p, const nic_hash_source* src) {
     }
     if (src->kind != NIC_HASH_SRC_U8 && src->kind != NIC_HASH_SRC_BITS) return NIC_E_ARG;
     if (src->num_bits < 1 || src->num_bits > 8) return NIC_E_ARG;
-    p.q_scale = (float)((1 << src->num_bits) - 1);
-    p.q_bias = (float)(1 << (src->num_bits - 1));
+    set_dequant(p, src->num_bits);
     if (src->kind == NIC_HASH_SRC_U8) {
         p.stored = (const uint8_t*)src->data;
         return NIC_OK;
@@ -512,25 +327,13 @@ int nic_hash_encode_points(const nic_hash_desc* desc, const nic_hash_source* src
     PointParams p{};
     p.d = *desc; p.points = points; p.n = n_points; p.out = out;
     if ((rc = set_source(p, src)) != NIC_OK) return rc;
-    bool noisy = false;
-    if (quant) {
-        if (src->kind != NIC_HASH_SRC_F32) return NIC_E_ARG;            // noise belongs to training, which reads the fp32 table
-        if (quant->num_bits < 1 || quant->num_bits > 8 || quant->sample_base < 0) return NIC_E_ARG;
-        if (quant->noise_mode == NIC_NOISE_TENSOR) return NIC_E_UNSUPPORTED;
-        if (quant->noise_mode != NIC_NOISE_NONE && quant->noise_mode != NIC_NOISE_KERNEL) return NIC_E_ARG;
-        if (quant->noise_mode == NIC_NOISE_KERNEL) {
-            noisy = true;
-            p.noise.mode = NIC_NOISE_KERNEL;
-            p.noise.k0 = (uint32_t)quant->noise_seed; p.noise.k1 = (uint32_t)(quant->noise_seed >> 32);
-            p.noise.off_lo = (uint32_t)quant->noise_offset; p.noise.off_hi = (uint32_t)(quant->noise_offset >> 32);
-            p.noise.scale = ldexpf(1.0f, -quant->num_bits);
-            p.sample_base = (uint64_t)quant->sample_base;
-        }
-    }
+    if (quant && src->kind != NIC_HASH_SRC_F32) return NIC_E_ARG;        // noise belongs to training, which reads the fp32 table
+    if ((rc = set_noise(quant, true, p.noise, p.sample_base)) != NIC_OK) return rc;
+    const bool noisy = p.noise.mode == NIC_NOISE_KERNEL;
     if (n_points < 0) return NIC_E_ARG;
     if (n_points == 0) return NIC_OK;
-    if (noisy) return launch_d<PK_FWD_NOISY, PSRC_F32>(p, point_blocks(n_points), stream);
-    return launch_src<PK_FWD>(p, src->kind, point_blocks(n_points), stream);
+    if (noisy) return launch_d<PK_FWD_NOISY, PSRC_F32>(p, strided_grid((n_points + 63) >> 6), stream);
+    return launch_src<PK_FWD>(p, src->kind, strided_grid((n_points + 63) >> 6), stream);
 }
 
 int nic_hash_encode_points_backward(const nic_hash_desc* desc, const float* points, int64_t n_points, const float* dx, float* table_grad, void* stream) {
@@ -541,7 +344,7 @@ int nic_hash_encode_points_backward(const nic_hash_desc* desc, const float* poin
     if (n_points == 0) return NIC_OK;
     PointParams p{};
     p.d = *desc; p.points = points; p.n = n_points; p.dx = dx; p.grad = table_grad;
-    return launch_d<PK_BWD, PSRC_F32>(p, point_blocks(n_points), stream);
+    return launch_d<PK_BWD, PSRC_F32>(p, strided_grid((n_points + 63) >> 6), stream);
 }
 
 int nic_hash_fused_forward_points(const nic_hash_desc* desc, const nic_hash_source* src, const float* points, int64_t n_points, const nic_mlp* mlp,
@@ -560,7 +363,7 @@ int nic_hash_fused_forward_points(const nic_hash_desc* desc, const nic_hash_sour
     if (n_points < 0) return NIC_E_ARG;
     if (n_points == 0) return NIC_OK;
     p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
-    return launch_src<PK_FUSED>(p, src->kind, fused_grid(n_points), stream);
+    return launch_src<PK_FUSED>(p, src->kind, persistent_grid((n_points + 63) >> 6), stream);
 }
 
 }  // extern "C"

@@ -9,18 +9,12 @@
 //   fused     hash_fused_kernel's training mode with hash_points_fused_kernel's sample source: a wave gathers the rows of 64 consecutive
 //             (ordered) points into its LDS tile, runs the decoder forward and backward on the fp32 matrix pipe, leaves d loss / d row in the
 //             tile and scatters it with the run sums keyed on the base vertex; one record per workgroup, reduced in a fixed order by
-//             hash_fused_reduce_kernel (linked from hash_fused.hip) with the optimiser tail riding on it.
+//             hash_fused_reduce_kernel (hash_fused.hip) with the optimiser tail riding on it.
 //
 // Every index read from `order` is clamped to [0, n_points - 1]: a buffer that is no permutation gives the sum over the rows it names.
 #include "hash_common.hpp"
 
 namespace nic {
-namespace hfused {
-// defined in hash_fused.hip; reads records of hcommon::RecLayout (the same layout as its own)
-__global__ void __launch_bounds__(256) hash_fused_reduce_kernel(const float* partials, int n_rec, int lf, nic_mlp_grads g, float* loss, float loss_mul,
-                                                                int add_grads, int add_loss, const StepTail tl);
-}  // namespace hfused
-
 namespace hptrain {
 using namespace hcommon;
 
@@ -146,23 +140,7 @@ __global__ void __launch_bounds__(256) hash_points_fused_train_kernel(const TPar
     write_record<KT>(sm, A, LF, p.partials + (int64_t)blockIdx.x * RecLayout(LF).rec, tid);
 }
 
-// ---- host side ------------------------------------------------------------------------------------------------------------------------
-static int fused_grid(int64_t n_points) {
-    const int64_t groups = (n_points + 255) / 256, want = (groups + 7) / 8 * 8;
-    return (int)(want < wg_cap() ? want : wg_cap());
-}
-static int point_blocks(int64_t n_points) {
-    const int64_t b = (n_points + 255) / 256;
-    return (int)(b > 2048 ? 2048 : b);                     // the cap of the other point launches
-}
-
-// the descriptor checks of the point entries, their only copy (hash_points.hip): the unordered scatter with no points decides every descriptor
-// error on the host, in the siblings' order, and launches nothing
-static int check_point_desc(const nic_hash_desc* d) {
-    static float dummy;
-    return nic_hash_encode_points_backward(d, &dummy, 0, &dummy, &dummy, nullptr);
-}
-
+// ---- host side (the checks and grid rules are hash_common.hpp's) -----------------------------------------------------------------------------
 enum TKernel { TK_KEYS, TK_BWD, TK_TRAIN, TK_TRAIN_NOISY };
 
 template <int K, int D, int F>
@@ -196,10 +174,6 @@ static int launch(const TParams& p, int nb, void* stream) {
     return (int)hipGetLastError();
 }
 
-struct KernelEndDrop {        // a training entry point consumes the parked nic_mark_kernel_end event on every return
-    ~KernelEndDrop() { kernel_end_drop(); }
-};
-
 }  // namespace hptrain
 }  // namespace nic
 
@@ -220,7 +194,7 @@ int nic_hash_point_keys(const nic_hash_desc* desc, const float* points, int64_t 
     for (uint32_t top = 256u * (uint32_t)desc->S_max - 1u; top; top >>= 1) ++b;
     const int k = desc->dim == 2 ? 31 : 21;
     p.key_shift = b > k ? b - k : 0;
-    return launch<TK_KEYS>(p, point_blocks(n_points), stream);
+    return launch<TK_KEYS>(p, strided_grid((n_points + 63) >> 6), stream);
 }
 
 int nic_hash_encode_points_backward_ordered(const nic_hash_desc* desc, const float* points, int64_t n_points, const float* dx, const int32_t* order,
@@ -233,7 +207,7 @@ int nic_hash_encode_points_backward_ordered(const nic_hash_desc* desc, const flo
     if (n_points == 0) return NIC_OK;
     TParams p{};
     p.d = *desc; p.points = points; p.n = n_points; p.dx = dx; p.order = order; p.grad = table_grad;
-    return launch<TK_BWD>(p, point_blocks(n_points), stream);
+    return launch<TK_BWD>(p, strided_grid((n_points + 63) >> 6), stream);
 }
 
 size_t nic_hash_fused_points_workspace_bytes(const nic_hash_desc* desc, const nic_mlp* mlp) {
@@ -258,18 +232,7 @@ int nic_hash_fused_forward_backward_points(const nic_hash_desc* desc, const nic_
     p.d = *desc; p.points = points; p.n = n_points; p.order = order; p.table = table; p.target = target; p.grad = table_grad; p.y = y;
     p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
     p.noise.mode = NIC_NOISE_NONE;
-    if (quant) {
-        if (quant->num_bits < 1 || quant->num_bits > 8 || quant->sample_base < 0) return NIC_E_ARG;
-        if (quant->noise_mode == NIC_NOISE_TENSOR) return NIC_E_UNSUPPORTED;
-        if (quant->noise_mode != NIC_NOISE_NONE && quant->noise_mode != NIC_NOISE_KERNEL) return NIC_E_ARG;
-        if (quant->noise_mode == NIC_NOISE_KERNEL) {
-            p.noise.mode = NIC_NOISE_KERNEL;
-            p.noise.k0 = (uint32_t)quant->noise_seed; p.noise.k1 = (uint32_t)(quant->noise_seed >> 32);
-            p.noise.off_lo = (uint32_t)quant->noise_offset; p.noise.off_hi = (uint32_t)(quant->noise_offset >> 32);
-            p.noise.scale = ldexpf(1.0f, -quant->num_bits);
-            p.sample_base = (uint64_t)quant->sample_base;
-        }
-    }
+    if ((rc = set_noise(quant, true, p.noise, p.sample_base)) != NIC_OK) return rc;
     if (n_points < 0 || (order && n_points >= (int64_t(1) << 31))) return NIC_E_ARG;
     const int lf = desc->levels * desc->features;
     const RecLayout rl(lf);
@@ -295,7 +258,7 @@ int nic_hash_fused_forward_backward_points(const nic_hash_desc* desc, const nic_
         tl.reduce_blocks = reduce_blocks;
     }
     if (n_points == 0) return NIC_OK;                                 // nothing to launch: *loss and every gradient stay as they are
-    const int grid = fused_grid(n_points);
+    const int grid = persistent_grid((n_points + 63) >> 6);
     const float loss_mul = (float)((double)loss_scale / (3.0 * (double)n_points));
     p.dscale = 2.0f * loss_mul;
     p.partials = (float*)workspace;

@@ -1,0 +1,73 @@
+"""The hash-grid translation units share ONE copy of their helpers (csrc/hash_common.hpp): every helper the five sources
+use in common is defined in the header and nowhere else, and every source includes it.  Read from the sources as text; nothing is compiled."""
+import glob
+import os
+import re
+
+from neural_image_compression_v2_amd import _build
+
+HEADER = "hash_common.hpp"
+UNITS = ["hash_grid.hip", "hash_fused.hip", "hash_points.hip", "hash_points_train.hip", "hash_mixed.hip"]
+
+FUNCTIONS = ["hash_level_dense", "hash_index", "hash_level_entries", "hash_level_dwords", "hash_bits_tight", "load_row", "store_row", "load_row_u8",
+             "load_row_bits", "corner_weight", "patch_sample", "level_cell", "sample_coords", "point_fixed", "point_cell", "wave_sync", "mfma", "row_of",
+             "wgrad_mfma", "put_tile", "half_sum", "device_cus", "wg_cap", "check_hash_desc", "check_point_desc", "count_patches", "set_dequant", "set_noise"]
+STRUCTS = ["PatchSample", "RecLayout"]
+
+# a definition opens its line with the specifiers of one (a call never does): [static] [__host__] [__device__] [inline | __forceinline__ |
+# constexpr], then the return type, then the name and its parameter list
+_SPEC = r"(?:static|__host__|__device__|inline|__forceinline__|constexpr)"
+
+
+def _function_re(name):
+    return re.compile(rf"^\s*(?:{_SPEC}\s+)+[\w:<>,&\*\s]*?\b{name}\s*\(")
+
+
+def _struct_re(name):
+    return re.compile(rf"^\s*struct\s+{name}\b")
+
+
+def _sources():
+    paths = sorted(glob.glob(os.path.join(_build.CSRC, "hash_*")))
+    out = {}
+    for p in paths:
+        with open(p) as f:
+            out[os.path.basename(p)] = f.read().splitlines()
+    return out
+
+
+def _definitions(pattern, sources):
+    return [(name, i + 1) for name, lines in sources.items() for i, ln in enumerate(lines) if pattern.match(ln)]
+
+
+def test_the_sources_are_the_ones_the_build_compiles():
+    src = _sources()
+    assert sorted(src) == sorted(UNITS + [HEADER])
+    assert all(u in _build.SOURCES for u in UNITS) and HEADER in _build.HEADERS
+
+
+def test_every_unit_includes_the_header():
+    src = _sources()
+    for u in UNITS:
+        assert any(re.match(r'\s*#include\s+"hash_common\.hpp"', ln) for ln in src[u]), u
+
+
+def test_every_shared_helper_is_defined_once_in_the_header():
+    src = _sources()
+    for name in FUNCTIONS + STRUCTS:
+        pattern = _struct_re(name) if name in STRUCTS else _function_re(name)
+        found = _definitions(pattern, src)
+        assert len(found) == 1 and found[0][0] == HEADER, (name, found)
+
+
+def test_the_definition_pattern_sees_a_definition_and_not_a_call():
+    assert _function_re("mfma").match("__device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) { return 0; }")
+    assert not _function_re("mfma").match("__device__ __forceinline__ void wgrad_mfma(const float* P) {")
+    assert not _function_re("mfma").match("            a1[0] = mfma(sm.w1[j * XS + 2 * k + half], b, a1[0]);")
+    assert _function_re("check_hash_desc").match("static int check_hash_desc(const nic_hash_desc* d) {")
+    assert _function_re("check_hash_desc").match("inline int check_hash_desc(const nic_hash_desc* d) {")
+    assert not _function_re("check_hash_desc").match("    const int rc = check_hash_desc(desc);")
+    assert _function_re("hash_index").match("__host__ __device__ inline uint32_t hash_index(bool dense, uint32_t R) {")
+    assert not _function_re("hash_index").match("    return (int)hash_index(hash_level_dense(desc->dim, R, desc->log2_table), (uint32_t)R);")
+    assert _function_re("patch_sample").match("__device__ __forceinline__ PatchSample<D> patch_sample(const nic_hash_desc& d, int64_t wv) {")
+    assert _struct_re("PatchSample").match("struct PatchSample {") and not _struct_re("PatchSample").match("    PatchSample<D> s;")
