@@ -668,6 +668,45 @@ int nic_hash_fused_forward_backward_levels(const nic_hash_desc *desc, const nic_
                                            const nic_mlp_grads *mlp_grads, float *loss, float *y, int flags, void *workspace,
                                            size_t workspace_bytes, const nic_step_tail *tail, void *stream);
 
+/* ---- the hash-grid field at points with a level of detail PER POINT (hashgrid.py, HashGridField.query / train_points(lod=), decode_mip,
+ *      fit_mips; csrc/lod_points.hip).  What a texture sampler has: lambda fades the levels finer than a query's footprint out,
+ *      before the decoder.
+ *      - lambda of point n = (lod ? lod[n] : 0) + lod_uniform in fp32; NaN becomes 0; the sum is then clamped to [0, 32].  lod = [n_points]
+ *        fp32 (device; the host never reads it) or NULL; with an `order` it is read at order[n] like the point.
+ *      - weight of level l: a_l = min(max((fade[l] - lambda) + 1.0f, 0), 1) in fp32, in exactly this order (one subtract, one add: nothing
+ *        contracts).  Level l is fully on up to lambda = fade[l] and off from fade[l] + 1.  fade[l] is the caller's; hashgrid.hash_lod_fade gives
+ *        max(0, log2(S_max / R_l)) (float64, rounded once), the level's cell size in octaves of samples: every weight is exactly 1 at lambda = 0.
+ *      - column l F + f of the row is fl(a_l r), r the value nic_hash_encode_points produces (the blend, plus the noise of `quant`): at
+ *        a_l = 1 the row is that entry's bit for bit.  A level of weight 0 contributes exactly 0 - no noise either - and its table is not read;
+ *        a level no lane of a wave weighs above 0 costs that wave no gather at all.
+ *      - backward: straight-through, dx of level l multiplied by a_l (fl(a_l dx) goes where nic_hash_encode_points_backward(_ordered) sends dx);
+ *        a point with a_l = 0 issues no atomic for level l, a level nobody weighs is not touched.
+ *      Everything else - fixed-point positions, cells, entry index, the three sources, the noise keys (sample_base + n, or + order[n] in the
+ *      fused step), the clamped `order` - is that of the entries without _lod, argument for argument:
+ *      nic_hash_encode_points_lod = nic_hash_encode_points; nic_hash_encode_points_backward_lod = nic_hash_encode_points_backward_ordered
+ *      (order may be NULL); nic_hash_fused_forward_points_lod = nic_hash_fused_forward_points; nic_hash_fused_forward_backward_points_lod =
+ *      nic_hash_fused_forward_backward_points: two launches, records, tail, flags and workspace exactly as there - the workspace query is
+ *      nic_hash_fused_points_workspace_bytes.  A bit depth per level (nic_hash_level_bits) is not served by these entries.
+ *      Host checks, all before any GPU work, in the siblings' order and with their codes (descriptor, null pointers, arguments); on top of
+ *      them lodp == NULL is NIC_E_NULL (with the other pointers), and right after the pointers a fade[l] (l < levels) that is not finite or is
+ *      negative, a lod_uniform that is not finite, or reserved != 0 is NIC_E_ARG.  fade entries past desc->levels are ignored. */
+typedef struct nic_hash_lod {
+    float fade[NIC_HASH_MAX_LEVELS];   /* finite, >= 0 */
+    float lod_uniform;                 /* finite; added to every point's lod */
+    int32_t reserved;                  /* 0 */
+} nic_hash_lod;
+int nic_hash_encode_points_lod(const nic_hash_desc *desc, const nic_hash_lod *lodp, const nic_hash_source *src, const nic_hash_quant *quant,
+                               const float *points, const float *lod, int64_t n_points, float *out, void *stream);
+int nic_hash_encode_points_backward_lod(const nic_hash_desc *desc, const nic_hash_lod *lodp, const float *points, const float *lod,
+                                        int64_t n_points, const float *dx, const int32_t *order, float *table_grad, void *stream);
+int nic_hash_fused_forward_points_lod(const nic_hash_desc *desc, const nic_hash_lod *lodp, const nic_hash_source *src, const float *points,
+                                      const float *lod, int64_t n_points, const nic_mlp *mlp, float *y, void *stream);
+int nic_hash_fused_forward_backward_points_lod(const nic_hash_desc *desc, const nic_hash_lod *lodp, const nic_hash_quant *quant,
+                                               const float *table, const float *points, const float *lod, int64_t n_points,
+                                               const int32_t *order, const nic_mlp *mlp, const float *target, float loss_scale,
+                                               float *table_grad, const nic_mlp_grads *mlp_grads, float *loss, float *y, int flags,
+                                               void *workspace, size_t workspace_bytes, const nic_step_tail *tail, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

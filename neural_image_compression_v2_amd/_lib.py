@@ -130,6 +130,11 @@ class NicHashLevelBits(ctypes.Structure):
     _fields_ = [("bits", ctypes.c_int32 * NIC_HASH_MAX_LEVELS)]
 
 
+class NicHashLod(ctypes.Structure):
+    """struct nic_hash_lod (include/nicv2_hip.h): the fade start of every level and the launch-wide level of detail of a point launch (hashgrid.py)"""
+    _fields_ = [("fade", ctypes.c_float * NIC_HASH_MAX_LEVELS), ("lod_uniform", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
 _P, _I, _L, _F, _SZ, _DBL = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t, ctypes.c_double
 _D = ctypes.POINTER(NicPathDesc)
 _M = ctypes.POINTER(NicMlp)
@@ -216,6 +221,13 @@ SIGNATURES = {
                                            _P, _P]),
     "nic_hash_fused_forward_backward_levels": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashLevelBits), ctypes.POINTER(NicHashQuant), _P, _P, _P,
                                                     _L, _P, _M, _P, _F, _P, _G, _P, _P, _I, _P, _SZ, ctypes.POINTER(NicStepTail), _P]),
+    "nic_hash_encode_points_lod": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashLod), ctypes.POINTER(NicHashSource),
+                                        ctypes.POINTER(NicHashQuant), _P, _P, _L, _P, _P]),
+    "nic_hash_encode_points_backward_lod": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashLod), _P, _P, _L, _P, _P, _P, _P]),
+    "nic_hash_fused_forward_points_lod": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashLod), ctypes.POINTER(NicHashSource), _P, _P, _L, _M,
+                                               _P, _P]),
+    "nic_hash_fused_forward_backward_points_lod": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashLod), ctypes.POINTER(NicHashQuant), _P, _P,
+                                                        _P, _L, _P, _M, _P, _F, _P, _G, _P, _P, _I, _P, _SZ, ctypes.POINTER(NicStepTail), _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -1,5 +1,5 @@
-// What the hash-grid kernels share, the one copy of it: all five translation units (hash_grid.hip, hash_fused.hip, hash_points.hip,
-// hash_points_train.hip, hash_mixed.hip) include this header and keep only their kernels, parameter structs and launch tables.
+// What the hash-grid kernels share, the one copy of it: all six translation units (hash_grid.hip, hash_fused.hip, hash_points.hip,
+// hash_points_train.hip, hash_mixed.hip, lod_points.hip) include this header and keep only their kernels, parameter structs and launch tables.
 // The index helpers, the fp32, uint8 and packed row loaders, the cell of a lattice sample (2 S_max arithmetic) and the fixed-point position and
 // cell of a point or of a lattice sample (include/nicv2_hip.h, nic_hash_encode_points), the level loops of the encode (row into an LDS tile) and
 // of the scatter (run sums keyed on the base vertex), the ColorDecoder(L F, 64, 3) forward + backward on v_mfma_f32_32x32x2_f32 with its

@@ -51,10 +51,18 @@ clamped fixed-point position, ``hash_point_order`` the int32 permutation that so
 that order sums the neighbouring lanes of one cell before the gradient atomics, which random batches otherwise lose.
 ``train_points(..., order="cell" | tensor, fused=True)`` opt into the ordered scatter (``nic_hash_encode_points_backward_ordered``) and the fused
 step at points (``nic_hash_fused_forward_backward_points``: two launches, the optimiser on the reduction); the defaults are the layer-wise,
-unordered call unchanged.  ``fit_points`` fits a fixed (point, colour) set: the order is computed once, every epoch walks it in compact chunks."""
+unordered call unchanged.  ``fit_points`` fits a fixed (point, colour) set: the order is computed once, every epoch walks it in compact chunks.
+
+A level of detail per point (include/nicv2_hip.h, nic_hash_lod; csrc/lod_points.hip): lambda = (lod[n] or 0) + lod_uniform, NaN ->
+0, clamped to [0, 32]; level l is weighed by a_l = min(max((fade[l] - lambda) + 1, 0), 1) before the decoder, ``hash_lod_fade`` gives the
+default fade start max(0, log2(S_max / R_l)), ``HashGridField(..., lod_fade=)`` another.  A level of weight 0 is not gathered, takes no noise
+and no gradient; at weight 1 the columns are the plain route's bit for bit.  ``query`` / ``train_points`` / ``fit_points`` take ``lod=`` (a
+float, or one value per point; None makes the launches made before), ``resample(size, lod="auto")`` derives it from the size,
+``decode_mip(m)`` decodes mip m and ``fit_mips`` fits the box-filtered mip chain with one table and one decoder."""
 from __future__ import annotations
 
 import ctypes
+import functools
 import itertools
 import math
 from dataclasses import dataclass
@@ -617,6 +625,165 @@ def hash_fused_forward_backward_points(geo: HashGeometry, table: torch.Tensor, p
     return loss, y
 
 
+@functools.lru_cache(maxsize=64)
+def hash_lod_fade(geo: HashGeometry) -> Tuple[float, ...]:
+    """the default fade start of every level (nic_hash_lod): max(0, log2(S_max / R_l)) in float64, rounded once to fp32 - the level's cell size
+    in octaves of samples, so a level whose cells are no larger than a sample (R_l >= S_max) starts to fade at once"""
+    return tuple(ctypes.c_float(max(0.0, math.log2(geo.s_max / int(r)))).value for r in geo.resolutions)
+
+
+def _check_fade(levels: int, fade) -> Tuple[float, ...]:
+    """a fade start per level: a sequence of ``levels`` finite values >= 0, as a tuple of fp32 values (anything else: ValueError)"""
+    if isinstance(fade, (str, bytes)) or not hasattr(fade, "__len__") or not hasattr(fade, "__iter__"):
+        raise ValueError(f"lod_fade is a sequence of {levels} finite values >= 0, got {fade!r}")
+    try:
+        out = tuple(ctypes.c_float(float(v)).value for v in fade)
+    except (TypeError, ValueError):
+        raise ValueError(f"lod_fade is a sequence of {levels} finite values >= 0, got {fade!r}") from None
+    if len(out) != int(levels):
+        raise ValueError(f"{len(out)} fade starts for {levels} levels")
+    if any(not math.isfinite(v) or v < 0 for v in out):
+        raise ValueError(f"lod_fade {out}: each finite and >= 0")
+    return out
+
+
+def _lod_struct(geo: HashGeometry, fade, lod_uniform: float) -> "_lib.NicHashLod":
+    lp = _lib.NicHashLod()
+    lp.fade[:geo.levels] = hash_lod_fade(geo) if fade is None else _check_fade(geo.levels, fade)
+    if not math.isfinite(float(lod_uniform)):
+        raise ValueError(f"lod_uniform {lod_uniform!r} is not finite")
+    lp.lod_uniform = float(lod_uniform)
+    return lp
+
+
+def _check_lod(lod: Optional[torch.Tensor], n: int, device) -> Optional[torch.Tensor]:
+    """None, or a level of detail per point: fp32 [N] on the points' device, contiguous; the values are the kernel's business (it clamps)"""
+    if lod is None:
+        return None
+    lod = _lib.require_cuda_f32(lod.detach() if isinstance(lod, torch.Tensor) else lod, "lod")
+    if tuple(lod.shape) != (n,):
+        raise ValueError(f"lod must be [{n}], one value per point, got {tuple(lod.shape)}")
+    if lod.device != device:
+        raise ValueError(f"lod lives on {lod.device}, the points on {device}")
+    return lod
+
+
+@fused._on_tensor_device
+def hash_encode_points_lod(geo: HashGeometry, data: torch.Tensor, points: torch.Tensor, lod: Optional[torch.Tensor] = None, lod_uniform: float = 0.0,
+                           fade=None, kind: str = "f32", num_bits: Optional[int] = None, quant=None) -> torch.Tensor:
+    """``hash_encode_points`` with a level of detail per point (nic_hash_encode_points_lod): lambda = (``lod`` [N] or 0) + ``lod_uniform``, NaN ->
+    0, clamped to [0, 32]; level l is weighed by min(max((fade[l] - lambda) + 1, 0), 1), ``fade`` = None for ``hash_lod_fade(geo)``.  At weight 1
+    the columns are ``hash_encode_points``' bit for bit, at weight 0 they are 0 and the level's table is not read."""
+    src, data = _point_source(geo, data, kind, num_bits)
+    pts = _check_points(geo, points)
+    lod = _check_lod(lod, pts.shape[0], pts.device)
+    d, lp = _point_desc(geo), _lod_struct(geo, fade, lod_uniform)
+    out = torch.empty(pts.shape[0], geo.width, dtype=torch.float32, device=data.device)
+    q = None
+    if quant is not None:
+        if kind != "f32":
+            raise ValueError("noise belongs to training, which reads the fp32 table")
+        bits, seed, offset, base = quant
+        q = _lib.NicHashQuant(int(bits), _lib.NIC_NOISE_KERNEL, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(base))
+    if pts.shape[0] == 0:
+        return out
+    _lib.check(_lib.load().nic_hash_encode_points_lod(ctypes.byref(d), ctypes.byref(lp), ctypes.byref(src), None if q is None else ctypes.byref(q),
+                                                      _lib.ptr(pts), _lib.ptr(lod), pts.shape[0], _lib.ptr(out), _lib.stream_ptr(data.device)),
+               "nic_hash_encode_points_lod")
+    return out
+
+
+@fused._on_tensor_device
+def hash_encode_points_backward_lod(geo: HashGeometry, points: torch.Tensor, dx: torch.Tensor, table_grad: torch.Tensor,
+                                    lod: Optional[torch.Tensor] = None, lod_uniform: float = 0.0, fade=None,
+                                    order: Optional[torch.Tensor] = None) -> None:
+    """``hash_encode_points_backward`` of ``hash_encode_points_lod`` (nic_hash_encode_points_backward_lod): ADDS the gradient of the table for
+    ``dx`` weighed per point and level into ``table_grad``; a level of weight 0 takes no atomic.  ``order`` as there (``lod`` is read at
+    ``order[n]`` like the point)."""
+    g = _check_table(geo, table_grad, "table_grad")
+    if g is not table_grad:
+        raise ValueError("table_grad must be contiguous: the kernel adds into it in place")
+    pts = _check_points(geo, points)
+    dx = _lib.require_cuda_f32(dx, "dx")
+    if tuple(dx.shape) != (pts.shape[0], geo.width):
+        raise ValueError(f"dx must be [{pts.shape[0]}, {geo.width}], got {tuple(dx.shape)}")
+    lod = _check_lod(lod, pts.shape[0], pts.device)
+    d, lp = _point_desc(geo), _lod_struct(geo, fade, lod_uniform)
+    if order is not None:
+        order = _check_order(order, pts.shape[0], pts.device)
+    if pts.shape[0] == 0:
+        return
+    _lib.check(_lib.load().nic_hash_encode_points_backward_lod(ctypes.byref(d), ctypes.byref(lp), _lib.ptr(pts), _lib.ptr(lod), pts.shape[0],
+                                                               _lib.ptr(dx), _lib.ptr(order), _lib.ptr(g), _lib.stream_ptr(g.device)),
+               "nic_hash_encode_points_backward_lod")
+
+
+@fused._on_tensor_device
+def hash_fused_forward_points_lod(geo: HashGeometry, data: torch.Tensor, points: torch.Tensor, params: Sequence[torch.Tensor],
+                                  lod: Optional[torch.Tensor] = None, lod_uniform: float = 0.0, fade=None, kind: str = "f32",
+                                  num_bits: Optional[int] = None) -> torch.Tensor:
+    """[N, 3] = ColorDecoder(hash_encode_points_lod(...)) in one launch (nic_hash_fused_forward_points_lod)"""
+    src, data = _point_source(geo, data, kind, num_bits)
+    params = _check_fused_decoder(geo, [q.detach() for q in params])
+    pts = _check_points(geo, points)
+    lod = _check_lod(lod, pts.shape[0], pts.device)
+    d, lp, m = _point_desc(geo), _lod_struct(geo, fade, lod_uniform), fused._mlp_struct(params)
+    y = torch.empty(pts.shape[0], 3, dtype=torch.float32, device=data.device)
+    if pts.shape[0] == 0:
+        return y
+    _lib.check(_lib.load().nic_hash_fused_forward_points_lod(ctypes.byref(d), ctypes.byref(lp), ctypes.byref(src), _lib.ptr(pts), _lib.ptr(lod),
+                                                             pts.shape[0], ctypes.byref(m), _lib.ptr(y), _lib.stream_ptr(data.device)),
+               "nic_hash_fused_forward_points_lod")
+    return y
+
+
+@fused._on_tensor_device
+def hash_fused_forward_backward_points_lod(geo: HashGeometry, table: torch.Tensor, points: torch.Tensor, params: Sequence[torch.Tensor],
+                                           target: torch.Tensor, mlp_grads: Sequence[torch.Tensor], lod: Optional[torch.Tensor] = None,
+                                           lod_uniform: float = 0.0, fade=None, table_grad: Optional[torch.Tensor] = None,
+                                           order: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None, loss_scale: float = 1.0,
+                                           want_y: bool = False, quant=None, add_grads: bool = False, add_loss: bool = False, tail=None):
+    """``hash_fused_forward_backward_points`` with a level of detail per point (nic_hash_fused_forward_backward_points_lod): the same two
+    launches, the row weighed as in ``hash_encode_points_lod`` and its gradient weighed again before the scatter.  Returns (loss [1], y or None)."""
+    t = _check_table(geo, table.detach())
+    params = _check_fused_decoder(geo, [q.detach() for q in params])
+    pts = _check_points(geo, points)
+    n = pts.shape[0]
+    if n < 1:
+        raise ValueError("no points")
+    target = _lib.require_cuda_f32(target, "target")
+    if tuple(target.shape) != (n, 3):
+        raise ValueError(f"target must be [{n}, 3], got {tuple(target.shape)}")
+    lod = _check_lod(lod, n, pts.device)
+    if order is not None:
+        order = _check_order(order, n, pts.device)
+    if table_grad is not None:
+        g = _check_table(geo, table_grad, "table_grad")
+        if g is not table_grad:
+            raise ValueError("table_grad must be contiguous: the kernel adds into it in place")
+    if len(mlp_grads) != 6 or any(not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.shape == q.shape) for g, q in zip(mlp_grads, params)):
+        raise ValueError("mlp_grads: six contiguous fp32 device buffers shaped like the decoder's parameters")
+    d, lp = _point_desc(geo), _lod_struct(geo, fade, lod_uniform)
+    loss = torch.empty(1, dtype=torch.float32, device=t.device) if loss is None else loss
+    y = torch.empty(n, 3, dtype=torch.float32, device=t.device) if want_y else None
+    lib = _lib.load()
+    m, gs = fused._mlp_struct(params), fused._grads_struct(list(mlp_grads))
+    q = None
+    if quant is not None:
+        bits, seed, offset, base = quant
+        q = _lib.NicHashQuant(int(bits), _lib.NIC_NOISE_KERNEL, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(base))
+    ws = _lib.workspace(t.device, int(lib.nic_hash_fused_points_workspace_bytes(ctypes.byref(d), ctypes.byref(m))))
+    flags = (_lib.NIC_HASH_FUSED_ADD_GRADS if add_grads else 0) | (_lib.NIC_HASH_FUSED_ADD_LOSS if add_loss else 0)
+    _lib.check(lib.nic_hash_fused_forward_backward_points_lod(ctypes.byref(d), ctypes.byref(lp), None if q is None else ctypes.byref(q), _lib.ptr(t),
+                                                              _lib.ptr(pts), _lib.ptr(lod), n, _lib.ptr(order), ctypes.byref(m), _lib.ptr(target),
+                                                              float(loss_scale), _lib.ptr(table_grad), ctypes.byref(gs), _lib.ptr(loss), _lib.ptr(y),
+                                                              flags, _lib.ptr(ws), ws.numel(), None if tail is None else ctypes.byref(tail.struct),
+                                                              _lib.stream_ptr(t.device)), "nic_hash_fused_forward_backward_points_lod")
+    if tail is not None:
+        tail.commit()
+    return loss, y
+
+
 @fused._on_tensor_device
 def hash_pack_bits_levels(geo: HashGeometry, table: torch.Tensor, level_bits, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """format /2 of an fp32 [L, T, F] table (nic_hash_pack_bits_levels): ``hash_pack_bits`` with ``level_bits[l]`` bits per value inside level
@@ -832,10 +999,12 @@ class HashGridField:
     ``noise_seed``; a sequence of ``levels`` depths = a bit depth per level (``level_bits`` holds the tuple, ``num_bits`` stays None).  ``fused``: ``train_step`` / ``fit`` / ``decode`` on the fused encode + decoder kernels where they exist (``route``)."""
 
     level_bits: Optional[Tuple[int, ...]] = None     # a bit depth per level (None: an int ``num_bits`` field, or no codec)
+    _lod_fade: Optional[Tuple[float, ...]] = None    # the fade start per level given at construction (None: ``hash_lod_fade`` of the geometry)
 
     def __init__(self, field_size: Union[int, Sequence[int]], levels: int = 16, features: int = 2, log2_table: int = 19, base_resolution: float = 16,
                  finest_resolution: Optional[float] = None, hidden: int = 64, n_linear: int = 3, device=None, seed: Optional[int] = None,
-                 num_bits: Union[None, int, Sequence[int]] = None, noise_seed: int = 7, fused: bool = False):
+                 num_bits: Union[None, int, Sequence[int]] = None, noise_seed: int = 7, fused: bool = False,
+                 lod_fade: Optional[Sequence[float]] = None):
         level_bits = None
         if _is_level_bits(num_bits):
             level_bits, num_bits = _check_level_bits(levels, num_bits), None
@@ -847,6 +1016,7 @@ class HashGridField:
             raise RuntimeError("HashGridField needs a HIP device: there is no CPU implementation of this path")
         n_max = max(self.field_size) if finest_resolution is None else finest_resolution
         self.geo = HashGeometry(self.field_size, tuple(level_resolutions(levels, base_resolution, n_max)), features, log2_table)
+        self._lod_fade = None if lod_fade is None else _check_fade(self.geo.levels, lod_fade)
         if seed is not None:
             torch.manual_seed(seed)
         self.table = torch.empty(self.geo.table_shape(), dtype=torch.float32, device=self.device).uniform_(-1e-4, 1e-4).requires_grad_(True)
@@ -867,6 +1037,26 @@ class HashGridField:
             self.optimizer.set_clamp([self.table], *models._q_range(self.num_bits))
         if self.level_bits is not None:              # the optimiser's one clamp is the widest range; _clamp_levels tightens the rest
             self.optimizer.set_clamp([self.table], *models._q_range(max(self.level_bits)))
+
+    @property
+    def lod_fade(self) -> Tuple[float, ...]:
+        """the fade start of every level for ``lod=`` calls: the constructor's ``lod_fade``, else ``hash_lod_fade(geo)``"""
+        return self._lod_fade if self._lod_fade is not None else hash_lod_fade(self.geo)
+
+    def _lod_args(self, lod) -> Tuple[Optional[torch.Tensor], float]:
+        """``lod`` of a call (a finite float, or a tensor with one value per point) as (per-point tensor or None, launch-wide value); the
+        tensor is checked against the points by ``_check_lod``"""
+        if self.level_bits is not None:
+            raise NotImplementedError("a level of detail with a bit depth per level is not built (DESIGN 7): use a uniform num_bits")
+        if isinstance(lod, torch.Tensor) and lod.dim() > 0:
+            return lod, 0.0
+        try:
+            v = float(lod)
+        except (TypeError, ValueError):
+            raise ValueError(f"lod is a float or a [N] tensor, got {lod!r}") from None
+        if not math.isfinite(v):
+            raise ValueError(f"lod {lod!r} is not finite")
+        return None, v
 
     @property
     def _codec(self) -> bool:
@@ -950,7 +1140,7 @@ class HashGridField:
         return loss.detach()
 
     def train_points(self, points: torch.Tensor, target: torch.Tensor, accumulate: bool = False, scale: float = 1.0, step: bool = True,
-                     noise: Optional[bool] = None, order=None, fused: bool = False) -> torch.Tensor:
+                     noise: Optional[bool] = None, order=None, fused: bool = False, lod=None) -> torch.Tensor:
         """``train_step`` on samples that are no raster: ``points`` [N, dim] (fp32, sample units, any order) with their colours ``target``
         [N, 3].  ``accumulate`` / ``scale`` / ``step`` / ``noise``, the noise keys (seed, optimiser step, samples of this pass before this
         chunk + row), the freeze behaviour and the optimiser bookkeeping are ``train_step``'s.  By default the call is layer-wise and unordered
@@ -958,15 +1148,19 @@ class HashGridField:
         ``order``: None, "cell" (``hash_point_order`` of these points, computed for this call) or an int32 [N] device tensor (a precomputed
         ``hash_point_order``, reused across steps for a fixed point set) - the launch walks the points in that order so that neighbouring
         lanes share their cells; rows, targets and noise keys stay the caller's.  ``fused``: the fused step at points (two launches,
-        ``nic_hash_fused_forward_backward_points``) - needs ``route == "fused"``."""
+        ``nic_hash_fused_forward_backward_points``) - needs ``route == "fused"``.  ``lod``: None (the calls above, unchanged), or a level of
+        detail for these samples - a float, or one value per point [N] - which fades the finer levels out of the row and of its gradient
+        (the ``_lod`` entry points, fade starts ``lod_fade``)."""
         if self.table is None:
             raise RuntimeError("a field from load_compressed decodes only")
+        lod_t, lod_u = (None, 0.0) if lod is None else self._lod_args(lod)
         params = self.decoder.linear_params()
         grad = self.table.grad
         frozen = self.frozen
         # every check comes before the first write: a refused call leaves an accumulate pass as it was
         pts = _check_points(self.geo, points)
         n = pts.shape[0]
+        lod_t = _check_lod(lod_t, n, pts.device)
         if n < 1:
             raise ValueError("no points")
         if tuple(target.shape) != (n, 3):
@@ -985,7 +1179,7 @@ class HashGridField:
         if isinstance(order, str):
             order = hash_point_order(self.geo, pts)
         if fused:
-            return self._fused_train_points(pts, target, accumulate, scale, step, noise, order)
+            return self._fused_train_points(pts, target, accumulate, scale, step, noise, order, None if lod is None else (lod_t, lod_u))
         if not accumulate:
             for p in params:
                 p.grad = None
@@ -993,7 +1187,9 @@ class HashGridField:
                 grad.zero_()
             self._pass_samples = 0
         quant = (self.num_bits, self.noise_seed, self.steps, self._pass_samples) if noise else None
-        if noise and self.level_bits is not None:
+        if lod is not None:
+            x = hash_encode_points_lod(self.geo, self.table, pts, lod_t, lod_u, self.lod_fade, quant=quant)
+        elif noise and self.level_bits is not None:
             x = hash_encode_levels(self.geo, self.table, self.level_bits, points=pts, quant=quant[1:])
         else:
             x = hash_encode_points(self.geo, self.table, pts, quant=quant)
@@ -1003,8 +1199,11 @@ class HashGridField:
         y = DecoderFunction.apply(x, *params)          # `fused` is this call's argument here
         loss = ((y - target) ** 2).mean() * scale
         loss.backward()
-        if not frozen:
+        if not frozen and lod is not None:
+            hash_encode_points_backward_lod(self.geo, pts, x.grad, grad, lod_t, lod_u, self.lod_fade, order=order)
+        elif not frozen:
             hash_encode_points_backward(self.geo, pts, x.grad, grad, order=order)
+        if not frozen:
             self._grad_clean = False
         if step:
             self.optimizer.step()
@@ -1017,9 +1216,10 @@ class HashGridField:
         return loss.detach()
 
     @torch.no_grad()
-    def _fused_train_points(self, pts, target, accumulate, scale, step, noise, order) -> torch.Tensor:
+    def _fused_train_points(self, pts, target, accumulate, scale, step, noise, order, lod=None) -> torch.Tensor:
         """``train_points`` as two launches, with ``_fused_train_step``'s bookkeeping: persistent decoder-gradient buffers, the chunks of a
-        pass adding into them and into the table gradient, the optimiser riding on the last chunk's reduction.  The arguments are checked."""
+        pass adding into them and into the table gradient, the optimiser riding on the last chunk's reduction.  The arguments are checked.
+        ``lod``: None or (per-point tensor or None, launch-wide value)."""
         params = self.decoder.linear_params()
         frozen = self.frozen
         grad = None if frozen else self.table.grad
@@ -1036,7 +1236,11 @@ class HashGridField:
         tail = None
         if step:
             tail = self.optimizer.step_tail([] if frozen else [(self.table, grad)], list(zip(params, gm)))
-        if self.level_bits is not None:
+        if lod is not None:
+            loss, _ = hash_fused_forward_backward_points_lod(self.geo, self.table, pts, params, target, gm, lod[0], lod[1], self.lod_fade,
+                                                             table_grad=grad, order=order, loss_scale=float(scale), quant=quant,
+                                                             add_grads=accumulate, tail=tail)
+        elif self.level_bits is not None:
             loss, _ = hash_fused_forward_backward_levels(self.geo, self.table, self.level_bits, params, target, gm, points=pts, order=order,
                                                          table_grad=grad, loss_scale=float(scale), quant=None if quant is None else quant[1:],
                                                          add_grads=accumulate, tail=tail)
@@ -1057,12 +1261,13 @@ class HashGridField:
         return loss
 
     def fit_points(self, points: torch.Tensor, target: torch.Tensor, epochs: int, batch: Optional[int] = None, order="cell",
-                   fused: Optional[bool] = None, freeze_at: float = 0.95) -> List[float]:
+                   fused: Optional[bool] = None, freeze_at: float = 0.95, lod=None) -> List[float]:
         """``fit`` for a fixed sample set: ``epochs`` passes over ``points`` [N, dim] with colours ``target`` [N, 3], one optimiser step per
         pass.  ``order``: "cell" (default), None or an int32 [N] device tensor; it is computed once and the set is laid out in that order, so
         every pass walks it in ``batch``-sized accumulate chunks that are contiguous ranges of the order - each chunk spatially compact (None:
         the whole set in one call).  ``fused``: None = the field's route.  With ``num_bits``: noise while the epoch is below ``freeze_at`` *
-        epochs, then ``freeze()``.  Returns the per-pass losses."""
+        epochs, then ``freeze()``.  ``lod``: ``train_points``' (a [N] tensor is laid out and cut with the points).  Returns the per-pass losses."""
+        lod_t, lod_u = (None, None) if lod is None else self._lod_args(lod)
         pts = _check_points(self.geo, points)
         n = pts.shape[0]
         if n < 1:
@@ -1070,6 +1275,7 @@ class HashGridField:
         target = _lib.require_cuda_f32(target, "target")
         if tuple(target.shape) != (n, 3):
             raise ValueError(f"target must be [{n}, 3], got {tuple(target.shape)}")
+        lod_t = _check_lod(lod_t, n, pts.device)
         fused = self.route == "fused" if fused is None else bool(fused)
         if fused and self.route != "fused":
             raise ValueError(f"fused=True on a field whose route is {self.route!r}")
@@ -1080,6 +1286,7 @@ class HashGridField:
             idx = hash_point_order(self.geo, pts) if isinstance(order, str) and order == "cell" else _check_order(order, n, pts.device)
             idx = idx.to(torch.int64).clamp_(0, n - 1)
             pts, target = pts[idx].contiguous(), target[idx].contiguous()       # laid out in the order once: a chunk is a slice
+            lod_t = None if lod_t is None else lod_t[idx].contiguous()
         cuts = list(range(0, n, batch))
         freeze_epoch = math.ceil(freeze_at * epochs) if self._codec else None
         hist = []
@@ -1089,7 +1296,8 @@ class HashGridField:
             tot = 0.0
             for k, c0 in enumerate(cuts):
                 c1 = min(c0 + batch, n)
-                tot = tot + self.train_points(pts[c0:c1], target[c0:c1], accumulate=k > 0, scale=(c1 - c0) / n, step=k == len(cuts) - 1, fused=fused)
+                tot = tot + self.train_points(pts[c0:c1], target[c0:c1], accumulate=k > 0, scale=(c1 - c0) / n, step=k == len(cuts) - 1, fused=fused,
+                                              lod=lod_u if lod_t is None else lod_t[c0:c1])
             hist.append(tot)
         return [float(h) for h in hist]
 
@@ -1223,10 +1431,10 @@ class HashGridField:
                     "n_linear": self.n_linear, "table": stored.cpu(), "decoder": {k: v.detach().cpu() for k, v in self.decoder.state_dict().items()}}, path)
 
     @classmethod
-    def load_compressed(cls, path, device=None, fused: bool = False) -> "HashGridField":
+    def load_compressed(cls, path, device=None, fused: bool = False, lod_fade: Optional[Sequence[float]] = None) -> "HashGridField":
         """a decode-only field from ``save_compressed``'s file, either format: ``decode()`` gathers from the table as stored - uint8
         (nic_hash_encode_u8; ``fused``: nic_hash_fused_forward_u8) or bit-packed (nic_hash_encode_bits / nic_hash_fused_forward_bits) - with no
-        fp32 table and no conversion between the two"""
+        fp32 table and no conversion between the two.  ``lod_fade``: the constructor's (the file does not hold it)."""
         d = torch.load(path, map_location="cpu", weights_only=True)
         if not isinstance(d, dict) or d.get("format") not in (COMPRESSED_FORMAT, PACKED_FORMAT, MIXED_FORMAT):
             raise ValueError(f"{path}: not a {COMPRESSED_FORMAT}, {PACKED_FORMAT} or {MIXED_FORMAT} file")
@@ -1236,6 +1444,7 @@ class HashGridField:
         self.field_size = tuple(int(v) for v in d["field_size"])
         self.geo = HashGeometry(self.field_size, tuple(int(r) for r in d["resolutions"]), int(d["features"]), int(d["log2_table"]))
         self.hidden, self.n_linear = int(d["hidden"]), int(d["n_linear"])
+        self._lod_fade = None if lod_fade is None else _check_fade(self.geo.levels, lod_fade)
         if is_mixed:
             try:
                 self.num_bits, self.level_bits = None, _check_level_bits(self.geo.levels, d.get("level_bits"))
@@ -1303,10 +1512,22 @@ class HashGridField:
         return self.stored, "u8", self.num_bits
 
     @torch.no_grad()
-    def query(self, points: torch.Tensor) -> torch.Tensor:
+    def query(self, points: torch.Tensor, lod=None) -> torch.Tensor:
         """[N, 3] colours at ``points`` [N, dim] (fp32, sample units: p = i is the centre of sample i, the field spans [-1/2, S - 1/2] and
         points outside it read its edge), from the fp32 table or - a field from ``load_compressed`` - straight from its uint8 or bit-packed
-        table.  One launch on the fused route (nic_hash_fused_forward_points), encode + general decoder on the layer-wise one."""
+        table.  One launch on the fused route (nic_hash_fused_forward_points), encode + general decoder on the layer-wise one.  ``lod``: None
+        (those launches, unchanged), or the level of detail of the query - a float, or one value per point [N]: the levels finer than the
+        footprint fade out before the decoder and are not gathered (the ``_lod`` entry points, fade starts ``lod_fade``)."""
+        if lod is not None:
+            lod_t, lod_u = self._lod_args(lod)
+            pts = _check_points(self.geo, points)
+            data, kind, bits = self._point_table()
+            params = [p.detach() for p in self.decoder.linear_params()]
+            if self.route == "fused":
+                return hash_fused_forward_points_lod(self.geo, data, pts, params, lod_t, lod_u, self.lod_fade, kind, bits)
+            if pts.shape[0] == 0:
+                return torch.empty(0, 3, dtype=torch.float32, device=self.device)
+            return fused.DecoderFunction.apply(hash_encode_points_lod(self.geo, data, pts, lod_t, lod_u, self.lod_fade, kind, bits), *params)
         data, kind, bits = self._point_table()
         params = [p.detach() for p in self.decoder.linear_params()]
         if kind == "bits" and self.level_bits is not None:       # a loaded mixed-depth field: its format /2 table
@@ -1331,16 +1552,61 @@ class HashGridField:
         return torch.stack([g.reshape(-1) for g in torch.meshgrid(*axes, indexing="ij")], dim=1).contiguous()
 
     @torch.no_grad()
-    def resample(self, size: Union[int, Sequence[int]], tile: int = 1024) -> torch.Tensor:
+    def resample(self, size: Union[int, Sequence[int]], tile: int = 1024, lod=None) -> torch.Tensor:
         """the field decoded on a regular grid of ANY size, [*size, 3]: output sample j of axis a sits at p_a = (j + 1/2) S_a / size_a - 1/2
         (``size`` = the field size gives ``decode()``'s sample centres).  Walked in tiles of side <= ``tile``; the points of a tile are
-        generated on the device."""
+        generated on the device.  ``lod``: None = point samples of the full-detail field; a float = ``query``'s level of detail for every
+        sample; "auto" = max(0, log2(max_a S_a / size_a)), the footprint of an output sample in octaves."""
         size = (int(size),) * self.geo.dim if isinstance(size, int) else tuple(int(v) for v in size)
         if len(size) != self.geo.dim or any(v < 1 for v in size):
             raise ValueError(f"size {size} for a {self.geo.dim}D field")
+        if isinstance(lod, str):
+            if lod != "auto":
+                raise ValueError(f"lod {lod!r}: None, 'auto' or a float")
+            lod = max(0.0, math.log2(max(s / v for s, v in zip(self.field_size, size))))
+        if lod is not None:
+            if isinstance(lod, torch.Tensor) and lod.dim() > 0:
+                raise ValueError("resample takes one level of detail for the whole grid: None, 'auto' or a float")
+            lod = self._lod_args(lod)[1]
         out = torch.empty(*size, 3, dtype=torch.float32, device=self.device)
         for o in itertools.product(*[range(0, s, tile) for s in size]):
             ext = [min(tile, s - a) for s, a in zip(size, o)]
             sl = tuple(slice(a, a + e) for a, e in zip(o, ext))
-            out[sl] = self.query(self._resample_points(size, o, ext)).reshape(*ext, 3)
+            out[sl] = self.query(self._resample_points(size, o, ext), lod=lod).reshape(*ext, 3)
         return out
+
+    def _mip_size(self, m: int) -> Tuple[int, ...]:
+        """the size of mip ``m``: S_a / 2^m on every axis, each divisible (else ValueError)"""
+        m = int(m)
+        if m < 0 or any(s % (1 << m) for s in self.field_size):
+            raise ValueError(f"mip {m} of a field of {self.field_size} samples: every axis must be divisible by 2^{m}")
+        return tuple(s >> m for s in self.field_size)
+
+    @torch.no_grad()
+    def decode_mip(self, m: int, tile: int = 1024) -> torch.Tensor:
+        """mip ``m`` of the field, [S_x / 2^m, S_y / 2^m(, S_z / 2^m), 3]: sample j sits at p = (j + 1/2) 2^m - 1/2, the centre of its block of
+        2^m samples per axis, and is queried with level of detail m - the levels finer than the block are faded out and not gathered"""
+        return self.resample(self._mip_size(m), tile=tile, lod=float(int(m)))
+
+    def fit_mips(self, target: torch.Tensor, epochs: int, mips: int = 2, batch: Optional[int] = None, order="cell", fused: Optional[bool] = None,
+                 freeze_at: float = 0.95) -> List[float]:
+        """fits the whole mip chain of ``target`` [S_x, S_y(, S_z), 3] with one table and one decoder: mip m = the mean over blocks of 2^m samples
+        per axis (m = 0 .. ``mips``), its samples at ``decode_mip(m)``'s points with level of detail m; the (point, lod, colour) sets of all mips go
+        to ``fit_points`` as one set, so cell order, chunks and the fused route are that method's.  Returns the per-pass losses."""
+        size, dim = self.field_size, self.geo.dim
+        if tuple(target.shape) != (*size, 3):
+            raise ValueError(f"target must be {(*size, 3)}, got {tuple(target.shape)}")
+        if int(mips) < 0:
+            raise ValueError("mips >= 0")
+        sizes = [self._mip_size(m) for m in range(int(mips) + 1)]
+        if self.level_bits is not None:
+            raise NotImplementedError("a level of detail with a bit depth per level is not built (DESIGN 7): use a uniform num_bits")
+        target = _lib.require_cuda_f32(target, "target")
+        pts, lods, cols = [], [], []
+        for m, sz in enumerate(sizes):
+            blocks = target.reshape(*[v for s in sz for v in (s, 1 << m)], 3)
+            cols.append(blocks.mean(dim=tuple(range(1, 2 * dim, 2))).reshape(-1, 3))
+            pts.append(self._resample_points(sz, [0] * dim, sz))
+            lods.append(torch.full((pts[-1].shape[0],), float(m), dtype=torch.float32, device=self.device))
+        return self.fit_points(torch.cat(pts).contiguous(), torch.cat(cols).contiguous(), epochs, batch=batch, order=order, fused=fused,
+                               freeze_at=freeze_at, lod=torch.cat(lods).contiguous())

@@ -1,0 +1,551 @@
+"""GPU tests of the hash-grid field's per-point level of detail (nic_hash_encode_points_lod / _backward_lod, nic_hash_fused_forward_points_lod,
+nic_hash_fused_forward_backward_points_lod, csrc/lod_points.hip; HashGridField.query / train_points / fit_points(lod=), resample(lod=),
+decode_mip, fit_mips).  The weight is restated here in torch fp32, operation for operation; everything else is compared with
+the entry points without _lod, which have their own restatement (tests/test_gpu_hashgrid_points.py).
+
+Tolerances are the project's own: bit for bit where only a factor of exactly 0, 1 or one rounded product separates the two sides; 1e-5 of the
+largest entry for the same sums in another atomic order (tests/test_gpu_hashgrid_points.py); TOL_Y = 5e-6 and TOL_G = 1e-4 of the reference's
+largest magnitude for fused against layer-wise (tests/test_gpu_hashgrid_points_train.py).
+
+1. lambda = 0 is today's route, bit for bit: encode (all F, 2D and 3D, three sources, noise) and the fused query;
+2. the weight is the definition: a * plain row bit for bit, thresholds, NaN, huge, a skipped wave next to a live one, noise across a skipped
+   block boundary, stored sources with skipped levels between live ones;
+3. the backward is the plain backward fed a * dx; it adds, orders, merges coinciding points and leaves unweighed levels exactly alone;
+4. fused against layer-wise with mixed lambda: query, step, ordered against unordered, chunks;
+5. the field: lod=None is untouched, decode_mip(0) is decode(), resample(lod=0) is resample(), stored files, the empty set;
+6. fit_mips + decode_mip beat fit + resample on the box-filtered mips."""
+import copy
+import math
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+TOL_Y, TOL_G, TOL_ORDER = 5e-6, 1e-4, 1e-5
+NAMES = ["dW1", "db1", "dW2", "db2", "dW3", "db3"]
+SIZES = {2: ((96, 80), {}), 3: ((40, 36, 28), dict(base_resolution=4))}
+GAPS = [0.0, 9.0, 9.0, 9.0, 0.0, 9.0, 0.5, 9.0]      # a custom fade: levels 0, 4 and 6 go first, leaving live levels between skipped ones
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a HIP device")
+    from neural_image_compression_v2_amd import _lib
+    _lib.load()
+    return torch.device("cuda:0")
+
+
+def relmax(a, b):
+    return float((a.double() - b.double()).abs().max() / (b.double().abs().max() + 1e-300))
+
+
+def check(a, b, tol, what):
+    e = relmax(a, b)
+    print(f"{what}: {e:.3e}")
+    assert e <= tol, f"{what}: max error over the reference's largest magnitude {e:.3e} > {tol:.1e}"
+
+
+def _geo_for(dim, F, log2_table=12):
+    """coarse levels dense, fine ones hashed; non-square, not a power of two"""
+    from neural_image_compression_v2_amd.hashgrid import HashGeometry, level_resolutions
+    size, n_min = ((96, 80), 16) if dim == 2 else ((40, 36, 28), 4)
+    geo = HashGeometry(size, tuple(level_resolutions(8, n_min, max(size))), F, log2_table)
+    assert {(r + 1) ** dim <= (1 << log2_table) for r in geo.resolutions} == {True, False}
+    return geo
+
+
+def _table(geo, dev, seed, amp=1.0):
+    g = torch.Generator(device=dev).manual_seed(seed)
+    return (torch.rand(geo.table_shape(), generator=g, device=dev) * 2 - 1) * amp
+
+
+def _odd_points(geo, dev, seed, n=5000):
+    """random fractional points over the whole field, then edges, points outside, huge, NaN and infinite coordinates"""
+    g = torch.Generator(device=dev).manual_seed(seed)
+    S = torch.tensor([float(s) for s in geo.field_size], device=dev)
+    inside = torch.rand(n, geo.dim, generator=g, device=dev) * S - 0.5
+    rows = []
+    for a in range(geo.dim):
+        for val in [-0.5, float("nan"), float("inf"), -3.7, 1e30, 0.0, geo.field_size[a] - 0.5, geo.field_size[a] + 10.25, geo.field_size[a] - 1.0]:
+            r = inside[len(rows) % n].clone()
+            r[a] = val
+            rows.append(r)
+    return torch.cat([inside, torch.stack(rows)], dim=0).contiguous()
+
+
+def _lambdas(fade, n, dev, seed):
+    """one lambda per point: the first 64 points far past every level, the next 64 at 0 (one wave skips everything, its neighbour nothing); then
+    every threshold fade[l], fade[l] + 1, their fp32 neighbours and values between, negatives, NaN, infinities and 1e9; then random ones"""
+    g = torch.Generator(device=dev).manual_seed(seed)
+    lam = torch.rand(n, generator=g, device=dev) * (max(fade) + 2.5) - 0.5
+    special = [-2.0, -0.0, float("nan"), 1e9, float("inf"), float("-inf"), 32.0, 31.99, 33.0]
+    for f in fade:
+        t = torch.tensor([f, f + 1.0], dtype=torch.float32)
+        special += [float(v) for v in t] + [float(v) for v in torch.nextafter(t, t + 1)] + [float(v) for v in torch.nextafter(t, t - 1)]
+        special += [f + 0.5, f + 0.25, f + 0.999]
+    sp = torch.tensor(special, dtype=torch.float32, device=dev)
+    assert n >= 128 + sp.shape[0]
+    lam[:64], lam[64:128] = 20.0, 0.0
+    lam[128:128 + sp.shape[0]] = sp
+    lam[-sp.shape[0]:] = sp                                                      # and on the odd tail rows
+    return lam.contiguous()
+
+
+def weights(fade, lod, uniform, n, dev):
+    """[N, L] fp32: lambda = (lod or 0) + uniform, NaN -> 0, clamped to [0, 32]; a = min(max((fade - lambda) + 1, 0), 1), one rounding per operation"""
+    lam = (torch.zeros(n, device=dev) if lod is None else lod) + torch.tensor(uniform, dtype=torch.float32, device=dev)
+    lam = torch.where(torch.isnan(lam), torch.zeros_like(lam), lam).clamp(0.0, 32.0)
+    d = torch.tensor(fade, dtype=torch.float32, device=dev)[None, :] - lam[:, None]
+    return (d + 1.0).clamp(0.0, 1.0)
+
+
+def weigh(a, rows, F):
+    return a.repeat_interleave(F, dim=1) * rows
+
+
+def _sources(geo, table, b):
+    """(data, kind, num_bits) of the three sources of one quantised table, and the fp32 table they all decode to"""
+    from neural_image_compression_v2_amd import hashgrid as hg
+    from neural_image_compression_v2_amd import models
+    clamped = models.quantize_clamp(table * 0.45, b)
+    stored, packed = hg.hash_pack_u8(geo, clamped, b), hg.hash_pack_bits(geo, clamped, b)
+    return [(hg._table_of_u8(geo, stored, b), "f32", None), (stored, "u8", b), (packed, "bits", b)]
+
+
+# ---- 1. lambda = 0 is today's route ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("F", [1, 2, 4, 8])
+@pytest.mark.parametrize("dim", [2, 3])
+def test_lambda_zero_is_the_plain_route(dev, dim, F):
+    from neural_image_compression_v2_amd import hashgrid as hg
+    geo = _geo_for(dim, F)
+    assert all(float(w) == 1.0 for w in weights(hg.hash_lod_fade(geo), None, 0.0, 1, dev)[0])      # the default fade: every weight exactly 1
+    table = _table(geo, dev, 10 * dim + F)
+    pts = _odd_points(geo, dev, seed=dim * 7 + F)
+    zero = torch.zeros(pts.shape[0], device=dev)
+    want = hg.hash_encode_points(geo, table, pts)
+    for lod in (None, zero):
+        assert torch.equal(hg.hash_encode_points_lod(geo, table, pts, lod), want)
+        for n in (1, 63, 65, 257):
+            assert torch.equal(hg.hash_encode_points_lod(geo, table, pts[:n].contiguous(), None if lod is None else lod[:n].contiguous()), want[:n]), n
+        for b in (8, 3):                                                         # F b = 3 F straddles dwords, 8 F does not
+            for data, kind, bits in _sources(geo, table, b):
+                assert torch.equal(hg.hash_encode_points_lod(geo, data, pts, lod, kind=kind, num_bits=bits),
+                                   hg.hash_encode_points(geo, data, pts, kind, bits)), (kind, b)
+        quant = (6, 77, 5, 12345)
+        want_n = hg.hash_encode_points(geo, table, pts, quant=quant)
+        assert not torch.equal(want_n, want)
+        assert torch.equal(hg.hash_encode_points_lod(geo, table, pts, lod, quant=quant), want_n)
+
+
+@pytest.mark.parametrize("dim", [2, 3])
+def test_lambda_zero_fused_query_is_the_plain_fused_query(dev, dim):
+    from neural_image_compression_v2_amd import hashgrid as hg
+    for F in (2, 8):
+        geo = _geo_for(dim, F)
+        f = _field(SIZES[dim][0], dev, 3, fused=True, features=F, **SIZES[dim][1])
+        assert f.route == "fused" and f.geo == geo
+        params = [p.detach() for p in f.decoder.linear_params()]
+        pts = _odd_points(geo, dev, seed=dim + F)
+        zero = torch.zeros(pts.shape[0], device=dev)
+        for b in (None, 5):
+            srcs = [(f.table.detach(), "f32", None)] if b is None else _sources(geo, f.table.detach(), b)
+            for data, kind, bits in srcs:
+                want = hg.hash_fused_forward_points(geo, data, pts, params, kind, bits)
+                assert torch.equal(hg.hash_fused_forward_points_lod(geo, data, pts, params, None, kind=kind, num_bits=bits), want), (F, kind)
+                assert torch.equal(hg.hash_fused_forward_points_lod(geo, data, pts, params, zero, kind=kind, num_bits=bits), want), (F, kind)
+        want = hg.hash_fused_forward_points(geo, f.table.detach(), pts, params)
+        for n in (1, 63, 65, 257):
+            assert torch.equal(hg.hash_fused_forward_points_lod(geo, f.table.detach(), pts[:n].contiguous(), params), want[:n]), n
+
+
+# ---- 2. the weight is the definition -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("F", [1, 2, 4, 8])
+@pytest.mark.parametrize("dim", [2, 3])
+def test_rows_are_the_weight_times_the_plain_rows(dev, dim, F):
+    from neural_image_compression_v2_amd import hashgrid as hg
+    geo = _geo_for(dim, F)
+    table = _table(geo, dev, 30 * dim + F)
+    pts = _odd_points(geo, dev, seed=dim * 11 + F)
+    n = pts.shape[0]
+    for fade in (hg.hash_lod_fade(geo), tuple(GAPS)):
+        lam = _lambdas(fade, n, dev, seed=F)
+        for uniform in (0.0, 0.75):
+            a = weights(fade, lam, uniform, n, dev)
+            assert bool((a == 0).any()) and bool((a == 1).any()) and bool(((a > 0) & (a < 1)).any())
+            assert bool((a[:64] == 0).all()) and (uniform > 0 or bool((a[64:128] == 1).all()))     # one wave skips every level, the next none
+            for data, kind, bits in [(table, "f32", None)] + _sources(geo, table, 3)[1:] + _sources(geo, table, 8)[1:]:
+                got = hg.hash_encode_points_lod(geo, data, pts, lam, uniform, fade, kind=kind, num_bits=bits)
+                want = weigh(a, hg.hash_encode_points(geo, data, pts, kind, bits), F)
+                assert torch.equal(got, want), (dim, F, kind, bits, uniform)
+                assert bool((got[:64] == 0).all())
+        # a launch-wide lambda alone, and short launches that start inside the skipped wave
+        a = weights(fade, None, fade[2] + 0.5, n, dev)
+        assert torch.equal(hg.hash_encode_points_lod(geo, table, pts, None, fade[2] + 0.5, fade), weigh(a, hg.hash_encode_points(geo, table, pts), F))
+        for k in (1, 63, 65, 257):
+            sl = slice(60, 60 + k)
+            got = hg.hash_encode_points_lod(geo, table, pts[sl].contiguous(), lam[sl].contiguous(), 0.0, fade)
+            assert torch.equal(got, weigh(weights(fade, lam[sl], 0.0, k, dev), hg.hash_encode_points(geo, table, pts[sl].contiguous()), F)), k
+
+
+@pytest.mark.parametrize("dim", [2, 3])
+def test_noise_survives_a_skipped_block_boundary(dev, dim):
+    """F = 4, L = 8: columns 0 .. 15 and 16 .. 31 are one generator block each, levels 0 and 4 open them.  With the GAPS fade those two levels
+    go at lambda >= 1 while levels 1 .. 3, 5 and 7 stay: the later levels of a block must still get its noise.  The default fade cuts from a
+    level on, per point, in mixed waves."""
+    from neural_image_compression_v2_amd import hashgrid as hg
+    geo = _geo_for(dim, 4)
+    table = _table(geo, dev, 40 + dim)
+    pts = _odd_points(geo, dev, seed=dim + 50)
+    n = pts.shape[0]
+    quant = (5, 91, 3, 4321)
+    plain = hg.hash_encode_points(geo, table, pts, quant=quant)
+    assert not torch.equal(plain, hg.hash_encode_points(geo, table, pts))
+    lam = torch.full((n,), 3.0, device=dev)                                      # every wave: levels 0, 4, 6 off, the rest on
+    a = weights(GAPS, lam, 0.0, n, dev)
+    assert a[0].tolist() == [0.0, 1.0, 1.0, 1.0, 0.0, 1.0, 0.0, 1.0]
+    assert torch.equal(hg.hash_encode_points_lod(geo, table, pts, lam, 0.0, GAPS, quant=quant), weigh(a, plain, 4))
+    for fade in (tuple(GAPS), hg.hash_lod_fade(geo)):
+        lam = _lambdas(fade, n, dev, seed=dim)
+        a = weights(fade, lam, 0.0, n, dev)
+        got = hg.hash_encode_points_lod(geo, table, pts, lam, 0.0, fade, quant=quant)
+        assert torch.equal(got, weigh(a, plain, 4))
+        off = a.repeat_interleave(4, dim=1) == 0
+        assert bool(off.any()) and bool((got[off] == 0).all())                   # a level of weight 0 is noise-free too
+    # the fused step reads the same noisy weighed rows: its y against the layer-wise decoder on them
+    from neural_image_compression_v2_amd import fused
+    f = _field(SIZES[dim][0], dev, 4, fused=True, features=4, **SIZES[dim][1])
+    params = [p.detach() for p in f.decoder.linear_params()]
+    target = torch.rand(n, 3, generator=torch.Generator(device=dev).manual_seed(1), device=dev)
+    gm = [torch.empty_like(p) for p in params]
+    lam = _lambdas(GAPS, n, dev, seed=9)
+    _, y = hg.hash_fused_forward_backward_points_lod(geo, f.table, pts, params, target, gm, lam, 0.0, GAPS, want_y=True, quant=quant)
+    with torch.no_grad():
+        want = fused.DecoderFunction.apply(hg.hash_encode_points_lod(geo, f.table, pts, lam, 0.0, GAPS, quant=quant), *params)
+    check(y, want, TOL_Y, f"noisy fused y {dim}D")
+
+
+# ---- 3. the backward ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("F", [1, 2, 4, 8])
+@pytest.mark.parametrize("dim", [2, 3])
+def test_backward_is_the_plain_backward_of_the_weighed_gradient(dev, dim, F):
+    from neural_image_compression_v2_amd import hashgrid as hg
+    geo = _geo_for(dim, F)
+    pts = _odd_points(geo, dev, seed=dim * 13 + F)
+    n = pts.shape[0]
+    g = torch.Generator(device=dev).manual_seed(F)
+    dx = torch.rand(n, geo.width, generator=g, device=dev) * 2 - 1
+    base = torch.rand(geo.table_shape(), generator=g, device=dev)                # the call ADDS
+    perm = torch.randperm(n, generator=torch.Generator().manual_seed(3)).to(torch.int32).to(dev)
+    for fade in (hg.hash_lod_fade(geo), tuple(GAPS)):
+        lam = _lambdas(fade, n, dev, seed=F + 1)
+        a = weights(fade, lam, 0.25, n, dev)
+        ref = base.clone()
+        hg.hash_encode_points_backward(geo, pts, weigh(a, dx, F), ref)
+        for name, order in (("none", None), ("random", perm), ("cell", hg.hash_point_order(geo, pts))):
+            got = base.clone()
+            hg.hash_encode_points_backward_lod(geo, pts, dx, got, lam, 0.25, fade, order=order)
+            e = relmax(got - base, ref - base)
+            print(f"lod backward {dim}D F={F} order {name}: {e:.3e}")
+            assert e <= TOL_ORDER, (dim, F, name, e)
+    for k in (1, 63, 65, 257):
+        sl = slice(60, 60 + k)
+        ref, got = torch.zeros(geo.table_shape(), device=dev), torch.zeros(geo.table_shape(), device=dev)
+        hg.hash_encode_points_backward(geo, pts[sl].contiguous(), weigh(a[sl], dx[sl], F).contiguous(), ref)
+        hg.hash_encode_points_backward_lod(geo, pts[sl].contiguous(), dx[sl].contiguous(), got, lam[sl].contiguous(), 0.25, fade)
+        assert relmax(got, ref) <= TOL_ORDER, k
+
+
+@pytest.mark.parametrize("dim", [2, 3])
+def test_backward_of_coinciding_points_and_of_unweighed_levels(dev, dim):
+    from neural_image_compression_v2_amd import hashgrid as hg
+    geo = _geo_for(dim, 2)
+    fade = hg.hash_lod_fade(geo)
+    n = 1000
+    pts = torch.tensor([17.3, 61.77, 5.5][:dim], device=dev).repeat(n, 1)        # every wave is one run; its lanes weigh differently
+    pts[100:350] = torch.tensor([3.25, 8.0, 20.125][:dim], device=dev)
+    pts = pts.contiguous()
+    g = torch.Generator(device=dev).manual_seed(n)
+    dx = torch.rand(n, geo.width, generator=g, device=dev) + 0.5                 # positive: a touched entry moves
+    lam = (torch.rand(n, generator=g, device=dev) * (fade[0] + 2)).contiguous()
+    lam[512:640] = 30.0                                                          # two whole waves with nothing to add
+    a = weights(fade, lam, 0.0, n, dev)
+    ref, got = torch.zeros(geo.table_shape(), device=dev), torch.zeros(geo.table_shape(), device=dev)
+    hg.hash_encode_points_backward(geo, pts, weigh(a, dx, 2), ref)
+    hg.hash_encode_points_backward_lod(geo, pts, dx, got, lam)
+    check(got, ref, TOL_ORDER, f"coinciding points {dim}D")
+    assert torch.equal(got == 0, ref == 0)
+    # a launch-wide lambda past level 3: a_l = 0 for every point at l >= 3 (the default fade falls with l), and those levels are not touched
+    pts = _odd_points(geo, dev, seed=dim)
+    dx = torch.rand(pts.shape[0], geo.width, generator=g, device=dev) + 0.5
+    cut = fade[3] + 1.0
+    assert bool((weights(fade, None, cut, 1, dev)[0, 3:] == 0).all()) and bool((weights(fade, None, cut, 1, dev)[0, :3] > 0).all())
+    grad = torch.zeros(geo.table_shape(), device=dev)
+    hg.hash_encode_points_backward_lod(geo, pts, dx, grad, None, cut)
+    assert bool((grad[3:] == 0).all()) and all(bool((grad[l] != 0).any()) for l in range(3))
+    poison = torch.full(geo.table_shape(), 3.25, device=dev)
+    hg.hash_encode_points_backward_lod(geo, pts, dx, poison, None, cut, order=hg.hash_point_order(geo, pts))
+    assert bool((poison[3:] == 3.25).all()) and bool((poison[:3] != 3.25).any())
+    none = torch.empty(0, dim, device=dev)
+    hg.hash_encode_points_backward_lod(geo, none, torch.empty(0, geo.width, device=dev), poison, torch.empty(0, device=dev))
+    assert hg.hash_encode_points_lod(geo, _table(geo, dev, 1), none, torch.empty(0, device=dev)).shape == (0, geo.width)
+
+
+# ---- fields --------------------------------------------------------------------------------------------------------------------------------
+def _field(size, dev, seed, fused=False, num_bits=None, **kw):
+    from neural_image_compression_v2_amd.hashgrid import HashGridField
+    kw = dict(dict(levels=8, features=2, log2_table=12), **kw)
+    f = HashGridField(size, device=dev, seed=seed, num_bits=num_bits, fused=fused, **kw)
+    with torch.no_grad():
+        f.table.uniform_(-0.4, 0.4, generator=torch.Generator(device=dev).manual_seed(seed))
+        for p in f.decoder.parameters():
+            p.mul_(1.5)                       # past torch's init: activations that are not all in GELU's linear part
+    return f
+
+
+def _twin(f, fused=False):
+    """a deep copy of a trainable field: its own table, decoder and optimiser state with the same values and step counts, on the asked route"""
+    from neural_image_compression_v2_amd.hashgrid import HashGridField
+    g = HashGridField(f.field_size, levels=f.geo.levels, features=f.geo.features, log2_table=f.geo.log2_table, hidden=f.hidden, n_linear=f.n_linear,
+                      device=f.device, num_bits=f.num_bits, noise_seed=f.noise_seed, lod_fade=f._lod_fade)
+    assert not f.frozen and g.geo.table_shape() == f.geo.table_shape()
+    g.geo = f.geo
+    g._set_route(fused)
+    with torch.no_grad():
+        g.table.copy_(f.table)
+    g.decoder.load_state_dict(copy.deepcopy(f.decoder.state_dict()))
+    g.optimizer.load_state_dict(copy.deepcopy(f.optimizer.state_dict()))
+    g.steps = f.steps
+    return g
+
+
+def _grads_of(f):
+    return [f.table.grad.clone()] + [p.grad.clone() for p in f.decoder.linear_params()]
+
+
+def _compare_grads(got, ref, tol, what):
+    """(loss, [table gradient, decoder gradients]) of two fields after a step=False call"""
+    check(got[0].reshape(1), ref[0].reshape(1), TOL_Y if tol == TOL_G else tol, f"{what} loss")
+    for n, a, b in zip(["table gradient"] + NAMES, got[1], ref[1]):
+        check(a, b, tol, f"{what} {n}")
+
+
+def _mixed(f, dev, seed, n):
+    """n odd points of field f with a lambda each (thresholds, NaN, a skipped wave and all) and random targets"""
+    pts = _odd_points(f.geo, dev, seed=seed, n=n)[-n:].contiguous()
+    lam = _lambdas(f.lod_fade, n, dev, seed=seed)
+    target = torch.rand(n, 3, generator=torch.Generator(device=dev).manual_seed(seed), device=dev)
+    return pts, lam, target
+
+
+# ---- 4. fused against layer-wise, with mixed lambda ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("num_bits", [None, 6])
+@pytest.mark.parametrize("dim", [2, 3])
+def test_fused_against_layerwise_with_mixed_lambda(dev, dim, num_bits):
+    size, kw = SIZES[dim]
+    base = _field(size, dev, 4, num_bits=num_bits, lod_fade=GAPS if num_bits else None, **kw)
+    for n in (257, 5001):
+        pts, lam, target = _mixed(base, dev, dim + n, n)
+        a, b = _twin(base), _twin(base, fused=True)
+        assert a.route == "layerwise" and b.route == "fused" and a.lod_fade == b.lod_fade == base.lod_fade
+        check(b.query(pts, lod=lam), a.query(pts, lod=lam), TOL_Y, f"query {dim}D N={n}")
+        check(b.query(pts, lod=1.5), a.query(pts, lod=1.5), TOL_Y, f"query {dim}D N={n} one lambda")
+        la = a.train_points(pts, target, step=False, lod=lam)
+        lb = b.train_points(pts, target, step=False, fused=True, lod=lam)
+        _compare_grads((lb, _grads_of(b)), (la, _grads_of(a)), TOL_G, f"step {dim}D bits {num_bits} N={n}")
+        # the weights are in it: lambda = 0 is another step
+        c = _twin(base)
+        c.train_points(pts, target, step=False)
+        assert relmax(c.table.grad, a.table.grad) > 100 * TOL_G
+    # any order computes the same step, on both routes
+    for fused_route, tol in ((False, TOL_ORDER), (True, TOL_G)):
+        ref = None
+        for name, order in (("none", None), ("cell", "cell"), ("random", torch.randperm(n, generator=torch.Generator().manual_seed(4)).to(torch.int32).to(dev))):
+            f = _twin(base, fused=fused_route)
+            got = (f.train_points(pts, target, step=False, order=order, fused=fused_route, lod=lam), _grads_of(f))
+            if ref is None:
+                ref = got
+            else:
+                _compare_grads(got, ref, tol, f"order {name} {dim}D {'fused' if fused_route else 'layer-wise'}")
+
+
+@pytest.mark.parametrize("dim", [2, 3])
+def test_chunks_and_the_tail_with_mixed_lambda(dev, dim):
+    from neural_image_compression_v2_amd import hashgrid as hg
+    size, kw = SIZES[dim]
+    base = _field(size, dev, 6, fused=True, num_bits=6, **kw)
+    n, cut = 4000, [0, 1000, 2048, 4000]
+    pts, lam, target = _mixed(base, dev, 12, n)
+    one, three = _twin(base, fused=True), _twin(base, fused=True)
+    l1 = one.train_points(pts, target, step=False, order="cell", fused=True, lod=lam)
+    tot = 0.0
+    for k in range(3):                                                           # NIC_HASH_FUSED_ADD_GRADS on the later chunks
+        s = slice(cut[k], cut[k + 1])
+        tot = tot + three.train_points(pts[s], target[s], accumulate=k > 0, scale=(cut[k + 1] - cut[k]) / n, step=False, order="cell", fused=True,
+                                       lod=lam[s])
+    assert three._pass_samples == one._pass_samples == n
+    _compare_grads((tot, _grads_of(three)), (l1, _grads_of(one)), TOL_G, f"three chunks {dim}D")
+    # NIC_HASH_FUSED_ADD_LOSS: two calls into one loss and one set of buffers
+    params = [p.detach() for p in base.decoder.linear_params()]
+    gm1, gm2 = [torch.empty_like(p) for p in params], [torch.empty_like(p) for p in params]
+    tg1, tg2 = torch.zeros_like(base.table), torch.zeros_like(base.table)
+    loss1, _ = hg.hash_fused_forward_backward_points_lod(base.geo, base.table, pts, params, target, gm1, lam, 0.5, table_grad=tg1)
+    loss2 = torch.full((1,), 7.0, device=dev)
+    for k, s in enumerate((slice(0, 1500), slice(1500, n))):
+        hg.hash_fused_forward_backward_points_lod(base.geo, base.table, pts[s], params, target[s], gm2, lam[s].contiguous(), 0.5, table_grad=tg2,
+                                                  loss=loss2, loss_scale=(s.stop - s.start) / n, add_grads=k > 0, add_loss=k > 0)
+    _compare_grads((loss2, [tg2] + gm2), (loss1, [tg1] + gm1), TOL_G, f"add_loss {dim}D")
+    # the optimiser tail: the same call without it followed by optimizer.step() - decoder bit for bit, table within the atomics' order
+    base.train_points(pts, target, fused=True, lod=lam)                          # off the first Adam step
+    a, b = _twin(base, fused=True), _twin(base, fused=True)
+    table = base.table.detach().clone()
+    la = a.train_points(pts, target, order="cell", fused=True, lod=lam)
+    lb = b.train_points(pts, target, order="cell", fused=True, lod=lam, step=False)
+    b.optimizer.step()
+    torch.cuda.synchronize()
+    assert torch.equal(la, lb) and a.steps == base.steps + 1
+    for pa, pb, p0 in zip(a.decoder.linear_params(), b.decoder.linear_params(), base.decoder.linear_params()):
+        assert torch.equal(pa, pb) and not torch.equal(pa, p0)
+    upd = float((a.table.detach() - table).abs().max())
+    e = float((a.table.detach() - b.table.detach()).abs().max()) / upd
+    print(f"tail against optimizer.step() {dim}D: table {e:.3e} of the largest update {upd:.3e}")
+    assert upd > 0 and e <= TOL_ORDER
+
+
+# ---- 5. the field ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fused_route", [False, True])
+def test_lod_none_makes_the_calls_it_made(dev, fused_route):
+    size, kw = SIZES[2]
+    base = _field(size, dev, 10, fused=fused_route, num_bits=6, **kw)
+    pts, lam, target = _mixed(base, dev, 16, 3000)
+    assert torch.equal(base.query(pts, lod=None), base.query(pts))
+    assert torch.equal(base.query(pts, lod=0.0), base.query(pts))                # and lambda = 0 answers the same through the new kernels
+    assert torch.equal(base.query(pts, lod=torch.zeros(3000, device=dev)), base.query(pts))
+    assert not torch.equal(base.query(pts, lod=lam), base.query(pts))
+    base.train_points(pts, target)
+    a, b = _twin(base, fused=fused_route), _twin(base, fused=fused_route)
+    a.freeze()
+    b.freeze()
+    la = a.train_points(pts, target, fused=fused_route)
+    lb = b.train_points(pts, target, fused=fused_route, lod=None)
+    assert torch.equal(la, lb) and torch.equal(a.table.detach(), b.table.detach()) and a.table.grad is None and b.table.grad is None
+    for pa, pb in zip(a.decoder.linear_params(), b.decoder.linear_params()):
+        assert torch.equal(pa, pb)                                               # no atomics on this path: the same launches
+    # a refused lod leaves a pass in progress alone
+    c = _twin(base, fused=fused_route)
+    c.train_points(pts[:2000].contiguous(), target[:2000].contiguous(), scale=0.5, step=False, fused=fused_route, lod=lam[:2000].contiguous())
+    grad = c.table.grad.clone()
+    assert bool((grad != 0).any()) and c._pass_samples == 2000
+    for bad in (lam[:999].contiguous(), lam[2000:].cpu(), lam[2000:].double(), float("nan"), "fine"):
+        with pytest.raises((ValueError, RuntimeError, NotImplementedError)):
+            c.train_points(pts[2000:].contiguous(), target[2000:].contiguous(), accumulate=True, fused=fused_route, lod=bad)
+    assert torch.equal(c.table.grad, grad) and c._pass_samples == 2000 and c.steps == base.steps
+
+
+@pytest.mark.parametrize("fused_route", [False, True])
+def test_mips_and_resample(dev, fused_route):
+    for size, kw in (((96, 80), {}), ((40, 36, 28), dict(base_resolution=4))):
+        f = _field(size, dev, 6, fused=fused_route, **kw)
+        e = float((f.decode_mip(0, tile=64) - f.decode()).abs().max())
+        assert e < 5e-6, (size, e)                                               # resample at the field size against decode(): its tolerance
+        assert torch.equal(f.decode_mip(0), f.resample(size))
+        half = tuple(s // 2 for s in size)
+        assert torch.equal(f.resample(half, lod=0.0), f.resample(half))
+        assert torch.equal(f.resample((33, 21, 9)[:len(size)], tile=16, lod=0.0), f.resample((33, 21, 9)[:len(size)], tile=16))
+        m1 = f.decode_mip(1, tile=32)
+        assert m1.shape == (*half, 3) and torch.equal(m1, f.resample(half, tile=32, lod=1.0)) and torch.equal(m1, f.resample(half, tile=32, lod="auto"))
+        assert not torch.equal(m1, f.resample(half))
+        # sample j of mip m sits at (j + 1/2) 2^m - 1/2 with lambda = m
+        m2 = f.decode_mip(2)
+        quarter = tuple(s // 4 for s in size)
+        axes = [(torch.arange(q, device=dev, dtype=torch.float32) + 0.5) * 4 - 0.5 for q in quarter]
+        pts = torch.stack([g.reshape(-1) for g in torch.meshgrid(*axes, indexing="ij")], dim=1).contiguous()
+        assert torch.equal(m2, f.query(pts, lod=2.0).reshape(*quarter, 3))
+        auto = f.resample(tuple(max(1, s // 3) for s in size), lod="auto")      # a footprint that is no power of two
+        lam = max(0.0, math.log2(max(s / max(1, s // 3) for s in size)))
+        assert torch.equal(auto, f.resample(tuple(max(1, s // 3) for s in size), lod=lam))
+        assert torch.equal(f.resample(tuple(2 * s for s in size), lod="auto"), f.resample(tuple(2 * s for s in size)))     # magnified: lambda = 0
+        with pytest.raises(ValueError):
+            f.decode_mip(5 if len(size) == 2 else 3)
+        assert f.query(torch.empty(0, len(size), device=dev), lod=1.0).shape == (0, 3)
+        assert f.query(torch.empty(0, len(size), device=dev), lod=torch.empty(0, device=dev)).shape == (0, 3)
+
+
+@pytest.mark.parametrize("fused_route", [False, True])
+def test_stored_file_answers_lod_queries_like_the_frozen_field(dev, fused_route, tmp_path):
+    from neural_image_compression_v2_amd.hashgrid import HashGridField
+    for size, kw, b in (((96, 80), {}, 6), ((40, 36, 28), dict(base_resolution=4), 3)):
+        f = _field(size, dev, 8, fused=fused_route, num_bits=b, lod_fade=GAPS if b == 3 else None, **kw)
+        f.freeze()
+        pts, lam, _ = _mixed(f, dev, 3, 3001)
+        want, want1 = f.query(pts, lod=lam), f.decode_mip(1)
+        for packed in (False, True):
+            path = tmp_path / f"s{len(size)}{int(packed)}.pt"
+            f.save_compressed(path, packed=packed)
+            g = HashGridField.load_compressed(path, dev, fused=fused_route, lod_fade=f._lod_fade)
+            assert g.table is None and (g.packed is not None) == packed and g.route == f.route and g.lod_fade == f.lod_fade
+            assert torch.equal(g.query(pts, lod=lam), want), (size, packed)
+            assert torch.equal(g.decode_mip(1), want1), (size, packed)
+            assert g.table is None and (g.stored is None) == packed             # nothing was converted
+
+
+def test_uniform_num_bits_trains_with_lod_and_a_depth_per_level_refuses(dev):
+    from neural_image_compression_v2_amd.hashgrid import HashGridField
+    size = (96, 80)
+    f = _field(size, dev, 11, num_bits=6)
+    pts, lam, target = _mixed(f, dev, 5, 3000)
+    quiet = _twin(f)
+    f.train_points(pts, target, step=False, lod=lam)
+    quiet.train_points(pts, target, step=False, lod=lam, noise=False)
+    assert relmax(quiet.table.grad, f.table.grad) > 20 * TOL_ORDER               # the noise is there
+    m = HashGridField(size, levels=8, features=2, log2_table=12, device=dev, seed=1, num_bits=[8, 8, 7, 7, 6, 6, 5, 5])
+    before = m.table.detach().clone()
+    for call in (lambda: m.query(pts, lod=1.0), lambda: m.train_points(pts, target, lod=lam), lambda: m.decode_mip(1),
+                 lambda: m.fit_mips(torch.zeros(*size, 3, device=dev), 1), lambda: m.resample((48, 40), lod="auto")):
+        with pytest.raises(NotImplementedError):
+            call()
+    assert torch.equal(m.table.detach(), before) and m.steps == 0
+    m.query(pts)                                                                 # without lod it answers as before
+
+
+# ---- 6. it does what it is for -----------------------------------------------------------------------------------------------------------------
+def psnr(a, b):
+    return float(10 * torch.log10(1.0 / ((a.double() - b.double()) ** 2).mean()))
+
+
+def _striped(size, dev):
+    """detail at the pixel scale on a smooth ramp: one-sample stripes along x and along y in two channels, a ramp under each"""
+    x = torch.arange(size[0], device=dev, dtype=torch.float32)[:, None].expand(*size)
+    y = torch.arange(size[1], device=dev, dtype=torch.float32)[None, :].expand(*size)
+    ramp = (x / (size[0] - 1) + y / (size[1] - 1)) / 2
+    r = 0.2 + 0.4 * ramp + 0.3 * (x % 2)
+    g = 0.7 - 0.4 * ramp + 0.2 * (y % 2)
+    b = 0.5 + 0.3 * torch.sin(6.0 * ramp) + 0.15 * ((x + y) % 2)
+    return torch.stack([r, g, b], dim=-1).clamp(0, 1).contiguous()
+
+
+def _box(image, m):
+    size = image.shape[:-1]
+    return image.reshape(*[v for s in size for v in (s >> m, 1 << m)], 3).mean(dim=tuple(range(1, 2 * len(size), 2)))
+
+
+def test_fit_mips_beats_point_sampling_the_full_detail_field(dev):
+    """field A is fit on the mip chain with fit_mips, field B (same budget, seeds and epoch count) on the image with fit.  Against the
+    box-filtered target, A.decode_mip(m) must beat B.resample(S / 2^m), which point-samples every level finer than its pixel.
+    Measured on an MI355X (PSNR in dB): see DESIGN 4.7.8."""
+    from neural_image_compression_v2_amd.hashgrid import HashGridField
+    size, epochs = (64, 64), 300
+    image = _striped(size, dev)
+    kw = dict(levels=8, features=2, log2_table=12, device=dev, seed=21, fused=True)
+    A, B = HashGridField(size, **kw), HashGridField(size, **kw)
+    assert A.route == B.route == "fused" and torch.equal(A.table, B.table)
+    ha = A.fit_mips(image, epochs, mips=2)
+    hb = B.fit(image, epochs)
+    assert len(ha) == len(hb) == epochs and A.steps == B.steps == epochs
+    print(f"m = 0: fit_mips + decode_mip(0) {psnr(A.decode_mip(0), image):.2f} dB, fit + decode {psnr(B.decode(), image):.2f} dB")
+    for m in (1, 2):
+        want = _box(image, m)
+        pa, pb = psnr(A.decode_mip(m), want), psnr(B.resample(tuple(s >> m for s in size)), want)
+        print(f"m = {m}: fit_mips + decode_mip {pa:.2f} dB, fit + resample {pb:.2f} dB")
+        assert pa > pb, (m, pa, pb)
