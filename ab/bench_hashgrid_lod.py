@@ -1,4 +1,4 @@
-"""The hash-grid field's per-point level of detail (hashgrid.py query / train_points(lod=), decode_mip; csrc/lod_points.hip): what
+"""The hash-grid field's per-point level of detail (hashgrid.py query / train_points(lod=), decode_mip; csrc/hash_points.hip, csrc/hash_points_train.hip): what
 the lambda = 0 lod routes cost over the plain point routes, and what a mip costs against the full decode and against point-sampling the
 full-detail field at the mip's size; prints one JSON line:
 

@@ -669,7 +669,7 @@ int nic_hash_fused_forward_backward_levels(const nic_hash_desc *desc, const nic_
                                            size_t workspace_bytes, const nic_step_tail *tail, void *stream);
 
 /* ---- the hash-grid field at points with a level of detail PER POINT (hashgrid.py, HashGridField.query / train_points(lod=), decode_mip,
- *      fit_mips; csrc/lod_points.hip).  What a texture sampler has: lambda fades the levels finer than a query's footprint out,
+ *      fit_mips; csrc/hash_points.hip, csrc/hash_points_train.hip).  What a texture sampler has: lambda fades the levels finer than a query's footprint out,
  *      before the decoder.
  *      - lambda of point n = (lod ? lod[n] : 0) + lod_uniform in fp32; NaN becomes 0; the sum is then clamped to [0, 32].  lod = [n_points]
  *        fp32 (device; the host never reads it) or NULL; with an `order` it is read at order[n] like the point.

@@ -1,5 +1,5 @@
-// What the hash-grid kernels share, the one copy of it: all six translation units (hash_grid.hip, hash_fused.hip, hash_points.hip,
-// hash_points_train.hip, hash_mixed.hip, lod_points.hip) include this header and keep only their kernels, parameter structs and launch tables.
+// What the hash-grid kernels share, the one copy of it: all five translation units (hash_grid.hip, hash_fused.hip, hash_points.hip,
+// hash_points_train.hip, hash_mixed.hip) include this header and keep only their kernels, parameter structs and launch tables.
 // The index helpers, the fp32, uint8 and packed row loaders, the cell of a lattice sample (2 S_max arithmetic) and the fixed-point position and
 // cell of a point or of a lattice sample (include/nicv2_hip.h, nic_hash_encode_points), the level loops of the encode (row into an LDS tile) and
 // of the scatter (run sums keyed on the base vertex), the ColorDecoder(L F, 64, 3) forward + backward on v_mfma_f32_32x32x2_f32 with its
@@ -8,6 +8,9 @@
 // does not depend on where a helper is declared (profiles/hashgrid_common_disasm.txt).  run_masks / run_sum, the noise generator and the
 // activations come from nic_device.hpp, the optimiser tail from nic_adam.hpp.
 #pragma once
+#include <cmath>
+#include <type_traits>
+
 #include "nic_device.hpp"
 #include "nic_adam.hpp"
 
@@ -228,54 +231,195 @@ __device__ __forceinline__ void lattice_fixed(const nic_hash_desc& d, const int3
     if (D == 2) t[2] = 0;
 }
 
-// the level loop of hash_points_encode_kernel from the fp32 table, the row going value by value into `row` (an LDS tile); NOISE: the noise of
-// nic_hash_encode_noisy keyed by `sample` and the column
-template <int D, int F, bool NOISE>
-__device__ __forceinline__ void encode_point_f32(const nic_hash_desc& d, const float* table, const uint32_t (&t)[3], const NoiseSrc& noise,
-                                                 uint64_t sample, float* row) {
+// ---- the field at points, with and without a level of detail per point ---------------------------------------------------------------------
+// the parameters of the four kernels with a level of detail per point (hash_points.hip, hash_points_train.hip)
+struct LodParams {
+    nic_hash_desc d;          // extent[a] = S_a, num_crops = 1
+    float fade[NIC_HASH_MAX_LEVELS];
+    float lod_uniform;
+    const float* lod;         // null, or [n]
+    const float* points;      // [n, dim]
+    int64_t n;
+    const int32_t* order;     // null, or [n] row indices (clamped); backward and fused training only
+    const float* table;       // NIC_HASH_SRC_F32
+    const uint8_t* stored;    // NIC_HASH_SRC_U8
+    const uint32_t* packed;   // NIC_HASH_SRC_BITS, 4-byte aligned
+    const float* dx;
+    float* out;
+    float* grad;              // table gradient (fused training: null = frozen table, no scatter)
+    NoiseSrc noise;
+    uint64_t sample_base;
+    float q_scale, q_bias;    // load4fp: (u - q_bias + 1) / q_scale
+    int32_t q_bits, q_tight;
+    // fused only
+    const float *w1, *b1, *w2, *b2, *w3, *b3;
+    const float* target;
+    float* y;
+    float* partials;
+    float dscale;             // 2 loss_scale / (3 N)
+};
+template <class Params>
+constexpr bool is_lod = std::is_same<Params, LodParams>::value;
+
+// the row lane `pos` of a launch handles: order[pos] clamped into the n points, or pos itself
+__device__ __forceinline__ int64_t ordered_row(const int32_t* order, int64_t n, int64_t pos) {
+    if (order == nullptr) return pos;
+    const int64_t i = order[pos];
+    return i < 0 ? 0 : (i >= n ? n - 1 : i);
+}
+// lambda of point n = (lod ? lod[n] : 0) + lod_uniform, NaN -> 0, clamped to [0, 32]
+__device__ __forceinline__ float point_lambda(const float* lod, float lod_uniform, int64_t n) {
+    float v = __fadd_rn(lod != nullptr ? lod[n] : 0.f, lod_uniform);
+    v = v == v ? v : 0.f;
+    v = v >= 0.f ? v : 0.f;
+    return v <= 32.f ? v : 32.f;
+}
+// a_l = min(max((fade[l] - lambda) + 1, 0), 1): one subtract, one add, nothing to contract
+__device__ __forceinline__ float level_weight(float fade, float lam) {
+    const float a = __fadd_rn(__fsub_rn(fade, lam), 1.0f);
+    return a >= 0.f ? (a <= 1.f ? a : 1.f) : 0.f;
+}
+// lambda of row n of a launch: LodParams', and 0 for every other parameter struct (which has no level of detail)
+__device__ __forceinline__ float point_lambda(const LodParams& p, int64_t n) { return point_lambda(p.lod, p.lod_uniform, n); }
+template <class Params>
+__device__ __forceinline__ float point_lambda(const Params&, int64_t) {
+    return 0.f;
+}
+__device__ __forceinline__ const float* level_fade(const LodParams& p) { return p.fade; }
+template <class Params>
+__device__ __forceinline__ const float* level_fade(const Params&) {
+    return nullptr;
+}
+
+// each XCD (blocks b, b + 8, ..) walks one contiguous range of groups of 4 wave items
+struct WaveRange {
+    int64_t begin, end;
+    int step;
+};
+__device__ __forceinline__ WaveRange xcd_range(int64_t n_waves) {
+    const int xcd = blockIdx.x & 7;
+    const int64_t n_groups = (n_waves + 3) >> 2, chunk = (n_groups + 7) >> 3;
+    const int64_t g_begin = xcd * chunk;
+    return WaveRange{g_begin + (blockIdx.x >> 3), g_begin + chunk < n_groups ? g_begin + chunk : n_groups, (int)(gridDim.x >> 3)};
+}
+
+// THE level loop of a table of one bit depth at one point (hash_encode_kernel's, on the fixed-point position t).  `s` is whatever holds the
+// source - a kernel's parameter struct: d, the table of SRC (table / stored + q_scale, q_bias / packed + q_bits too), with NOISE noise and
+// sample_base, with LOD fade - and each field is read where the loop uses it: filled into a struct of its own at the call site, the kernarg
+// loads move and every kernel compiles to other code.  SRC picks the loader; NOISE: the noise of nic_hash_encode_noisy keyed
+// by sample_base + n and the column; VEC: the row goes out in F-wide stores (global), else value by value (an LDS tile).
+// LOD: level l is weighed by a_l = level_weight(fade[l], lam), column l F + f is fl(a_l r).  A level no lane of the wave weighs
+// above 0 is jumped over by the whole wave (the ballot is wave-uniform: no cell arithmetic, no gather, no noise - its stored offsets still
+// advance); inside a live level a lane of weight 0 reads nothing and writes zeros; the generator block of columns (l F) & ~15 .. is made by
+// the first LIVE level of this lane that needs it, so a skipped level at a block boundary leaves the later levels of the block their noise.
+// `dense` and the zero fill stand where the loop without and the loop with a level of detail each had them: the order is the schedule's.
+template <int D, int F, int SRC, bool NOISE, bool TIGHT, bool VEC, bool LOD, class Src>
+__device__ __forceinline__ void encode_point_levels(const Src& s, const uint32_t (&t)[3], int64_t n, float lam, float* row) {
+    const nic_hash_desc& d = s.d;
     const uint32_t S = (uint32_t)d.S_max, mask = (1u << d.log2_table) - 1u;
     const float fdiv = (float)(256u * S);
-    [[maybe_unused]] U4 nblk{0u, 0u, 0u, 0u};
+    [[maybe_unused]] int64_t lev_off = 0;              // _U8: byte offset of level l = F * sum_{k<l} E_k
+    [[maybe_unused]] int64_t lev_dw = 0;               // _BITS: dword offset of level l = sum_{k<l} ceil(E_k F b / 32)
+    [[maybe_unused]] U4 nblk{0u, 0u, 0u, 0u};          // NOISE: the generator block of columns (l F) & ~15 ..; LOD: block `nblk_id` (-1: none yet)
+    [[maybe_unused]] int nblk_id = -1;
 #pragma unroll 2
     for (int l = 0; l < d.levels; ++l) {
         const uint32_t R = (uint32_t)d.resolution[l];
-        const bool dense = hash_level_dense(D, (int32_t)R, d.log2_table);
-        const float* tab = table + ((int64_t)l << d.log2_table) * F;
-        uint32_t v[3];
-        float w[3];
-        point_cell<D>(t, R, S, fdiv, v, w);
+        [[maybe_unused]] bool dense = false;
+        if constexpr (!LOD) dense = hash_level_dense(D, (int32_t)R, d.log2_table);
+        [[maybe_unused]] const float* tab = nullptr;
+        if constexpr (SRC == NIC_HASH_SRC_F32) tab = s.table + ((int64_t)l << d.log2_table) * F;
+        [[maybe_unused]] const uint8_t* stab = nullptr;
+        if constexpr (SRC == NIC_HASH_SRC_U8) {
+            stab = s.stored + lev_off;
+            lev_off += (int64_t)F * hash_level_entries(D, (int32_t)R, d.log2_table);
+        }
+        [[maybe_unused]] const uint32_t* btab = nullptr;
+        if constexpr (SRC == NIC_HASH_SRC_BITS) {
+            btab = s.packed + lev_dw;
+            lev_dw += hash_level_dwords(D, (int32_t)R, d.log2_table, F, s.q_bits);
+        }
+        [[maybe_unused]] float a = 1.0f;
+        if constexpr (LOD) a = level_weight(s.fade[l], lam);
         float acc[F];
+        if constexpr (LOD) {
 #pragma unroll
-        for (int f = 0; f < F; ++f) acc[f] = 0.f;
-#pragma unroll
-        for (int c = 0; c < (1 << D); ++c) {
-            const uint32_t e = hash_index(dense, R, mask, v[0] + (c & 1), v[1] + ((c >> 1) & 1), D == 3 ? v[2] + ((c >> 2) & 1) : 0u);
-            float tv[F];
-            load_row<F>(tab + (int64_t)e * F, tv);
-            const float cw = corner_weight<D>(w, c);
-#pragma unroll
-            for (int f = 0; f < F; ++f) acc[f] += cw * tv[f];
+            for (int f = 0; f < F; ++f) acc[f] = 0.f;
         }
-        if constexpr (NOISE) {
-            // 16 % F == 0: a level's F columns lie in one generator block; it is generated at its first column and reused by the next levels
-            const int c0 = l * F;
-            if ((c0 & 15) == 0) nblk = noise_block(noise, sample, c0 >> 4);
+        if (!LOD || (__ballot(a > 0.f) != 0ull && a > 0.f)) {
+            if constexpr (LOD) dense = hash_level_dense(D, (int32_t)R, d.log2_table);      // only a live level asks
+            uint32_t v[3];
+            float w[3];
+            point_cell<D>(t, R, S, fdiv, v, w);
+            if constexpr (!LOD) {
 #pragma unroll
-            for (int f = 0; f < F; ++f) acc[f] += noise_from_block(noise, nblk, (c0 + f) & 15);
+                for (int f = 0; f < F; ++f) acc[f] = 0.f;
+            }
+#pragma unroll
+            for (int c = 0; c < (1 << D); ++c) {
+                const uint32_t e = hash_index(dense, R, mask, v[0] + (c & 1), v[1] + ((c >> 1) & 1), D == 3 ? v[2] + ((c >> 2) & 1) : 0u);
+                float tv[F];
+                if constexpr (SRC == NIC_HASH_SRC_U8) load_row_u8<F>(stab + (int64_t)e * F, s.q_scale, s.q_bias, tv);
+                else if constexpr (SRC == NIC_HASH_SRC_BITS) load_row_bits<F, TIGHT>(btab, e, s.q_bits, s.q_scale, s.q_bias, tv);
+                else load_row<F>(tab + (int64_t)e * F, tv);
+                const float cw = corner_weight<D>(w, c);
+#pragma unroll
+                for (int f = 0; f < F; ++f) acc[f] += cw * tv[f];
+            }
+            if constexpr (NOISE) {
+                // 16 % F == 0: a level's F columns lie in one generator block, made once (at its first column; LOD: by the block's first live level)
+                const int c0 = l * F;
+                if constexpr (LOD) {
+                    if ((c0 >> 4) != nblk_id) {
+                        nblk_id = c0 >> 4;
+                        nblk = noise_block(s.noise, s.sample_base + (uint64_t)n, nblk_id);
+                    }
+                } else {
+                    if ((c0 & 15) == 0) nblk = noise_block(s.noise, s.sample_base + (uint64_t)n, c0 >> 4);
+                }
+#pragma unroll
+                for (int f = 0; f < F; ++f) acc[f] += noise_from_block(s.noise, nblk, (c0 + f) & 15);
+            }
+            if constexpr (LOD) {
+#pragma unroll
+                for (int f = 0; f < F; ++f) acc[f] = __fmul_rn(a, acc[f]);
+            }
         }
+        if constexpr (VEC) {
+            store_row<F>(row + l * F, acc);
+        } else {
 #pragma unroll
-        for (int f = 0; f < F; ++f) row[l * F + f] = acc[f];
+            for (int f = 0; f < F; ++f) row[l * F + f] = acc[f];
+        }
+    }
+}
+// b is uniform over the launch: the width of the packed window is decided once per row, not per corner
+template <int D, int F, int SRC, bool NOISE, bool VEC, bool LOD, class Src>
+__device__ __forceinline__ void encode_point(const Src& s, const uint32_t (&t)[3], int64_t n, float lam, float* row) {
+    if constexpr (SRC == NIC_HASH_SRC_BITS) {
+        if (s.q_tight) encode_point_levels<D, F, SRC, NOISE, true, VEC, LOD>(s, t, n, lam, row);
+        else encode_point_levels<D, F, SRC, NOISE, false, VEC, LOD>(s, t, n, lam, row);
+    } else {
+        encode_point_levels<D, F, SRC, NOISE, false, VEC, LOD>(s, t, n, lam, row);
     }
 }
 
-// the level loop of hash_points_backward_kernel for one lane's point: `grow(l, g)` hands over the F gradient values of level l (a dead lane
-// gets zeros without the call).  Runs are keyed on the base VERTEX; each lane weighs its own gradient before the sum and only NEIGHBOURING
-// lanes merge, so any point order is right - and cell order makes the runs long.  The whole wave must call this together (shuffles).
-template <int D, int F, class GRow>
-__device__ __forceinline__ void scatter_point(const nic_hash_desc& d, const uint32_t (&t)[3], float* grad, bool live, int lane, GRow grow) {
+// the level loop of the backward for one lane's point: `grow(l, g)` hands over the F gradient values of level l (a dead lane gets zeros without
+// the call).  Runs are keyed on the base VERTEX; each lane weighs its own gradient before the sum and only NEIGHBOURING lanes merge, so any point
+// order is right - and cell order makes the runs long.  The whole wave must call this together (shuffles).  LOD: the gradient of level l is
+// weighed by a_l here; the run sums shuffle across the whole wave, so a level is skipped only when the ballot finds no lane for it, a lane of
+// weight 0 takes part in its run with zeros, and a run whose lanes all weigh 0 issues no atomic.
+template <int D, int F, bool LOD, class GRow>
+__device__ __forceinline__ void scatter_point(const nic_hash_desc& d, const uint32_t (&t)[3], float* grad, const float* fade, float lam, bool live,
+                                              int lane, GRow grow) {
     const uint32_t S = (uint32_t)d.S_max, mask = (1u << d.log2_table) - 1u;
     const float fdiv = (float)(256u * S);
     for (int l = 0; l < d.levels; ++l) {
+        [[maybe_unused]] float a = 1.0f;
+        if constexpr (LOD) {
+            a = live ? level_weight(fade[l], lam) : 0.f;
+            if (__ballot(a > 0.f) == 0ull) continue;
+        }
         const uint32_t R = (uint32_t)d.resolution[l];
         const bool dense = hash_level_dense(D, (int32_t)R, d.log2_table);
         float* gtab = grad + ((int64_t)l << d.log2_table) * F;
@@ -285,10 +429,23 @@ __device__ __forceinline__ void scatter_point(const nic_hash_desc& d, const uint
         float g[F];
 #pragma unroll
         for (int f = 0; f < F; ++f) g[f] = 0.f;
-        if (live) grow(l, g);
+        if constexpr (LOD) {
+            if (a > 0.f) {
+                grow(l, g);
+#pragma unroll
+                for (int f = 0; f < F; ++f) g[f] = __fmul_rn(a, g[f]);
+            }
+        } else {
+            if (live) grow(l, g);
+        }
         const int64_t key = (int64_t)v[0] + ((int64_t)R + 1) * ((int64_t)v[1] + ((int64_t)R + 1) * (int64_t)v[2]);
         const RunMasks m = run_masks(live ? key : -1 - (int64_t)lane, lane);
-        const bool issue = live && m.head;
+        [[maybe_unused]] float weighed = 1.f;           // LOD: lanes of this run with something to add
+        if constexpr (LOD) {
+            weighed = a > 0.f ? 1.f : 0.f;
+            if (m.any_shared) weighed = run_sum(weighed, m);
+        }
+        const bool issue = live && m.head && (!LOD || weighed > 0.f);
 #pragma unroll
         for (int c = 0; c < (1 << D); ++c) {
             const uint32_t e = hash_index(dense, R, mask, v[0] + (c & 1), v[1] + ((c >> 1) & 1), D == 3 ? v[2] + ((c >> 2) & 1) : 0u);
@@ -714,6 +871,64 @@ inline int set_noise(const nic_hash_quant* quant, bool uniform_depth, NoiseSrc& 
     return NIC_OK;
 }
 
+// the table source of a point launch into its parameters (PointParams, LodParams); the caller has refused a null source.  NIC_E_ARG in the
+// order of the _u8 / _bits siblings (bit depth, alignment)
+template <class Params>
+inline int set_point_source(Params& p, const nic_hash_source* src) {
+    if (src->kind == NIC_HASH_SRC_F32) {
+        if (src->num_bits != 0) return NIC_E_ARG;
+        p.table = (const float*)src->data;
+        return NIC_OK;
+    }
+    if (src->kind != NIC_HASH_SRC_U8 && src->kind != NIC_HASH_SRC_BITS) return NIC_E_ARG;
+    if (src->num_bits < 1 || src->num_bits > 8) return NIC_E_ARG;
+    set_dequant(p, src->num_bits);
+    if (src->kind == NIC_HASH_SRC_U8) {
+        p.stored = (const uint8_t*)src->data;
+        return NIC_OK;
+    }
+    if ((uintptr_t)src->data & 3u) return NIC_E_ARG;                 // the gather reads aligned dwords
+    p.packed = (const uint32_t*)src->data;
+    p.q_bits = src->num_bits;
+    p.q_tight = hash_bits_tight(p.d.features, src->num_bits) ? 1 : 0;
+    return NIC_OK;
+}
+// a nic_hash_lod: its checks, and the struct with the per-point array into the parameters
+inline int check_lod(const nic_hash_desc* d, const nic_hash_lod* lp) {
+    for (int l = 0; l < d->levels; ++l)
+        if (!std::isfinite(lp->fade[l]) || lp->fade[l] < 0.f) return NIC_E_ARG;
+    if (!std::isfinite(lp->lod_uniform) || lp->reserved != 0) return NIC_E_ARG;
+    return NIC_OK;
+}
+inline void set_lod(LodParams& p, const nic_hash_lod* lp, const float* lod) {
+    for (int l = 0; l < NIC_HASH_MAX_LEVELS; ++l) p.fade[l] = l < p.d.levels ? lp->fade[l] : 0.f;
+    p.lod_uniform = lp->lod_uniform;
+    p.lod = lod;
+}
+
+// dim x features of a checked descriptor as compile-time constants: fn(std::integral_constant<int, D>, std::integral_constant<int, F>), then the
+// error of the launch fn made; `kind` of a checked nic_hash_source likewise
+template <class Fn>
+inline int dispatch_dim_features(const nic_hash_desc& d, Fn fn) {
+    auto features = [&](auto dim) {
+        switch (d.features) {
+            case 1: fn(dim, std::integral_constant<int, 1>{}); break;
+            case 2: fn(dim, std::integral_constant<int, 2>{}); break;
+            case 4: fn(dim, std::integral_constant<int, 4>{}); break;
+            default: fn(dim, std::integral_constant<int, 8>{}); break;
+        }
+    };
+    if (d.dim == 2) features(std::integral_constant<int, 2>{});
+    else features(std::integral_constant<int, 3>{});
+    return (int)hipGetLastError();
+}
+template <class Fn>
+inline int dispatch_source(int kind, Fn fn) {
+    if (kind == NIC_HASH_SRC_U8) return fn(std::integral_constant<int, NIC_HASH_SRC_U8>{});
+    if (kind == NIC_HASH_SRC_BITS) return fn(std::integral_constant<int, NIC_HASH_SRC_BITS>{});
+    return fn(std::integral_constant<int, NIC_HASH_SRC_F32>{});
+}
+
 struct KernelEndDrop {        // a training entry point consumes the parked nic_mark_kernel_end event on every return
     ~KernelEndDrop() { kernel_end_drop(); }
 };
@@ -725,4 +940,48 @@ namespace hfused {
 __global__ void __launch_bounds__(256) hash_fused_reduce_kernel(const float* partials, int n_rec, int lf, nic_mlp_grads g, float* loss, float loss_mul,
                                                                 int add_grads, int add_loss, const StepTail tl);
 }  // namespace hfused
+
+namespace hcommon {
+// ---- the end of a fused training step, the same at every entry point ------------------------------------------------------------------------
+// The optimiser tail that rides on the record reduction (fused_capi.hip, TailScope::open): a decoder entry's gradient must be one of the buffers
+// this call's reduction writes.  Split in two because the entry points return NIC_E_WORKSPACE before the tail's codes and NIC_OK for no points
+// after them.
+struct FusedTail {
+    StepTail tl;
+    int64_t tail_blocks;
+    int reduce_blocks;
+};
+inline int check_fused_tail(const nic_step_tail* tail, const nic_mlp_grads* mlp_grads, int lf, FusedTail& ft) {
+    ft.reduce_blocks = (RecLayout(lf).rec + 31) / 32;
+    ft.tl.t.count = 0; ft.tl.t.sched = nullptr; ft.tl.n_stream = 0; ft.tl.reduce_blocks = 0x7fffffff;
+    ft.tail_blocks = 0;
+    if (!tail) return NIC_OK;
+    if (!tail->tensors) return NIC_E_NULL;
+    if (tail->count < 1 || tail->count > NIC_ADAM_MAX_TENSORS || tail->n_stream < 0 || tail->n_stream > tail->count) return NIC_E_ARG;
+    if (tail->sched != nullptr) return NIC_E_ARG;                     // the device schedule belongs to the captured dense step
+    for (int i = tail->n_stream; i < tail->count; ++i) {
+        bool found = false;
+        for (int k = 0; k < 3; ++k)
+            found = found || (tail->tensors[i].grad != nullptr && (tail->tensors[i].grad == mlp_grads->w[k] || tail->tensors[i].grad == mlp_grads->b[k]));
+        if (!found) return NIC_E_ARG;
+    }
+    const int rc = adam_build_table(tail->tensors, tail->count, tail->n_stream, tail->beta1, tail->beta2, tail->eps, nullptr, 0, nullptr, ft.tl.t,
+                                    ft.tl.n_stream, ft.tail_blocks);
+    if (rc) return rc;
+    ft.tl.reduce_blocks = ft.reduce_blocks;
+    return NIC_OK;
+}
+// `launch()` starts the training kernel, which leaves `grid` records in `partials`; then the end mark and the reduction with the tail
+template <class Launch>
+inline int finish_fused_step(const FusedTail& ft, const nic_mlp_grads* mlp_grads, int flags, int lf, int grid, float loss_mul, float* loss,
+                             const float* partials, void* stream, Launch launch) {
+    const int rc = launch();
+    if (rc) return rc;
+    kernel_end_mark((hipStream_t)stream);
+    hipLaunchKernelGGL(hfused::hash_fused_reduce_kernel, dim3((unsigned)(ft.reduce_blocks + ft.tail_blocks)), dim3(256), 0, (hipStream_t)stream, partials,
+                       grid, lf, *mlp_grads, loss, loss_mul, (flags & NIC_HASH_FUSED_ADD_GRADS) ? 1 : 0, (flags & NIC_HASH_FUSED_ADD_LOSS) ? 1 : 0,
+                       ft.tl);
+    return (int)hipGetLastError();
+}
+}  // namespace hcommon
 }  // namespace nic

@@ -435,20 +435,11 @@ static void launch_kt(const FParams& p, int grid, hipStream_t s) {
     if (p.d.levels * F > 32) hipLaunchKernelGGL((hash_fused_kernel<D, F, 2, MODE>), dim3(grid), dim3(256), 0, s, p);
     else hipLaunchKernelGGL((hash_fused_kernel<D, F, 1, MODE>), dim3(grid), dim3(256), 0, s, p);
 }
-template <int MODE, int D>
-static void launch_f(const FParams& p, int grid, hipStream_t s) {
-    switch (p.d.features) {
-        case 1: launch_kt<MODE, D, 1>(p, grid, s); break;
-        case 2: launch_kt<MODE, D, 2>(p, grid, s); break;
-        case 4: launch_kt<MODE, D, 4>(p, grid, s); break;
-        default: launch_kt<MODE, D, 8>(p, grid, s); break;
-    }
-}
 template <int MODE>
 static int launch(const FParams& p, int grid, void* stream) {
-    if (p.d.dim == 2) launch_f<MODE, 2>(p, grid, (hipStream_t)stream);
-    else launch_f<MODE, 3>(p, grid, (hipStream_t)stream);
-    return (int)hipGetLastError();
+    return dispatch_dim_features(p.d, [&](auto dim, auto features) {
+        launch_kt<MODE, decltype(dim)::value, decltype(features)::value>(p, grid, (hipStream_t)stream);
+    });
 }
 
 static void fill_common(FParams& p, const nic_hash_desc* d, const int32_t* origins, const nic_mlp* mlp, float* y) {
@@ -529,39 +520,14 @@ int nic_hash_fused_forward_backward(const nic_hash_desc* desc, const nic_hash_qu
     p.table = table; p.target = target; p.grad = table_grad;
     if ((rc = set_noise(quant, true, p.noise, p.sample_base)) != NIC_OK) return rc;
     const int lf = desc->levels * desc->features, grid = persistent_grid(p.n_patches);
-    const RecLayout rl(lf);
-    if (workspace_bytes < (size_t)grid * rl.rec * sizeof(float)) return NIC_E_WORKSPACE;
-    // the optimiser tail (fused_capi.hip, TailScope::open): a decoder entry's gradient is one of the buffers this call's reduction writes
-    const int reduce_blocks = (rl.rec + 31) / 32;
-    StepTail tl;
-    tl.t.count = 0; tl.t.sched = nullptr; tl.n_stream = 0; tl.reduce_blocks = 0x7fffffff;
-    int64_t tail_blocks = 0;
-    if (tail) {
-        if (!tail->tensors) return NIC_E_NULL;
-        if (tail->count < 1 || tail->count > NIC_ADAM_MAX_TENSORS || tail->n_stream < 0 || tail->n_stream > tail->count) return NIC_E_ARG;
-        if (tail->sched != nullptr) return NIC_E_ARG;                 // the device schedule belongs to the captured dense step
-        for (int i = tail->n_stream; i < tail->count; ++i) {
-            bool found = false;
-            for (int k = 0; k < 3; ++k)
-                found = found || (tail->tensors[i].grad != nullptr && (tail->tensors[i].grad == mlp_grads->w[k] || tail->tensors[i].grad == mlp_grads->b[k]));
-            if (!found) return NIC_E_ARG;
-        }
-        rc = adam_build_table(tail->tensors, tail->count, tail->n_stream, tail->beta1, tail->beta2, tail->eps, nullptr, 0, nullptr, tl.t, tl.n_stream,
-                              tail_blocks);
-        if (rc) return rc;
-        tl.reduce_blocks = reduce_blocks;
-    }
+    if (workspace_bytes < (size_t)grid * RecLayout(lf).rec * sizeof(float)) return NIC_E_WORKSPACE;
+    FusedTail ft;
+    if ((rc = check_fused_tail(tail, mlp_grads, lf, ft)) != NIC_OK) return rc;
     const double n_samples = (double)desc->num_crops * desc->extent[0] * desc->extent[1] * (desc->dim == 3 ? desc->extent[2] : 1);
     const float loss_mul = (float)((double)loss_scale / (3.0 * n_samples));
     p.dscale = 2.0f * loss_mul;
     p.partials = (float*)workspace;
-    rc = launch<HF_TRAIN>(p, grid, stream);
-    if (rc) return rc;
-    kernel_end_mark((hipStream_t)stream);
-    hipLaunchKernelGGL(hash_fused_reduce_kernel, dim3((unsigned)(reduce_blocks + tail_blocks)), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)p.partials, grid, lf, *mlp_grads, loss, loss_mul, (flags & NIC_HASH_FUSED_ADD_GRADS) ? 1 : 0,
-                       (flags & NIC_HASH_FUSED_ADD_LOSS) ? 1 : 0, tl);
-    return (int)hipGetLastError();
+    return finish_fused_step(ft, mlp_grads, flags, lf, grid, loss_mul, loss, p.partials, stream, [&] { return launch<HF_TRAIN>(p, grid, stream); });
 }
 
 }  // extern "C"

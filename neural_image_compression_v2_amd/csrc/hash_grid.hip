@@ -254,22 +254,12 @@ static void launch_k(const HashParams& p, int nb, hipStream_t s) {
     else hipLaunchKernelGGL((hash_encode_kernel<D, F>), dim3(nb), dim3(256), 0, s, p);
 }
 
-template <int K, int D>
-static void launch_f(const HashParams& p, int nb, hipStream_t s) {
-    switch (p.d.features) {
-        case 1: launch_k<K, D, 1>(p, nb, s); break;
-        case 2: launch_k<K, D, 2>(p, nb, s); break;
-        case 4: launch_k<K, D, 4>(p, nb, s); break;
-        default: launch_k<K, D, 8>(p, nb, s); break;
-    }
-}
-
 template <int K>
 static int hash_launch(const HashParams& p, void* stream) {
     const int nb = strided_grid(count_patches(&p.d));         // one wave per patch, four waves per block
-    if (p.d.dim == 2) launch_f<K, 2>(p, nb, (hipStream_t)stream);
-    else launch_f<K, 3>(p, nb, (hipStream_t)stream);
-    return (int)hipGetLastError();
+    return dispatch_dim_features(p.d, [&](auto dim, auto features) {
+        launch_k<K, decltype(dim)::value, decltype(features)::value>(p, nb, (hipStream_t)stream);
+    });
 }
 
 // F * sum_l E_l; pre (optional) gets the byte offset of every level and the total at [levels]

@@ -55,11 +55,7 @@ __device__ __forceinline__ bool sample_position(const MParams& p, int64_t wv, in
     }
     const int64_t pos = (wv << 6) + lane;
     const bool live = wv < p.n_waves && pos < p.n;
-    row = live ? pos : p.n - 1;
-    if (p.order != nullptr) {
-        const int64_t i = p.order[row];
-        row = i < 0 ? 0 : (i >= p.n ? p.n - 1 : i);
-    }
+    row = ordered_row(p.order, p.n, live ? pos : p.n - 1);
     point_fixed<D>(p.d, p.points, row, t);
     return live;
 }
@@ -148,18 +144,6 @@ __global__ void __launch_bounds__(256) hash_mixed_encode_kernel(const MParams p)
     }
 }
 
-// each XCD (blocks b, b + 8, ..) walks one contiguous range of groups of 4 wave items
-struct WaveRange {
-    int64_t begin, end;
-    int step;
-};
-__device__ __forceinline__ WaveRange xcd_range(int64_t n_waves) {
-    const int xcd = blockIdx.x & 7;
-    const int64_t n_groups = (n_waves + 3) >> 2, chunk = (n_groups + 7) >> 3;
-    const int64_t g_begin = xcd * chunk;
-    return WaveRange{g_begin + (blockIdx.x >> 3), g_begin + chunk < n_groups ? g_begin + chunk : n_groups, (int)(gridDim.x >> 3)};
-}
-
 // ---- gather + decoder in one launch (hash_points_fused_kernel's shape) ----------------------------------------------------------------------
 template <int D, int F, int SRC>
 __global__ void __launch_bounds__(256) hash_mixed_fused_kernel(const MParams p) {
@@ -231,7 +215,7 @@ __global__ void __launch_bounds__(256) hash_mixed_fused_train_kernel(const MPara
         }
         wave_sync();
         if (p.grad != nullptr)
-            scatter_point<D, F>(p.d, t, p.grad, live_lane, lane, [&](int l, float (&gv)[F]) {
+            scatter_point<D, F, false>(p.d, t, p.grad, nullptr, 0.f, live_lane, lane, [&](int l, float (&gv)[F]) {
 #pragma unroll
                 for (int f = 0; f < F; ++f) gv[f] = xrow[l * F + f];
             });
@@ -359,20 +343,11 @@ static void launch_k(const MParams& p, int nb, hipStream_t s) {
         else hipLaunchKernelGGL((hash_mixed_fused_train_kernel<D, F, 1, NOISE>), dim3(nb), dim3(256), 0, s, p);
     }
 }
-template <int K, int D>
-static void launch_f(const MParams& p, int nb, hipStream_t s) {
-    switch (p.d.features) {
-        case 1: launch_k<K, D, 1>(p, nb, s); break;
-        case 2: launch_k<K, D, 2>(p, nb, s); break;
-        case 4: launch_k<K, D, 4>(p, nb, s); break;
-        default: launch_k<K, D, 8>(p, nb, s); break;
-    }
-}
 template <int K>
 static int launch(const MParams& p, int nb, void* stream) {
-    if (p.d.dim == 2) launch_f<K, 2>(p, nb, (hipStream_t)stream);
-    else launch_f<K, 3>(p, nb, (hipStream_t)stream);
-    return (int)hipGetLastError();
+    return dispatch_dim_features(p.d, [&](auto dim, auto features) {
+        launch_k<K, decltype(dim)::value, decltype(features)::value>(p, nb, (hipStream_t)stream);
+    });
 }
 
 }  // namespace hmixed
@@ -492,41 +467,18 @@ int nic_hash_fused_forward_backward_levels(const nic_hash_desc* desc, const nic_
     if ((rc = set_noise(quant, false, p.noise, p.sample_base)) != NIC_OK) return rc;
     if (points && (n_points < 0 || (order && n_points >= (int64_t(1) << 31)))) return NIC_E_ARG;
     const int lf = desc->levels * desc->features;
-    const RecLayout rl(lf);
-    if (workspace_bytes < (size_t)wg_cap() * rl.rec * sizeof(float)) return NIC_E_WORKSPACE;
-    // the optimiser tail (nic_hash_fused_forward_backward): a decoder entry's gradient is one of the buffers this call's reduction writes
-    const int reduce_blocks = (rl.rec + 31) / 32;
-    StepTail tl;
-    tl.t.count = 0; tl.t.sched = nullptr; tl.n_stream = 0; tl.reduce_blocks = 0x7fffffff;
-    int64_t tail_blocks = 0;
-    if (tail) {
-        if (!tail->tensors) return NIC_E_NULL;
-        if (tail->count < 1 || tail->count > NIC_ADAM_MAX_TENSORS || tail->n_stream < 0 || tail->n_stream > tail->count) return NIC_E_ARG;
-        if (tail->sched != nullptr) return NIC_E_ARG;                 // the device schedule belongs to the captured dense step
-        for (int i = tail->n_stream; i < tail->count; ++i) {
-            bool found = false;
-            for (int k = 0; k < 3; ++k)
-                found = found || (tail->tensors[i].grad != nullptr && (tail->tensors[i].grad == mlp_grads->w[k] || tail->tensors[i].grad == mlp_grads->b[k]));
-            if (!found) return NIC_E_ARG;
-        }
-        rc = adam_build_table(tail->tensors, tail->count, tail->n_stream, tail->beta1, tail->beta2, tail->eps, nullptr, 0, nullptr, tl.t, tl.n_stream,
-                              tail_blocks);
-        if (rc) return rc;
-        tl.reduce_blocks = reduce_blocks;
-    }
+    if (workspace_bytes < (size_t)wg_cap() * RecLayout(lf).rec * sizeof(float)) return NIC_E_WORKSPACE;
+    FusedTail ft;
+    if ((rc = check_fused_tail(tail, mlp_grads, lf, ft)) != NIC_OK) return rc;
     if (points && n_points == 0) return NIC_OK;                       // nothing to launch: *loss and every gradient stay as they are
     const double n_samples = points ? (double)n_points : (double)desc->num_crops * desc->extent[0] * desc->extent[1] * (desc->dim == 3 ? desc->extent[2] : 1);
     const int grid = persistent_grid(p.n_waves);
     const float loss_mul = (float)((double)loss_scale / (3.0 * n_samples));
     p.dscale = 2.0f * loss_mul;
     p.partials = (float*)workspace;
-    rc = p.noise.mode == NIC_NOISE_KERNEL ? launch<MK_TRAIN_NOISY>(p, grid, stream) : launch<MK_TRAIN>(p, grid, stream);
-    if (rc) return rc;
-    kernel_end_mark((hipStream_t)stream);
-    hipLaunchKernelGGL(hfused::hash_fused_reduce_kernel, dim3((unsigned)(reduce_blocks + tail_blocks)), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)p.partials, grid, lf, *mlp_grads, loss, loss_mul, (flags & NIC_HASH_FUSED_ADD_GRADS) ? 1 : 0,
-                       (flags & NIC_HASH_FUSED_ADD_LOSS) ? 1 : 0, tl);
-    return (int)hipGetLastError();
+    return finish_fused_step(ft, mlp_grads, flags, lf, grid, loss_mul, loss, p.partials, stream, [&] {
+        return p.noise.mode == NIC_NOISE_KERNEL ? launch<MK_TRAIN_NOISY>(p, grid, stream) : launch<MK_TRAIN>(p, grid, stream);
+    });
 }
 
 }  // extern "C"

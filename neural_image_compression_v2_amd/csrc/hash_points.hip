@@ -10,21 +10,23 @@
 // One lane per point, row n = point n, in any order: the run sums of the backward merge whichever NEIGHBOURING lanes share a base vertex (whole
 // runs in raster order, none for random points, the whole wave when all points coincide).  The fused decode is hash_fused.hip's forward mode
 // with the lane's coordinates taken from the point array.  The helpers are hash_common.hpp's.
+//
+// With a level of detail per point (nic_hash_lod, nic_hash_encode_points_lod, nic_hash_fused_forward_points_lod): level l of point n
+// is weighed by a_l = min(max((fade[l] - lambda_n) + 1, 0), 1), column l F + f of its row is fl(a_l r), r the value without it.  The encode is the
+// same kernel on LodParams; the level loop of hash_common.hpp says what a weight of 0 skips.
 #include "hash_common.hpp"
 
 namespace nic {
 namespace hpoints {
 using namespace hcommon;
 
-enum PointSrc { PSRC_F32 = NIC_HASH_SRC_F32, PSRC_U8 = NIC_HASH_SRC_U8, PSRC_BITS = NIC_HASH_SRC_BITS };
-
 struct PointParams {
     nic_hash_desc d;          // extent[a] = S_a, num_crops = 1
     const float* points;      // [n, dim]
     int64_t n;
-    const float* table;       // PSRC_F32
-    const uint8_t* stored;    // PSRC_U8
-    const uint32_t* packed;   // PSRC_BITS, 4-byte aligned
+    const float* table;       // NIC_HASH_SRC_F32
+    const uint8_t* stored;    // NIC_HASH_SRC_U8
+    const uint32_t* packed;   // NIC_HASH_SRC_BITS, 4-byte aligned
     const float* dx;
     float* out;
     float* grad;
@@ -37,84 +39,19 @@ struct PointParams {
     float* y;
 };
 
-// the level loop of hash_encode_kernel for one point; VEC: the row goes out in F-wide stores (global), else value by value (an LDS tile)
-template <int D, int F, int SRC, bool NOISE, bool TIGHT, bool VEC>
-__device__ __forceinline__ void encode_levels(const PointParams& p, const uint32_t (&t)[3], int64_t n, float* row) {
-    const nic_hash_desc& d = p.d;
-    const uint32_t S = (uint32_t)d.S_max, mask = (1u << d.log2_table) - 1u;
-    const float fdiv = (float)(256u * S);
-    [[maybe_unused]] int64_t lev_off = 0;              // PSRC_U8: byte offset of level l = F * sum_{k<l} E_k
-    [[maybe_unused]] int64_t lev_dw = 0;               // PSRC_BITS: dword offset of level l = sum_{k<l} ceil(E_k F b / 32)
-    [[maybe_unused]] U4 nblk{0u, 0u, 0u, 0u};          // NOISE: the generator block of columns (l F) & ~15 ..
-#pragma unroll 2
-    for (int l = 0; l < d.levels; ++l) {
-        const uint32_t R = (uint32_t)d.resolution[l];
-        const bool dense = hash_level_dense(D, (int32_t)R, d.log2_table);
-        [[maybe_unused]] const float* tab = nullptr;
-        if constexpr (SRC == PSRC_F32) tab = p.table + ((int64_t)l << d.log2_table) * F;
-        [[maybe_unused]] const uint8_t* stab = nullptr;
-        if constexpr (SRC == PSRC_U8) {
-            stab = p.stored + lev_off;
-            lev_off += (int64_t)F * hash_level_entries(D, (int32_t)R, d.log2_table);
-        }
-        [[maybe_unused]] const uint32_t* btab = nullptr;
-        if constexpr (SRC == PSRC_BITS) {
-            btab = p.packed + lev_dw;
-            lev_dw += hash_level_dwords(D, (int32_t)R, d.log2_table, F, p.q_bits);
-        }
-        uint32_t v[3];
-        float w[3];
-        point_cell<D>(t, R, S, fdiv, v, w);
-        float acc[F];
-#pragma unroll
-        for (int f = 0; f < F; ++f) acc[f] = 0.f;
-#pragma unroll
-        for (int c = 0; c < (1 << D); ++c) {
-            const uint32_t e = hash_index(dense, R, mask, v[0] + (c & 1), v[1] + ((c >> 1) & 1), D == 3 ? v[2] + ((c >> 2) & 1) : 0u);
-            float tv[F];
-            if constexpr (SRC == PSRC_U8) load_row_u8<F>(stab + (int64_t)e * F, p.q_scale, p.q_bias, tv);
-            else if constexpr (SRC == PSRC_BITS) load_row_bits<F, TIGHT>(btab, e, p.q_bits, p.q_scale, p.q_bias, tv);
-            else load_row<F>(tab + (int64_t)e * F, tv);
-            const float cw = corner_weight<D>(w, c);
-#pragma unroll
-            for (int f = 0; f < F; ++f) acc[f] += cw * tv[f];
-        }
-        if constexpr (NOISE) {
-            // 16 % F == 0: a level's F columns lie in one block; it is generated once, at its first column, and reused by the next levels
-            const int c0 = l * F;
-            if ((c0 & 15) == 0) nblk = noise_block(p.noise, p.sample_base + (uint64_t)n, c0 >> 4);
-#pragma unroll
-            for (int f = 0; f < F; ++f) acc[f] += noise_from_block(p.noise, nblk, (c0 + f) & 15);
-        }
-        if constexpr (VEC) {
-            store_row<F>(row + l * F, acc);
-        } else {
-#pragma unroll
-            for (int f = 0; f < F; ++f) row[l * F + f] = acc[f];
-        }
-    }
-}
-// b is uniform over the launch: the width of the packed window is decided once per row, not per corner
-template <int D, int F, int SRC, bool NOISE, bool VEC>
-__device__ __forceinline__ void encode_point(const PointParams& p, const uint32_t (&t)[3], int64_t n, float* row) {
-    if constexpr (SRC == PSRC_BITS) {
-        if (p.q_tight) encode_levels<D, F, SRC, NOISE, true, VEC>(p, t, n, row);
-        else encode_levels<D, F, SRC, NOISE, false, VEC>(p, t, n, row);
-    } else {
-        encode_levels<D, F, SRC, NOISE, false, VEC>(p, t, n, row);
-    }
-}
-
-template <int D, int F, int SRC, bool NOISE>
-__global__ void __launch_bounds__(256) hash_points_encode_kernel(const PointParams p) {
+// Params: PointParams, or LodParams with a level of detail per point (hash_common.hpp; the level loop and the scatter are the header's)
+template <int D, int F, int SRC, bool NOISE, class Params>
+__global__ void __launch_bounds__(256) hash_points_encode_kernel(const Params p) {
     const int LF = p.d.levels * F;
     for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < p.n; n += (int64_t)gridDim.x * 256) {
         uint32_t t[3];
         point_fixed<D>(p.d, p.points, n, t);
-        encode_point<D, F, SRC, NOISE, true>(p, t, n, p.out + n * LF);
+        encode_point<D, F, SRC, NOISE, true, is_lod<Params>>(p, t, n, point_lambda(p, n), p.out + n * LF);
     }
 }
 
+// The loop of hash_common.hpp's scatter_point, written out: calling scatter_point here compiles to other code (the zero fill of a dead lane's
+// gradient moves), and that code has not been timed on a GPU
 template <int D, int F>
 __global__ void __launch_bounds__(256) hash_points_backward_kernel(const PointParams p) {
     const nic_hash_desc& d = p.d;
@@ -183,19 +120,16 @@ __global__ void __launch_bounds__(256) hash_points_fused_kernel(const PointParam
     __syncthreads();
     float* xrow = xs + lane * XS;
 
-    // each XCD (blocks b, b + 8, ..) walks one contiguous range of groups of 4 waves of points
     const int64_t n_waves = (p.n + 63) >> 6;
-    const int xcd = blockIdx.x & 7, nb8 = gridDim.x >> 3;
-    const int64_t n_groups = (n_waves + 3) >> 2, chunk = (n_groups + 7) >> 3;
-    const int64_t g_begin = xcd * chunk, g_end = g_begin + chunk < n_groups ? g_begin + chunk : n_groups;
+    const WaveRange wr = xcd_range(n_waves);
     const int ks1 = (LF + 1) >> 1;
-    for (int64_t g = g_begin + (blockIdx.x >> 3); g < g_end; g += nb8) {
+    for (int64_t g = wr.begin; g < wr.end; g += wr.step) {
         const int64_t wv = 4 * g + wave;
         if (wv >= n_waves) continue;                            // wave-uniform; nothing below synchronises the workgroup
         const int64_t n0 = wv << 6, n_raw = n0 + lane;
         uint32_t t[3];
         point_fixed<D>(p.d, p.points, n_raw < p.n ? n_raw : p.n - 1, t);    // a lane past the end decodes the last point; its output is not stored
-        encode_point<D, F, SRC, false, false>(p, t, n_raw, xrow);
+        encode_point<D, F, SRC, false, false, false>(p, t, 0, 0.f, xrow);
         wave_sync();
 #pragma unroll 1
         for (int nt = 0; nt < 2; ++nt) {
@@ -253,61 +187,63 @@ __global__ void __launch_bounds__(256) hash_points_fused_kernel(const PointParam
     }
 }
 
+// the same with the weighed row, on the decoder of hash_common.hpp
+template <int D, int F, int SRC>
+__global__ void __launch_bounds__(256) hash_lod_fused_kernel(const LodParams p) {
+    __shared__ DecoderSmem sm;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 31, half = lane >> 5;
+    const int LF = p.d.levels * F;
+    load_decoder(sm, p.w1, p.b1, p.w2, p.b2, p.w3, p.b3, LF, tid);
+    __syncthreads();
+    float* xs = sm.x[wave];
+    float* xrow = xs + lane * XS;
+    const int64_t n_waves = (p.n + 63) >> 6;
+    const WaveRange wr = xcd_range(n_waves);
+    const int ks1 = (LF + 1) >> 1;
+    for (int64_t g = wr.begin; g < wr.end; g += wr.step) {
+        const int64_t wv = 4 * g + wave;
+        if (wv >= n_waves) continue;                            // wave-uniform; nothing below synchronises the workgroup
+        const int64_t n0 = wv << 6, n_raw = n0 + lane, row = n_raw < p.n ? n_raw : p.n - 1;
+        uint32_t t[3];
+        point_fixed<D>(p.d, p.points, row, t);                  // a lane past the end decodes the last point; its output is not stored
+        encode_point<D, F, SRC, false, false, true>(p, t, 0, point_lambda(p, row), xrow);
+        wave_sync();
+#pragma unroll 1
+        for (int nt = 0; nt < 2; ++nt) {
+            const int64_t n = n0 + 32 * nt + j;
+            float yv[3];
+            decoder_forward_half(sm, xs, nt, j, half, ks1, yv);
+            if (half == 0 && n < p.n) {
+#pragma unroll
+                for (int o = 0; o < 3; ++o) p.y[n * 3 + o] = yv[o];
+            }
+        }
+        wave_sync();
+    }
+}
+
 // ---- host side (the descriptor checks and grid rules are hash_common.hpp's) -------------------------------------------------------------
-// the table source into the parameters; NIC_E_NULL / NIC_E_ARG in the order of the _u8 / _bits siblings (null, bit depth, alignment)
 static int check_source(const nic_hash_source* src) {
     if (!src || !src->data) return NIC_E_NULL;
-    return NIC_OK;
-}
-static int set_source(PointParams& p, const nic_hash_source* src) {
-    if (src->kind == NIC_HASH_SRC_F32) {
-        if (src->num_bits != 0) return NIC_E_ARG;
-        p.table = (const float*)src->data;
-        return NIC_OK;
-    }
-    if (src->kind != NIC_HASH_SRC_U8 && src->kind != NIC_HASH_SRC_BITS) return NIC_E_ARG;
-    if (src->num_bits < 1 || src->num_bits > 8) return NIC_E_ARG;
-    set_dequant(p, src->num_bits);
-    if (src->kind == NIC_HASH_SRC_U8) {
-        p.stored = (const uint8_t*)src->data;
-        return NIC_OK;
-    }
-    if ((uintptr_t)src->data & 3u) return NIC_E_ARG;                 // the gather reads aligned dwords
-    p.packed = (const uint32_t*)src->data;
-    p.q_bits = src->num_bits;
-    p.q_tight = hash_bits_tight(p.d.features, src->num_bits) ? 1 : 0;
     return NIC_OK;
 }
 
 enum PointKernel { PK_FWD, PK_FWD_NOISY, PK_BWD, PK_FUSED };
 
-template <int K, int SRC, int D, int F>
-static void launch_k(const PointParams& p, int nb, hipStream_t s) {
-    if constexpr (K == PK_BWD) hipLaunchKernelGGL((hash_points_backward_kernel<D, F>), dim3(nb), dim3(256), 0, s, p);
-    else if constexpr (K == PK_FUSED) hipLaunchKernelGGL((hash_points_fused_kernel<D, F, SRC>), dim3(nb), dim3(256), 0, s, p);
-    else if constexpr (K == PK_FWD_NOISY) hipLaunchKernelGGL((hash_points_encode_kernel<D, F, PSRC_F32, true>), dim3(nb), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((hash_points_encode_kernel<D, F, SRC, false>), dim3(nb), dim3(256), 0, s, p);
+template <int K, int SRC, class Params>
+static int launch(const Params& p, int nb, void* stream) {
+    return dispatch_dim_features(p.d, [&](auto dim, auto features) {
+        constexpr int D = decltype(dim)::value, F = decltype(features)::value;
+        const hipStream_t s = (hipStream_t)stream;
+        if constexpr (K == PK_FUSED && is_lod<Params>) hipLaunchKernelGGL((hash_lod_fused_kernel<D, F, SRC>), dim3(nb), dim3(256), 0, s, p);
+        else if constexpr (K == PK_FUSED) hipLaunchKernelGGL((hash_points_fused_kernel<D, F, SRC>), dim3(nb), dim3(256), 0, s, p);
+        else if constexpr (K == PK_BWD) hipLaunchKernelGGL((hash_points_backward_kernel<D, F>), dim3(nb), dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((hash_points_encode_kernel<D, F, SRC, K == PK_FWD_NOISY, Params>), dim3(nb), dim3(256), 0, s, p);
+    });
 }
-template <int K, int SRC, int D>
-static void launch_f(const PointParams& p, int nb, hipStream_t s) {
-    switch (p.d.features) {
-        case 1: launch_k<K, SRC, D, 1>(p, nb, s); break;
-        case 2: launch_k<K, SRC, D, 2>(p, nb, s); break;
-        case 4: launch_k<K, SRC, D, 4>(p, nb, s); break;
-        default: launch_k<K, SRC, D, 8>(p, nb, s); break;
-    }
-}
-template <int K, int SRC>
-static int launch_d(const PointParams& p, int nb, void* stream) {
-    if (p.d.dim == 2) launch_f<K, SRC, 2>(p, nb, (hipStream_t)stream);
-    else launch_f<K, SRC, 3>(p, nb, (hipStream_t)stream);
-    return (int)hipGetLastError();
-}
-template <int K>
-static int launch_src(const PointParams& p, int kind, int nb, void* stream) {
-    if (kind == NIC_HASH_SRC_U8) return launch_d<K, PSRC_U8>(p, nb, stream);
-    if (kind == NIC_HASH_SRC_BITS) return launch_d<K, PSRC_BITS>(p, nb, stream);
-    return launch_d<K, PSRC_F32>(p, nb, stream);
+template <int K, class Params>
+static int launch_src(const Params& p, int kind, int nb, void* stream) {
+    return dispatch_source(kind, [&](auto src) { return launch<K, decltype(src)::value>(p, nb, stream); });
 }
 
 }  // namespace hpoints
@@ -326,13 +262,13 @@ int nic_hash_encode_points(const nic_hash_desc* desc, const nic_hash_source* src
     if (!points || !out) return NIC_E_NULL;
     PointParams p{};
     p.d = *desc; p.points = points; p.n = n_points; p.out = out;
-    if ((rc = set_source(p, src)) != NIC_OK) return rc;
+    if ((rc = set_point_source(p, src)) != NIC_OK) return rc;
     if (quant && src->kind != NIC_HASH_SRC_F32) return NIC_E_ARG;        // noise belongs to training, which reads the fp32 table
     if ((rc = set_noise(quant, true, p.noise, p.sample_base)) != NIC_OK) return rc;
     const bool noisy = p.noise.mode == NIC_NOISE_KERNEL;
     if (n_points < 0) return NIC_E_ARG;
     if (n_points == 0) return NIC_OK;
-    if (noisy) return launch_d<PK_FWD_NOISY, PSRC_F32>(p, strided_grid((n_points + 63) >> 6), stream);
+    if (noisy) return launch<PK_FWD_NOISY, NIC_HASH_SRC_F32>(p, strided_grid((n_points + 63) >> 6), stream);
     return launch_src<PK_FWD>(p, src->kind, strided_grid((n_points + 63) >> 6), stream);
 }
 
@@ -344,7 +280,7 @@ int nic_hash_encode_points_backward(const nic_hash_desc* desc, const float* poin
     if (n_points == 0) return NIC_OK;
     PointParams p{};
     p.d = *desc; p.points = points; p.n = n_points; p.dx = dx; p.grad = table_grad;
-    return launch_d<PK_BWD, PSRC_F32>(p, strided_grid((n_points + 63) >> 6), stream);
+    return launch<PK_BWD, NIC_HASH_SRC_F32>(p, strided_grid((n_points + 63) >> 6), stream);
 }
 
 int nic_hash_fused_forward_points(const nic_hash_desc* desc, const nic_hash_source* src, const float* points, int64_t n_points, const nic_mlp* mlp,
@@ -359,7 +295,46 @@ int nic_hash_fused_forward_points(const nic_hash_desc* desc, const nic_hash_sour
         if (!mlp->w[i] || !mlp->b[i]) return NIC_E_NULL;
     PointParams p{};
     p.d = *desc; p.points = points; p.n = n_points; p.y = y;
-    if ((rc = set_source(p, src)) != NIC_OK) return rc;
+    if ((rc = set_point_source(p, src)) != NIC_OK) return rc;
+    if (n_points < 0) return NIC_E_ARG;
+    if (n_points == 0) return NIC_OK;
+    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
+    return launch_src<PK_FUSED>(p, src->kind, persistent_grid((n_points + 63) >> 6), stream);
+}
+
+// ---- with a level of detail per point: the same checks with those of the nic_hash_lod after the null checks, the same launches ------------
+int nic_hash_encode_points_lod(const nic_hash_desc* desc, const nic_hash_lod* lodp, const nic_hash_source* src, const nic_hash_quant* quant,
+                               const float* points, const float* lod, int64_t n_points, float* out, void* stream) {
+    int rc = check_point_desc(desc);
+    if (rc) return rc;
+    if (check_source(src) != NIC_OK || !lodp || !points || !out) return NIC_E_NULL;
+    if ((rc = check_lod(desc, lodp)) != NIC_OK) return rc;
+    LodParams p{};
+    p.d = *desc; p.points = points; p.n = n_points; p.out = out;
+    set_lod(p, lodp, lod);
+    if ((rc = set_point_source(p, src)) != NIC_OK) return rc;
+    if (quant && src->kind != NIC_HASH_SRC_F32) return NIC_E_ARG;        // noise belongs to training, which reads the fp32 table
+    if ((rc = set_noise(quant, true, p.noise, p.sample_base)) != NIC_OK) return rc;
+    if (n_points < 0) return NIC_E_ARG;
+    if (n_points == 0) return NIC_OK;
+    if (p.noise.mode == NIC_NOISE_KERNEL) return launch<PK_FWD_NOISY, NIC_HASH_SRC_F32>(p, strided_grid((n_points + 63) >> 6), stream);
+    return launch_src<PK_FWD>(p, src->kind, strided_grid((n_points + 63) >> 6), stream);
+}
+
+int nic_hash_fused_forward_points_lod(const nic_hash_desc* desc, const nic_hash_lod* lodp, const nic_hash_source* src, const float* points,
+                                      const float* lod, int64_t n_points, const nic_mlp* mlp, float* y, void* stream) {
+    if (!desc || !mlp) return NIC_E_NULL;
+    int rc = nic_hash_fused_supported(desc, kH, mlp->n_linear);          // the only copy of the fused set (hash_fused.hip)
+    if (rc) return rc;
+    if ((rc = check_point_desc(desc)) != NIC_OK) return rc;
+    if (check_source(src) != NIC_OK || !lodp || !points || !y) return NIC_E_NULL;
+    for (int i = 0; i < 3; ++i)
+        if (!mlp->w[i] || !mlp->b[i]) return NIC_E_NULL;
+    if ((rc = check_lod(desc, lodp)) != NIC_OK) return rc;
+    LodParams p{};
+    p.d = *desc; p.points = points; p.n = n_points; p.y = y;
+    set_lod(p, lodp, lod);
+    if ((rc = set_point_source(p, src)) != NIC_OK) return rc;
     if (n_points < 0) return NIC_E_ARG;
     if (n_points == 0) return NIC_OK;
     p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];

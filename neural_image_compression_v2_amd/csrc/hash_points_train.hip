@@ -11,6 +11,9 @@
 //             tile and scatters it with the run sums keyed on the base vertex; one record per workgroup, reduced in a fixed order by
 //             hash_fused_reduce_kernel (hash_fused.hip) with the optimiser tail riding on it.
 //
+// With a level of detail per point (nic_hash_encode_points_backward_lod, nic_hash_fused_forward_backward_points_lod) the ordered
+// scatter and the fused step are the same kernels on LodParams: the weight a_l of hash_points.hip on the row and again on its gradient.
+//
 // Every index read from `order` is clamped to [0, n_points - 1]: a buffer that is no permutation gives the sum over the rows it names.
 #include "hash_common.hpp"
 
@@ -37,13 +40,6 @@ struct TParams {
     uint64_t sample_base;
     float dscale;             // 2 loss_scale / (3 N)
 };
-
-// the row lane `pos` of the launch handles: order[pos] clamped into the point set, or pos itself
-__device__ __forceinline__ int64_t ordered_row(const TParams& p, int64_t pos) {
-    if (p.order == nullptr) return pos;
-    const int64_t i = p.order[pos];
-    return i < 0 ? 0 : (i >= p.n ? p.n - 1 : i);
-}
 
 // bit j of x -> bit 2 j (x < 2^31) / bit 3 j (x < 2^21)
 __device__ __forceinline__ uint64_t spread2(uint64_t x) {
@@ -75,23 +71,26 @@ __global__ void __launch_bounds__(256) hash_point_keys_kernel(const TParams p) {
     }
 }
 
-template <int D, int F>
-__global__ void __launch_bounds__(256) hash_points_backward_ordered_kernel(const TParams p) {
+// Params: TParams, or LodParams with a level of detail per point (hash_common.hpp), in both kernels below
+template <int D, int F, class Params>
+__global__ void __launch_bounds__(256) hash_points_backward_ordered_kernel(const Params p) {
     const int lane = threadIdx.x & 63;
     const int LF = p.d.levels * F;
     for (int64_t nb = (int64_t)blockIdx.x * 256; nb < p.n; nb += (int64_t)gridDim.x * 256) {      // block-uniform trip count: the shuffles see whole waves
         const int64_t pos = nb + threadIdx.x;
         const bool live = pos < p.n;
-        const int64_t n = ordered_row(p, live ? pos : p.n - 1);                                     // a dead lane reads the last point, adds nothing
+        const int64_t last = live ? pos : p.n - 1;                                                  // a dead lane reads the last point, adds nothing
+        const int64_t n = ordered_row(p.order, p.n, last);                                          // (`last` first: n is read before order, as it was)
         uint32_t t[3];
         point_fixed<D>(p.d, p.points, n, t);
         const float* drow = p.dx + n * LF;
-        scatter_point<D, F>(p.d, t, p.grad, live, lane, [&](int l, float (&g)[F]) { load_row<F>(drow + l * F, g); });
+        scatter_point<D, F, is_lod<Params>>(p.d, t, p.grad, level_fade(p), point_lambda(p, n), live, lane, [&](int l, float (&g)[F]) { load_row<F>(drow + l * F, g); });
     }
 }
 
-template <int D, int F, int KT, bool NOISE>
-__global__ void __launch_bounds__(256) hash_points_fused_train_kernel(const TParams p) {
+// LodParams: the weight is applied where the row enters the LDS tile and again on d loss / d row before the scatter
+template <int D, int F, int KT, bool NOISE, class Params>
+__global__ void __launch_bounds__(256) hash_points_fused_train_kernel(const Params p) {
     __shared__ TrainSmem sm;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 31, half = lane >> 5;
     const int LF = p.d.levels * F;
@@ -104,21 +103,19 @@ __global__ void __launch_bounds__(256) hash_points_fused_train_kernel(const TPar
     TrainAcc<KT> A;
     A.clear();
 
-    // each XCD (blocks b, b + 8, ..) walks one contiguous range of groups of 4 waves of (ordered) points
     const int64_t n_waves = (p.n + 63) >> 6;
-    const int xcd = blockIdx.x & 7, nb8 = gridDim.x >> 3;
-    const int64_t n_groups = (n_waves + 3) >> 2, chunk = (n_groups + 7) >> 3;
-    const int64_t g_begin = xcd * chunk, g_end = g_begin + chunk < n_groups ? g_begin + chunk : n_groups;
+    const WaveRange wr = xcd_range(n_waves);
     const int ks1 = (LF + 1) >> 1;
-    for (int64_t g = g_begin + (blockIdx.x >> 3); g < g_end; g += nb8) {
+    for (int64_t g = wr.begin; g < wr.end; g += wr.step) {
         const int64_t wv = 4 * g + wave;
         if (wv >= n_waves) continue;                            // wave-uniform; nothing below synchronises the workgroup
         const int64_t pos = (wv << 6) + lane;
         const bool live_lane = pos < p.n;
-        const int64_t row = ordered_row(p, live_lane ? pos : p.n - 1);       // a lane past the end takes the last point; it stores and adds nothing
+        const int64_t row = ordered_row(p.order, p.n, live_lane ? pos : p.n - 1);      // a lane past the end takes the last point; it stores and adds nothing
+        const float lam = point_lambda(p, row);
         uint32_t t[3];
         point_fixed<D>(p.d, p.points, row, t);
-        encode_point_f32<D, F, NOISE>(p.d, p.table, t, p.noise, p.sample_base + (uint64_t)row, xrow);
+        encode_point<D, F, NIC_HASH_SRC_F32, NOISE, false, is_lod<Params>>(p, t, row, lam, xrow);
         wave_sync();
         const unsigned long long live_mask = __ballot(live_lane);
 #pragma unroll 1
@@ -131,7 +128,7 @@ __global__ void __launch_bounds__(256) hash_points_fused_train_kernel(const TPar
         }
         wave_sync();
         if (p.grad != nullptr)
-            scatter_point<D, F>(p.d, t, p.grad, live_lane, lane, [&](int l, float (&gv)[F]) {
+            scatter_point<D, F, is_lod<Params>>(p.d, t, p.grad, level_fade(p), lam, live_lane, lane, [&](int l, float (&gv)[F]) {
 #pragma unroll
                 for (int f = 0; f < F; ++f) gv[f] = xrow[l * F + f];
             });
@@ -141,37 +138,41 @@ __global__ void __launch_bounds__(256) hash_points_fused_train_kernel(const TPar
 }
 
 // ---- host side (the checks and grid rules are hash_common.hpp's) -----------------------------------------------------------------------------
-enum TKernel { TK_KEYS, TK_BWD, TK_TRAIN, TK_TRAIN_NOISY };
+enum TKernel { TK_BWD, TK_TRAIN, TK_TRAIN_NOISY };
 
-template <int K, int D, int F>
-static void launch_k(const TParams& p, int nb, hipStream_t s) {
-    if constexpr (K == TK_BWD) {
-        hipLaunchKernelGGL((hash_points_backward_ordered_kernel<D, F>), dim3(nb), dim3(256), 0, s, p);
-    } else {
+template <int K, class Params>
+static int launch(const Params& p, int nb, void* stream) {
+    return dispatch_dim_features(p.d, [&](auto dim, auto features) {
+        constexpr int D = decltype(dim)::value, F = decltype(features)::value;
         constexpr bool NOISE = K == TK_TRAIN_NOISY;
-        if (p.d.levels * F > 32) hipLaunchKernelGGL((hash_points_fused_train_kernel<D, F, 2, NOISE>), dim3(nb), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((hash_points_fused_train_kernel<D, F, 1, NOISE>), dim3(nb), dim3(256), 0, s, p);
-    }
+        const hipStream_t s = (hipStream_t)stream;
+        if constexpr (K == TK_BWD) hipLaunchKernelGGL((hash_points_backward_ordered_kernel<D, F, Params>), dim3(nb), dim3(256), 0, s, p);
+        else if (p.d.levels * F > 32) hipLaunchKernelGGL((hash_points_fused_train_kernel<D, F, 2, NOISE, Params>), dim3(nb), dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((hash_points_fused_train_kernel<D, F, 1, NOISE, Params>), dim3(nb), dim3(256), 0, s, p);
+    });
 }
-template <int K, int D>
-static void launch_f(const TParams& p, int nb, hipStream_t s) {
-    switch (p.d.features) {
-        case 1: launch_k<K, D, 1>(p, nb, s); break;
-        case 2: launch_k<K, D, 2>(p, nb, s); break;
-        case 4: launch_k<K, D, 4>(p, nb, s); break;
-        default: launch_k<K, D, 8>(p, nb, s); break;
-    }
-}
-template <int K>
-static int launch(const TParams& p, int nb, void* stream) {
-    if constexpr (K == TK_KEYS) {
-        if (p.d.dim == 2) hipLaunchKernelGGL(hash_point_keys_kernel<2>, dim3(nb), dim3(256), 0, (hipStream_t)stream, p);
-        else hipLaunchKernelGGL(hash_point_keys_kernel<3>, dim3(nb), dim3(256), 0, (hipStream_t)stream, p);
-    } else {
-        if (p.d.dim == 2) launch_f<K, 2>(p, nb, (hipStream_t)stream);
-        else launch_f<K, 3>(p, nb, (hipStream_t)stream);
-    }
-    return (int)hipGetLastError();
+
+// what the two fused training entry points share from the first check that needs the parameters on: the quantiser, the point count, the
+// workspace, the tail, then the step.  `p` arrives with everything but noise, dscale and partials set
+template <class Params>
+static int fused_step(Params& p, const nic_hash_quant* quant, const int32_t* order, float loss_scale, const nic_mlp_grads* mlp_grads, float* loss,
+                      int flags, void* workspace, size_t workspace_bytes, const nic_step_tail* tail, void* stream) {
+    p.noise.mode = NIC_NOISE_NONE;
+    int rc = set_noise(quant, true, p.noise, p.sample_base);
+    if (rc) return rc;
+    if (p.n < 0 || (order && p.n >= (int64_t(1) << 31))) return NIC_E_ARG;
+    const int lf = p.d.levels * p.d.features;
+    if (workspace_bytes < (size_t)wg_cap() * RecLayout(lf).rec * sizeof(float)) return NIC_E_WORKSPACE;
+    FusedTail ft;
+    if ((rc = check_fused_tail(tail, mlp_grads, lf, ft)) != NIC_OK) return rc;
+    if (p.n == 0) return NIC_OK;                                      // nothing to launch: *loss and every gradient stay as they are
+    const int grid = persistent_grid((p.n + 63) >> 6);
+    const float loss_mul = (float)((double)loss_scale / (3.0 * (double)p.n));
+    p.dscale = 2.0f * loss_mul;
+    p.partials = (float*)workspace;
+    return finish_fused_step(ft, mlp_grads, flags, lf, grid, loss_mul, loss, p.partials, stream, [&] {
+        return p.noise.mode == NIC_NOISE_KERNEL ? launch<TK_TRAIN_NOISY>(p, grid, stream) : launch<TK_TRAIN>(p, grid, stream);
+    });
 }
 
 }  // namespace hptrain
@@ -194,7 +195,10 @@ int nic_hash_point_keys(const nic_hash_desc* desc, const float* points, int64_t 
     for (uint32_t top = 256u * (uint32_t)desc->S_max - 1u; top; top >>= 1) ++b;
     const int k = desc->dim == 2 ? 31 : 21;
     p.key_shift = b > k ? b - k : 0;
-    return launch<TK_KEYS>(p, strided_grid((n_points + 63) >> 6), stream);
+    const int nb = strided_grid((n_points + 63) >> 6);
+    if (desc->dim == 2) hipLaunchKernelGGL(hash_point_keys_kernel<2>, dim3(nb), dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(hash_point_keys_kernel<3>, dim3(nb), dim3(256), 0, (hipStream_t)stream, p);
+    return (int)hipGetLastError();
 }
 
 int nic_hash_encode_points_backward_ordered(const nic_hash_desc* desc, const float* points, int64_t n_points, const float* dx, const int32_t* order,
@@ -231,44 +235,43 @@ int nic_hash_fused_forward_backward_points(const nic_hash_desc* desc, const nic_
     TParams p{};
     p.d = *desc; p.points = points; p.n = n_points; p.order = order; p.table = table; p.target = target; p.grad = table_grad; p.y = y;
     p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
-    p.noise.mode = NIC_NOISE_NONE;
-    if ((rc = set_noise(quant, true, p.noise, p.sample_base)) != NIC_OK) return rc;
-    if (n_points < 0 || (order && n_points >= (int64_t(1) << 31))) return NIC_E_ARG;
-    const int lf = desc->levels * desc->features;
-    const RecLayout rl(lf);
-    if (workspace_bytes < (size_t)wg_cap() * rl.rec * sizeof(float)) return NIC_E_WORKSPACE;
-    // the optimiser tail (nic_hash_fused_forward_backward): a decoder entry's gradient is one of the buffers this call's reduction writes
-    const int reduce_blocks = (rl.rec + 31) / 32;
-    StepTail tl;
-    tl.t.count = 0; tl.t.sched = nullptr; tl.n_stream = 0; tl.reduce_blocks = 0x7fffffff;
-    int64_t tail_blocks = 0;
-    if (tail) {
-        if (!tail->tensors) return NIC_E_NULL;
-        if (tail->count < 1 || tail->count > NIC_ADAM_MAX_TENSORS || tail->n_stream < 0 || tail->n_stream > tail->count) return NIC_E_ARG;
-        if (tail->sched != nullptr) return NIC_E_ARG;                 // the device schedule belongs to the captured dense step
-        for (int i = tail->n_stream; i < tail->count; ++i) {
-            bool found = false;
-            for (int k = 0; k < 3; ++k)
-                found = found || (tail->tensors[i].grad != nullptr && (tail->tensors[i].grad == mlp_grads->w[k] || tail->tensors[i].grad == mlp_grads->b[k]));
-            if (!found) return NIC_E_ARG;
-        }
-        rc = adam_build_table(tail->tensors, tail->count, tail->n_stream, tail->beta1, tail->beta2, tail->eps, nullptr, 0, nullptr, tl.t, tl.n_stream,
-                              tail_blocks);
-        if (rc) return rc;
-        tl.reduce_blocks = reduce_blocks;
-    }
-    if (n_points == 0) return NIC_OK;                                 // nothing to launch: *loss and every gradient stay as they are
-    const int grid = persistent_grid((n_points + 63) >> 6);
-    const float loss_mul = (float)((double)loss_scale / (3.0 * (double)n_points));
-    p.dscale = 2.0f * loss_mul;
-    p.partials = (float*)workspace;
-    rc = p.noise.mode == NIC_NOISE_KERNEL ? launch<TK_TRAIN_NOISY>(p, grid, stream) : launch<TK_TRAIN>(p, grid, stream);
+    return fused_step(p, quant, order, loss_scale, mlp_grads, loss, flags, workspace, workspace_bytes, tail, stream);
+}
+
+// ---- with a level of detail per point: the checks of the nic_hash_lod follow the null checks, the launches are the same ------
+int nic_hash_encode_points_backward_lod(const nic_hash_desc* desc, const nic_hash_lod* lodp, const float* points, const float* lod, int64_t n_points,
+                                        const float* dx, const int32_t* order, float* table_grad, void* stream) {
+    int rc = check_point_desc(desc);
     if (rc) return rc;
-    kernel_end_mark((hipStream_t)stream);
-    hipLaunchKernelGGL(hfused::hash_fused_reduce_kernel, dim3((unsigned)(reduce_blocks + tail_blocks)), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)p.partials, grid, lf, *mlp_grads, loss, loss_mul, (flags & NIC_HASH_FUSED_ADD_GRADS) ? 1 : 0,
-                       (flags & NIC_HASH_FUSED_ADD_LOSS) ? 1 : 0, tl);
-    return (int)hipGetLastError();
+    if (!lodp || !points || !dx || !table_grad) return NIC_E_NULL;
+    if ((rc = check_lod(desc, lodp)) != NIC_OK) return rc;
+    if (n_points < 0 || (order && n_points >= (int64_t(1) << 31))) return NIC_E_ARG;
+    if (n_points == 0) return NIC_OK;
+    LodParams p{};
+    p.d = *desc; p.points = points; p.n = n_points; p.dx = dx; p.order = order; p.grad = table_grad;
+    set_lod(p, lodp, lod);
+    return launch<TK_BWD>(p, strided_grid((n_points + 63) >> 6), stream);
+}
+
+int nic_hash_fused_forward_backward_points_lod(const nic_hash_desc* desc, const nic_hash_lod* lodp, const nic_hash_quant* quant, const float* table,
+                                               const float* points, const float* lod, int64_t n_points, const int32_t* order, const nic_mlp* mlp,
+                                               const float* target, float loss_scale, float* table_grad, const nic_mlp_grads* mlp_grads, float* loss,
+                                               float* y, int flags, void* workspace, size_t workspace_bytes, const nic_step_tail* tail, void* stream) {
+    const KernelEndDrop end;
+    if (!desc || !mlp) return NIC_E_NULL;
+    int rc = nic_hash_fused_supported(desc, kH, mlp->n_linear);          // the only copy of the fused set (hash_fused.hip)
+    if (rc) return rc;
+    if ((rc = check_point_desc(desc)) != NIC_OK) return rc;
+    bool mlp_ok = true;
+    for (int i = 0; i < 3; ++i) mlp_ok = mlp_ok && mlp->w[i] && mlp->b[i];
+    if (!lodp || !table || !points || !mlp_ok || !target || !mlp_grads || !loss || !workspace) return NIC_E_NULL;
+    if ((rc = check_lod(desc, lodp)) != NIC_OK) return rc;
+    if (flags & ~(NIC_HASH_FUSED_ADD_GRADS | NIC_HASH_FUSED_ADD_LOSS)) return NIC_E_ARG;
+    LodParams p{};
+    p.d = *desc; p.points = points; p.n = n_points; p.order = order; p.table = table; p.target = target; p.grad = table_grad; p.y = y;
+    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
+    set_lod(p, lodp, lod);
+    return fused_step(p, quant, order, loss_scale, mlp_grads, loss, flags, workspace, workspace_bytes, tail, stream);
 }
 
 }  // extern "C"

@@ -53,7 +53,7 @@ that order sums the neighbouring lanes of one cell before the gradient atomics, 
 step at points (``nic_hash_fused_forward_backward_points``: two launches, the optimiser on the reduction); the defaults are the layer-wise,
 unordered call unchanged.  ``fit_points`` fits a fixed (point, colour) set: the order is computed once, every epoch walks it in compact chunks.
 
-A level of detail per point (include/nicv2_hip.h, nic_hash_lod; csrc/lod_points.hip): lambda = (lod[n] or 0) + lod_uniform, NaN ->
+A level of detail per point (include/nicv2_hip.h, nic_hash_lod; csrc/hash_points.hip, hash_points_train.hip): lambda = (lod[n] or 0) + lod_uniform, NaN ->
 0, clamped to [0, 32]; level l is weighed by a_l = min(max((fade[l] - lambda) + 1, 0), 1) before the decoder, ``hash_lod_fade`` gives the
 default fade start max(0, log2(S_max / R_l)), ``HashGridField(..., lod_fade=)`` another.  A level of weight 0 is not gathered, takes no noise
 and no gradient; at weight 1 the columns are the plain route's bit for bit.  ``query`` / ``train_points`` / ``fit_points`` take ``lod=`` (a
@@ -172,6 +172,24 @@ def _check_table(geo: HashGeometry, table: torch.Tensor, name: str = "table") ->
     return t
 
 
+def _quant_struct(quant) -> Optional["_lib.NicHashQuant"]:
+    """``nic_hash_quant`` of a (num_bits, seed, offset, sample_base) tuple - the kernel's own noise keyed by sample_base + row - or None"""
+    if quant is None:
+        return None
+    bits, seed, offset, base = quant
+    return _lib.NicHashQuant(int(bits), _lib.NIC_NOISE_KERNEL, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(base))
+
+
+def _check_grads(geo: HashGeometry, table_grad: Optional[torch.Tensor], mlp_grads=None, params=None) -> None:
+    """the buffers a training kernel writes: ``table_grad`` an fp32 [L, T, F] device table it can add into in place; with ``params``, ``mlp_grads``
+    six buffers shaped like them, and ``table_grad`` may be None (a frozen table)"""
+    if (table_grad is not None or params is None) and _check_table(geo, table_grad, "table_grad") is not table_grad:
+        raise ValueError("table_grad must be contiguous: the kernel adds into it in place")
+    if params is not None and (len(mlp_grads) != 6 or any(not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.shape == q.shape)
+                                                            for g, q in zip(mlp_grads, params))):
+        raise ValueError("mlp_grads: six contiguous fp32 device buffers shaped like the decoder's parameters")
+
+
 def _n_samples(num_crops: int, extent: Sequence[int]) -> int:
     n = int(num_crops)
     for e in extent:
@@ -194,16 +212,14 @@ def hash_encode(geo: HashGeometry, table: torch.Tensor, coord, extent: Sequence[
 @fused._on_tensor_device
 def hash_encode_backward(geo: HashGeometry, org: torch.Tensor, extent: Sequence[int], dx: torch.Tensor, table_grad: torch.Tensor) -> None:
     """ADDS d loss / d table for the [N, L F] gradient ``dx`` of the encoding into ``table_grad`` (nic_hash_encode_backward; fp32 atomics)"""
-    g = _check_table(geo, table_grad, "table_grad")
-    if g is not table_grad:
-        raise ValueError("table_grad must be contiguous: the kernel adds into it in place")
+    _check_grads(geo, table_grad)
     dx = _lib.require_cuda_f32(dx, "dx")
     num_crops = org.shape[0]
     if tuple(dx.shape) != (_n_samples(num_crops, extent), geo.width):
         raise ValueError(f"dx must be [{_n_samples(num_crops, extent)}, {geo.width}], got {tuple(dx.shape)}")
     d = geo.to_desc(num_crops, extent)
-    _lib.check(_lib.load().nic_hash_encode_backward(ctypes.byref(d), _lib.ptr(org), _lib.ptr(dx), _lib.ptr(g), _lib.stream_ptr(g.device)),
-               "nic_hash_encode_backward")
+    _lib.check(_lib.load().nic_hash_encode_backward(ctypes.byref(d), _lib.ptr(org), _lib.ptr(dx), _lib.ptr(table_grad),
+                                                    _lib.stream_ptr(table_grad.device)), "nic_hash_encode_backward")
 
 
 @fused._on_tensor_device
@@ -216,7 +232,7 @@ def hash_encode_noisy(geo: HashGeometry, table: torch.Tensor, coord, extent: Seq
     num_crops = org.shape[0]
     out = torch.empty(_n_samples(num_crops, extent), geo.width, dtype=torch.float32, device=t.device)
     d = geo.to_desc(num_crops, extent)
-    q = _lib.NicHashQuant(int(num_bits), _lib.NIC_NOISE_KERNEL, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(sample_base))
+    q = _quant_struct((num_bits, seed, offset, sample_base))
     _lib.check(_lib.load().nic_hash_encode_noisy(ctypes.byref(d), ctypes.byref(q), _lib.ptr(t), _lib.ptr(org), _lib.ptr(out), _lib.stream_ptr(t.device)),
                "nic_hash_encode_noisy")
     return out
@@ -415,20 +431,12 @@ def hash_fused_forward_backward(geo: HashGeometry, table: torch.Tensor, coord, e
     target = _lib.require_cuda_f32(target, "target")
     if tuple(target.shape) != (n, 3):
         raise ValueError(f"target must be [{n}, 3], got {tuple(target.shape)}")
-    if table_grad is not None:
-        g = _check_table(geo, table_grad, "table_grad")
-        if g is not table_grad:
-            raise ValueError("table_grad must be contiguous: the kernel adds into it in place")
-    if len(mlp_grads) != 6 or any(not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.shape == q.shape) for g, q in zip(mlp_grads, params)):
-        raise ValueError("mlp_grads: six contiguous fp32 device buffers shaped like the decoder's parameters")
+    _check_grads(geo, table_grad, mlp_grads, params)
     loss = torch.empty(1, dtype=torch.float32, device=t.device) if loss is None else loss
     y = torch.empty(n, 3, dtype=torch.float32, device=t.device) if want_y else None
     lib = _lib.load()
     d, m, gs = geo.to_desc(org.shape[0], extent), fused._mlp_struct(params), fused._grads_struct(list(mlp_grads))
-    q = None
-    if quant is not None:
-        bits, seed, offset, base = quant
-        q = _lib.NicHashQuant(int(bits), _lib.NIC_NOISE_KERNEL, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(base))
+    q = _quant_struct(quant)
     ws = _lib.workspace(t.device, int(lib.nic_hash_fused_workspace_bytes(ctypes.byref(d), ctypes.byref(m))))
     flags = (_lib.NIC_HASH_FUSED_ADD_GRADS if add_grads else 0) | (_lib.NIC_HASH_FUSED_ADD_LOSS if add_loss else 0)
     _lib.check(lib.nic_hash_fused_forward_backward(ctypes.byref(d), None if q is None else ctypes.byref(q), _lib.ptr(t), _lib.ptr(org), ctypes.byref(m),
@@ -478,27 +486,44 @@ def _point_source(geo: HashGeometry, data: torch.Tensor, kind: str, num_bits: Op
     return _lib.NicHashSource(POINT_SOURCES[kind], int(num_bits), data.data_ptr()), data
 
 
+def _lod_args(geo: HashGeometry, lod, n: int, device):
+    """() without a level of detail (``lod`` None: the plain entry point is called), else (``nic_hash_lod``, the checked per-point tensor or None)
+    of ``lod`` = (lod, lod_uniform, fade)"""
+    if lod is None:
+        return ()
+    per_point = _check_lod(lod[0], n, device)          # the tensor first, then fade and lod_uniform: the order the errors always had
+    return _lod_struct(geo, lod[2], lod[1]), per_point
+
+
+def _encode_points(geo, data, points, kind, num_bits, quant, lod):
+    """``hash_encode_points`` (``lod`` None) and ``hash_encode_points_lod`` (``lod`` = (lod, lod_uniform, fade))"""
+    src, data = _point_source(geo, data, kind, num_bits)
+    pts = _check_points(geo, points)
+    la = _lod_args(geo, lod, pts.shape[0], pts.device)
+    d = _point_desc(geo)
+    out = torch.empty(pts.shape[0], geo.width, dtype=torch.float32, device=data.device)
+    if quant is not None and kind != "f32":
+        raise ValueError("noise belongs to training, which reads the fp32 table")
+    q = _quant_struct(quant)
+    if pts.shape[0] == 0:
+        return out
+    qp, stream = None if q is None else ctypes.byref(q), _lib.stream_ptr(data.device)
+    if la:
+        _lib.check(_lib.load().nic_hash_encode_points_lod(ctypes.byref(d), ctypes.byref(la[0]), ctypes.byref(src), qp, _lib.ptr(pts), _lib.ptr(la[1]),
+                                                          pts.shape[0], _lib.ptr(out), stream), "nic_hash_encode_points_lod")
+    else:
+        _lib.check(_lib.load().nic_hash_encode_points(ctypes.byref(d), ctypes.byref(src), qp, _lib.ptr(pts), pts.shape[0], _lib.ptr(out), stream),
+                   "nic_hash_encode_points")
+    return out
+
+
 @fused._on_tensor_device
 def hash_encode_points(geo: HashGeometry, data: torch.Tensor, points: torch.Tensor, kind: str = "f32", num_bits: Optional[int] = None,
                        quant=None) -> torch.Tensor:
     """[N, L F] encoding at ``points`` [N, dim] (fp32, sample units: p = i is the centre of sample i; anything outside [-1/2, S - 1/2] or not
     finite is clamped by the kernel) from the table ``data`` of ``kind`` "f32" / "u8" / "bits" (nic_hash_encode_points).  ``quant``: None or
     (num_bits, seed, offset, sample_base) for ``hash_encode_noisy``'s noise keyed by sample_base + row (fp32 table only)."""
-    src, data = _point_source(geo, data, kind, num_bits)
-    pts = _check_points(geo, points)
-    d = _point_desc(geo)
-    out = torch.empty(pts.shape[0], geo.width, dtype=torch.float32, device=data.device)
-    q = None
-    if quant is not None:
-        if kind != "f32":
-            raise ValueError("noise belongs to training, which reads the fp32 table")
-        bits, seed, offset, base = quant
-        q = _lib.NicHashQuant(int(bits), _lib.NIC_NOISE_KERNEL, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(base))
-    if pts.shape[0] == 0:
-        return out
-    _lib.check(_lib.load().nic_hash_encode_points(ctypes.byref(d), ctypes.byref(src), None if q is None else ctypes.byref(q), _lib.ptr(pts), pts.shape[0],
-                                                  _lib.ptr(out), _lib.stream_ptr(data.device)), "nic_hash_encode_points")
-    return out
+    return _encode_points(geo, data, points, kind, num_bits, quant, None)
 
 
 def _check_order(order, n: int, device) -> torch.Tensor:
@@ -536,46 +561,103 @@ def hash_point_order(geo: HashGeometry, points: torch.Tensor) -> torch.Tensor:
     return torch.sort(keys, stable=True).indices.to(torch.int32)
 
 
+def _encode_points_backward(geo, points, dx, table_grad, order, lod):
+    """``hash_encode_points_backward`` (``lod`` None) and ``hash_encode_points_backward_lod`` (``lod`` = (lod, lod_uniform, fade))"""
+    _check_grads(geo, table_grad)
+    pts = _check_points(geo, points)
+    n = pts.shape[0]
+    dx = _lib.require_cuda_f32(dx, "dx")
+    if tuple(dx.shape) != (n, geo.width):
+        raise ValueError(f"dx must be [{n}, {geo.width}], got {tuple(dx.shape)}")
+    la = _lod_args(geo, lod, n, pts.device)
+    d = _point_desc(geo)
+    if order is not None:
+        order = _check_order(order, n, pts.device)
+    if n == 0:
+        return
+    lib, stream = _lib.load(), _lib.stream_ptr(table_grad.device)
+    if la:
+        _lib.check(lib.nic_hash_encode_points_backward_lod(ctypes.byref(d), ctypes.byref(la[0]), _lib.ptr(pts), _lib.ptr(la[1]), n, _lib.ptr(dx),
+                                                           _lib.ptr(order), _lib.ptr(table_grad), stream), "nic_hash_encode_points_backward_lod")
+    elif order is not None:
+        _lib.check(lib.nic_hash_encode_points_backward_ordered(ctypes.byref(d), _lib.ptr(pts), n, _lib.ptr(dx), _lib.ptr(order), _lib.ptr(table_grad),
+                                                               stream), "nic_hash_encode_points_backward_ordered")
+    else:
+        _lib.check(lib.nic_hash_encode_points_backward(ctypes.byref(d), _lib.ptr(pts), n, _lib.ptr(dx), _lib.ptr(table_grad), stream),
+                   "nic_hash_encode_points_backward")
+
+
 @fused._on_tensor_device
 def hash_encode_points_backward(geo: HashGeometry, points: torch.Tensor, dx: torch.Tensor, table_grad: torch.Tensor,
                                 order: Optional[torch.Tensor] = None) -> None:
     """ADDS d loss / d table for the [N, L F] gradient ``dx`` of ``hash_encode_points`` into ``table_grad`` (nic_hash_encode_points_backward;
     fp32 atomics, neighbouring points of one cell summed first).  ``order``: an int32 [N] device tensor (``hash_point_order``) - lane n of the
     launch takes point ``order[n]`` (nic_hash_encode_points_backward_ordered): the same sums, neighbours in cell order merged."""
-    g = _check_table(geo, table_grad, "table_grad")
-    if g is not table_grad:
-        raise ValueError("table_grad must be contiguous: the kernel adds into it in place")
+    _encode_points_backward(geo, points, dx, table_grad, order, None)
+
+
+def _fused_forward_points(geo, data, points, params, kind, num_bits, lod):
+    """``hash_fused_forward_points`` (``lod`` None) and ``hash_fused_forward_points_lod`` (``lod`` = (lod, lod_uniform, fade))"""
+    src, data = _point_source(geo, data, kind, num_bits)
+    params = _check_fused_decoder(geo, [q.detach() for q in params])
     pts = _check_points(geo, points)
-    dx = _lib.require_cuda_f32(dx, "dx")
-    if tuple(dx.shape) != (pts.shape[0], geo.width):
-        raise ValueError(f"dx must be [{pts.shape[0]}, {geo.width}], got {tuple(dx.shape)}")
-    d = _point_desc(geo)
-    if order is not None:
-        order = _check_order(order, pts.shape[0], pts.device)
-    if pts.shape[0] == 0:
-        return
-    if order is not None:
-        _lib.check(_lib.load().nic_hash_encode_points_backward_ordered(ctypes.byref(d), _lib.ptr(pts), pts.shape[0], _lib.ptr(dx), _lib.ptr(order),
-                                                                       _lib.ptr(g), _lib.stream_ptr(g.device)), "nic_hash_encode_points_backward_ordered")
-        return
-    _lib.check(_lib.load().nic_hash_encode_points_backward(ctypes.byref(d), _lib.ptr(pts), pts.shape[0], _lib.ptr(dx), _lib.ptr(g), _lib.stream_ptr(g.device)),
-               "nic_hash_encode_points_backward")
+    n = pts.shape[0]
+    la = _lod_args(geo, lod, n, pts.device)
+    d, m = _point_desc(geo), fused._mlp_struct(params)
+    y = torch.empty(n, 3, dtype=torch.float32, device=data.device)
+    if n == 0:
+        return y
+    if la:
+        _lib.check(_lib.load().nic_hash_fused_forward_points_lod(ctypes.byref(d), ctypes.byref(la[0]), ctypes.byref(src), _lib.ptr(pts), _lib.ptr(la[1]), n,
+                                                                 ctypes.byref(m), _lib.ptr(y), _lib.stream_ptr(data.device)),
+                   "nic_hash_fused_forward_points_lod")
+    else:
+        _lib.check(_lib.load().nic_hash_fused_forward_points(ctypes.byref(d), ctypes.byref(src), _lib.ptr(pts), n, ctypes.byref(m), _lib.ptr(y),
+                                                             _lib.stream_ptr(data.device)), "nic_hash_fused_forward_points")
+    return y
 
 
 @fused._on_tensor_device
 def hash_fused_forward_points(geo: HashGeometry, data: torch.Tensor, points: torch.Tensor, params: Sequence[torch.Tensor], kind: str = "f32",
                               num_bits: Optional[int] = None) -> torch.Tensor:
     """[N, 3] = ColorDecoder(hash_encode_points(...)) in one launch (nic_hash_fused_forward_points); ``params`` = W1, b1, W2, b2, W3, b3"""
-    src, data = _point_source(geo, data, kind, num_bits)
+    return _fused_forward_points(geo, data, points, params, kind, num_bits, None)
+
+
+def _fused_forward_backward_points(geo, table, points, params, target, mlp_grads, table_grad, order, loss, loss_scale, want_y, quant, add_grads,
+                                   add_loss, tail, lod):
+    """``hash_fused_forward_backward_points`` (``lod`` None) and ``hash_fused_forward_backward_points_lod`` (``lod`` = (lod, lod_uniform, fade))"""
+    t = _check_table(geo, table.detach())
     params = _check_fused_decoder(geo, [q.detach() for q in params])
     pts = _check_points(geo, points)
-    d, m = _point_desc(geo), fused._mlp_struct(params)
-    y = torch.empty(pts.shape[0], 3, dtype=torch.float32, device=data.device)
-    if pts.shape[0] == 0:
-        return y
-    _lib.check(_lib.load().nic_hash_fused_forward_points(ctypes.byref(d), ctypes.byref(src), _lib.ptr(pts), pts.shape[0], ctypes.byref(m), _lib.ptr(y),
-                                                         _lib.stream_ptr(data.device)), "nic_hash_fused_forward_points")
-    return y
+    n = pts.shape[0]
+    if n < 1:
+        raise ValueError("no points")
+    target = _lib.require_cuda_f32(target, "target")
+    if tuple(target.shape) != (n, 3):
+        raise ValueError(f"target must be [{n}, 3], got {tuple(target.shape)}")
+    lod_tensor = None if lod is None else _check_lod(lod[0], n, pts.device)
+    if order is not None:
+        order = _check_order(order, n, pts.device)
+    _check_grads(geo, table_grad, mlp_grads, params)
+    d = _point_desc(geo)
+    lp = None if lod is None else _lod_struct(geo, lod[2], lod[1])
+    loss = torch.empty(1, dtype=torch.float32, device=t.device) if loss is None else loss
+    y = torch.empty(n, 3, dtype=torch.float32, device=t.device) if want_y else None
+    lib = _lib.load()
+    m, gs = fused._mlp_struct(params), fused._grads_struct(list(mlp_grads))
+    q = _quant_struct(quant)
+    ws = _lib.workspace(t.device, int(lib.nic_hash_fused_points_workspace_bytes(ctypes.byref(d), ctypes.byref(m))))
+    flags = (_lib.NIC_HASH_FUSED_ADD_GRADS if add_grads else 0) | (_lib.NIC_HASH_FUSED_ADD_LOSS if add_loss else 0)
+    qp, head = None if q is None else ctypes.byref(q), (ctypes.byref(d),) if lp is None else (ctypes.byref(d), ctypes.byref(lp))
+    where = (_lib.ptr(pts), n) if lp is None else (_lib.ptr(pts), _lib.ptr(lod_tensor), n)
+    name = "nic_hash_fused_forward_backward_points" if lp is None else "nic_hash_fused_forward_backward_points_lod"
+    _lib.check(getattr(lib, name)(*head, qp, _lib.ptr(t), *where, _lib.ptr(order), ctypes.byref(m), _lib.ptr(target), float(loss_scale),
+                                  _lib.ptr(table_grad), ctypes.byref(gs), _lib.ptr(loss), _lib.ptr(y), flags, _lib.ptr(ws), ws.numel(),
+                                  None if tail is None else ctypes.byref(tail.struct), _lib.stream_ptr(t.device)), name)
+    if tail is not None:
+        tail.commit()
+    return loss, y
 
 
 @fused._on_tensor_device
@@ -587,42 +669,8 @@ def hash_fused_forward_backward_points(geo: HashGeometry, table: torch.Tensor, p
     loss_scale over ``points`` [N, dim] with ``target`` [N, 3], in two launches.  ``order``: None or an int32 [N] device tensor
     (``hash_point_order``) - wave w takes points order[64 w ..]; targets, outputs and noise keys stay at the caller's rows, so the result is the
     unordered call's up to the order of the sums.  Everything else as there.  Returns (loss [1], y or None)."""
-    t = _check_table(geo, table.detach())
-    params = _check_fused_decoder(geo, [q.detach() for q in params])
-    pts = _check_points(geo, points)
-    n = pts.shape[0]
-    if n < 1:
-        raise ValueError("no points")
-    target = _lib.require_cuda_f32(target, "target")
-    if tuple(target.shape) != (n, 3):
-        raise ValueError(f"target must be [{n}, 3], got {tuple(target.shape)}")
-    if order is not None:
-        order = _check_order(order, n, pts.device)
-    if table_grad is not None:
-        g = _check_table(geo, table_grad, "table_grad")
-        if g is not table_grad:
-            raise ValueError("table_grad must be contiguous: the kernel adds into it in place")
-    if len(mlp_grads) != 6 or any(not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.shape == q.shape) for g, q in zip(mlp_grads, params)):
-        raise ValueError("mlp_grads: six contiguous fp32 device buffers shaped like the decoder's parameters")
-    d = _point_desc(geo)
-    loss = torch.empty(1, dtype=torch.float32, device=t.device) if loss is None else loss
-    y = torch.empty(n, 3, dtype=torch.float32, device=t.device) if want_y else None
-    lib = _lib.load()
-    m, gs = fused._mlp_struct(params), fused._grads_struct(list(mlp_grads))
-    q = None
-    if quant is not None:
-        bits, seed, offset, base = quant
-        q = _lib.NicHashQuant(int(bits), _lib.NIC_NOISE_KERNEL, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(base))
-    ws = _lib.workspace(t.device, int(lib.nic_hash_fused_points_workspace_bytes(ctypes.byref(d), ctypes.byref(m))))
-    flags = (_lib.NIC_HASH_FUSED_ADD_GRADS if add_grads else 0) | (_lib.NIC_HASH_FUSED_ADD_LOSS if add_loss else 0)
-    _lib.check(lib.nic_hash_fused_forward_backward_points(ctypes.byref(d), None if q is None else ctypes.byref(q), _lib.ptr(t), _lib.ptr(pts), n,
-                                                          _lib.ptr(order), ctypes.byref(m), _lib.ptr(target), float(loss_scale), _lib.ptr(table_grad),
-                                                          ctypes.byref(gs), _lib.ptr(loss), _lib.ptr(y), flags, _lib.ptr(ws), ws.numel(),
-                                                          None if tail is None else ctypes.byref(tail.struct), _lib.stream_ptr(t.device)),
-               "nic_hash_fused_forward_backward_points")
-    if tail is not None:
-        tail.commit()
-    return loss, y
+    return _fused_forward_backward_points(geo, table, points, params, target, mlp_grads, table_grad, order, loss, loss_scale, want_y, quant,
+                                          add_grads, add_loss, tail, None)
 
 
 @functools.lru_cache(maxsize=64)
@@ -674,23 +722,7 @@ def hash_encode_points_lod(geo: HashGeometry, data: torch.Tensor, points: torch.
     """``hash_encode_points`` with a level of detail per point (nic_hash_encode_points_lod): lambda = (``lod`` [N] or 0) + ``lod_uniform``, NaN ->
     0, clamped to [0, 32]; level l is weighed by min(max((fade[l] - lambda) + 1, 0), 1), ``fade`` = None for ``hash_lod_fade(geo)``.  At weight 1
     the columns are ``hash_encode_points``' bit for bit, at weight 0 they are 0 and the level's table is not read."""
-    src, data = _point_source(geo, data, kind, num_bits)
-    pts = _check_points(geo, points)
-    lod = _check_lod(lod, pts.shape[0], pts.device)
-    d, lp = _point_desc(geo), _lod_struct(geo, fade, lod_uniform)
-    out = torch.empty(pts.shape[0], geo.width, dtype=torch.float32, device=data.device)
-    q = None
-    if quant is not None:
-        if kind != "f32":
-            raise ValueError("noise belongs to training, which reads the fp32 table")
-        bits, seed, offset, base = quant
-        q = _lib.NicHashQuant(int(bits), _lib.NIC_NOISE_KERNEL, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(base))
-    if pts.shape[0] == 0:
-        return out
-    _lib.check(_lib.load().nic_hash_encode_points_lod(ctypes.byref(d), ctypes.byref(lp), ctypes.byref(src), None if q is None else ctypes.byref(q),
-                                                      _lib.ptr(pts), _lib.ptr(lod), pts.shape[0], _lib.ptr(out), _lib.stream_ptr(data.device)),
-               "nic_hash_encode_points_lod")
-    return out
+    return _encode_points(geo, data, points, kind, num_bits, quant, (lod, lod_uniform, fade))
 
 
 @fused._on_tensor_device
@@ -700,22 +732,7 @@ def hash_encode_points_backward_lod(geo: HashGeometry, points: torch.Tensor, dx:
     """``hash_encode_points_backward`` of ``hash_encode_points_lod`` (nic_hash_encode_points_backward_lod): ADDS the gradient of the table for
     ``dx`` weighed per point and level into ``table_grad``; a level of weight 0 takes no atomic.  ``order`` as there (``lod`` is read at
     ``order[n]`` like the point)."""
-    g = _check_table(geo, table_grad, "table_grad")
-    if g is not table_grad:
-        raise ValueError("table_grad must be contiguous: the kernel adds into it in place")
-    pts = _check_points(geo, points)
-    dx = _lib.require_cuda_f32(dx, "dx")
-    if tuple(dx.shape) != (pts.shape[0], geo.width):
-        raise ValueError(f"dx must be [{pts.shape[0]}, {geo.width}], got {tuple(dx.shape)}")
-    lod = _check_lod(lod, pts.shape[0], pts.device)
-    d, lp = _point_desc(geo), _lod_struct(geo, fade, lod_uniform)
-    if order is not None:
-        order = _check_order(order, pts.shape[0], pts.device)
-    if pts.shape[0] == 0:
-        return
-    _lib.check(_lib.load().nic_hash_encode_points_backward_lod(ctypes.byref(d), ctypes.byref(lp), _lib.ptr(pts), _lib.ptr(lod), pts.shape[0],
-                                                               _lib.ptr(dx), _lib.ptr(order), _lib.ptr(g), _lib.stream_ptr(g.device)),
-               "nic_hash_encode_points_backward_lod")
+    _encode_points_backward(geo, points, dx, table_grad, order, (lod, lod_uniform, fade))
 
 
 @fused._on_tensor_device
@@ -723,18 +740,7 @@ def hash_fused_forward_points_lod(geo: HashGeometry, data: torch.Tensor, points:
                                   lod: Optional[torch.Tensor] = None, lod_uniform: float = 0.0, fade=None, kind: str = "f32",
                                   num_bits: Optional[int] = None) -> torch.Tensor:
     """[N, 3] = ColorDecoder(hash_encode_points_lod(...)) in one launch (nic_hash_fused_forward_points_lod)"""
-    src, data = _point_source(geo, data, kind, num_bits)
-    params = _check_fused_decoder(geo, [q.detach() for q in params])
-    pts = _check_points(geo, points)
-    lod = _check_lod(lod, pts.shape[0], pts.device)
-    d, lp, m = _point_desc(geo), _lod_struct(geo, fade, lod_uniform), fused._mlp_struct(params)
-    y = torch.empty(pts.shape[0], 3, dtype=torch.float32, device=data.device)
-    if pts.shape[0] == 0:
-        return y
-    _lib.check(_lib.load().nic_hash_fused_forward_points_lod(ctypes.byref(d), ctypes.byref(lp), ctypes.byref(src), _lib.ptr(pts), _lib.ptr(lod),
-                                                             pts.shape[0], ctypes.byref(m), _lib.ptr(y), _lib.stream_ptr(data.device)),
-               "nic_hash_fused_forward_points_lod")
-    return y
+    return _fused_forward_points(geo, data, points, params, kind, num_bits, (lod, lod_uniform, fade))
 
 
 @fused._on_tensor_device
@@ -745,43 +751,8 @@ def hash_fused_forward_backward_points_lod(geo: HashGeometry, table: torch.Tenso
                                            want_y: bool = False, quant=None, add_grads: bool = False, add_loss: bool = False, tail=None):
     """``hash_fused_forward_backward_points`` with a level of detail per point (nic_hash_fused_forward_backward_points_lod): the same two
     launches, the row weighed as in ``hash_encode_points_lod`` and its gradient weighed again before the scatter.  Returns (loss [1], y or None)."""
-    t = _check_table(geo, table.detach())
-    params = _check_fused_decoder(geo, [q.detach() for q in params])
-    pts = _check_points(geo, points)
-    n = pts.shape[0]
-    if n < 1:
-        raise ValueError("no points")
-    target = _lib.require_cuda_f32(target, "target")
-    if tuple(target.shape) != (n, 3):
-        raise ValueError(f"target must be [{n}, 3], got {tuple(target.shape)}")
-    lod = _check_lod(lod, n, pts.device)
-    if order is not None:
-        order = _check_order(order, n, pts.device)
-    if table_grad is not None:
-        g = _check_table(geo, table_grad, "table_grad")
-        if g is not table_grad:
-            raise ValueError("table_grad must be contiguous: the kernel adds into it in place")
-    if len(mlp_grads) != 6 or any(not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.shape == q.shape) for g, q in zip(mlp_grads, params)):
-        raise ValueError("mlp_grads: six contiguous fp32 device buffers shaped like the decoder's parameters")
-    d, lp = _point_desc(geo), _lod_struct(geo, fade, lod_uniform)
-    loss = torch.empty(1, dtype=torch.float32, device=t.device) if loss is None else loss
-    y = torch.empty(n, 3, dtype=torch.float32, device=t.device) if want_y else None
-    lib = _lib.load()
-    m, gs = fused._mlp_struct(params), fused._grads_struct(list(mlp_grads))
-    q = None
-    if quant is not None:
-        bits, seed, offset, base = quant
-        q = _lib.NicHashQuant(int(bits), _lib.NIC_NOISE_KERNEL, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(base))
-    ws = _lib.workspace(t.device, int(lib.nic_hash_fused_points_workspace_bytes(ctypes.byref(d), ctypes.byref(m))))
-    flags = (_lib.NIC_HASH_FUSED_ADD_GRADS if add_grads else 0) | (_lib.NIC_HASH_FUSED_ADD_LOSS if add_loss else 0)
-    _lib.check(lib.nic_hash_fused_forward_backward_points_lod(ctypes.byref(d), ctypes.byref(lp), None if q is None else ctypes.byref(q), _lib.ptr(t),
-                                                              _lib.ptr(pts), _lib.ptr(lod), n, _lib.ptr(order), ctypes.byref(m), _lib.ptr(target),
-                                                              float(loss_scale), _lib.ptr(table_grad), ctypes.byref(gs), _lib.ptr(loss), _lib.ptr(y),
-                                                              flags, _lib.ptr(ws), ws.numel(), None if tail is None else ctypes.byref(tail.struct),
-                                                              _lib.stream_ptr(t.device)), "nic_hash_fused_forward_backward_points_lod")
-    if tail is not None:
-        tail.commit()
-    return loss, y
+    return _fused_forward_backward_points(geo, table, points, params, target, mlp_grads, table_grad, order, loss, loss_scale, want_y, quant,
+                                          add_grads, add_loss, tail, (lod, lod_uniform, fade))
 
 
 @fused._on_tensor_device
@@ -839,7 +810,7 @@ def _levels_quant(quant) -> Optional["_lib.NicHashQuant"]:
     if quant is None:
         return None
     seed, offset, base = quant
-    return _lib.NicHashQuant(0, _lib.NIC_NOISE_KERNEL, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(base))
+    return _quant_struct((0, seed, offset, base))
 
 
 @fused._on_tensor_device
@@ -903,12 +874,7 @@ def hash_fused_forward_backward_levels(geo: HashGeometry, table: torch.Tensor, l
         if pts is None:
             raise ValueError("an order names points: it goes with points, not with crops")
         order = _check_order(order, n, pts.device)
-    if table_grad is not None:
-        g = _check_table(geo, table_grad, "table_grad")
-        if g is not table_grad:
-            raise ValueError("table_grad must be contiguous: the kernel adds into it in place")
-    if len(mlp_grads) != 6 or any(not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.shape == q.shape) for g, q in zip(mlp_grads, params)):
-        raise ValueError("mlp_grads: six contiguous fp32 device buffers shaped like the decoder's parameters")
+    _check_grads(geo, table_grad, mlp_grads, params)
     loss = torch.empty(1, dtype=torch.float32, device=t.device) if loss is None else loss
     y = torch.empty(n, 3, dtype=torch.float32, device=t.device) if want_y else None
     lib = _lib.load()

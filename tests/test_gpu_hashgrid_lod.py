@@ -1,5 +1,5 @@
 """GPU tests of the hash-grid field's per-point level of detail (nic_hash_encode_points_lod / _backward_lod, nic_hash_fused_forward_points_lod,
-nic_hash_fused_forward_backward_points_lod, csrc/lod_points.hip; HashGridField.query / train_points / fit_points(lod=), resample(lod=),
+nic_hash_fused_forward_backward_points_lod, csrc/hash_points.hip, csrc/hash_points_train.hip; HashGridField.query / train_points / fit_points(lod=), resample(lod=),
 decode_mip, fit_mips).  The weight is restated here in torch fp32, operation for operation; everything else is compared with
 the entry points without _lod, which have their own restatement (tests/test_gpu_hashgrid_points.py).
 

@@ -11,8 +11,13 @@ UNITS = ["hash_grid.hip", "hash_fused.hip", "hash_points.hip", "hash_points_trai
 
 FUNCTIONS = ["hash_level_dense", "hash_index", "hash_level_entries", "hash_level_dwords", "hash_bits_tight", "load_row", "store_row", "load_row_u8",
              "load_row_bits", "corner_weight", "patch_sample", "level_cell", "sample_coords", "point_fixed", "point_cell", "wave_sync", "mfma", "row_of",
-             "wgrad_mfma", "put_tile", "half_sum", "device_cus", "wg_cap", "check_hash_desc", "check_point_desc", "count_patches", "set_dequant", "set_noise"]
-STRUCTS = ["PatchSample", "RecLayout"]
+             "wgrad_mfma", "put_tile", "half_sum", "device_cus", "wg_cap", "check_hash_desc", "check_point_desc", "count_patches", "set_dequant", "set_noise",
+             # the level loop and the scatter of a point, with and without a level of detail, and what the point units share around them
+             "encode_point_levels", "encode_point", "scatter_point", "ordered_row", "level_weight", "xcd_range", "set_point_source",
+             "check_lod", "set_lod", "dispatch_dim_features", "dispatch_source", "check_fused_tail", "finish_fused_step"]
+# defined in the header only, as overloads: from LodParams, and (0 / null) from any other parameter struct; point_lambda also from the values
+OVERLOADS = {"point_lambda": 3, "level_fade": 2}
+STRUCTS = ["PatchSample", "RecLayout", "LodParams", "WaveRange", "FusedTail"]
 
 # a definition opens its line with the specifiers of one (a call never does): [static] [__host__] [__device__] [inline | __forceinline__ |
 # constexpr], then the return type, then the name and its parameter list
@@ -58,6 +63,13 @@ def test_every_shared_helper_is_defined_once_in_the_header():
         pattern = _struct_re(name) if name in STRUCTS else _function_re(name)
         found = _definitions(pattern, src)
         assert len(found) == 1 and found[0][0] == HEADER, (name, found)
+
+
+def test_overloaded_helpers_are_defined_in_the_header_only():
+    src = _sources()
+    for name, count in OVERLOADS.items():
+        found = _definitions(_function_re(name), src)
+        assert len(found) == count and all(f[0] == HEADER for f in found), (name, found)
 
 
 def test_the_definition_pattern_sees_a_definition_and_not_a_call():

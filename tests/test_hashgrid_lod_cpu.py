@@ -72,7 +72,7 @@ def test_new_symbols_are_exported_declared_and_mirrored(lib):
     assert re.search(r"\}\s*nic_hash_lod\s*;", header)
     assert _lib.NIC_ABI_VERSION == 9 == lib.nic_abi_version()                  # additive: the version stays
     assert re.search(r"#define\s+NIC_ABI_VERSION\s+9\b", header)
-    assert "lod_points.hip" in _build.SOURCES
+    assert all(os.path.isfile(os.path.join(_build.CSRC, src)) for src in _build.SOURCES)
     for n in ("hash_lod_fade", "hash_encode_points_lod", "hash_encode_points_backward_lod", "hash_fused_forward_points_lod",
               "hash_fused_forward_backward_points_lod"):
         assert callable(getattr(hashgrid, n)), n
@@ -85,21 +85,14 @@ def test_new_symbols_are_exported_declared_and_mirrored(lib):
         assert _lib.SIGNATURES[n][1][1] == ctypes.POINTER(_lib.NicHashLod), n
 
 
-def test_the_new_unit_shares_the_helpers_of_the_header():
-    """the rules tests/test_hashgrid_common_cpu.py holds the csrc/hash_* units to, for csrc/lod_points.hip: it includes hash_common.hpp and
-    defines none of the helpers and structs that header owns (read from the source as text)"""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("_hashgrid_common_rules", os.path.join(ROOT, "tests", "test_hashgrid_common_cpu.py"))
-    common = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(common)
+def test_the_lod_kernels_live_in_the_point_units():
+    """there is no translation unit of their own any more: no csrc/lod_* file, and the build names only files that exist (the point units, with
+    every other csrc/hash_* file, are held to one copy of the shared helpers by tests/test_hashgrid_common_cpu.py)"""
+    import glob
     from neural_image_compression_v2_amd import _build
-    assert "lod_points.hip" in _build.SOURCES and "lod_points.hip" not in common.UNITS
-    with open(os.path.join(_build.CSRC, "lod_points.hip")) as f:
-        lines = f.read().splitlines()
-    assert any(re.match(r'\s*#include\s+"hash_common\.hpp"', ln) for ln in lines)
-    for name in common.FUNCTIONS + common.STRUCTS:
-        pattern = common._struct_re(name) if name in common.STRUCTS else common._function_re(name)
-        assert not [i + 1 for i, ln in enumerate(lines) if pattern.match(ln)], name
+    assert glob.glob(os.path.join(_build.CSRC, "lod_*")) == []
+    missing = [src for src in _build.SOURCES if not os.path.isfile(os.path.join(_build.CSRC, src))]
+    assert missing == [] and len(set(_build.SOURCES)) == len(_build.SOURCES)
 
 
 def test_hash_lod_layout_matches_the_c_header():
