@@ -15,6 +15,8 @@
 //     of the contraction.  Every LDS image whose columns are hidden units (W2, W3, the a1 / a2 / dZ images) is stored in position
 //     order, so a forward A fragment is ONE ds_read_b128 and a fragment store ONE ds_write_b128;
 //   * transposed products (dA2, dA1, dX) read their A fragments from the same weight images with ds_read_b64_tr_b16;
+//   * dX for the G0 slots is W1^T applied to the SUM of dZ1 over the rounds of a work unit (a lane's slot stays in one G0 cell and W1 is
+//     constant for the launch): the round adds dZ1 into 16 registers and keeps only the G1 row tile of the product;
 //   * weight-gradient products contract over the samples of all 8 waves ([sample][position] bf16 images, hi + lo, of every wave):
 //     dW2 and the first 64 columns of dW1 as 32x32 tiles on v_mfma_f32_32x32x16_bf16, wave w owning tile w & 3 over the samples of
 //     waves 4 (w >> 2) .. + 3 (two partial sums per tile, added by reduce16_kernel); the last 16 columns of dW1 as 16x16 tiles
@@ -141,7 +143,7 @@ struct CellRaw16 {
     float g1[4 * 3];     // [corner q][cc]
 };
 struct GridAcc16 {
-    float g1[4 * 3];     // [corner q][cc]; the G0 sums live in the dX accumulator tiles
+    float g1[4 * 3];     // [corner q][cc]; the G0 sums are formed once per work unit from the running sum of dZ1 (dxacc[0..2])
 };
 
 // Lane ids are re-derived from an opaque copy of the lane number at the start of every phase: everything computed from them
@@ -469,7 +471,8 @@ __global__ void __launch_bounds__(NIC_T16_LB) fused_train16_kernel(FusedParams p
         int org[3] = {0, 0, 0}, blk[3] = {0, 0, 0};
         const int crop = tile / tiles_per_crop;
         GridAcc16 gacc;
-        f32x4 dxacc[4];                                                      // tiles 0..2: the cell's G0 gradient sums (persistent over the rounds)
+        f32x4 dxacc[4];                                                      // tiles 0..2: the cell's G0 gradient sums, formed once after the last round
+        f32x4 sdz1[4];                                                       // sum of dZ1 over the rounds of this work unit (the lane's slot stays in one G0 cell)
         uint32_t blk_off0, blk_off1;
         CellRaw16 raw;
         {
@@ -493,7 +496,7 @@ __global__ void __launch_bounds__(NIC_T16_LB) fused_train16_kernel(FusedParams p
 #pragma unroll
             for (int i = 0; i < 12; ++i) gacc.g1[i] = 0.f;
 #pragma unroll
-            for (int t = 0; t < 4; ++t) dxacc[t] = f32x4(0.f);
+            for (int t = 0; t < 4; ++t) { dxacc[t] = f32x4(0.f); sdz1[t] = f32x4(0.f); }
             const int qb[3] = {blk[0] << p.lm, blk[1] << p.lm, 0};
             cell_offsets<L>(p, qb, blk_off0, blk_off1);
             gather_cell16(p, blk_off0, blk_off1, g, raw);
@@ -772,7 +775,10 @@ __global__ void __launch_bounds__(NIC_T16_LB) fused_train16_kernel(FusedParams p
                         else kstep16<4>(acc, bf, la);
                     }
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) dz1[t] = acc[t] * d1[t];
+                    for (int t = 0; t < 4; ++t) {
+                        dz1[t] = acc[t] * d1[t];
+                        sdz1[t] += dz1[t];                                     // invalid samples have dZ3 = 0 and add zeros
+                    }
                 }
                 wave_lds_fence();
                 // ---------- db2[pos = lane] += sum_n dZ2[pos][n]: 4x4x4 MFMAs against a block of ones
@@ -813,32 +819,35 @@ __global__ void __launch_bounds__(NIC_T16_LB) fused_train16_kernel(FusedParams p
             STAMP(5);    // dW2 MFMAs
             wg_lds_barrier();                       // everyone is done reading dZ2 before dZ1 replaces it
             STAMP(6);    // wait at barrier 2
-            // ---------- dX = W1^T dZ1 for the grid slots (tiles 0..3 = slots 0..15); the split dZ1 fragments are the dZ1 image.
-            // Tiles 0..2 (the G0 channels) keep their running sums over the rounds in the product's C operand.
+            // ---------- dX = W1^T dZ1 for the G1 slots (tile 3 = slots 12..15: their corner weights change per sample); the split dZ1
+            // fragments are the dZ1 image.  Tiles 0..2 (the G0 channels) are linear in dZ1 with weights that are constant for the launch:
+            // W1^T (sum_r dZ1_r) is formed once per work unit from sdz1, after the last round.
             {
                 const int ln = opaque_i(lane), n16 = ln & 15, g = ln >> 4, q4 = (ln & 15) >> 2, p4 = ln & 3;
                 lds_cbf* const w1_tr = opaque((lds_cbf*)(sm + S::OFF_W1 + ((LOFF & 4) ? lo_tW : (4 * g + q4) * LD1 + 8 * p4)));
                 lds_bf* const dz_st = (LOFF & 2) ? opaque(img0 + lo_rZ) : opaque(img0 + wave * S::SPW + n16 * LDZ + 8 * g);
-                dxacc[3] = f32x4(0.f);
+                f32x4 dx3[1];
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
                     const Frag2 bf = split_pair(dz1[2 * s], dz1[2 * s + 1]);
                     st_frag(&dz_st[32 * s], bf.hi);
                     st_frag(&dz_st[S::DZLO + 32 * s], bf.lo);
-                    kstep16<4>(dxacc, bf, [&](int t) {
-                        const int co = 32 * (t >> 1) + 4 * (t & 1);
+                    auto la = [&](int) {
+                        constexpr int co = 32 * (3 >> 1) + 4 * (3 & 1);
                         Frag2 a;
                         a.hi = join8(tr4(&w1_tr[32 * s * LD1 + co]), tr4(&w1_tr[(32 * s + 16) * LD1 + co]));
                         a.lo = join8(tr4(&w1_tr[S::W1LO + 32 * s * LD1 + co]), tr4(&w1_tr[S::W1LO + (32 * s + 16) * LD1 + co]));
                         return a;
-                    });
+                    };
+                    if (s == 0) kstep16<1, true>(dx3, bf, la);
+                    else kstep16<1>(dx3, bf, la);
                 }
                 const G1FactorsT<2> gf = g1_factors<2>(p.d.g1_weight_mode, kx1, ky1, 0.f);
 #pragma unroll
                 for (int c4 = 0; c4 < 4; ++c4) {
                     const float w = g1_corner_factor<2>(gf, c4);
 #pragma unroll
-                    for (int cc = 0; cc < 3; ++cc) gacc.g1[c4 * 3 + cc] = fmaf(dxacc[3][cc], w, gacc.g1[c4 * 3 + cc]);
+                    for (int cc = 0; cc < 3; ++cc) gacc.g1[c4 * 3 + cc] = fmaf(dx3[0][cc], w, gacc.g1[c4 * 3 + cc]);
                 }
             }
             STAMP(7);    // dX (+ dZ1 image), grid-gradient accumulation
@@ -877,6 +886,35 @@ __global__ void __launch_bounds__(NIC_T16_LB) fused_train16_kernel(FusedParams p
             STAMP(10);   // wait at barrier 4
         }  // rounds of one macro-tile
 
+        // ---------- G0 gradient sums of the unit: dxacc[0..2] = W1^T (sum of dZ1) - the same transposed reads of the W1 images as the round's
+        // tile 3, once per work unit (no barrier: the weight images are constant for the launch).  The sum is carried as THREE bf16 terms
+        // (24 significant bits) and the lo x lo term is kept: how the rounds of a cell are dealt out to units (passes in one launch or the
+        // crops listed again, round groups, the stagger shift) then changes the result by the order of fp32 additions only, as it did
+        // when every round split its own dZ1.  Five MFMAs per tile and k-step instead of three, once per unit.
+        {
+            const int ln = opaque_i(lane), g = ln >> 4, q4 = (ln & 15) >> 2, p4 = ln & 3;
+            lds_cbf* const w1_tr = opaque((lds_cbf*)(sm + S::OFF_W1 + ((LOFF & 4) ? lo_tW : (4 * g + q4) * LD1 + 8 * p4)));
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const float x[8] = {sdz1[2 * s][0], sdz1[2 * s][1], sdz1[2 * s][2], sdz1[2 * s][3],
+                                    sdz1[2 * s + 1][0], sdz1[2 * s + 1][1], sdz1[2 * s + 1][2], sdz1[2 * s + 1][3]};
+                const Frag2 bf = split8(x);
+                float r[8];                                                  // what hi + lo leave of the sum: exact in fp32
+#pragma unroll
+                for (int i = 0; i < 8; ++i) r[i] = (x[i] - (float)bf.hi[i]) - (float)bf.lo[i];
+                const bf16x8 b3 = split8(r).hi;
+#pragma unroll
+                for (int t = 0; t < 3; ++t) {
+                    const int co = 32 * (t >> 1) + 4 * (t & 1);
+                    Frag2 a;
+                    a.hi = join8(tr4(&w1_tr[32 * s * LD1 + co]), tr4(&w1_tr[(32 * s + 16) * LD1 + co]));
+                    a.lo = join8(tr4(&w1_tr[S::W1LO + 32 * s * LD1 + co]), tr4(&w1_tr[S::W1LO + (32 * s + 16) * LD1 + co]));
+                    f32x4 c = mfma16_bf(a.lo, bf.lo, s == 0 ? f32x4(0.f) : dxacc[t]);
+                    c = mfma16_bf(a.hi, b3, c);
+                    dxacc[t] = mfma16_split(a, bf, c);
+                }
+            }
+        }
         // ---------- flush of the cell's gradient sums
         {
             const int ln = opaque_i(lane), g = ln >> 4;
