@@ -26,13 +26,29 @@ REC, NWG = 20992, 256
 off = NWG * REC * 4
 st = ws[off:off + NWG * 8 * 16 * 8].view(torch.int64).view(NWG * 8, 16).cpu().numpy().astype(np.float64)
 names = ["0 coords, blend, PE, noise", "1 L1, L2, L3 (+ image stores, GELUs)", "2 dZ3 image, dW3, dA2", "3 dA1 (+ dZ2 image), db2", "4 wait barrier 1",
-         "5 dW2 MFMAs", "6 wait barrier 2", "7 dX (+ dZ1 image), grid acc", "8 wait barrier 3", "9 dW1 MFMAs", "10 wait barrier 4", "11 -",
+         "5 dW2 MFMAs", "6 wait barrier 2", "7 dX (+ dZ1 image), grid acc", "8 wait barrier 3", "9 dW1 MFMAs", "10 wait barrier 4", "11 phase 0 of a unit's first round",
          "12 macro-tile setup", "13 grid flush"]
 tot = st[:, :14].sum(1)
 print(f"waves {st.shape[0]}, total cycles/wave median {np.median(tot):.3e} (min {tot.min():.3e}, max {tot.max():.3e})")
 rounds = NS / 16 / (NWG * 8)
 for i, n in enumerate(names):
     print(f"{n:40s} {100 * np.median(st[:, i] / tot):6.2f} %   {np.median(st[:, i]) / rounds:9.0f} cycles/round")
+# the unit boundary: stamps 12 / 13 per work unit (16 rounds at 4K), and what the first round's phase 0 pays over the other rounds' (the latency of
+# the unit's gathers, which stamp 12 does not see: it closes when they are issued)
+RU = 16
+units = rounds / RU
+ph0_first, ph0_rest = np.median(st[:, 11]) / units, np.median(st[:, 0]) / (rounds - units)
+summary = {"cycles_per_wave": float(np.median(tot)), "units_per_wave": units,
+           "per_round": {n: float(np.median(st[:, i]) / rounds) for i, n in enumerate(names)},
+           "setup_per_unit": float(np.median(st[:, 12]) / units), "flush_per_unit": float(np.median(st[:, 13]) / units),
+           "phase0_first_round": float(ph0_first), "phase0_other_rounds": float(ph0_rest), "first_round_surplus_per_unit": float(ph0_first - ph0_rest)}
+summary["boundary_share"] = (summary["setup_per_unit"] + summary["flush_per_unit"] + summary["first_round_surplus_per_unit"]) * units / summary["cycles_per_wave"]
+print(f"per unit: setup {summary['setup_per_unit']:.0f}, flush {summary['flush_per_unit']:.0f}, phase 0 first round {ph0_first:.0f} / other rounds {ph0_rest:.0f} cycles; "
+      f"boundary + first-round surplus = {100 * summary['boundary_share']:.2f} % of a wave's cycles")
+if os.environ.get("STAMPS_JSON"):
+    import json
+    with open(os.environ["STAMPS_JSON"], "w") as f:
+        json.dump(summary, f, indent=1)
 wave_id = np.arange(st.shape[0]) % 8
 for kh in (0, 1):
     sel = (wave_id >> 2) == kh

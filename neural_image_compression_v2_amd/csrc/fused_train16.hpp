@@ -172,8 +172,7 @@ __device__ __forceinline__ float grid_load16(const char* base, uint32_t ob, int 
     if (kind == 1) return __builtin_bit_cast(float, hbits << 16);                          // bfloat16
     return (float)__builtin_bit_cast(_Float16, (uint16_t)hbits);                            // IEEE half
 }
-__device__ __forceinline__ void gather_cell16(const FusedParams& p, uint32_t off0, uint32_t off1, int g, CellRaw16& raw) {
-    const int kind = p.grid_kind;
+__device__ __forceinline__ void gather_cell16_kind(const FusedParams& p, const int kind, uint32_t off0, uint32_t off1, int g, CellRaw16& raw) {
     const uint32_t eb = kind == 0 ? 4u : (kind == 3 ? 1u : 2u);   // bytes per stored element
     const uint32_t pb0 = (uint32_t)p.g0.plane * eb, pb1 = (uint32_t)p.g1.plane * eb;
     {
@@ -188,6 +187,19 @@ __device__ __forceinline__ void gather_cell16(const FusedParams& p, uint32_t off
         const char* base = reinterpret_cast<const char*>(p.g1.p);
 #pragma unroll
         for (int cc = 0; cc < 3; ++cc, ob += pb1) raw.g1[c4 * 3 + cc] = grid_load16(base, ob, kind, p);
+    }
+}
+__device__ __forceinline__ void gather_cell16(const FusedParams& p, uint32_t off0, uint32_t off1, int g, CellRaw16& raw) {
+    gather_cell16_kind(p, p.grid_kind, off0, off1, g, raw);
+}
+// .. with the storage kind decided once for the 24 loads: one scalar switch per unit and the loads back to back, instead of a four-way switch in
+// front of every load (and, for the 16-bit and uint8 kinds, a wait for each value before the next load is issued)
+__device__ __forceinline__ void gather_cell16_switched(const FusedParams& p, uint32_t off0, uint32_t off1, int g, CellRaw16& raw) {
+    switch (p.grid_kind) {
+        case 0: gather_cell16_kind(p, 0, off0, off1, g, raw); break;
+        case 1: gather_cell16_kind(p, 1, off0, off1, g, raw); break;
+        case 3: gather_cell16_kind(p, 3, off0, off1, g, raw); break;
+        default: gather_cell16_kind(p, 2, off0, off1, g, raw); break;
     }
 }
 
@@ -264,6 +276,11 @@ __device__ __forceinline__ void add_noise16(const NoiseSrc& ns, uint64_t sample_
     xs[18] += g == 0 ? nl : 0.f;
 }
 
+// __shfl for a source lane that is known to be a lane number (0..63): the library's version adds `own lane & ~63`, which the optimiser cannot fold,
+// hoists to the launch prologue and, at this kernel's register count, spills - and a scratch reload in the flush waits for every memory operation issued
+// before it, the next unit's gathers included
+__device__ __forceinline__ int shfl_lane(int v, int src_lane) { return __builtin_amdgcn_ds_bpermute(src_lane << 2, v); }
+__device__ __forceinline__ float shfl_lane(float v, int src_lane) { return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src_lane << 2, __builtin_bit_cast(int, v))); }
 // G1 sums of the lanes whose G0 cells share a G1 cell are added across lanes before the flush (see combine_g1_lanes)
 __device__ __forceinline__ void combine_g1_lanes16(GridAcc16& ga, uint32_t off1, const int (&blk)[3], int lane, int lw) {
     const int T[2] = {1 << lw, 16 >> lw};
@@ -276,10 +293,10 @@ __device__ __forceinline__ void combine_g1_lanes16(GridAcc16& ga, uint32_t off1,
         const int pc = lc[a] + (odd ? -1 : 1);
         const bool inb = pc >= 0 && pc < T[a];
         const int partner = inb ? lane + (odd ? -STR[a] : STR[a]) : lane;
-        const bool pair = inb && (uint32_t)__shfl((int)off1, partner) == off1;
+        const bool pair = inb && (uint32_t)shfl_lane((int)off1, partner) == off1;
 #pragma unroll
         for (int i = 0; i < 12; ++i) {
-            const float pv = __shfl(ga.g1[i], partner);
+            const float pv = shfl_lane(ga.g1[i], partner);
             ga.g1[i] = pair ? (odd ? 0.f : ga.g1[i] + pv) : ga.g1[i];
         }
     }
@@ -294,11 +311,11 @@ __device__ __forceinline__ void preadd_x16(f32x4 (&dxacc)[4], uint32_t off0, int
     const bool recv = g < 2;
     const bool inb = recv ? n16 >= 1 : n16 <= 14;
     const int partner = inb ? (recv ? ln + 31 : ln - 31) : ln;
-    const uint32_t poff = (uint32_t)__shfl((int)off0, partner);
+    const uint32_t poff = (uint32_t)shfl_lane((int)off0, partner);
     const bool pair = inb && (recv ? off0 == poff + 1u : poff == off0 + 1u);
 #pragma unroll
     for (int c = 0; c < kC; ++c) {
-        const float pv = __shfl(dxacc[c >> 2][c & 3], partner);
+        const float pv = shfl_lane(dxacc[c >> 2][c & 3], partner);
         dxacc[c >> 2][c & 3] = pair ? (recv ? dxacc[c >> 2][c & 3] + pv : 0.f) : dxacc[c >> 2][c & 3];
     }
 }
@@ -334,6 +351,67 @@ __device__ __forceinline__ void preadd_y16(f32x4 (&dxacc)[4], uint32_t off0, uin
         for (int i = 0; i < 12; ++i) dxacc[i >> 2][i & 3] = pair ? 0.f : dxacc[i >> 2][i & 3];
     }
     barrier();
+}
+
+// The header of a work unit: everything the rounds and the flush of one piece of the walk need to know about it.  The kernel runs it one unit
+// AHEAD (see the macro-tile loop): after the last round of unit k the header of unit k + 1 is issued, so that its scalar chain (divisions,
+// origin read, cell offsets) and the latency of its 24 gathers per lane pass under the once-per-unit product and the flush of unit k.
+struct Seg16 {               // what a header reads of its segment of the walk (segment-uniform)
+    int tile0, rg, t_end, base0, lstride, n_my, tiles_per_crop, tiles_main, rounds_unit, shift;
+};
+struct Unit16 {
+    int org[3], blk[3];      // crop origin; absolute block coordinates of the lane's cell
+    int qb[2];               // blk << lm: what the rounds read (blk itself is left to the flush, so that nothing at the top of a unit needs it back from scratch)
+    int lw, crop;            // log2 of the tile's width in cells; crop of the tile
+    int base, tile;          // first unit of the workgroup's step, macro-tile of this wave's unit (the group sum compares them across waves)
+    int it_begin, it_len;    // rounds of this piece
+    bool tile_ok;
+    uint32_t blk_off0, blk_off1;
+    CellRaw16 raw;           // gathered here, first read by encode16 in the piece's first round
+};
+// what the flush of a finished unit still needs of its header once the next header has replaced it
+struct UnitFlush16 {
+    int blk[3], lw, base, tile;
+    bool tile_ok;
+    uint32_t blk_off0, blk_off1;
+};
+template <class L>
+__device__ __forceinline__ void unit_header16(const FusedParams& p, const Seg16& sg, int kk, int lane, int wave, Unit16& u) {
+    u.base = sg.base0 + (kk < sg.n_my ? kk : 0) * sg.lstride;
+    u.tile_ok = u.base + wave < sg.t_end;
+    const int unit = u.tile_ok ? u.base + wave : sg.t_end - 1;
+    u.tile = sg.tile0 + (unit >> sg.rg);
+    u.it_len = sg.rounds_unit;
+    u.it_begin = (int)(unit & ((1 << sg.rg) - 1)) * sg.rounds_unit;
+    if (sg.shift) {                                   // the stagger cuts the first tile in two pieces: kk == 0 and kk == n_my
+        if (kk == 0) { u.it_begin += sg.shift; u.it_len -= sg.shift; }
+        else if (kk == sg.n_my) u.it_len = sg.shift;
+    }
+    // ---------- macro-tile -> this lane's cell (absolute block coordinates) and crop
+    u.lw = 4;
+    u.crop = u.tile / sg.tiles_per_crop;
+    const int ln = opaque_i(lane), n16 = ln & 15, g = ln >> 4;
+    const int tt = u.tile - u.crop * sg.tiles_per_crop;
+    int boff[2];
+    if (p.edge_lw < 0 || tt < sg.tiles_main) {
+        boff[1] = tt % p.tiles_y;                 // regular tile: 16 x 1 cells
+        boff[0] = (tt / p.tiles_y) * 16;
+    } else {
+        u.lw = p.edge_lw;                         // edge tile: 2^lw x (16 >> lw) cells
+        boff[1] = (tt - sg.tiles_main) * (16 >> u.lw);
+        boff[0] = p.full_x * 16;
+    }
+    const int lc[2] = {n16 & ((1 << u.lw) - 1), n16 >> u.lw};
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        u.org[a] = origin_of(p, u.crop * 2 + a);
+        u.blk[a] = (u.org[a] >> p.lm) + boff[a] + lc[a];
+    }
+    u.org[2] = 0; u.blk[2] = 0;
+    u.qb[0] = u.blk[0] << p.lm; u.qb[1] = u.blk[1] << p.lm;
+    const int qb[3] = {u.qb[0], u.qb[1], 0};
+    cell_offsets<L>(p, qb, u.blk_off0, u.blk_off1);
+    gather_cell16_switched(p, u.blk_off0, u.blk_off1, g, u.raw);
 }
 
 // =====================================================================================================
@@ -456,54 +534,27 @@ __global__ void __launch_bounds__(NIC_T16_LB) fused_train16_kernel(FusedParams p
     const int nph = rounds_unit >= NIC_PHASES ? NIC_PHASES : (rounds_unit >= 2 ? 2 : 1);
     const int shift = (NIC_STAGGER && (NIC_STAGGER_RG || rg == 0)) ? (int)((blockIdx.x >> 3) & (nph - 1)) * (rounds_unit / nph) : 0;
 
-    for (int kk = 0; kk < n_my + (shift ? 1 : 0); ++kk) {
-        const int base = base0 + (kk < n_my ? kk : 0) * lstride;
-        const bool tile_ok = base + wave < t_end;
-        const int unit = tile_ok ? base + wave : t_end - 1;
-        const int tile = seg_tile0 + (unit >> rg);
-        int it_len = rounds_unit, it_begin = (int)(unit & ((1 << rg) - 1)) * rounds_unit;
-        if (shift) {
-            if (kk == 0) { it_begin += shift; it_len -= shift; }
-            else if (kk == n_my) it_len = shift;
-        }
-        // ---------- macro-tile -> this lane's cell (absolute block coordinates) and crop
-        int lw = 4;
-        int org[3] = {0, 0, 0}, blk[3] = {0, 0, 0};
-        const int crop = tile / tiles_per_crop;
+    // The walk is software-pipelined by one piece: the header of piece kk + 1 is issued between the last round of piece kk and its flush.  The
+    // first header runs ahead of the loop, the last piece issues none (workgroup-uniform: n_pieces depends on the workgroup alone).
+    const Seg16 sg = {seg_tile0, rg, t_end, base0, lstride, n_my, tiles_per_crop, tiles_main, rounds_unit, shift};
+    const int n_pieces = n_my + (shift ? 1 : 0);
+    Unit16 u;
+    if (n_pieces > 0) unit_header16<L>(p, sg, 0, lane, wave, u);
+    STAMP(12);   // macro-tile setup, raw gathers issued
+
+    for (int kk = 0; kk < n_pieces; ++kk) {
         GridAcc16 gacc;
         f32x4 dxacc[4];                                                      // tiles 0..2: the cell's G0 gradient sums, formed once after the last round
         f32x4 sdz1[4];                                                       // sum of dZ1 over the rounds of this work unit (the lane's slot stays in one G0 cell)
-        uint32_t blk_off0, blk_off1;
-        CellRaw16 raw;
-        {
-            const int ln = opaque_i(lane), n16 = ln & 15, g = ln >> 4;
-            const int tt = tile - crop * tiles_per_crop;
-            int boff[2];
-            if (p.edge_lw < 0 || tt < tiles_main) {
-                boff[1] = tt % p.tiles_y;                 // regular tile: 16 x 1 cells
-                boff[0] = (tt / p.tiles_y) * 16;
-            } else {
-                lw = p.edge_lw;                           // edge tile: 2^lw x (16 >> lw) cells
-                boff[1] = (tt - tiles_main) * (16 >> lw);
-                boff[0] = p.full_x * 16;
-            }
-            const int lc[2] = {n16 & ((1 << lw) - 1), n16 >> lw};
+        // (a zero made here, per unit: a constant zero 4-vector for these resets is hoisted out of the walk, kept across the round loop and spilled)
+        float zero = 0.f;
+        asm volatile("" : "+v"(zero));
 #pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                org[a] = origin_of(p, crop * 2 + a);
-                blk[a] = (org[a] >> p.lm) + boff[a] + lc[a];
-            }
+        for (int i = 0; i < 12; ++i) gacc.g1[i] = zero;
 #pragma unroll
-            for (int i = 0; i < 12; ++i) gacc.g1[i] = 0.f;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) { dxacc[t] = f32x4(0.f); sdz1[t] = f32x4(0.f); }
-            const int qb[3] = {blk[0] << p.lm, blk[1] << p.lm, 0};
-            cell_offsets<L>(p, qb, blk_off0, blk_off1);
-            gather_cell16(p, blk_off0, blk_off1, g, raw);
-        }
-        STAMP(12);   // macro-tile setup, raw gathers issued
+        for (int t = 0; t < 4; ++t) { dxacc[t] = f32x4(zero); sdz1[t] = f32x4(zero); }
 
-        for (int it = it_begin; it < it_begin + it_len; ++it) {
+        for (int it = u.it_begin; it < u.it_begin + u.it_len; ++it) {
             // ================= forward =================
             f32x4 a1[4], d1[4], a2[4], d2[4];
             float dz3[3];
@@ -511,7 +562,7 @@ __global__ void __launch_bounds__(NIC_T16_LB) fused_train16_kernel(FusedParams p
             {
                 const int ln = opaque_i(lane), n16 = ln & 15, g = ln >> 4;
                 // ---------- which sample does this lane own in this round
-                bool valid = tile_ok;
+                bool valid = u.tile_ok;
                 int64_t n;
                 int q[3] = {0, 0, 0};
                 {
@@ -522,12 +573,12 @@ __global__ void __launch_bounds__(NIC_T16_LB) fused_train16_kernel(FusedParams p
                     int idx[2];
 #pragma unroll
                     for (int a = 0; a < 2; ++a) {
-                        const int i = (blk[a] << p.lm) + j[a] - org[a];
+                        const int i = u.qb[a] + j[a] - u.org[a];
                         valid = valid && i >= 0 && i < ext[a];
                         idx[a] = i < 0 ? 0 : (i >= ext[a] ? ext[a] - 1 : i);
-                        q[a] = org[a] + idx[a];
+                        q[a] = u.org[a] + idx[a];
                     }
-                    n = ((int64_t)crop * p.passes + pass) * p.n_per_crop + (int64_t)idx[0] * ext[1] + idx[1];
+                    n = ((int64_t)u.crop * p.passes + pass) * p.n_per_crop + (int64_t)idx[0] * ext[1] + idx[1];
                 }
                 // ---------- target (or incoming dY) of the sample: fetched now, used after the forward pass
                 float tgt[3] = {0.f, 0.f, 0.f};
@@ -565,11 +616,12 @@ __global__ void __launch_bounds__(NIC_T16_LB) fused_train16_kernel(FusedParams p
                 float xs[20];
                 {
                     EncCtx cx;
-                    encode16<L>(p, q, g, xs, cx, raw);
+                    encode16<L>(p, q, g, xs, cx, u.raw);
                     kx1 = cx.kx; ky1 = cx.ky;
                     add_noise16<L>(nsrc, (uint64_t)(p.d.sample_base + n), n, g, xs);
                 }
-                STAMP(0);    // coordinates, blend, PE, noise
+                if (it == u.it_begin) STAMP(11);   // the same phase of a unit's first round: the only one that can wait for the unit's gathers
+                else STAMP(0);    // coordinates, blend, PE, noise
                 lds_bf* const imgw = img0 + wave * S::SPW;
                 // ---------- layer 1: Z1[o][n] = sum_rho W1[o][rho] X[rho][n]   (b1 rides on the constant-one slot)
                 {
@@ -669,8 +721,9 @@ __global__ void __launch_bounds__(NIC_T16_LB) fused_train16_kernel(FusedParams p
                         st_frag(&dz_st[S::DZLO + 32 * s], bf.lo);
                         z3 = mfma16_split(af, bf, s == 0 ? f32x4(0.f) : z3);
                     }
+                    lds_cf* const b3_row = opaque(Bs + kH);            // (its constant address otherwise shares a register tuple with the hoisted zero)
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) yv[c] = sigmoid_f(z3[c] + ((lds_cf*)Bs)[kH + c]);
+                    for (int c = 0; c < 3; ++c) yv[c] = sigmoid_f(z3[c] + b3_row[c]);
                 }
                 STAMP(1);    // layers 1 - 3 with their image stores and GELUs
                 const bool own = valid && g == 0;
@@ -886,6 +939,15 @@ __global__ void __launch_bounds__(NIC_T16_LB) fused_train16_kernel(FusedParams p
             STAMP(10);   // wait at barrier 4
         }  // rounds of one macro-tile
 
+        // ---------- the next piece's header, issued under the product and the flush below: its gathers are older than the flush's atomics on the
+        // memory counter and are first read by encode16 in the next round.  The flush keeps what it needs of the finished unit.
+        UnitFlush16 fu = {{u.blk[0], u.blk[1], 0}, u.lw, u.base, u.tile, u.tile_ok, u.blk_off0, u.blk_off1};
+        // (the two offsets are not read in the round loop and may sit in scratch across it: used here, they are reloaded BEFORE the gathers are
+        //  issued - a scratch reload further down would wait on the memory counter behind them and drain the gathers it is meant to overlap)
+        asm volatile("" : "+v"(fu.blk_off0), "+v"(fu.blk_off1), "+v"(fu.blk[0]), "+v"(fu.blk[1]));
+        if (kk + 1 < n_pieces) unit_header16<L>(p, sg, kk + 1, lane, wave, u);
+        STAMP(12);   // macro-tile setup of the next piece, raw gathers issued
+
         // ---------- G0 gradient sums of the unit: dxacc[0..2] = W1^T (sum of dZ1) - the same transposed reads of the W1 images as the round's
         // tile 3, once per work unit (no barrier: the weight images are constant for the launch).  The sum is carried as THREE bf16 terms
         // (24 significant bits) and the lo x lo term is kept: how the rounds of a cell are dealt out to units (passes in one launch or the
@@ -918,16 +980,16 @@ __global__ void __launch_bounds__(NIC_T16_LB) fused_train16_kernel(FusedParams p
         // ---------- flush of the cell's gradient sums
         {
             const int ln = opaque_i(lane), g = ln >> 4;
-            combine_g1_lanes16(gacc, blk_off1, blk, ln, lw);
+            combine_g1_lanes16(gacc, fu.blk_off1, fu.blk, ln, fu.lw);
             bool flush = true;
             if (NIC_GROUP_SUM && rg > 0) {                                  // segment-uniform: groups of one macro-tile sit in one workgroup
                 lds_f* const reg0 = (lds_f*)img0;
                 constexpr int REGION = S::SPW / 2;                         // floats per wave
                 static_assert(24 * 64 <= REGION, "group-sum scratch");
                 int leader = wave;
-                if (tile_ok)
+                if (fu.tile_ok)
                     for (int w = wave - 1; w >= 4 * kh; --w)
-                        if (seg_tile0 + ((base + w) >> rg) == tile) leader = w;
+                        if (seg_tile0 + ((fu.base + w) >> rg) == fu.tile) leader = w;
                 if (leader != wave) {
                     lds_f* const mine = opaque(reg0 + wave * REGION + ln);
 #pragma unroll
@@ -936,9 +998,9 @@ __global__ void __launch_bounds__(NIC_T16_LB) fused_train16_kernel(FusedParams p
                     for (int i = 0; i < 12; ++i) mine[(12 + i) * 64] = gacc.g1[i];
                 }
                 wg_lds_barrier();
-                if (leader == wave && tile_ok) {
+                if (leader == wave && fu.tile_ok) {
                     for (int w = wave + 1; w < 4 * kh + 4; ++w) {
-                        if (base + w >= t_end || seg_tile0 + ((base + w) >> rg) != tile) break;
+                        if (fu.base + w >= t_end || seg_tile0 + ((fu.base + w) >> rg) != fu.tile) break;
                         lds_cf* const theirs = opaque(reg0 + w * REGION + ln);
 #pragma unroll
                         for (int i = 0; i < 12; ++i) dxacc[i >> 2][i & 3] += theirs[i * 64];
@@ -949,10 +1011,10 @@ __global__ void __launch_bounds__(NIC_T16_LB) fused_train16_kernel(FusedParams p
                 wg_lds_barrier();
                 flush = leader == wave;
             }
-            if (flush && NIC_T16_PREADD) preadd_x16(dxacc, blk_off0, ln);
+            if (flush && NIC_T16_PREADD) preadd_x16(dxacc, fu.blk_off0, ln);
             if (NIC_T16_PREADD >= 2 && rg == 0 && (p.preadd_y || !NIC_PREADD_Y_SMALL)) {      // segment-uniform
                 static_assert(13 * 64 <= S::SPW / 2, "pre-add scratch");
-                preadd_y16<8>(dxacc, blk_off0, (uint32_t)p.g0.nx, ln, wave, (lds_f*)img0, S::SPW / 2, [&]() { wg_lds_barrier(); });
+                preadd_y16<8>(dxacc, fu.blk_off0, (uint32_t)p.g0.nx, ln, wave, (lds_f*)img0, S::SPW / 2, [&]() { wg_lds_barrier(); });
             }
             if (flush) {
                 // one predicate per lane and grid instead of one per value: a lane whose 12 sums are all exact zeros (cell outside the
@@ -965,7 +1027,7 @@ __global__ void __launch_bounds__(NIC_T16_LB) fused_train16_kernel(FusedParams p
                     nz1 |= __builtin_bit_cast(uint32_t, gacc.g1[c]);
                 }
                 if ((nz0 << 1) != 0u) {
-                    uint32_t ob = (blk_off0 + (uint32_t)p.g0.at(g >> 1, g & 1, 0)) * 4u;
+                    uint32_t ob = (fu.blk_off0 + (uint32_t)p.g0.at(g >> 1, g & 1, 0)) * 4u;
                     char* gbase = reinterpret_cast<char*>(p.g0_grad);
 #pragma unroll
                     for (int c = 0; c < kC; ++c, ob += pb0) atomicAdd(reinterpret_cast<float*>(gbase + ob), dxacc[c >> 2][c & 3]);
@@ -973,7 +1035,7 @@ __global__ void __launch_bounds__(NIC_T16_LB) fused_train16_kernel(FusedParams p
                 if ((nz1 << 1) != 0u) {
 #pragma unroll
                     for (int c4 = 0; c4 < 4; ++c4) {
-                        uint32_t ob = (blk_off1 + (uint32_t)p.g1.at(c4 >> 1, c4 & 1, 0)) * 4u + (uint32_t)(3 * g) * pb1;
+                        uint32_t ob = (fu.blk_off1 + (uint32_t)p.g1.at(c4 >> 1, c4 & 1, 0)) * 4u + (uint32_t)(3 * g) * pb1;
                         char* gbase = reinterpret_cast<char*>(p.g1_grad);
 #pragma unroll
                         for (int cc = 0; cc < 3; ++cc, ob += pb1) atomicAdd(reinterpret_cast<float*>(gbase + ob), gacc.g1[c4 * 3 + cc]);
