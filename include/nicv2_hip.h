@@ -707,6 +707,29 @@ int nic_hash_fused_forward_backward_points_lod(const nic_hash_desc *desc, const 
                                                float *table_grad, const nic_mlp_grads *mlp_grads, float *loss, float *y, int flags,
                                                void *workspace, size_t workspace_bytes, const nic_step_tail *tail, void *stream);
 
+/* ---- the forward-only fused routes with the decoder on the 16-bit matrix pipe (hashgrid.py, HashGridField.decode / query / resample
+ *      (precision=); csrc/hashgrid_fused16.hip).  nic_hash_fused_forward / _u8 / _bits (origins) and
+ *      nic_hash_fused_forward_points (points) with the products of the three Linear layers taken in 16-bit operands; y is [N, 3] in the
+ *      sample order of those entries.  One launch, no atomics: the same call gives the same bits.
+ *      - the row x [L F] is the existing route's, bit for bit: nic_hash_encode / _u8 / _bits on the lattice, nic_hash_encode_points at points.
+ *      - per layer, W the fp32 nn.Linear weight and a the fp32 input (the row, then the fp32 GELU outputs), hi = bf16_rne(v),
+ *        lo = bf16_rne(v - hi) for both operands:
+ *          NIC_HASH_PREC_SPLIT  z = sum_k (a_lo W_hi + a_hi W_lo + a_hi W_hi)   products exact, fp32 accumulation, no lo x lo term
+ *          NIC_HASH_PREC_BF16   z = sum_k a_hi W_hi                             products exact, fp32 accumulation
+ *        the bias is added in fp32; GELU and the output sigmoid are the fp32 functions of the fp32 route.  Columns past L F and output rows
+ *        3 .. 31 of the matrix tiles are exact zero padding.  The modes differ from the fp32 route in the products alone.
+ *      Positions: exactly one of `origins` / `points` is non-null (else NIC_E_ARG), as in nic_hash_fused_forward_levels: a lattice sample i
+ *      is the point t = 256 i + 128, so the lattice route needs 256 S_max < 2^30 too; n_points is ignored with `origins`.
+ *      Source (src): NIC_HASH_SRC_F32, _U8 or _BITS with the rules of nic_hash_encode_points (num_bits 0 for F32 and 1 .. 8 for U8 / BITS, a
+ *      BITS table 4-byte aligned).  Supported: what nic_hash_fused_supported answers for.  No level of detail, no bit depth per level.
+ *      Every argument error is returned on the host before any GPU work, in the order of nic_hash_fused_forward_levels: null desc / mlp,
+ *      nic_hash_fused_supported, the position pair, the descriptor of that position source, null pointers, the source, `precision` not
+ *      NIC_HASH_PREC_SPLIT or NIC_HASH_PREC_BF16 (NIC_E_ARG), n_points < 0 (NIC_E_ARG); n_points == 0 at points is NIC_OK without a launch. */
+#define NIC_HASH_PREC_SPLIT 1
+#define NIC_HASH_PREC_BF16 2
+int nic_hash_fused_forward_p16(const nic_hash_desc *desc, const nic_hash_source *src, const int32_t *origins, const float *points,
+                               int64_t n_points, const nic_mlp *mlp, int precision, float *y, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,6 +118,7 @@ class NicHashQuant(ctypes.Structure):
 
 
 NIC_HASH_SRC_F32, NIC_HASH_SRC_U8, NIC_HASH_SRC_BITS = 0, 1, 2
+NIC_HASH_PREC_SPLIT, NIC_HASH_PREC_BF16 = 1, 2      # nic_hash_fused_forward_p16: split-bf16 / plain bf16 products
 
 
 class NicHashSource(ctypes.Structure):
@@ -228,6 +229,7 @@ SIGNATURES = {
                                                _P, _P]),
     "nic_hash_fused_forward_backward_points_lod": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashLod), ctypes.POINTER(NicHashQuant), _P, _P,
                                                         _P, _L, _P, _M, _P, _F, _P, _G, _P, _P, _I, _P, _SZ, ctypes.POINTER(NicStepTail), _P]),
+    "nic_hash_fused_forward_p16": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashSource), _P, _P, _L, _M, _I, _P, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

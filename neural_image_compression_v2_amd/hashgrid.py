@@ -58,7 +58,12 @@ A level of detail per point (include/nicv2_hip.h, nic_hash_lod; cs
 default fade start max(0, log2(S_max / R_l)), ``HashGridField(..., lod_fade=)`` another.  A level of weight 0 is not gathered, takes no noise
 and no gradient; at weight 1 the columns are the plain route's bit for bit.  ``query`` / ``train_points`` / ``fit_points`` take ``lod=`` (a
 float, or one value per point; None makes the launches made before), ``resample(size, lod="auto")`` derives it from the size,
-``decode_mip(m)`` decodes mip m and ``fit_mips`` fits the box-filtered mip chain with one table and one decoder."""
+``decode_mip(m)`` decodes mip m and ``fit_mips`` fits the box-filtered mip chain with one table and one decoder.
+
+The decoder on the 16-bit matrix pipe (include/nicv2_hip.h, nic_hash_fused_forward_p16; csrc/hashgrid_fused16.hip): ``decode`` /
+``query`` / ``resample`` take ``precision="split" | "bf16"`` - the same gather, the three Linear layers' products in split-bf16 (hi hi + hi lo +
+lo hi) or plain bf16 operands with fp32 accumulation, bias, GELU and sigmoid in fp32.  ``None`` makes the launches made before.  Forward only, no
+level of detail, no bit depth per level."""
 from __future__ import annotations
 
 import ctypes
@@ -852,6 +857,43 @@ def hash_fused_forward_levels(geo: HashGeometry, data: torch.Tensor, level_bits,
     return y
 
 
+PRECISIONS = {"split": _lib.NIC_HASH_PREC_SPLIT, "bf16": _lib.NIC_HASH_PREC_BF16}
+
+
+def _check_precision(precision) -> int:
+    if not isinstance(precision, str) or precision not in PRECISIONS:
+        raise ValueError(f"precision {precision!r}: one of {sorted(PRECISIONS)} (or None: the fp32 route)")
+    return PRECISIONS[precision]
+
+
+def _check_p16_set(geo: HashGeometry, hidden: int, n_linear: int) -> None:
+    if not hash_fused_supported(geo, hidden, n_linear):
+        raise ValueError("precision= needs a geometry and decoder of the fused set (nic_hash_fused_supported): dim 2 / 3, features 1 / 2 / 4 / 8, "
+                         "levels * features <= 64, 64 hidden units, 3 Linear layers")
+
+
+@fused._on_tensor_device
+def hash_fused_forward_p16(geo: HashGeometry, data: torch.Tensor, params: Sequence[torch.Tensor], precision: str, coord=None,
+                           extent: Optional[Sequence[int]] = None, points: Optional[torch.Tensor] = None, kind: str = "f32",
+                           num_bits: Optional[int] = None) -> torch.Tensor:
+    """[N, 3] = ColorDecoder(hash_encode(...)) in one launch with the decoder's products on the 16-bit matrix pipe
+    (nic_hash_fused_forward_p16; ``precision`` "split" or "bf16"), on the crops ``coord`` / ``extent`` or at ``points`` (exactly one), from
+    the fp32 table (``kind`` "f32"), the compact uint8 one ("u8") or the bit-packed one ("bits", both with ``num_bits``)"""
+    prec = _check_precision(precision)
+    _check_p16_set(geo, params[0].shape[0] if len(params) else 0, len(params) // 2)
+    src, data = _point_source(geo, data, kind, num_bits)
+    params = _check_fused_decoder(geo, [q.detach() for q in params])
+    d, org, pts, n = _levels_positions(geo, coord, extent, points, data.device)
+    y = torch.empty(n, 3, dtype=torch.float32, device=data.device)
+    if n == 0:
+        return y
+    m = fused._mlp_struct(params)
+    _lib.check(_lib.load().nic_hash_fused_forward_p16(ctypes.byref(d), ctypes.byref(src), _lib.ptr(org), _lib.ptr(pts), n if pts is not None else 0,
+                                                      ctypes.byref(m), prec, _lib.ptr(y), _lib.stream_ptr(data.device)),
+               "nic_hash_fused_forward_p16")
+    return y
+
+
 @fused._on_tensor_device
 def hash_fused_forward_backward_levels(geo: HashGeometry, table: torch.Tensor, level_bits, params: Sequence[torch.Tensor], target: torch.Tensor,
                                        mlp_grads: Sequence[torch.Tensor], coord=None, extent: Optional[Sequence[int]] = None,
@@ -1437,9 +1479,22 @@ class HashGridField:
         self._set_route(fused)
         return self
 
+    def _check_p16(self, precision, lod=None) -> None:
+        """the refusals of ``precision=``, on the host and before anything is launched or changed"""
+        _check_precision(precision)
+        if lod is not None:
+            raise NotImplementedError("precision= with a level of detail is not built (DESIGN 7): call without lod, or without precision")
+        if self.level_bits is not None:
+            raise NotImplementedError("precision= with a bit depth per level is not built (DESIGN 7): use a uniform num_bits")
+        _check_p16_set(self.geo, self.hidden, self.n_linear)
+
     @torch.no_grad()
-    def decode(self, tile: int = 1024) -> torch.Tensor:
-        """the whole field [S_x, S_y(, S_z), 3], in tiles of side <= ``tile`` (a field from ``load_compressed``: from its uint8 or bit-packed table)"""
+    def decode(self, tile: int = 1024, precision: Optional[str] = None) -> torch.Tensor:
+        """the whole field [S_x, S_y(, S_z), 3], in tiles of side <= ``tile`` (a field from ``load_compressed``: from its uint8 or bit-packed table).
+        ``precision``: None (those launches, unchanged), or "split" / "bf16" - every tile through ``hash_fused_forward_p16`` whatever ``route``
+        is, the decoder's products on the 16-bit matrix pipe"""
+        if precision is not None:
+            self._check_p16(precision)
         size = self.field_size
         out = torch.empty(*size, 3, dtype=torch.float32, device=self.device)
         params = [p.detach() for p in self.decoder.linear_params()]
@@ -1447,6 +1502,10 @@ class HashGridField:
         for o in itertools.product(*[range(0, s, tile) for s in size]):
             ext = [min(tile, s - a) for s, a in zip(size, o)]
             sl = tuple(slice(a, a + e) for a, e in zip(o, ext))
+            if precision is not None:
+                data, kind, bits = self._point_table()
+                out[sl] = hash_fused_forward_p16(self.geo, data, params, precision, coord=[o], extent=ext, kind=kind, num_bits=bits).reshape(*ext, 3)
+                continue
             if self.route == "fused":
                 if table is not None:
                     y = hash_fused_forward(self.geo, table, [o], ext, params)
@@ -1478,12 +1537,18 @@ class HashGridField:
         return self.stored, "u8", self.num_bits
 
     @torch.no_grad()
-    def query(self, points: torch.Tensor, lod=None) -> torch.Tensor:
+    def query(self, points: torch.Tensor, lod=None, precision: Optional[str] = None) -> torch.Tensor:
         """[N, 3] colours at ``points`` [N, dim] (fp32, sample units: p = i is the centre of sample i, the field spans [-1/2, S - 1/2] and
         points outside it read its edge), from the fp32 table or - a field from ``load_compressed`` - straight from its uint8 or bit-packed
         table.  One launch on the fused route (nic_hash_fused_forward_points), encode + general decoder on the layer-wise one.  ``lod``: None
         (those launches, unchanged), or the level of detail of the query - a float, or one value per point [N]: the levels finer than the
-        footprint fade out before the decoder and are not gathered (the ``_lod`` entry points, fade starts ``lod_fade``)."""
+        footprint fade out before the decoder and are not gathered (the ``_lod`` entry points, fade starts ``lod_fade``).
+        ``precision``: None, or "split" / "bf16" - one launch of ``hash_fused_forward_p16`` whatever ``route`` is (not with ``lod``)."""
+        if precision is not None:
+            self._check_p16(precision, lod)
+            data, kind, bits = self._point_table()
+            return hash_fused_forward_p16(self.geo, data, [p.detach() for p in self.decoder.linear_params()], precision, points=points, kind=kind,
+                                          num_bits=bits)
         if lod is not None:
             lod_t, lod_u = self._lod_args(lod)
             pts = _check_points(self.geo, points)
@@ -1518,14 +1583,16 @@ class HashGridField:
         return torch.stack([g.reshape(-1) for g in torch.meshgrid(*axes, indexing="ij")], dim=1).contiguous()
 
     @torch.no_grad()
-    def resample(self, size: Union[int, Sequence[int]], tile: int = 1024, lod=None) -> torch.Tensor:
+    def resample(self, size: Union[int, Sequence[int]], tile: int = 1024, lod=None, precision: Optional[str] = None) -> torch.Tensor:
         """the field decoded on a regular grid of ANY size, [*size, 3]: output sample j of axis a sits at p_a = (j + 1/2) S_a / size_a - 1/2
         (``size`` = the field size gives ``decode()``'s sample centres).  Walked in tiles of side <= ``tile``; the points of a tile are
         generated on the device.  ``lod``: None = point samples of the full-detail field; a float = ``query``'s level of detail for every
-        sample; "auto" = max(0, log2(max_a S_a / size_a)), the footprint of an output sample in octaves."""
+        sample; "auto" = max(0, log2(max_a S_a / size_a)), the footprint of an output sample in octaves.  ``precision``: ``query``'s (not with ``lod``)."""
         size = (int(size),) * self.geo.dim if isinstance(size, int) else tuple(int(v) for v in size)
         if len(size) != self.geo.dim or any(v < 1 for v in size):
             raise ValueError(f"size {size} for a {self.geo.dim}D field")
+        if precision is not None:
+            self._check_p16(precision, lod)
         if isinstance(lod, str):
             if lod != "auto":
                 raise ValueError(f"lod {lod!r}: None, 'auto' or a float")
@@ -1538,7 +1605,7 @@ class HashGridField:
         for o in itertools.product(*[range(0, s, tile) for s in size]):
             ext = [min(tile, s - a) for s, a in zip(size, o)]
             sl = tuple(slice(a, a + e) for a, e in zip(o, ext))
-            out[sl] = self.query(self._resample_points(size, o, ext), lod=lod).reshape(*ext, 3)
+            out[sl] = self.query(self._resample_points(size, o, ext), lod=lod, precision=precision).reshape(*ext, 3)
         return out
 
     def _mip_size(self, m: int) -> Tuple[int, ...]:
@@ -1549,10 +1616,11 @@ class HashGridField:
         return tuple(s >> m for s in self.field_size)
 
     @torch.no_grad()
-    def decode_mip(self, m: int, tile: int = 1024) -> torch.Tensor:
+    def decode_mip(self, m: int, tile: int = 1024, precision: Optional[str] = None) -> torch.Tensor:
         """mip ``m`` of the field, [S_x / 2^m, S_y / 2^m(, S_z / 2^m), 3]: sample j sits at p = (j + 1/2) 2^m - 1/2, the centre of its block of
-        2^m samples per axis, and is queried with level of detail m - the levels finer than the block are faded out and not gathered"""
-        return self.resample(self._mip_size(m), tile=tile, lod=float(int(m)))
+        2^m samples per axis, and is queried with level of detail m - the levels finer than the block are faded out and not gathered
+        (``precision`` other than None is refused: a mip is a level of detail)"""
+        return self.resample(self._mip_size(m), tile=tile, lod=float(int(m)), precision=precision)
 
     def fit_mips(self, target: torch.Tensor, epochs: int, mips: int = 2, batch: Optional[int] = None, order="cell", fused: Optional[bool] = None,
                  freeze_at: float = 0.95) -> List[float]:
