@@ -730,6 +730,47 @@ int nic_hash_fused_forward_backward_points_lod(const nic_hash_desc *desc, const 
 int nic_hash_fused_forward_p16(const nic_hash_desc *desc, const nic_hash_source *src, const int32_t *origins, const float *points,
                                int64_t n_points, const nic_mlp *mlp, int precision, float *y, void *stream);
 
+/* ---- gradients with respect to the POINT COORDINATES (hashgrid.py, HashGridField.point_gradient / jacobian / query_differentiable;
+ *      csrc/hashgrid_pointgrad.hip).  The spatial derivative of what the field represents.
+ *      Notation is that of nic_hash_encode_points: p_a in sample units, clamped to [-1/2, S_a - 1/2]; t_a = rint(256 p_a) + 128, clamped; per
+ *      level q = t_a R_l, v_a and w_a from the cell arithmetic there.  Column l F + f of the row is a_l sum_c prod_b cw_b(c) value[l, idx(v + c), f]
+ *      with cw_b(c) = c_b ? w_b : 1 - w_b and a_l = 1 without a level of detail.  One sample is 1/256 of 256 p_a and one cell of level l is
+ *      256 S_max / R_l of those units, so d w_a / d p_a = R_l / S_max, and
+ *
+ *        d row[l F + f] / d p_a  =  a_l (R_l / S_max) sum_c (c_a ? +1 : -1) prod_{b != a} cw_b(c) value[l, idx(v + c), f]
+ *        dpoints[n, a]           =  sum_l sum_f dx[n, l F + f] d row[l F + f] / d p_a
+ *
+ *      - the interpolant, at the rounded position: the derivative of the multilinear interpolant at the position the forward route uses (the
+ *        1/256 rounding and the integer clamp of t are passed straight through).  It is piecewise constant along its own axis inside a cell
+ *        and discontinuous across cell faces; there is no smoothstep variant.
+ *      - clamped axes: axis a of a point whose floating-point clamp changed p_a (p_a < -1/2, p_a > S_a - 1/2, NaN, -inf / +inf) gives exactly
+ *        0.0f on that axis; its other axes are those of the clamped point, bit for bit.  p_a = S_a - 1/2 itself is not clamped and takes the
+ *        last cell's derivative.
+ *      - values: what the forward route blends - the fp32 entry, or the dequantised uint8 / bit-packed entry (both window forms of the packed one).
+ *      - noise is additive on the row and does not enter.
+ *      - level of detail: lodp == NULL is none (then lod must be NULL too, else NIC_E_ARG); else a_l is nic_hash_encode_points_lod's and depends
+ *        on lambda only: a level of weight 0 is not gathered and adds nothing, a level no lane of a wave weighs is skipped by the wave.  There is
+ *        no gradient with respect to lambda.
+ *      - outputs are WRITTEN, not added; row n belongs to point n; there are no atomics: the same call gives the same bits.
+ *      nic_hash_encode_points_grad: dx = [n_points, L F] (d loss / d row), dpoints = [n_points, dim]; one lane per point; the three sources,
+ *        dim 2 / 3, features 1 / 2 / 4 / 8.
+ *      nic_hash_fused_points_grad: one launch for the set nic_hash_fused_supported answers for (plus num_crops == 1 and 256 S_max < 2^30): the
+ *        row of nic_hash_encode_points(_lod) stays on the chip, y = ColorDecoder(row) as nic_hash_fused_forward_points(_lod) (y null or
+ *        [n_points, 3]), then the decoder's backward to its input with the products of nic_hash_fused_forward_backward_points in their order -
+ *        dZ3 = dy y (1 - y), dA2 = W3^T dZ3, dZ2 = dA2 gelu', dA1 = W2^T dZ2, dZ1 = dA1 gelu', dx = W1^T dZ1 - and dpoints from that dx.
+ *        Exactly one of dy / target ([n_points, 3]) is non-null: with target, dy = 2 (y - target) loss_scale / (3 n_points), the gradient of
+ *        mean((y - target)^2) loss_scale; loss_scale is ignored with dy.  The loss is not an output (the caller has y).  The decoder and the
+ *        table are constants: no parameter gradient, no workspace, no reduction launch.
+ *      Host checks, all before any GPU work, in the siblings' order and with their codes: descriptor (null desc / mlp, then the fused set, for
+ *      the fused entry), null pointers (src, src->data, points, dx / the decoder's layers, dpoints), the source (nic_hash_encode_points' rules),
+ *      the nic_hash_lod (nic_hash_encode_points_lod's rules), both or neither of dy / target (NIC_E_ARG), n_points < 0 (NIC_E_ARG);
+ *      n_points == 0 is NIC_OK with no launch. */
+int nic_hash_encode_points_grad(const nic_hash_desc *desc, const nic_hash_lod *lodp, const nic_hash_source *src, const float *points,
+                                const float *lod, int64_t n_points, const float *dx, float *dpoints, void *stream);
+int nic_hash_fused_points_grad(const nic_hash_desc *desc, const nic_hash_lod *lodp, const nic_hash_source *src, const float *points,
+                               const float *lod, int64_t n_points, const nic_mlp *mlp, const float *dy, const float *target, float loss_scale,
+                               float *y, float *dpoints, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,387 @@
+// The gradient of the hash-grid field with respect to the POINT COORDINATES (include/nicv2_hip.h: nic_hash_encode_points_grad,
+// nic_hash_fused_points_grad; hashgrid.py, HashGridField.point_gradient / jacobian / query_differentiable).
+//
+//   The row of a point is the multilinear blend of the 2^dim corner entries of its cell per level, with the weights w_a = fp32(q mod 256 S_max) /
+//   fp32(256 S_max), q = t_a R_l (hash_common.hpp, point_cell).  One sample is 1/256 of t and one cell of level l is 256 S_max / R_l of those
+//   units, so d w_a / d p_a = R_l / S_max and
+//       d row[l F + f] / d p_a = a_l (R_l / S_max) sum_c (c_a ? +1 : -1) prod_{b != a} cw_b(c) value[l, idx(v + c), f]
+//   - the derivative of the interpolant at the rounded position the forward route uses; an axis whose floating-point clamp moved the point gives 0.
+//   The layer-wise kernel takes d loss / d row from memory, one lane per point.  The fused kernel keeps row and row gradient on the chip: a wave
+//   gathers the rows of 64 points into its LDS tile (THE level loop of hash_common.hpp), runs the 64-64-3 decoder forward and its backward to the
+//   input alone on v_mfma_f32_32x32x2_f32 (decoder_train_half without its weight-gradient passes, the same products in the same order) with d loss /
+//   d row written over the row, and walks the levels a second time for the position gradient - the corner lines were fetched microseconds ago.
+//   Nothing is added anywhere: row n of every output is written once by the lane of point n, so the result does not change from run to run.
+#include "hash_common.hpp"
+
+namespace nic {
+namespace hpgrad {
+using namespace hcommon;
+
+struct GradParams {
+    nic_hash_desc d;          // extent[a] = S_a, num_crops = 1
+    float fade[NIC_HASH_MAX_LEVELS];
+    float lod_uniform;
+    const float* lod;         // null, or [n]
+    const float* points;      // [n, dim]
+    int64_t n;
+    const float* table;       // NIC_HASH_SRC_F32
+    const uint8_t* stored;    // NIC_HASH_SRC_U8
+    const uint32_t* packed;   // NIC_HASH_SRC_BITS, 4-byte aligned
+    float q_scale, q_bias;    // load4fp: (u - q_bias + 1) / q_scale
+    int32_t q_bits, q_tight;
+    const float* dx;          // layer-wise: [n, L F]
+    float* dpoints;           // [n, dim]
+    // fused only
+    const float *w1, *b1, *w2, *b2, *w3, *b3;
+    const float* dy;          // [n, 3], or null: the gradient comes from `target`
+    const float* target;      // [n, 3]
+    float* y;                 // null, or [n, 3]
+    float dscale;             // 2 loss_scale / (3 N)
+};
+
+// bit a: the floating-point clamp of point_fixed kept p_a as it was (a NaN fails both comparisons)
+template <int D>
+__device__ __forceinline__ uint32_t kept_axes(const nic_hash_desc& d, const float* points, int64_t n) {
+    uint32_t m = 0u;
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        const float x = points[n * D + a];
+        if (x >= -0.5f && x <= (float)d.extent[a] - 0.5f) m |= 1u << a;
+    }
+    return m;
+}
+
+// the level loop of encode_point_levels (same offsets, same index, same loaders, same point_cell) with the D signed weights per corner in
+// the place of the one weight: g[a] = sum_l a_l (R_l / S_max) sum_c sign_a(c) prod_{b != a} cw_b(c) sum_f grow(l)[f] value[l, idx(v + c), f].
+// `grow(l, gv)` hands over the F values of d loss / d row of level l.  LOD: a level of weight 0 is not gathered, a level no lane of the wave
+// weighs is jumped over by the wave.
+template <int D, int F, int SRC, bool TIGHT, bool LOD, class GRow>
+__device__ __forceinline__ void point_grad_levels(const GradParams& s, const uint32_t (&t)[3], float lam, GRow grow, float (&g)[D]) {
+    const nic_hash_desc& d = s.d;
+    const uint32_t S = (uint32_t)d.S_max, mask = (1u << d.log2_table) - 1u;
+    const float fdiv = (float)(256u * S);
+    [[maybe_unused]] int64_t lev_off = 0;              // _U8: byte offset of level l
+    [[maybe_unused]] int64_t lev_dw = 0;               // _BITS: dword offset of level l
+#pragma unroll
+    for (int a = 0; a < D; ++a) g[a] = 0.f;
+    for (int l = 0; l < d.levels; ++l) {
+        const uint32_t R = (uint32_t)d.resolution[l];
+        [[maybe_unused]] const float* tab = nullptr;
+        if constexpr (SRC == NIC_HASH_SRC_F32) tab = s.table + ((int64_t)l << d.log2_table) * F;
+        [[maybe_unused]] const uint8_t* stab = nullptr;
+        if constexpr (SRC == NIC_HASH_SRC_U8) {
+            stab = s.stored + lev_off;
+            lev_off += (int64_t)F * hash_level_entries(D, (int32_t)R, d.log2_table);
+        }
+        [[maybe_unused]] const uint32_t* btab = nullptr;
+        if constexpr (SRC == NIC_HASH_SRC_BITS) {
+            btab = s.packed + lev_dw;
+            lev_dw += hash_level_dwords(D, (int32_t)R, d.log2_table, F, s.q_bits);
+        }
+        [[maybe_unused]] float wl = 1.0f;
+        if constexpr (LOD) wl = level_weight(s.fade[l], lam);
+        if (!LOD || (__ballot(wl > 0.f) != 0ull && wl > 0.f)) {
+            const bool dense = hash_level_dense(D, (int32_t)R, d.log2_table);
+            uint32_t v[3];
+            float w[3];
+            point_cell<D>(t, R, S, fdiv, v, w);
+            float gv[F];
+            grow(l, gv);
+            float acc[D];
+#pragma unroll
+            for (int a = 0; a < D; ++a) acc[a] = 0.f;
+#pragma unroll
+            for (int c = 0; c < (1 << D); ++c) {
+                const uint32_t e = hash_index(dense, R, mask, v[0] + (c & 1), v[1] + ((c >> 1) & 1), D == 3 ? v[2] + ((c >> 2) & 1) : 0u);
+                float tv[F];
+                if constexpr (SRC == NIC_HASH_SRC_U8) load_row_u8<F>(stab + (int64_t)e * F, s.q_scale, s.q_bias, tv);
+                else if constexpr (SRC == NIC_HASH_SRC_BITS) load_row_bits<F, TIGHT>(btab, e, s.q_bits, s.q_scale, s.q_bias, tv);
+                else load_row<F>(tab + (int64_t)e * F, tv);
+                // every operation spelled out (nothing for the compiler to contract one way here and another way there): the instantiation
+                // with a level of detail gives the plain one's bits at weight 1
+                float dot = 0.f;
+#pragma unroll
+                for (int f = 0; f < F; ++f) dot = fmaf(gv[f], tv[f], dot);
+                float cw[3];
+#pragma unroll
+                for (int a = 0; a < D; ++a) cw[a] = ((c >> a) & 1) ? w[a] : __fsub_rn(1.0f, w[a]);
+#pragma unroll
+                for (int a = 0; a < D; ++a) {
+                    float sw = ((c >> a) & 1) ? 1.0f : -1.0f;
+#pragma unroll
+                    for (int b = 0; b < D; ++b)
+                        if (b != a) sw = __fmul_rn(sw, cw[b]);
+                    acc[a] = fmaf(sw, dot, acc[a]);
+                }
+            }
+            float scale = __fdiv_rn((float)R, (float)S);
+            if constexpr (LOD) scale = __fmul_rn(scale, wl);
+#pragma unroll
+            for (int a = 0; a < D; ++a) g[a] = fmaf(scale, acc[a], g[a]);
+        }
+    }
+}
+// b is uniform over the launch: the width of the packed window is decided once per point (encode_point's rule)
+template <int D, int F, int SRC, bool LOD, class GRow>
+__device__ __forceinline__ void point_grad(const GradParams& s, const uint32_t (&t)[3], float lam, GRow grow, float (&g)[D]) {
+    if constexpr (SRC == NIC_HASH_SRC_BITS) {
+        if (s.q_tight) point_grad_levels<D, F, SRC, true, LOD>(s, t, lam, grow, g);
+        else point_grad_levels<D, F, SRC, false, LOD>(s, t, lam, grow, g);
+    } else {
+        point_grad_levels<D, F, SRC, false, LOD>(s, t, lam, grow, g);
+    }
+}
+// row n of dpoints: 0 on an axis whose clamp moved the point
+template <int D>
+__device__ __forceinline__ void store_point_grad(float* dpoints, int64_t n, uint32_t kept, const float (&g)[D]) {
+#pragma unroll
+    for (int a = 0; a < D; ++a) dpoints[n * D + a] = ((kept >> a) & 1u) ? g[a] : 0.0f;
+}
+
+// ---- layer-wise: d loss / d row from memory, one lane per point ----------------------------------------------------------------------------
+template <int D, int F, int SRC, bool LOD>
+__global__ void __launch_bounds__(256) hash_points_grad_kernel(const GradParams p) {
+    const int LF = p.d.levels * F;
+    for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < p.n; n += (int64_t)gridDim.x * 256) {
+        uint32_t t[3];
+        point_fixed<D>(p.d, p.points, n, t);
+        const float lam = LOD ? point_lambda(p.lod, p.lod_uniform, n) : 0.f;
+        const float* drow = p.dx + n * LF;
+        float g[D];
+        point_grad<D, F, SRC, LOD>(p, t, lam, [&](int l, float (&gv)[F]) { load_row<F>(drow + l * F, gv); }, g);
+        store_point_grad<D>(p.dpoints, n, kept_axes<D>(p.d, p.points, n), g);
+    }
+}
+
+// ---- the decoder's backward to the input alone -----------------------------------------------------------------------------------------------
+// decoder_train_half (hash_common.hpp) without its three weight-gradient passes and without TrainAcc, the same products in the same order:
+// forward of the 32 samples `32 nt + j` of the row tile `xs` keeping the two GELU derivative tiles, dZ3 = dy y (1 - y), dA2 = W3^T dZ3,
+// dZ2 = dA2 gelu', dA1 = W2^T dZ2, dZ1 = dA1 gelu', dX = W1^T dZ1 written over the rows of this half.  `mine`: this lane (half 0) owns a live
+// sample; its dy is read at `dyrow`, or formed from `trow` as dscale (y - target); y goes to `yrow` when that is not null.
+template <int KT>
+__device__ __forceinline__ void decoder_dx_half(const DecoderSmem& sm, float* xs, int nt, int j, int half, int ks1, bool mine, const float* dyrow,
+                                                const float* trow, float* yrow, float dscale) {
+    const int src = 32 * nt + j;
+    const float* xb = xs + src * XS;
+    // ---- layer 1
+    f32x16 a1[2] = {f32x16{}, f32x16{}};
+    f32x16 d1[2];
+    for (int k = 0; k < ks1; ++k) {
+        const float b = xb[2 * k + half];
+        a1[0] = mfma(sm.w1[j * XS + 2 * k + half], b, a1[0]);
+        a1[1] = mfma(sm.w1[(32 + j) * XS + 2 * k + half], b, a1[1]);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float av, dv;
+            gelu_and_grad(a1[t][r] + sm.b1[32 * t + row_of(r, half)], av, dv);
+            a1[t][r] = av;
+            d1[t][r] = dv;
+        }
+    // ---- layer 2
+    f32x16 a2[2] = {f32x16{}, f32x16{}};
+    f32x16 d2[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int k = 32 * t + row_of(r, half);
+            a2[0] = mfma(sm.w2[j * XS + k], a1[t][r], a2[0]);
+            a2[1] = mfma(sm.w2[(32 + j) * XS + k], a1[t][r], a2[1]);
+        }
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float av, dv;
+            gelu_and_grad(a2[t][r] + sm.b2[32 * t + row_of(r, half)], av, dv);
+            a2[t][r] = av;
+            d2[t][r] = dv;
+        }
+    // ---- output layer: rows 0 .. 2 of one tile (registers 0 .. 2 of half 0)
+    f32x16 z3 = f32x16{};
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int k = 32 * t + row_of(r, half);
+            z3 = mfma(j < 3 ? sm.w3[j * kH + k] : 0.f, a2[t][r], z3);
+        }
+    float yv[3];
+#pragma unroll
+    for (int o = 0; o < 3; ++o) yv[o] = sigmoid_f(z3[o] + sm.b3[o]);
+    if (mine && yrow != nullptr) {
+#pragma unroll
+        for (int o = 0; o < 3; ++o) yrow[o] = yv[o];
+    }
+    // ---- dZ3 = dy y (1 - y); with a target dy = 2 (y - t) loss_scale / (3 N)
+    float dz3[3] = {0.f, 0.f, 0.f};
+    if (mine) {
+#pragma unroll
+        for (int o = 0; o < 3; ++o) {
+            if (dyrow != nullptr) dz3[o] = dyrow[o] * yv[o] * (1.0f - yv[o]);
+            else dz3[o] = dscale * (yv[o] - trow[o]) * yv[o] * (1.0f - yv[o]);
+        }
+    }
+    // dA2 = W3^T dZ3 (k-steps: o = s of half 0; half 1 carries zeros), dZ2 = dA2 gelu'
+    f32x16 dz2[2] = {f32x16{}, f32x16{}};
+#pragma unroll
+    for (int o = 0; o < 3; ++o) {
+        const float b = half == 0 ? dz3[o] : 0.f;
+        dz2[0] = mfma(half == 0 ? sm.w3[o * kH + j] : 0.f, b, dz2[0]);
+        dz2[1] = mfma(half == 0 ? sm.w3[o * kH + 32 + j] : 0.f, b, dz2[1]);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) dz2[t] *= d2[t];
+    // dA1 = W2^T dZ2, dZ1 = dA1 gelu'
+    f32x16 dz1[2] = {f32x16{}, f32x16{}};
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int k = 32 * t + row_of(r, half);
+            dz1[0] = mfma(sm.w2[k * XS + j], dz2[t][r], dz1[0]);
+            dz1[1] = mfma(sm.w2[k * XS + 32 + j], dz2[t][r], dz1[1]);
+        }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) dz1[t] *= d1[t];
+    // dX = W1^T dZ1 over the rows of this half (their X is spent: every lane of the wave has issued its layer-1 reads)
+    f32x16 dx[KT];
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) dx[kt] = f32x16{};
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int h = 32 * t + row_of(r, half);
+#pragma unroll
+            for (int kt = 0; kt < KT; ++kt) dx[kt] = mfma(sm.w1[h * XS + 32 * kt + j], dz1[t][r], dx[kt]);
+        }
+    float* xw = xs + src * XS;
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) xw[32 * kt + row_of(r, half)] = dx[kt][r];
+}
+
+// ---- fused: gather, decoder forward, backward to the row, position gradient; one wave per 64 consecutive points ------------------------------
+template <int D, int F, int SRC, int KT, bool LOD>
+__global__ void __launch_bounds__(256) hash_points_fused_grad_kernel(const GradParams p) {
+    __shared__ DecoderSmem sm;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 31, half = lane >> 5;
+    const int LF = p.d.levels * F;
+    load_decoder(sm, p.w1, p.b1, p.w2, p.b2, p.w3, p.b3, LF, tid);
+    __syncthreads();
+    float* xs = sm.x[wave];
+    float* xrow = xs + lane * XS;
+    const int64_t n_waves = (p.n + 63) >> 6;
+    const WaveRange wr = xcd_range(n_waves);
+    const int ks1 = (LF + 1) >> 1;
+    for (int64_t g = wr.begin; g < wr.end; g += wr.step) {
+        const int64_t wv = 4 * g + wave;
+        if (wv >= n_waves) continue;                            // wave-uniform; nothing below synchronises the workgroup
+        const int64_t n0 = wv << 6, n_raw = n0 + lane;
+        const bool live_lane = n_raw < p.n;
+        const int64_t row = live_lane ? n_raw : p.n - 1;        // a lane past the end takes the last point; it stores nothing
+        const float lam = LOD ? point_lambda(p.lod, p.lod_uniform, row) : 0.f;
+        uint32_t t[3];
+        point_fixed<D>(p.d, p.points, row, t);
+        encode_point<D, F, SRC, false, false, LOD>(p, t, 0, lam, xrow);
+        wave_sync();
+        const unsigned long long live_mask = __ballot(live_lane);
+#pragma unroll 1
+        for (int nt = 0; nt < 2; ++nt) {
+            if (((live_mask >> (32 * nt)) & 0xFFFFFFFFull) == 0ull) continue;      // a half tile without a live sample (wave-uniform)
+            const int64_t n = n0 + 32 * nt + j;
+            const bool mine = half == 0 && n < p.n;
+            const int64_t r = n < p.n ? n : p.n - 1;
+            decoder_dx_half<KT>(sm, xs, nt, j, half, ks1, mine, p.dy != nullptr ? p.dy + r * 3 : nullptr, p.target != nullptr ? p.target + r * 3 : nullptr,
+                                p.y != nullptr ? p.y + r * 3 : nullptr, p.dscale);
+        }
+        wave_sync();
+        float gp[D];
+        point_grad<D, F, SRC, LOD>(p, t, lam, [&](int l, float (&gv)[F]) {
+#pragma unroll
+            for (int f = 0; f < F; ++f) gv[f] = xrow[l * F + f];
+        }, gp);
+        if (live_lane) store_point_grad<D>(p.dpoints, n_raw, kept_axes<D>(p.d, p.points, row), gp);
+        wave_sync();
+    }
+}
+
+// ---- host side (the descriptor checks, the source and the grid rules are hash_common.hpp's) --------------------------------------------------
+template <bool FUSED, int SRC, bool LOD>
+static int launch(const GradParams& p, int nb, void* stream) {
+    return dispatch_dim_features(p.d, [&](auto dim, auto features) {
+        constexpr int D = decltype(dim)::value, F = decltype(features)::value;
+        const hipStream_t s = (hipStream_t)stream;
+        if constexpr (!FUSED) hipLaunchKernelGGL((hash_points_grad_kernel<D, F, SRC, LOD>), dim3(nb), dim3(256), 0, s, p);
+        else if (p.d.levels * F > 32) hipLaunchKernelGGL((hash_points_fused_grad_kernel<D, F, SRC, 2, LOD>), dim3(nb), dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((hash_points_fused_grad_kernel<D, F, SRC, 1, LOD>), dim3(nb), dim3(256), 0, s, p);
+    });
+}
+template <bool FUSED>
+static int launch_src(const GradParams& p, int kind, bool lod, int nb, void* stream) {
+    return dispatch_source(kind, [&](auto src) {
+        constexpr int SRC = decltype(src)::value;
+        return lod ? launch<FUSED, SRC, true>(p, nb, stream) : launch<FUSED, SRC, false>(p, nb, stream);
+    });
+}
+// a null nic_hash_lod is "no level of detail" and then takes no per-point array; else the checks of check_lod, and the struct into the parameters
+static int set_grad_lod(GradParams& p, const nic_hash_lod* lodp, const float* lod) {
+    if (!lodp) return lod ? NIC_E_ARG : NIC_OK;
+    const int rc = check_lod(&p.d, lodp);
+    if (rc) return rc;
+    for (int l = 0; l < NIC_HASH_MAX_LEVELS; ++l) p.fade[l] = l < p.d.levels ? lodp->fade[l] : 0.f;
+    p.lod_uniform = lodp->lod_uniform;
+    p.lod = lod;
+    return NIC_OK;
+}
+
+}  // namespace hpgrad
+}  // namespace nic
+
+using namespace nic;
+using namespace nic::hpgrad;
+
+extern "C" {
+
+int nic_hash_encode_points_grad(const nic_hash_desc* desc, const nic_hash_lod* lodp, const nic_hash_source* src, const float* points, const float* lod,
+                                int64_t n_points, const float* dx, float* dpoints, void* stream) {
+    int rc = check_point_desc(desc);
+    if (rc) return rc;
+    if (!src || !src->data || !points || !dx || !dpoints) return NIC_E_NULL;
+    GradParams p{};
+    p.d = *desc; p.points = points; p.n = n_points; p.dx = dx; p.dpoints = dpoints;
+    if ((rc = set_point_source(p, src)) != NIC_OK) return rc;
+    if ((rc = set_grad_lod(p, lodp, lod)) != NIC_OK) return rc;
+    if (n_points < 0) return NIC_E_ARG;
+    if (n_points == 0) return NIC_OK;
+    return launch_src<false>(p, src->kind, lodp != nullptr, strided_grid((n_points + 63) >> 6), stream);
+}
+
+int nic_hash_fused_points_grad(const nic_hash_desc* desc, const nic_hash_lod* lodp, const nic_hash_source* src, const float* points, const float* lod,
+                               int64_t n_points, const nic_mlp* mlp, const float* dy, const float* target, float loss_scale, float* y, float* dpoints,
+                               void* stream) {
+    if (!desc || !mlp) return NIC_E_NULL;
+    int rc = nic_hash_fused_supported(desc, kH, mlp->n_linear);          // the only copy of the fused set (hash_fused.hip)
+    if (rc) return rc;
+    if ((rc = check_point_desc(desc)) != NIC_OK) return rc;
+    if (!src || !src->data || !points || !dpoints) return NIC_E_NULL;
+    for (int i = 0; i < 3; ++i)
+        if (!mlp->w[i] || !mlp->b[i]) return NIC_E_NULL;
+    GradParams p{};
+    p.d = *desc; p.points = points; p.n = n_points; p.dy = dy; p.target = target; p.y = y; p.dpoints = dpoints;
+    if ((rc = set_point_source(p, src)) != NIC_OK) return rc;
+    if ((rc = set_grad_lod(p, lodp, lod)) != NIC_OK) return rc;
+    if ((dy != nullptr) == (target != nullptr)) return NIC_E_ARG;        // exactly one of the two
+    if (n_points < 0) return NIC_E_ARG;
+    if (n_points == 0) return NIC_OK;
+    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
+    p.dscale = 2.0f * (float)((double)loss_scale / (3.0 * (double)n_points));
+    return launch_src<true>(p, src->kind, lodp != nullptr, persistent_grid((n_points + 63) >> 6), stream);
+}
+
+}  // extern "C"

@@ -63,7 +63,13 @@ float, or one value per point; None makes the launches made before), ``resample(
 The decoder on the 16-bit matrix pipe (include/nicv2_hip.h, nic_hash_fused_forward_p16; csrc/hashgrid_fused16.hip): ``decode`` /
 ``query`` / ``resample`` take ``precision="split" | "bf16"`` - the same gather, the three Linear layers' products in split-bf16 (hi hi + hi lo +
 lo hi) or plain bf16 operands with fp32 accumulation, bias, GELU and sigmoid in fp32.  ``None`` makes the launches made before.  Forward only, no
-level of detail, no bit depth per level."""
+level of detail, no bit depth per level.
+
+Gradients with respect to the point coordinates (include/nicv2_hip.h, nic_hash_encode_points_grad; csrc/hashgrid_pointgrad.hip):
+d w_a / d p_a = R_l / S_max, so the derivative of a level is the signed-weight sum over its corners - the derivative of the multilinear
+interpolant at the rounded position, 0 on an axis where the point lies outside the field.  ``hash_encode_points_grad`` turns a row gradient
+into a position gradient, ``hash_fused_points_grad`` does gather, decoder, its backward to the row and the position gradient in one launch;
+``HashGridField.point_gradient`` / ``jacobian`` / ``query_differentiable`` are the surface.  The field's parameters are constants there."""
 from __future__ import annotations
 
 import ctypes
@@ -760,6 +766,77 @@ def hash_fused_forward_backward_points_lod(geo: HashGeometry, table: torch.Tenso
                                           add_grads, add_loss, tail, (lod, lod_uniform, fade))
 
 
+def _grad_lod(geo: HashGeometry, lod, lod_uniform, fade, n: int, device):
+    """(``nic_hash_lod`` or None, the checked per-point tensor or None) of the gradient entries: no level of detail at all - ``lod`` None,
+    ``lod_uniform`` 0 and ``fade`` None - is the plain launch"""
+    if lod is None and fade is None and float(lod_uniform) == 0.0:
+        return None, None
+    per_point = _check_lod(lod, n, device)
+    return _lod_struct(geo, fade, lod_uniform), per_point
+
+
+def _check_dy_target(dy, target, n: int):
+    """exactly one of ``dy`` / ``target``, [N, 3] (ValueError otherwise; decided on the shapes alone, before any device is asked)"""
+    if (dy is None) == (target is None):
+        raise ValueError("exactly one of dy and target: the gradient of the output, or the colours of a mean squared error")
+    for name, v in (("dy", dy), ("target", target)):
+        if v is not None and (not isinstance(v, torch.Tensor) or tuple(v.shape) != (n, 3)):
+            raise ValueError(f"{name} must be [{n}, 3], got {tuple(v.shape) if isinstance(v, torch.Tensor) else type(v).__name__}")
+
+
+@fused._on_tensor_device
+def hash_encode_points_grad(geo: HashGeometry, data: torch.Tensor, points: torch.Tensor, dx: torch.Tensor, kind: str = "f32",
+                            num_bits: Optional[int] = None, lod: Optional[torch.Tensor] = None, lod_uniform: float = 0.0, fade=None) -> torch.Tensor:
+    """[N, dim] = d loss / d points for the [N, L F] gradient ``dx`` of ``hash_encode_points`` (``hash_encode_points_lod`` with any of ``lod`` /
+    ``lod_uniform`` / ``fade``) from the table ``data`` of ``kind`` (nic_hash_encode_points_grad): the derivative of the multilinear
+    interpolant at the rounded position, written (not added), 0 on an axis whose clamp moved the point.  The table is a constant."""
+    src, data = _point_source(geo, data, kind, num_bits)
+    pts = _check_points(geo, points)
+    n = pts.shape[0]
+    dx = _lib.require_cuda_f32(dx.detach() if isinstance(dx, torch.Tensor) else dx, "dx")
+    if tuple(dx.shape) != (n, geo.width):
+        raise ValueError(f"dx must be [{n}, {geo.width}], got {tuple(dx.shape)}")
+    lp, lod_t = _grad_lod(geo, lod, lod_uniform, fade, n, pts.device)
+    d = _point_desc(geo)
+    out = torch.empty(n, geo.dim, dtype=torch.float32, device=data.device)
+    if n == 0:
+        return out
+    _lib.check(_lib.load().nic_hash_encode_points_grad(ctypes.byref(d), None if lp is None else ctypes.byref(lp), ctypes.byref(src), _lib.ptr(pts),
+                                                       _lib.ptr(lod_t), n, _lib.ptr(dx), _lib.ptr(out), _lib.stream_ptr(data.device)),
+               "nic_hash_encode_points_grad")
+    return out
+
+
+@fused._on_tensor_device
+def hash_fused_points_grad(geo: HashGeometry, data: torch.Tensor, points: torch.Tensor, params: Sequence[torch.Tensor],
+                           dy: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None, loss_scale: float = 1.0, want_y: bool = True,
+                           kind: str = "f32", num_bits: Optional[int] = None, lod: Optional[torch.Tensor] = None, lod_uniform: float = 0.0,
+                           fade=None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+    """(y [N, 3] or None, dpoints [N, dim]) in one launch (nic_hash_fused_points_grad): y = ColorDecoder(hash_encode_points(...)),
+    then d loss / d points for the output gradient ``dy`` [N, 3], or for loss = mean((y - ``target``)^2) * ``loss_scale`` - exactly one of the
+    two.  Row and row gradient stay on the chip; table and decoder are constants."""
+    n = points.shape[0] if isinstance(points, torch.Tensor) and points.dim() == 2 else -1
+    if n >= 0:
+        _check_dy_target(dy, target, n)
+    src, data = _point_source(geo, data, kind, num_bits)
+    params = _check_fused_decoder(geo, [q.detach() for q in params])
+    pts = _check_points(geo, points)
+    n = pts.shape[0]
+    _check_dy_target(dy, target, n)
+    dy = None if dy is None else _lib.require_cuda_f32(dy.detach(), "dy")
+    target = None if target is None else _lib.require_cuda_f32(target.detach(), "target")
+    lp, lod_t = _grad_lod(geo, lod, lod_uniform, fade, n, pts.device)
+    d, m = _point_desc(geo), fused._mlp_struct(params)
+    y = torch.empty(n, 3, dtype=torch.float32, device=data.device) if want_y else None
+    out = torch.empty(n, geo.dim, dtype=torch.float32, device=data.device)
+    if n == 0:
+        return y, out
+    _lib.check(_lib.load().nic_hash_fused_points_grad(ctypes.byref(d), None if lp is None else ctypes.byref(lp), ctypes.byref(src), _lib.ptr(pts),
+                                                      _lib.ptr(lod_t), n, ctypes.byref(m), _lib.ptr(dy), _lib.ptr(target), float(loss_scale),
+                                                      _lib.ptr(y), _lib.ptr(out), _lib.stream_ptr(data.device)), "nic_hash_fused_points_grad")
+    return y, out
+
+
 @fused._on_tensor_device
 def hash_pack_bits_levels(geo: HashGeometry, table: torch.Tensor, level_bits, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """format /2 of an fp32 [L, T, F] table (nic_hash_pack_bits_levels): ``hash_pack_bits`` with ``level_bits[l]`` bits per value inside level
@@ -981,6 +1058,22 @@ def hash_encode_points_differentiable(geo: HashGeometry, table: torch.Tensor, po
     if not table.requires_grad:
         return hash_encode_points(geo, table, pts)
     return HashEncodePointsFunction.apply(table, geo, pts)
+
+
+class _QueryPointsFunction(torch.autograd.Function):
+    """``HashGridField.query`` as a differentiable op of the points (``query_differentiable``): backward = ``point_gradient`` with the
+    output gradient; nothing for the field's parameters"""
+
+    @staticmethod
+    def forward(ctx, points, field, lod):
+        ctx.field, ctx.lod = field, lod
+        ctx.save_for_backward(points)
+        return field.query(points, lod=lod)
+
+    @staticmethod
+    def backward(ctx, dy):
+        points, = ctx.saved_tensors
+        return ctx.field.point_gradient(points, dy=dy.contiguous(), lod=ctx.lod)[1], None, None
 
 
 def _table_of_u8(geo: HashGeometry, stored: torch.Tensor, num_bits: int) -> torch.Tensor:
@@ -1574,6 +1667,67 @@ class HashGridField:
         if pts.shape[0] == 0:
             return torch.empty(0, 3, dtype=torch.float32, device=self.device)
         return fused.DecoderFunction.apply(hash_encode_points(self.geo, data, pts, kind, bits), *params)
+
+    def point_gradient(self, points: torch.Tensor, dy: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None, scale: float = 1.0,
+                       lod=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(y [N, 3], dpoints [N, dim]): ``query(points, lod)`` and the gradient with respect to the point COORDINATES of
+        sum(y * ``dy``) for an output gradient ``dy`` [N, 3], or of mean((y - ``target``)^2) * ``scale`` for colours ``target`` [N, 3] -
+        exactly one of the two.  It is the derivative of the multilinear interpolant at the rounded position ``query`` uses (piecewise
+        constant along its own axis inside a cell), exactly 0 on an axis where the point lies outside the field, in sample units.  Reads
+        whichever table the field holds (a field from ``load_compressed`` works).  One launch on the fused route
+        (nic_hash_fused_points_grad); encode, general decoder forward and backward and nic_hash_encode_points_grad on the layer-wise one.
+        The field's parameters are constants here: no ``.grad`` of the table or the decoder is touched and no optimiser state moves."""
+        if self.level_bits is not None:
+            raise NotImplementedError("gradients with respect to the points with a bit depth per level are not built (DESIGN 7): use a uniform num_bits")
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != self.geo.dim:
+            raise ValueError(f"points must be [N, {self.geo.dim}] for a {self.geo.dim}D field, got "
+                             f"{tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__}")
+        n = points.shape[0]
+        _check_dy_target(dy, target, n)
+        lod_t, lod_u, fade = None, 0.0, None
+        if lod is not None:
+            lod_t, lod_u = self._lod_args(lod)
+            fade = self.lod_fade
+        pts = _check_points(self.geo, points)
+        data, kind, bits = self._point_table()
+        params = [p.detach() for p in self.decoder.linear_params()]
+        if self.route == "fused":
+            return hash_fused_points_grad(self.geo, data, pts, params, dy=dy, target=target, loss_scale=scale, want_y=True, kind=kind, num_bits=bits,
+                                          lod=lod_t, lod_uniform=lod_u, fade=fade)
+        if n == 0:
+            return torch.empty(0, 3, dtype=torch.float32, device=self.device), torch.empty(0, self.geo.dim, dtype=torch.float32, device=self.device)
+        if lod is None:
+            x = hash_encode_points(self.geo, data, pts, kind, bits)
+        else:
+            x = hash_encode_points_lod(self.geo, data, pts, lod_t, lod_u, fade, kind, bits)
+        with torch.enable_grad():
+            x.requires_grad_(True)
+            y = fused.DecoderFunction.apply(x, *params)
+            if dy is None:
+                g = (y.detach() - _lib.require_cuda_f32(target.detach(), "target")) * (2.0 * float(scale) / (3.0 * n))
+            else:
+                g = _lib.require_cuda_f32(dy.detach(), "dy")
+            dx, = torch.autograd.grad(y, x, g)
+        return y.detach(), hash_encode_points_grad(self.geo, data, pts, dx, kind, bits, lod=lod_t, lod_uniform=lod_u, fade=fade)
+
+    def jacobian(self, points: torch.Tensor, lod=None) -> torch.Tensor:
+        """[N, 3, dim]: d y[n, o] / d points[n, a], as three ``point_gradient`` calls with a one-hot ``dy``"""
+        rows = []
+        for o in range(3):
+            dy = torch.zeros(points.shape[0], 3, dtype=torch.float32, device=points.device)
+            dy[:, o] = 1.0
+            rows.append(self.point_gradient(points, dy=dy, lod=lod)[1])
+        return torch.stack(rows, dim=1)
+
+    def query_differentiable(self, points: torch.Tensor, lod=None) -> torch.Tensor:
+        """``query(points, lod)`` as a differentiable op of ``points``: the backward hands the output gradient to ``point_gradient``, so
+        ``points.requires_grad_()`` works with any torch loss and optimiser on the positions, or on whatever produced them (a shift, a warp, a
+        pose).  No gradient reaches the field's parameters through it: table and decoder are constants here (``train_points`` trains them)."""
+        if self.level_bits is not None:
+            raise NotImplementedError("gradients with respect to the points with a bit depth per level are not built (DESIGN 7): use a uniform num_bits")
+        if not (isinstance(points, torch.Tensor) and points.requires_grad and torch.is_grad_enabled()):
+            return self.query(points, lod=lod)
+        return _QueryPointsFunction.apply(points, self, lod)
 
     def _resample_points(self, size: Sequence[int], origin: Sequence[int], extent: Sequence[int]) -> torch.Tensor:
         """[prod(extent), dim] fp32 points of the block ``origin`` .. ``origin + extent`` of a regular grid of ``size`` samples over the field,
