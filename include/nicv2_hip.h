@@ -771,6 +771,32 @@ int nic_hash_fused_points_grad(const nic_hash_desc *desc, const nic_hash_lod *lo
                                const float *lod, int64_t n_points, const nic_mlp *mlp, const float *dy, const float *target, float loss_scale,
                                float *y, float *dpoints, void *stream);
 
+/* ---- the field AND the point positions in one training step (hashgrid.py, HashGridField.train_points(dpoints=) /
+ *      train_points_differentiable; csrc/hashgrid_points_joint.hip).
+ *      nic_hash_fused_forward_backward_points_grad: with lodp == NULL it is nic_hash_fused_forward_backward_points, otherwise
+ *      nic_hash_fused_forward_backward_points_lod, argument for argument - two launches, the per-workgroup records, the fixed-order reduction
+ *      with `tail` riding on it, NIC_HASH_FUSED_ADD_GRADS / _ADD_LOSS, the workspace (the query is nic_hash_fused_points_workspace_bytes), the
+ *      noise keys (sample_base + order[n] and the column), the clamped `order`, nic_mark_kernel_end, the fp32 table as the only source.  loss,
+ *      y and the decoder gradients are those entries' bit for bit; table_grad is theirs up to the order of the atomics.
+ *      On top of that row n of dpoints [n_points, dim] is written once, by the lane that handles point n (with an `order` that is row order[pos],
+ *      not pos): d loss / d points[n] of the loss this call returns, loss_scale mean((y - target)^2) over the call's points -
+ *      nic_hash_fused_points_grad's value with `target`, bit for bit.  The derivative is taken at the parameters the forward used (before the
+ *      tail's step), with the codec noise and the level weights as constants, as the derivative of the multilinear interpolant at the rounded
+ *      position (previous section), in sample units, exactly 0.0f on an axis whose floating-point clamp moved the point.  dpoints is
+ *      OVERWRITTEN, never added to, whatever NIC_HASH_FUSED_ADD_GRADS says; no atomic touches it: the same call gives the same bits.
+ *      table_grad == NULL is a frozen table: no scatter; dpoints and the decoder records are still produced.
+ *      Host checks, all before any GPU work, with the siblings' codes, in this order: null desc / mlp, the fused set
+ *      (nic_hash_fused_supported), the conditions of the point entries (num_crops == 1, 256 S_max < 2^30), null pointers (table, points, the
+ *      decoder's layers, target, mlp_grads, loss, dpoints, workspace: NIC_E_NULL; lodp, lod, order, table_grad, y and tail may be null), flags
+ *      outside the two above (NIC_E_ARG), the nic_hash_lod when given (nic_hash_encode_points_lod's rules), lodp == NULL with lod != NULL
+ *      (NIC_E_ARG, nic_hash_fused_points_grad's rule), quant, n_points < 0 or n_points >= 2^31 with an order (NIC_E_ARG), the workspace
+ *      (NIC_E_WORKSPACE), the tail.  n_points == 0 is NIC_OK with nothing written. */
+int nic_hash_fused_forward_backward_points_grad(const nic_hash_desc *desc, const nic_hash_lod *lodp, const nic_hash_quant *quant,
+                                                const float *table, const float *points, const float *lod, int64_t n_points,
+                                                const int32_t *order, const nic_mlp *mlp, const float *target, float loss_scale,
+                                                float *table_grad, const nic_mlp_grads *mlp_grads, float *loss, float *y, float *dpoints,
+                                                int flags, void *workspace, size_t workspace_bytes, const nic_step_tail *tail, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@
 //   d row written over the row, and walks the levels a second time for the position gradient - the corner lines were fetched microseconds ago.
 //   Nothing is added anywhere: row n of every output is written once by the lane of point n, so the result does not change from run to run.
 #include "hash_common.hpp"
+#include "hashgrid_pointgrad.hpp"
 
 namespace nic {
 namespace hpgrad {
@@ -39,104 +40,8 @@ struct GradParams {
     float dscale;             // 2 loss_scale / (3 N)
 };
 
-// bit a: the floating-point clamp of point_fixed kept p_a as it was (a NaN fails both comparisons)
-template <int D>
-__device__ __forceinline__ uint32_t kept_axes(const nic_hash_desc& d, const float* points, int64_t n) {
-    uint32_t m = 0u;
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-        const float x = points[n * D + a];
-        if (x >= -0.5f && x <= (float)d.extent[a] - 0.5f) m |= 1u << a;
-    }
-    return m;
-}
-
-// the level loop of encode_point_levels (same offsets, same index, same loaders, same point_cell) with the D signed weights per corner in
-// the place of the one weight: g[a] = sum_l a_l (R_l / S_max) sum_c sign_a(c) prod_{b != a} cw_b(c) sum_f grow(l)[f] value[l, idx(v + c), f].
-// `grow(l, gv)` hands over the F values of d loss / d row of level l.  LOD: a level of weight 0 is not gathered, a level no lane of the wave
-// weighs is jumped over by the wave.
-template <int D, int F, int SRC, bool TIGHT, bool LOD, class GRow>
-__device__ __forceinline__ void point_grad_levels(const GradParams& s, const uint32_t (&t)[3], float lam, GRow grow, float (&g)[D]) {
-    const nic_hash_desc& d = s.d;
-    const uint32_t S = (uint32_t)d.S_max, mask = (1u << d.log2_table) - 1u;
-    const float fdiv = (float)(256u * S);
-    [[maybe_unused]] int64_t lev_off = 0;              // _U8: byte offset of level l
-    [[maybe_unused]] int64_t lev_dw = 0;               // _BITS: dword offset of level l
-#pragma unroll
-    for (int a = 0; a < D; ++a) g[a] = 0.f;
-    for (int l = 0; l < d.levels; ++l) {
-        const uint32_t R = (uint32_t)d.resolution[l];
-        [[maybe_unused]] const float* tab = nullptr;
-        if constexpr (SRC == NIC_HASH_SRC_F32) tab = s.table + ((int64_t)l << d.log2_table) * F;
-        [[maybe_unused]] const uint8_t* stab = nullptr;
-        if constexpr (SRC == NIC_HASH_SRC_U8) {
-            stab = s.stored + lev_off;
-            lev_off += (int64_t)F * hash_level_entries(D, (int32_t)R, d.log2_table);
-        }
-        [[maybe_unused]] const uint32_t* btab = nullptr;
-        if constexpr (SRC == NIC_HASH_SRC_BITS) {
-            btab = s.packed + lev_dw;
-            lev_dw += hash_level_dwords(D, (int32_t)R, d.log2_table, F, s.q_bits);
-        }
-        [[maybe_unused]] float wl = 1.0f;
-        if constexpr (LOD) wl = level_weight(s.fade[l], lam);
-        if (!LOD || (__ballot(wl > 0.f) != 0ull && wl > 0.f)) {
-            const bool dense = hash_level_dense(D, (int32_t)R, d.log2_table);
-            uint32_t v[3];
-            float w[3];
-            point_cell<D>(t, R, S, fdiv, v, w);
-            float gv[F];
-            grow(l, gv);
-            float acc[D];
-#pragma unroll
-            for (int a = 0; a < D; ++a) acc[a] = 0.f;
-#pragma unroll
-            for (int c = 0; c < (1 << D); ++c) {
-                const uint32_t e = hash_index(dense, R, mask, v[0] + (c & 1), v[1] + ((c >> 1) & 1), D == 3 ? v[2] + ((c >> 2) & 1) : 0u);
-                float tv[F];
-                if constexpr (SRC == NIC_HASH_SRC_U8) load_row_u8<F>(stab + (int64_t)e * F, s.q_scale, s.q_bias, tv);
-                else if constexpr (SRC == NIC_HASH_SRC_BITS) load_row_bits<F, TIGHT>(btab, e, s.q_bits, s.q_scale, s.q_bias, tv);
-                else load_row<F>(tab + (int64_t)e * F, tv);
-                // every operation spelled out (nothing for the compiler to contract one way here and another way there): the instantiation
-                // with a level of detail gives the plain one's bits at weight 1
-                float dot = 0.f;
-#pragma unroll
-                for (int f = 0; f < F; ++f) dot = fmaf(gv[f], tv[f], dot);
-                float cw[3];
-#pragma unroll
-                for (int a = 0; a < D; ++a) cw[a] = ((c >> a) & 1) ? w[a] : __fsub_rn(1.0f, w[a]);
-#pragma unroll
-                for (int a = 0; a < D; ++a) {
-                    float sw = ((c >> a) & 1) ? 1.0f : -1.0f;
-#pragma unroll
-                    for (int b = 0; b < D; ++b)
-                        if (b != a) sw = __fmul_rn(sw, cw[b]);
-                    acc[a] = fmaf(sw, dot, acc[a]);
-                }
-            }
-            float scale = __fdiv_rn((float)R, (float)S);
-            if constexpr (LOD) scale = __fmul_rn(scale, wl);
-#pragma unroll
-            for (int a = 0; a < D; ++a) g[a] = fmaf(scale, acc[a], g[a]);
-        }
-    }
-}
-// b is uniform over the launch: the width of the packed window is decided once per point (encode_point's rule)
-template <int D, int F, int SRC, bool LOD, class GRow>
-__device__ __forceinline__ void point_grad(const GradParams& s, const uint32_t (&t)[3], float lam, GRow grow, float (&g)[D]) {
-    if constexpr (SRC == NIC_HASH_SRC_BITS) {
-        if (s.q_tight) point_grad_levels<D, F, SRC, true, LOD>(s, t, lam, grow, g);
-        else point_grad_levels<D, F, SRC, false, LOD>(s, t, lam, grow, g);
-    } else {
-        point_grad_levels<D, F, SRC, false, LOD>(s, t, lam, grow, g);
-    }
-}
-// row n of dpoints: 0 on an axis whose clamp moved the point
-template <int D>
-__device__ __forceinline__ void store_point_grad(float* dpoints, int64_t n, uint32_t kept, const float (&g)[D]) {
-#pragma unroll
-    for (int a = 0; a < D; ++a) dpoints[n * D + a] = ((kept >> a) & 1u) ? g[a] : 0.0f;
-}
+// kept_axes, point_grad (the level loop: point_cell<D>(t, R, S, fdiv, v, w), the 2^D corner rows, the D signed weights per corner) and
+// store_point_grad live in hashgrid_pointgrad.hpp: the joint training kernel (hashgrid_points_joint.hip) walks the levels with the same code
 
 // ---- layer-wise: d loss / d row from memory, one lane per point ----------------------------------------------------------------------------
 template <int D, int F, int SRC, bool LOD>

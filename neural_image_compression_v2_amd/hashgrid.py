@@ -636,8 +636,9 @@ def hash_fused_forward_points(geo: HashGeometry, data: torch.Tensor, points: tor
 
 
 def _fused_forward_backward_points(geo, table, points, params, target, mlp_grads, table_grad, order, loss, loss_scale, want_y, quant, add_grads,
-                                   add_loss, tail, lod):
-    """``hash_fused_forward_backward_points`` (``lod`` None) and ``hash_fused_forward_backward_points_lod`` (``lod`` = (lod, lod_uniform, fade))"""
+                                   add_loss, tail, lod, dpoints=None):
+    """``hash_fused_forward_backward_points`` (``lod`` None) and ``hash_fused_forward_backward_points_lod`` (``lod`` = (lod, lod_uniform, fade));
+    with ``dpoints`` (checked by the caller) ``hash_fused_forward_backward_points_grad``, which takes either"""
     t = _check_table(geo, table.detach())
     params = _check_fused_decoder(geo, [q.detach() for q in params])
     pts = _check_points(geo, points)
@@ -663,8 +664,12 @@ def _fused_forward_backward_points(geo, table, points, params, target, mlp_grads
     qp, head = None if q is None else ctypes.byref(q), (ctypes.byref(d),) if lp is None else (ctypes.byref(d), ctypes.byref(lp))
     where = (_lib.ptr(pts), n) if lp is None else (_lib.ptr(pts), _lib.ptr(lod_tensor), n)
     name = "nic_hash_fused_forward_backward_points" if lp is None else "nic_hash_fused_forward_backward_points_lod"
+    out = (_lib.ptr(y),)
+    if dpoints is not None:                                # the one entry with a nullable nic_hash_lod, and the gradient after y
+        head, where = (ctypes.byref(d), None if lp is None else ctypes.byref(lp)), (_lib.ptr(pts), _lib.ptr(lod_tensor), n)
+        name, out = "nic_hash_fused_forward_backward_points_grad", (_lib.ptr(y), _lib.ptr(dpoints))
     _lib.check(getattr(lib, name)(*head, qp, _lib.ptr(t), *where, _lib.ptr(order), ctypes.byref(m), _lib.ptr(target), float(loss_scale),
-                                  _lib.ptr(table_grad), ctypes.byref(gs), _lib.ptr(loss), _lib.ptr(y), flags, _lib.ptr(ws), ws.numel(),
+                                  _lib.ptr(table_grad), ctypes.byref(gs), _lib.ptr(loss), *out, flags, _lib.ptr(ws), ws.numel(),
                                   None if tail is None else ctypes.byref(tail.struct), _lib.stream_ptr(t.device)), name)
     if tail is not None:
         tail.commit()
@@ -764,6 +769,50 @@ def hash_fused_forward_backward_points_lod(geo: HashGeometry, table: torch.Tenso
     launches, the row weighed as in ``hash_encode_points_lod`` and its gradient weighed again before the scatter.  Returns (loss [1], y or None)."""
     return _fused_forward_backward_points(geo, table, points, params, target, mlp_grads, table_grad, order, loss, loss_scale, want_y, quant,
                                           add_grads, add_loss, tail, (lod, lod_uniform, fade))
+
+
+def _check_dpoints(geo: HashGeometry, points, dpoints) -> torch.Tensor:
+    """the output of a joint step: an fp32 [N, dim] tensor on the points' HIP device, contiguous - the kernel writes it in place, so nothing is
+    converted or copied (shapes and dtype are decided before any device is asked)"""
+    if not isinstance(dpoints, torch.Tensor):
+        raise TypeError("dpoints must be a torch.Tensor")
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != geo.dim:
+        raise ValueError(f"points must be [N, {geo.dim}] for a {geo.dim}D field, got "
+                         f"{tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__}")
+    if tuple(dpoints.shape) != tuple(points.shape):
+        raise ValueError(f"dpoints must be [{points.shape[0]}, {geo.dim}], one row per point, got {tuple(dpoints.shape)}")
+    if dpoints.dtype != torch.float32:
+        raise ValueError(f"dpoints has dtype {dpoints.dtype}; the kernel writes fp32")
+    if not dpoints.is_contiguous():
+        raise ValueError("dpoints must be contiguous: the kernel writes it in place")
+    if not dpoints.is_cuda:
+        raise RuntimeError(f"dpoints lives on {dpoints.device}: this package only runs on a HIP device (no CPU path)")
+    if dpoints.device != points.device:
+        raise ValueError(f"dpoints lives on {dpoints.device}, the points on {points.device}")
+    return dpoints
+
+
+@fused._on_tensor_device
+def hash_fused_forward_backward_points_grad(geo: HashGeometry, table: torch.Tensor, points: torch.Tensor, params: Sequence[torch.Tensor],
+                                            target: torch.Tensor, mlp_grads: Sequence[torch.Tensor], lod: Optional[torch.Tensor] = None,
+                                            lod_uniform: float = 0.0, fade=None, table_grad: Optional[torch.Tensor] = None,
+                                            order: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None, loss_scale: float = 1.0,
+                                            want_y: bool = False, quant=None, add_grads: bool = False, add_loss: bool = False, tail=None,
+                                            dpoints: Optional[torch.Tensor] = None):
+    """``hash_fused_forward_backward_points`` - with any of ``lod`` / ``lod_uniform`` / ``fade``, ``hash_fused_forward_backward_points_lod`` -
+    that also writes d loss / d points of the loss it returns (nic_hash_fused_forward_backward_points_grad): the same two
+    launches, loss, y and gradients; the position gradient is ``hash_fused_points_grad``'s with ``target``, taken at the parameters the forward
+    used (before the ``tail``'s step), noise and level weights constant.  ``dpoints``: None for a fresh tensor, or an fp32 [N, dim] device tensor
+    that is overwritten (never added to).  Returns (loss [1], y or None, dpoints)."""
+    if dpoints is None:
+        pts = _check_points(geo, points)
+        dpoints = torch.empty(pts.shape[0], geo.dim, dtype=torch.float32, device=pts.device)
+    else:
+        dpoints = _check_dpoints(geo, points, dpoints)
+    plain = lod is None and fade is None and float(lod_uniform) == 0.0
+    loss, y = _fused_forward_backward_points(geo, table, points, params, target, mlp_grads, table_grad, order, loss, loss_scale, want_y, quant,
+                                             add_grads, add_loss, tail, None if plain else (lod, lod_uniform, fade), dpoints=dpoints)
+    return loss, y, dpoints
 
 
 def _grad_lod(geo: HashGeometry, lod, lod_uniform, fade, n: int, device):
@@ -1076,6 +1125,24 @@ class _QueryPointsFunction(torch.autograd.Function):
         return ctx.field.point_gradient(points, dy=dy.contiguous(), lod=ctx.lod)[1], None, None
 
 
+class _TrainPointsFunction(torch.autograd.Function):
+    """``HashGridField.train_points`` as a differentiable op of the points (``train_points_differentiable``): the forward trains the field and
+    keeps d loss / d points of the loss it returns, the backward hands upstream * dpoints to the points"""
+
+    @staticmethod
+    def forward(ctx, points, field, target, kwargs):
+        dp = torch.empty(points.shape, dtype=torch.float32, device=points.device)
+        with torch.enable_grad():                      # the layer-wise step runs its own backward
+            loss = field.train_points(points.detach(), target, dpoints=dp, **kwargs)
+        ctx.save_for_backward(dp)
+        return loss.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        dp, = ctx.saved_tensors
+        return g.reshape(()) * dp, None, None, None
+
+
 def _table_of_u8(geo: HashGeometry, stored: torch.Tensor, num_bits: int) -> torch.Tensor:
     """the fp32 [L, T, F] table a compact uint8 one stores (load4fp per level; the entries a dense level cannot address stay zero) - the input
     ``hash_pack_bits`` takes when a uint8 file is re-saved packed; save4fp of these values gives the bytes back"""
@@ -1241,7 +1308,7 @@ class HashGridField:
         return loss.detach()
 
     def train_points(self, points: torch.Tensor, target: torch.Tensor, accumulate: bool = False, scale: float = 1.0, step: bool = True,
-                     noise: Optional[bool] = None, order=None, fused: bool = False, lod=None) -> torch.Tensor:
+                     noise: Optional[bool] = None, order=None, fused: bool = False, lod=None, dpoints: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``train_step`` on samples that are no raster: ``points`` [N, dim] (fp32, sample units, any order) with their colours ``target``
         [N, 3].  ``accumulate`` / ``scale`` / ``step`` / ``noise``, the noise keys (seed, optimiser step, samples of this pass before this
         chunk + row), the freeze behaviour and the optimiser bookkeeping are ``train_step``'s.  By default the call is layer-wise and unordered
@@ -1251,9 +1318,18 @@ class HashGridField:
         lanes share their cells; rows, targets and noise keys stay the caller's.  ``fused``: the fused step at points (two launches,
         ``nic_hash_fused_forward_backward_points``) - needs ``route == "fused"``.  ``lod``: None (the calls above, unchanged), or a level of
         detail for these samples - a float, or one value per point [N] - which fades the finer levels out of the row and of its gradient
-        (the ``_lod`` entry points, fade starts ``lod_fade``)."""
+        (the ``_lod`` entry points, fade starts ``lod_fade``).  ``dpoints``: None (exactly the calls above), or an fp32
+        [N, dim] contiguous device tensor that the call OVERWRITES with d loss / d points of the loss it returns: the
+        derivative ``point_gradient(points, target=, scale=)`` gives, taken at the parameters this step's forward used (before the optimiser
+        moves them), noise and level weights constant - registration while fitting, in the step's own launches (``fused=True``:
+        nic_hash_fused_forward_backward_points_grad; layer-wise: nic_hash_encode_points_grad on the row gradient the step has anyway, also
+        after ``freeze()``).  Each chunk of an ``accumulate`` pass fills its own ``dpoints``."""
         if self.table is None:
             raise RuntimeError("a field from load_compressed decodes only")
+        if dpoints is not None:
+            if self.level_bits is not None:
+                raise NotImplementedError("gradients with respect to the points with a bit depth per level are not built (DESIGN 7): use a uniform num_bits")
+            dpoints = _check_dpoints(self.geo, points, dpoints)
         lod_t, lod_u = (None, 0.0) if lod is None else self._lod_args(lod)
         params = self.decoder.linear_params()
         grad = self.table.grad
@@ -1280,7 +1356,7 @@ class HashGridField:
         if isinstance(order, str):
             order = hash_point_order(self.geo, pts)
         if fused:
-            return self._fused_train_points(pts, target, accumulate, scale, step, noise, order, None if lod is None else (lod_t, lod_u))
+            return self._fused_train_points(pts, target, accumulate, scale, step, noise, order, None if lod is None else (lod_t, lod_u), dpoints)
         if not accumulate:
             for p in params:
                 p.grad = None
@@ -1295,11 +1371,14 @@ class HashGridField:
         else:
             x = hash_encode_points(self.geo, self.table, pts, quant=quant)
         self._pass_samples += n
-        if not frozen:
+        if not frozen or dpoints is not None:
             x.requires_grad_(True)
         y = DecoderFunction.apply(x, *params)          # `fused` is this call's argument here
         loss = ((y - target) ** 2).mean() * scale
         loss.backward()
+        if dpoints is not None:                        # before the optimiser moves the table: the derivative at the forward's parameters
+            dpoints.copy_(hash_encode_points_grad(self.geo, self.table, pts, x.grad, lod=lod_t, lod_uniform=lod_u,
+                                                  fade=None if lod is None else self.lod_fade))
         if not frozen and lod is not None:
             hash_encode_points_backward_lod(self.geo, pts, x.grad, grad, lod_t, lod_u, self.lod_fade, order=order)
         elif not frozen:
@@ -1317,10 +1396,10 @@ class HashGridField:
         return loss.detach()
 
     @torch.no_grad()
-    def _fused_train_points(self, pts, target, accumulate, scale, step, noise, order, lod=None) -> torch.Tensor:
+    def _fused_train_points(self, pts, target, accumulate, scale, step, noise, order, lod=None, dpoints=None) -> torch.Tensor:
         """``train_points`` as two launches, with ``_fused_train_step``'s bookkeeping: persistent decoder-gradient buffers, the chunks of a
         pass adding into them and into the table gradient, the optimiser riding on the last chunk's reduction.  The arguments are checked.
-        ``lod``: None or (per-point tensor or None, launch-wide value)."""
+        ``lod``: None or (per-point tensor or None, launch-wide value).  ``dpoints``: None, or the tensor the joint entry overwrites."""
         params = self.decoder.linear_params()
         frozen = self.frozen
         grad = None if frozen else self.table.grad
@@ -1337,7 +1416,11 @@ class HashGridField:
         tail = None
         if step:
             tail = self.optimizer.step_tail([] if frozen else [(self.table, grad)], list(zip(params, gm)))
-        if lod is not None:
+        if dpoints is not None:
+            loss, _, _ = hash_fused_forward_backward_points_grad(self.geo, self.table, pts, params, target, gm, *((None, 0.0, None) if lod is None else
+                                                                 (lod[0], lod[1], self.lod_fade)), table_grad=grad, order=order,
+                                                                 loss_scale=float(scale), quant=quant, add_grads=accumulate, tail=tail, dpoints=dpoints)
+        elif lod is not None:
             loss, _ = hash_fused_forward_backward_points_lod(self.geo, self.table, pts, params, target, gm, lod[0], lod[1], self.lod_fade,
                                                              table_grad=grad, order=order, loss_scale=float(scale), quant=quant,
                                                              add_grads=accumulate, tail=tail)
@@ -1360,6 +1443,18 @@ class HashGridField:
                 self.scheduler.step()
             self.steps += 1
         return loss
+
+    def train_points_differentiable(self, points: torch.Tensor, target: torch.Tensor, **kwargs) -> torch.Tensor:
+        """``train_points(points, target, **kwargs)`` as a differentiable op of ``points``: the call steps the field as it
+        always does, and the loss it returns has a backward that hands upstream * d loss / d points to ``points`` - so with
+        ``loss = f.train_points_differentiable(warp(theta, p0), target, fused=True, order="cell"); loss.backward(); pose_opt.step()`` the
+        field steps inside the call and the warp outside it, from one forward.  No gradient reaches the field's parameters through autograd:
+        their step is the call's own.  Without ``points.requires_grad``, or under ``torch.no_grad()``, it is plain ``train_points``."""
+        if "dpoints" in kwargs:
+            raise TypeError("train_points_differentiable keeps dpoints for the backward: call train_points(dpoints=) for the tensor itself")
+        if not (isinstance(points, torch.Tensor) and points.requires_grad and torch.is_grad_enabled()):
+            return self.train_points(points, target, **kwargs)
+        return _TrainPointsFunction.apply(points, self, target, kwargs)
 
     def fit_points(self, points: torch.Tensor, target: torch.Tensor, epochs: int, batch: Optional[int] = None, order="cell",
                    fused: Optional[bool] = None, freeze_at: float = 0.95, lod=None) -> List[float]:
