@@ -797,6 +797,35 @@ int nic_hash_fused_forward_backward_points_grad(const nic_hash_desc *desc, const
                                                 float *table_grad, const nic_mlp_grads *mlp_grads, float *loss, float *y, float *dpoints,
                                                 int flags, void *workspace, size_t workspace_bytes, const nic_step_tail *tail, void *stream);
 
+/* ---- B hash-grid fields of one geometry per launch (hashgrid.py, HashGridFieldBatch; csrc/hashgrid_batch.hip).
+ *      All n_fields fields share `desc`: dim, levels, features, log2_table, resolutions, the crop extent and num_crops.  Storage is stacked and
+ *      contiguous, and the field strides follow from desc - the arguments are the BASES: tables and table_grads [B, L, T, F] fp32; mlp / mlp_grads
+ *      the bases of W1 [B, 64, L F], b1 [B, 64], W2 [B, 64, 64], b2 [B, 64], W3 [B, 3, 64], b3 [B, 3]; origins [B, num_crops, dim] int32 on the
+ *      device (every field has its own crops); target and y [B, N, 3], N = num_crops x the extents; loss [B].
+ *      nic_hash_batch_forward is nic_hash_fused_forward per field in ONE launch, nic_hash_batch_forward_backward is
+ *      nic_hash_fused_forward_backward per field in TWO launches (the training kernel and the fixed-order reduction of its records) whatever
+ *      n_fields is: loss[b] = loss_scale mean((y_b - target_b)^2) over field b's N samples, table_grads (null: frozen tables, no scatter) is
+ *      ADDED to with fp32 atomics, the decoder gradients are overwritten (NIC_HASH_FUSED_ADD_GRADS: added to), likewise loss
+ *      (NIC_HASH_FUSED_ADD_LOSS); y null or [B, N, 3]; nic_mark_kernel_end honoured.  The noise of `quant` is keyed by sample_base + the row
+ *      INSIDE the field and the column: field b sees exactly the noise of a single-field call with the same quant.  There is no optimiser
+ *      tail: one nic_adam_multi over the stacked tensors steps every field.  Against the single-field entries y, loss and the gradients agree
+ *      to the summation order (the records of a field are split over other workgroups).
+ *      A workgroup belongs to one field: field b has groups_per_field = G workgroups, the launch n_fields x G.  G = 0 is automatic: the
+ *      workgroup cap of a persistent launch (one per CU, a multiple of 8) / n_fields, rounded up to a multiple of 8, at least 8, at most the
+ *      grid nic_hash_fused_forward would use for one field.  A positive G must be a multiple of 8 and at most that grid.  n_fields x G may exceed
+ *      the CU count (nothing synchronises across workgroups).  workspace >= nic_hash_batch_workspace_bytes (n_fields x G records; 0: refused).
+ *      Host checks, all before any GPU work, in nic_hash_fused_forward_backward's order: null desc / mlp (NIC_E_NULL), the fused set
+ *      (nic_hash_fused_supported's code; then 256 S_max < 2^30, NIC_E_ARG: the lattice is read through the fixed-point cell), n_fields in
+ *      1 .. 65535 (NIC_E_ARG), groups_per_field (NIC_E_ARG), null pointers (NIC_E_NULL; table_grads and y may be null), flags (NIC_E_ARG), quant
+ *      (nic_hash_fused_forward_backward's rules), the workspace (NIC_E_WORKSPACE). */
+size_t nic_hash_batch_workspace_bytes(const nic_hash_desc *desc, int n_fields, int groups_per_field, const nic_mlp *mlp);   /* 0: refused */
+int nic_hash_batch_forward(const nic_hash_desc *desc, int n_fields, int groups_per_field, const float *tables, const int32_t *origins,
+                           const nic_mlp *mlp, float *y, void *stream);
+int nic_hash_batch_forward_backward(const nic_hash_desc *desc, int n_fields, int groups_per_field, const nic_hash_quant *quant,
+                                    const float *tables, const int32_t *origins, const nic_mlp *mlp, const float *target, float loss_scale,
+                                    float *table_grads, const nic_mlp_grads *mlp_grads, float *loss, float *y, int flags, void *workspace,
+                                    size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

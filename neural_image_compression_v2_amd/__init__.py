@@ -14,3 +14,14 @@ from . import _lib  # noqa: F401
 
 def library_path() -> str:
     return _lib.LIB_PATH
+
+
+_HASHGRID_NAMES = ("HashGeometry", "HashGridField", "HashGridFieldBatch", "hash_batch_forward", "hash_batch_forward_backward", "hash_batch_groups")
+
+
+def __getattr__(name):
+    """the hash-grid field classes and the batched wrappers, from ``hashgrid`` on first use (importing the package stays light)"""
+    if name in _HASHGRID_NAMES:
+        from . import hashgrid
+        return getattr(hashgrid, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -235,6 +235,10 @@ SIGNATURES = {
                                         _P, _P, _P]),
     "nic_hash_fused_forward_backward_points_grad": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashLod), ctypes.POINTER(NicHashQuant), _P, _P,
                                                          _P, _L, _P, _M, _P, _F, _P, _G, _P, _P, _P, _I, _P, _SZ, ctypes.POINTER(NicStepTail), _P]),
+    "nic_hash_batch_workspace_bytes": (_SZ, [ctypes.POINTER(NicHashDesc), _I, _I, _M]),
+    "nic_hash_batch_forward": (_I, [ctypes.POINTER(NicHashDesc), _I, _I, _P, _P, _M, _P, _P]),
+    "nic_hash_batch_forward_backward": (_I, [ctypes.POINTER(NicHashDesc), _I, _I, ctypes.POINTER(NicHashQuant), _P, _P, _M, _P, _F, _P, _G, _P, _P, _I,
+                                             _P, _SZ, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -1,0 +1,282 @@
+// B hash-grid fields of ONE geometry per launch (include/nicv2_hip.h: nic_hash_batch_*; hashgrid.py, HashGridFieldBatch).
+// A small field cannot fill the chip: a 256 x 256 image is 256 groups of four patches, each workgroup of the single-field kernel stages the whole
+// decoder to decode one of them, and a folder of such images pays that one after the other.  Here a workgroup BELONGS to a field:
+//
+//   field b = blockIdx.x / G, local block lb = blockIdx.x % G.  G is a multiple of 8, so lb & 7 is still the workgroup's XCD and the patch walk
+//   is xcd_range's arithmetic on (lb, G) over the patches of ONE field (field_range below).  The workgroup loads field b's decoder once and
+//   walks only field b's patches; nothing synchronises across workgroups, so B G may exceed the CU count (the grid is then not persistent).
+//   storage is stacked and contiguous, the field strides follow from the descriptor: tables / table gradients [B, L, T, F], decoder tensors and
+//   their gradients [B, ...], origins [B, num_crops, dim], target / y [B, N, 3], records [B, G, rec], loss [B].
+//   training: encode_point on lattice_fixed's position (the crop route's row bit for bit) with the noise keyed by the field-LOCAL sample id - field
+//   b sees the noise of a single-field call with the same nic_hash_quant -, decoder_train_half, scatter_point into field b's gradient,
+//   write_record to record (b, lb); a workgroup without a patch writes its all-zero record.  hash_batch_reduce_kernel is
+//   hash_fused_reduce_kernel's fixed-order sum with blockIdx.y = b, without the optimiser tail: one nic_adam_multi over the stacked tensors
+//   steps every field.
+// Every device helper is hash_common.hpp's; this unit holds the two kernels, their parameters and the host side.
+#include "hash_common.hpp"
+
+namespace nic {
+namespace hbatch {
+using namespace hcommon;
+
+struct BParams {
+    nic_hash_desc d;          // one field's: every field of the batch shares it
+    const float* tables;      // [B, L, T, F]
+    const int32_t* origins;   // [B, num_crops, dim]
+    const float *w1, *b1, *w2, *b2, *w3, *b3;      // bases of the stacked decoder
+    const float* target;      // [B, N, 3]
+    float* y;                 // [B, N, 3] (training: may be null)
+    float* grads;             // [B, L, T, F] (null: frozen tables, no scatter)
+    float* partials;          // [B, G, rec]
+    NoiseSrc noise;           // mode NIC_NOISE_NONE / NIC_NOISE_KERNEL
+    uint64_t sample_base;
+    float dscale;             // 2 loss_scale / (3 N), N = the samples of ONE field
+    int64_t n_patches;        // of one field
+    int64_t n_samples;        // N
+    int32_t groups;           // G
+};
+
+// what encode_point reads of a source, for field b: the shared descriptor and noise by reference, the field's own table
+struct FieldSrc {
+    const nic_hash_desc& d;
+    const float* table;
+    const NoiseSrc& noise;
+    uint64_t sample_base;
+};
+
+// xcd_range on (lb, G) instead of (blockIdx.x, gridDim.x): each XCD (local blocks x, x + 8, ..) walks one contiguous range of groups of 4 patches
+__device__ __forceinline__ WaveRange field_range(int64_t n_waves, int lb, int G) {
+    const int xcd = lb & 7;
+    const int64_t n_groups = (n_waves + 3) >> 2, chunk = (n_groups + 7) >> 3;
+    const int64_t g_begin = xcd * chunk;
+    return WaveRange{g_begin + (lb >> 3), g_begin + chunk < n_groups ? g_begin + chunk : n_groups, G >> 3};
+}
+
+// the sample of lane `lane` in patch `wv` of a field: its row inside the field (targets, outputs, noise keys) and its fixed-point position.  A
+// lane on the rim of a patch gets the position of a real sample; it stores and adds nothing.
+template <int D>
+__device__ __forceinline__ bool lattice_position(const nic_hash_desc& d, const int32_t* origins, int64_t wv, int64_t n_patches, int lane, int64_t& row,
+                                                 uint32_t (&t)[3]) {
+    const PatchSample<D> s = patch_sample<D>(d, wv, n_patches, lane);
+    lattice_fixed<D>(d, origins, s, t);
+    row = s.n;
+    return s.live;
+}
+
+// MODE: forward only (DecoderSmem, y stored), training, training with the codec's noise on the row
+enum { HB_FWD = 0, HB_TRAIN = 1, HB_TRAIN_NOISY = 2 };
+
+template <int D, int F, int KT, int MODE>
+__global__ void __launch_bounds__(256) hash_batch_kernel(const BParams p) {
+    constexpr bool TRAIN = MODE != HB_FWD;
+    __shared__ std::conditional_t<TRAIN, TrainSmem, DecoderSmem> sm;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 31, half = lane >> 5;
+    const int LF = p.d.levels * F;
+    const int b = (int)(blockIdx.x / (unsigned)p.groups), lb = (int)(blockIdx.x - (unsigned)b * (unsigned)p.groups);
+    const int64_t tab_off = (((int64_t)b * p.d.levels) << p.d.log2_table) * F, row_off = (int64_t)b * p.n_samples * 3;
+    load_decoder(sm, p.w1 + (int64_t)b * kH * LF, p.b1 + b * kH, p.w2 + (int64_t)b * kH * kH, p.b2 + b * kH, p.w3 + b * 3 * kH, p.b3 + b * 3, LF, tid);
+    __syncthreads();
+    float* xs = sm.x[wave];
+    float* xrow = xs + lane * XS;
+    const int32_t* origins = p.origins + (int64_t)b * p.d.num_crops * D;
+    const FieldSrc src_b{p.d, p.tables + tab_off, p.noise, p.sample_base};
+    const int ks1 = (LF + 1) >> 1;
+    const WaveRange wr = field_range(p.n_patches, lb, p.groups);
+    if constexpr (TRAIN) {
+        float* P = sm.p[wave];
+        float* Q = sm.q[wave];
+        float* grad = p.grads != nullptr ? p.grads + tab_off : nullptr;
+        const float* target = p.target + row_off;
+        float* y = p.y != nullptr ? p.y + row_off : nullptr;
+        TrainAcc<KT> A;
+        A.clear();
+        for (int64_t g = wr.begin; g < wr.end; g += wr.step) {
+            const int64_t wv = 4 * g + wave;
+            if (wv >= p.n_patches) continue;                    // wave-uniform; nothing below synchronises the workgroup
+            int64_t row;
+            uint32_t t[3];
+            const bool live_lane = lattice_position<D>(p.d, origins, wv, p.n_patches, lane, row, t);
+            encode_point<D, F, NIC_HASH_SRC_F32, MODE == HB_TRAIN_NOISY, false, false>(src_b, t, row, 0.f, xrow);
+            wave_sync();
+            const unsigned long long live_mask = __ballot(live_lane);
+#pragma unroll 1
+            for (int nt = 0; nt < 2; ++nt) {
+                const int src = 32 * nt + j;
+                const bool mine = half == 0 && ((live_mask >> src) & 1ull);
+                const int64_t r = (int64_t)(uint32_t)__shfl((int)(uint32_t)row, src) | ((int64_t)__shfl((int)(row >> 32), src) << 32);
+                decoder_train_half<KT>(sm, xs, P, Q, nt, j, half, ks1, mine, target + r * 3, y != nullptr ? y + r * 3 : nullptr, p.dscale,
+                                       grad != nullptr, A);
+            }
+            wave_sync();
+            if (grad != nullptr)
+                scatter_point<D, F, false>(p.d, t, grad, nullptr, 0.f, live_lane, lane, [&](int l, float (&gv)[F]) {
+#pragma unroll
+                    for (int f = 0; f < F; ++f) gv[f] = xrow[l * F + f];
+                });
+            wave_sync();
+        }
+        write_record<KT>(sm, A, LF, p.partials + (int64_t)blockIdx.x * RecLayout(LF).rec, tid);      // record (b, lb); all zero without a patch
+    } else {
+        float* y = p.y + row_off;
+        for (int64_t g = wr.begin; g < wr.end; g += wr.step) {
+            const int64_t wv = 4 * g + wave;
+            if (wv >= p.n_patches) continue;                    // wave-uniform; nothing below synchronises the workgroup
+            int64_t row;
+            uint32_t t[3];
+            const bool live_lane = lattice_position<D>(p.d, origins, wv, p.n_patches, lane, row, t);
+            encode_point<D, F, NIC_HASH_SRC_F32, false, false, false>(src_b, t, row, 0.f, xrow);
+            wave_sync();
+            const unsigned long long live_mask = __ballot(live_lane);
+#pragma unroll 1
+            for (int nt = 0; nt < 2; ++nt) {
+                const int src = 32 * nt + j;
+                const int64_t r = (int64_t)(uint32_t)__shfl((int)(uint32_t)row, src) | ((int64_t)__shfl((int)(row >> 32), src) << 32);
+                float yv[3];
+                decoder_forward_half(sm, xs, nt, j, half, ks1, yv);
+                if (half == 0 && ((live_mask >> src) & 1ull)) {
+#pragma unroll
+                    for (int o = 0; o < 3; ++o) y[r * 3 + o] = yv[o];
+                }
+            }
+            wave_sync();
+        }
+    }
+}
+
+// hash_fused_reduce_kernel's fixed-order sum, field blockIdx.y: a block = 32 outputs x 8 slices of the field's G records, the slices combined
+// through LDS in slice order.  `g` holds the BASES of the stacked gradients, `loss` is [B].  No optimiser tail.
+__global__ void __launch_bounds__(256) hash_batch_reduce_kernel(const float* partials, int n_rec, int lf, nic_mlp_grads g, float* loss, float loss_mul,
+                                                                int add_grads, int add_loss) {
+    __shared__ float red[8][32];
+    const RecLayout rl(lf);
+    const int64_t b = blockIdx.y;
+    const int slice = threadIdx.x >> 5, e = blockIdx.x * 32 + (threadIdx.x & 31);
+    float part[4] = {0.f, 0.f, 0.f, 0.f};
+    const int per = (n_rec + 7) >> 3, w_lo = slice * per, w_hi = w_lo + per < n_rec ? w_lo + per : n_rec;
+    if (e < rl.rec) {
+        const float* src = partials + b * n_rec * rl.rec + e;
+        int w = w_lo;
+        for (; w + 4 <= w_hi; w += 4) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) part[k] += src[(int64_t)(w + k) * rl.rec];
+        }
+        for (; w < w_hi; ++w) part[0] += src[(int64_t)w * rl.rec];
+    }
+    red[slice][threadIdx.x & 31] = (part[0] + part[1]) + (part[2] + part[3]);
+    __syncthreads();
+    if (slice != 0 || e >= rl.rec) return;
+    float acc = red[0][threadIdx.x];
+#pragma unroll
+    for (int k = 1; k < 8; ++k) acc += red[k][threadIdx.x];
+    if (e == rl.loss) {
+        if (loss) loss[b] = add_loss ? loss[b] + acc * loss_mul : acc * loss_mul;
+        return;
+    }
+    float* dst = e < rl.b1 ? (g.w[0] ? g.w[0] + b * rl.b1 + e : nullptr) : e < rl.w2 ? (g.b[0] ? g.b[0] + b * kH + (e - rl.b1) : nullptr)
+               : e < rl.b2 ? (g.w[1] ? g.w[1] + b * kH * kH + (e - rl.w2) : nullptr) : e < rl.w3 ? (g.b[1] ? g.b[1] + b * kH + (e - rl.b2) : nullptr)
+               : e < rl.b3 ? (g.w[2] ? g.w[2] + b * 3 * kH + (e - rl.w3) : nullptr) : (g.b[2] ? g.b[2] + b * 3 + (e - rl.b3) : nullptr);
+    if (!dst) return;
+    *dst = add_grads ? acc + *dst : acc;
+}
+
+// ---- host side (the checks and grid rules are hash_common.hpp's) -----------------------------------------------------------------------------
+constexpr int kMaxFields = 65535;                 // the reduction's blockIdx.y
+
+// the lattice goes through the fixed-point cell: 256 S_max < 2^30, as in every unit that reads a crop through lattice_fixed
+static int check_batch_desc(const nic_hash_desc* d, int n_linear) {
+    const int rc = nic_hash_fused_supported(d, kH, n_linear);            // the only copy of the fused set (hash_fused.hip)
+    if (rc) return rc;
+    return 256 * (int64_t)d->S_max >= (int64_t(1) << 30) ? NIC_E_ARG : NIC_OK;
+}
+// G: 0 = wg_cap() / B rounded up to a multiple of 8, at least 8, at most the single field's persistent grid; a positive value must be a
+// multiple of 8 within that grid.  -1: refused
+static int batch_groups(const nic_hash_desc* d, int n_fields, int groups_per_field) {
+    const int top = persistent_grid(count_patches(d));
+    if (groups_per_field < 0 || (groups_per_field & 7) || groups_per_field > top) return -1;
+    if (groups_per_field > 0) return groups_per_field;
+    int g = (wg_cap() / n_fields + 7) / 8 * 8;
+    g = g < 8 ? 8 : g;
+    return g < top ? g : top;
+}
+static bool mlp3_ok(const nic_mlp* m) {
+    for (int i = 0; i < 3; ++i)
+        if (!m->w[i] || !m->b[i]) return false;
+    return true;
+}
+static void fill(BParams& p, const nic_hash_desc* d, const float* tables, const int32_t* origins, const nic_mlp* mlp, float* y, int groups) {
+    p.d = *d; p.tables = tables; p.origins = origins; p.y = y; p.groups = groups;
+    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
+    p.n_patches = count_patches(d);
+    p.n_samples = (int64_t)d->num_crops * d->extent[0] * d->extent[1] * (d->dim == 3 ? d->extent[2] : 1);
+    p.noise.mode = NIC_NOISE_NONE;
+}
+template <int MODE>
+static int launch(const BParams& p, int n_fields, void* stream) {
+    const dim3 grid((unsigned)n_fields * (unsigned)p.groups);
+    return dispatch_dim_features(p.d, [&](auto dim, auto features) {
+        constexpr int D = decltype(dim)::value, F = decltype(features)::value;
+        if (p.d.levels * F > 32) hipLaunchKernelGGL((hash_batch_kernel<D, F, 2, MODE>), grid, dim3(256), 0, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL((hash_batch_kernel<D, F, 1, MODE>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    });
+}
+
+}  // namespace hbatch
+}  // namespace nic
+
+using namespace nic;
+using namespace nic::hbatch;
+
+extern "C" {
+
+size_t nic_hash_batch_workspace_bytes(const nic_hash_desc* desc, int n_fields, int groups_per_field, const nic_mlp* mlp) {
+    if (!desc || !mlp || check_batch_desc(desc, mlp->n_linear) != NIC_OK || n_fields < 1 || n_fields > kMaxFields) return 0;
+    const int g = batch_groups(desc, n_fields, groups_per_field);
+    if (g < 0) return 0;
+    return (size_t)n_fields * g * RecLayout(desc->levels * desc->features).rec * sizeof(float);
+}
+
+int nic_hash_batch_forward(const nic_hash_desc* desc, int n_fields, int groups_per_field, const float* tables, const int32_t* origins,
+                           const nic_mlp* mlp, float* y, void* stream) {
+    if (!desc || !mlp) return NIC_E_NULL;
+    const int rc = check_batch_desc(desc, mlp->n_linear);
+    if (rc) return rc;
+    if (n_fields < 1 || n_fields > kMaxFields) return NIC_E_ARG;
+    const int g = batch_groups(desc, n_fields, groups_per_field);
+    if (g < 0) return NIC_E_ARG;
+    if (!tables || !origins || !mlp3_ok(mlp) || !y) return NIC_E_NULL;
+    BParams p{};
+    fill(p, desc, tables, origins, mlp, y, g);
+    return launch<HB_FWD>(p, n_fields, stream);
+}
+
+int nic_hash_batch_forward_backward(const nic_hash_desc* desc, int n_fields, int groups_per_field, const nic_hash_quant* quant, const float* tables,
+                                    const int32_t* origins, const nic_mlp* mlp, const float* target, float loss_scale, float* table_grads,
+                                    const nic_mlp_grads* mlp_grads, float* loss, float* y, int flags, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+    const KernelEndDrop end;
+    if (!desc || !mlp) return NIC_E_NULL;
+    int rc = check_batch_desc(desc, mlp->n_linear);
+    if (rc) return rc;
+    if (n_fields < 1 || n_fields > kMaxFields) return NIC_E_ARG;
+    const int g = batch_groups(desc, n_fields, groups_per_field);
+    if (g < 0) return NIC_E_ARG;
+    if (!tables || !origins || !mlp3_ok(mlp) || !target || !mlp_grads || !loss || !workspace) return NIC_E_NULL;
+    if (flags & ~(NIC_HASH_FUSED_ADD_GRADS | NIC_HASH_FUSED_ADD_LOSS)) return NIC_E_ARG;
+    BParams p{};
+    fill(p, desc, tables, origins, mlp, y, g);
+    p.target = target; p.grads = table_grads;
+    if ((rc = set_noise(quant, true, p.noise, p.sample_base)) != NIC_OK) return rc;
+    const int lf = desc->levels * desc->features;
+    const RecLayout rl(lf);
+    if (workspace_bytes < (size_t)n_fields * g * rl.rec * sizeof(float)) return NIC_E_WORKSPACE;
+    const float loss_mul = (float)((double)loss_scale / (3.0 * (double)p.n_samples));
+    p.dscale = 2.0f * loss_mul;
+    p.partials = (float*)workspace;
+    if ((rc = p.noise.mode == NIC_NOISE_KERNEL ? launch<HB_TRAIN_NOISY>(p, n_fields, stream) : launch<HB_TRAIN>(p, n_fields, stream)) != NIC_OK) return rc;
+    kernel_end_mark((hipStream_t)stream);
+    hipLaunchKernelGGL(hash_batch_reduce_kernel, dim3((unsigned)((rl.rec + 31) / 32), (unsigned)n_fields), dim3(256), 0, (hipStream_t)stream, p.partials, g,
+                       lf, *mlp_grads, loss, loss_mul, (flags & NIC_HASH_FUSED_ADD_GRADS) ? 1 : 0, (flags & NIC_HASH_FUSED_ADD_LOSS) ? 1 : 0);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -69,7 +69,12 @@ Gradients with respect to the point coordinates (include/nicv2_hi
 d w_a / d p_a = R_l / S_max, so the derivative of a level is the signed-weight sum over its corners - the derivative of the multilinear
 interpolant at the rounded position, 0 on an axis where the point lies outside the field.  ``hash_encode_points_grad`` turns a row gradient
 into a position gradient, ``hash_fused_points_grad`` does gather, decoder, its backward to the row and the position gradient in one launch;
-``HashGridField.point_gradient`` / ``jacobian`` / ``query_differentiable`` are the surface.  The field's parameters are constants there."""
+``HashGridField.point_gradient`` / ``jacobian`` / ``query_differentiable`` are the surface.  The field's parameters are constants there.
+
+B fields per launch (include/nicv2_hip.h, nic_hash_batch_forward_backward; csrc/hashgrid_batch.hip): ``HashGridFieldBatch`` holds
+the stacked tables [B, L, T, F] and decoder tensors of B fields of one geometry; a workgroup of the batched kernel belongs to one field, a step is
+three launches whatever B is (the kernel, the reduction per field, one ``FusedAdam`` over the stacked tensors), ``decode`` one per tile.
+``hash_batch_forward`` / ``hash_batch_forward_backward`` are the functional forms; ``extract(b)`` / ``insert(b, field)`` move single fields out and in."""
 from __future__ import annotations
 
 import ctypes
@@ -456,6 +461,159 @@ def hash_fused_forward_backward(geo: HashGeometry, table: torch.Tensor, coord, e
                                                    _lib.stream_ptr(t.device)), "nic_hash_fused_forward_backward")
     if tail is not None:
         tail.commit()
+    return loss, y
+
+
+# ---- B fields of one geometry per launch (include/nicv2_hip.h, nic_hash_batch_*; csrc/hashgrid_batch.hip) ---------------------------
+def _persistent_grid(n_waves: int, cap: int) -> int:
+    """workgroups of a persistent launch over ``n_waves`` patches, four to a workgroup: a multiple of 8, at most ``cap`` (hash_common.hpp)"""
+    return min((((int(n_waves) + 3) // 4) + 7) // 8 * 8, int(cap))
+
+
+def _patches(geo: HashGeometry, num_crops: int, extent: Sequence[int]) -> int:
+    ps = 8 if geo.dim == 2 else 4
+    n = int(num_crops)
+    for e in extent:
+        n *= (int(e) + ps - 1) // ps
+    return n
+
+
+def hash_batch_groups(n_fields: int, patches: int, cap: int, groups_per_field: int = 0) -> int:
+    """G, the workgroups one field of a batched launch gets (nic_hash_batch_*; the rule in Python ints).  ``patches``: the 8 x 8 / 4 x 4 x 4
+    patches of ONE field's crops; ``cap``: the workgroups of a persistent launch (one per CU, a multiple of 8).  0 = automatic: ``cap // n_fields``
+    rounded up to a multiple of 8, at least 8, at most the grid one field alone would launch; a positive value must be a multiple of 8 within
+    that grid."""
+    n_fields, g = int(n_fields), int(groups_per_field)
+    if n_fields < 1:
+        raise ValueError("a batch holds at least one field")
+    top = _persistent_grid(patches, cap)
+    if g < 0 or g % 8 or g > top:
+        raise ValueError(f"groups_per_field {g}: 0 (automatic) or a multiple of 8 up to {top}, the grid of one field alone")
+    if g > 0:
+        return g
+    return min(max((int(cap) // n_fields + 7) // 8 * 8, 8), top)
+
+
+BATCH_DECODER_SHAPES = ((64, None), (64,), (64, 64), (64,), (3, 64), (3,))     # None: L F
+
+
+def _check_batch_tables(geo: HashGeometry, tables: torch.Tensor, name: str = "tables") -> None:
+    """the shape of stacked tables: [B, L, T, F] (the field strides follow from the geometry)"""
+    if not isinstance(tables, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if tables.dim() != 4 or tuple(tables.shape[1:]) != geo.table_shape() or tables.shape[0] < 1:
+        raise ValueError(f"{name} must be [B, {', '.join(str(v) for v in geo.table_shape())}] = [fields, levels, 2^log2_table, features], got {tuple(tables.shape)}")
+
+
+def _check_batch_decoder(geo: HashGeometry, params: Sequence[torch.Tensor], n_fields: int, name: str = "params") -> List[torch.Tensor]:
+    """the shapes of six stacked tensors W1 [B, 64, L F], b1 [B, 64], W2 [B, 64, 64], b2 [B, 64], W3 [B, 3, 64], b3 [B, 3]"""
+    params = list(params)
+    if len(params) != 6:
+        raise ValueError(f"{name}: six stacked tensors W1, b1, W2, b2, W3, b3 (the batched kernels decode with 3 Linear layers of 64 hidden units)")
+    for t, s, n in zip(params, BATCH_DECODER_SHAPES, ("W1", "b1", "W2", "b2", "W3", "b3")):
+        want = (n_fields, *(geo.width if v is None else v for v in s))
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != want:
+            raise ValueError(f"{name}: {n} must be {want}, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    return params
+
+
+def _require_stacked(tensors: Sequence[torch.Tensor], name: str) -> None:
+    """after every shape check: contiguous fp32 on the device - the kernel reads the fields at the strides of the geometry, in place"""
+    for t in tensors:
+        if _lib.require_cuda_f32(t, name) is not t:
+            raise ValueError(f"{name} must be contiguous: the kernel reads the fields at the strides of the geometry")
+
+
+def _batch_origins(geo: HashGeometry, coord, extent: Sequence[int], n_fields: int, device) -> torch.Tensor:
+    """int32 [B, num_crops, dim] on the device.  ``coord`` [num_crops, dim]: the crops of every field; [B, num_crops, dim]: each field's own.
+    Host origins are validated per field like ``check_crops``; a device tensor is taken as is (validating it would sync)."""
+    if isinstance(coord, torch.Tensor) and coord.is_cuda:
+        o = coord.to(torch.int32)
+        if o.dim() == 3 and (o.shape[0] != n_fields or o.shape[2] != geo.dim):
+            raise ValueError(f"per-field origins must be [{n_fields}, num_crops, {geo.dim}], got {tuple(o.shape)}")
+        o = o if o.dim() == 3 else o.reshape(1, -1, geo.dim).expand(n_fields, -1, -1)
+        return o.contiguous()
+    c = torch.as_tensor(coord)
+    if c.dim() == 3:
+        if c.shape[0] != n_fields or c.shape[2] != geo.dim:
+            raise ValueError(f"per-field origins must be [{n_fields}, num_crops, {geo.dim}], got {tuple(c.shape)}")
+        o = torch.stack([geo.check_crops(c[b], extent) for b in range(n_fields)])
+    else:
+        o = geo.check_crops(c, extent).unsqueeze(0).expand(n_fields, -1, -1)
+    return o.to(torch.int32).contiguous().to(device, non_blocking=True)
+
+
+@fused._on_tensor_device
+def hash_batch_forward(geo: HashGeometry, tables: torch.Tensor, coord, extent: Sequence[int], params: Sequence[torch.Tensor],
+                       groups_per_field: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[B, N, 3]: ``hash_fused_forward`` of B stacked fields of one geometry in ONE launch (nic_hash_batch_forward).  ``tables`` [B, L, T, F],
+    ``params`` the six stacked decoder tensors, ``coord`` [num_crops, dim] (shared) or [B, num_crops, dim] (per field)."""
+    t = tables.detach() if isinstance(tables, torch.Tensor) else tables
+    _check_batch_tables(geo, t)
+    n_fields = t.shape[0]
+    params = _check_batch_decoder(geo, [q.detach() if isinstance(q, torch.Tensor) else q for q in params], n_fields)
+    _require_stacked([t], "tables")
+    _require_stacked(params, "params")
+    org = _batch_origins(geo, coord, extent, n_fields, t.device)
+    n = _n_samples(org.shape[1], extent)
+    if out is not None and not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n_fields, n, 3)):
+        raise ValueError(f"out must be a contiguous fp32 device tensor [{n_fields}, {n}, 3]")
+    y = torch.empty(n_fields, n, 3, dtype=torch.float32, device=t.device) if out is None else out
+    d, m = geo.to_desc(org.shape[1], extent), fused._mlp_struct(params)
+    _lib.check(_lib.load().nic_hash_batch_forward(ctypes.byref(d), n_fields, int(groups_per_field), _lib.ptr(t), _lib.ptr(org), ctypes.byref(m), _lib.ptr(y),
+                                                  _lib.stream_ptr(t.device)), "nic_hash_batch_forward")
+    return y
+
+
+@fused._on_tensor_device
+def hash_batch_forward_backward(geo: HashGeometry, tables: torch.Tensor, coord, extent: Sequence[int], params: Sequence[torch.Tensor],
+                                target: torch.Tensor, mlp_grads: Sequence[torch.Tensor], table_grads: Optional[torch.Tensor] = None,
+                                loss: Optional[torch.Tensor] = None, loss_scale: float = 1.0, want_y: bool = False, quant=None,
+                                add_grads: bool = False, add_loss: bool = False, groups_per_field: int = 0):
+    """``hash_fused_forward_backward`` of B stacked fields in TWO launches whatever B is (nic_hash_batch_forward_backward): loss[b] =
+    mean((y_b - target_b)^2) * loss_scale over field b's samples.  ``target`` [B, N, 3]; ``table_grads`` [B, L, T, F] is ADDED to (None: frozen
+    tables, no scatter); ``mlp_grads``: six buffers like ``params``, overwritten (``add_grads``: added to); ``quant``: None or (num_bits, seed,
+    offset, sample_base) - every field sees the noise of a single-field call with the same tuple.  There is no optimiser tail: one ``FusedAdam``
+    over the stacked tensors steps every field.  Returns (loss [B], y [B, N, 3] or None)."""
+    t = tables.detach() if isinstance(tables, torch.Tensor) else tables
+    _check_batch_tables(geo, t)
+    n_fields = t.shape[0]
+    params = _check_batch_decoder(geo, [q.detach() if isinstance(q, torch.Tensor) else q for q in params], n_fields)
+    mlp_grads = _check_batch_decoder(geo, mlp_grads, n_fields, "mlp_grads")
+    if table_grads is not None:
+        _check_batch_tables(geo, table_grads, "table_grads")
+        if table_grads.shape[0] != n_fields:
+            raise ValueError(f"table_grads holds {table_grads.shape[0]} fields, tables {n_fields}")
+    if len(extent) != geo.dim or any(int(e) < 1 for e in extent):
+        raise ValueError(f"extent {tuple(extent)} for a {geo.dim}D field")
+    if not isinstance(target, torch.Tensor) or target.dim() != 3 or target.shape[0] != n_fields or target.shape[2] != 3:
+        raise ValueError(f"target must be [{n_fields}, N, 3], got {tuple(target.shape) if isinstance(target, torch.Tensor) else type(target).__name__}")
+    _require_stacked([t], "tables")
+    _require_stacked(params, "params")
+    _require_stacked(mlp_grads, "mlp_grads")
+    if table_grads is not None:
+        _require_stacked([table_grads], "table_grads")
+    org = _batch_origins(geo, coord, extent, n_fields, t.device)
+    n = _n_samples(org.shape[1], extent)
+    if tuple(target.shape) != (n_fields, n, 3):
+        raise ValueError(f"target must be [{n_fields}, {n}, 3], got {tuple(target.shape)}")
+    target = _lib.require_cuda_f32(target, "target")
+    if loss is not None and not (loss.is_cuda and loss.dtype == torch.float32 and loss.is_contiguous() and tuple(loss.shape) == (n_fields,)):
+        raise ValueError(f"loss must be a contiguous fp32 device tensor [{n_fields}]")
+    loss = torch.empty(n_fields, dtype=torch.float32, device=t.device) if loss is None else loss
+    y = torch.empty(n_fields, n, 3, dtype=torch.float32, device=t.device) if want_y else None
+    lib = _lib.load()
+    d, m, gs = geo.to_desc(org.shape[1], extent), fused._mlp_struct(params), fused._grads_struct(list(mlp_grads))
+    q = _quant_struct(quant)
+    nbytes = int(lib.nic_hash_batch_workspace_bytes(ctypes.byref(d), n_fields, int(groups_per_field), ctypes.byref(m)))
+    if nbytes == 0:          # refused: the entry point below names the reason with its code, and launches nothing on a 16-byte workspace
+        nbytes = 16
+    ws = _lib.workspace(t.device, nbytes)
+    flags = (_lib.NIC_HASH_FUSED_ADD_GRADS if add_grads else 0) | (_lib.NIC_HASH_FUSED_ADD_LOSS if add_loss else 0)
+    _lib.check(lib.nic_hash_batch_forward_backward(ctypes.byref(d), n_fields, int(groups_per_field), None if q is None else ctypes.byref(q), _lib.ptr(t),
+                                                   _lib.ptr(org), ctypes.byref(m), _lib.ptr(target), float(loss_scale), _lib.ptr(table_grads),
+                                                   ctypes.byref(gs), _lib.ptr(loss), _lib.ptr(y), flags, _lib.ptr(ws), nbytes, _lib.stream_ptr(t.device)),
+               "nic_hash_batch_forward_backward")
     return loss, y
 
 
@@ -1893,3 +2051,252 @@ class HashGridField:
             lods.append(torch.full((pts[-1].shape[0],), float(m), dtype=torch.float32, device=self.device))
         return self.fit_points(torch.cat(pts).contiguous(), torch.cat(cols).contiguous(), epochs, batch=batch, order=order, fused=fused,
                                freeze_at=freeze_at, lod=torch.cat(lods).contiguous())
+
+
+class HashGridFieldBatch:
+    """``n_fields`` hash-grid fields of ONE geometry - the images of a folder, the tiles of a large image, the frames of a clip - trained and
+    decoded together (csrc/hashgrid_batch.hip): stacked tables [B, L, T, F] and decoder tensors [B, ...], one ``FusedAdam``
+    over the seven stacked tensors with the single field's learning rates.  A training step is three launches whatever B is (the batched
+    kernel, the reduction of its records, the optimiser), ``decode`` one launch per tile.  The arithmetic of field b is ``HashGridField(
+    fused=True)``'s: ``extract(b)`` hands it out as such a field, ``insert(b, field)`` takes one in.  ``num_bits``: None or one depth b in
+    1 .. 8 for every field (the codec of ``HashGridField``); ``groups_per_field``: the workgroups a field gets per launch (0: automatic,
+    ``hash_batch_groups``; a positive value is cut to the grid one field's crops admit).
+
+    Not built: batched ``query`` / ``train_points``, a level of detail, ``precision=``, a bit depth per level, decoding from the
+    stored (uint8 / bit-packed) tables, fields of differing geometry in one batch, a ``load_compressed`` that builds a batch."""
+
+    def __init__(self, n_fields: int, field_size: Union[int, Sequence[int]], levels: int = 16, features: int = 2, log2_table: int = 19,
+                 base_resolution: float = 16, finest_resolution: Optional[float] = None, device=None, seed: Optional[int] = None,
+                 num_bits: Optional[int] = None, noise_seed: int = 7, groups_per_field: int = 0, hidden: int = 64, n_linear: int = 3):
+        # every refusal comes before the device is touched
+        if int(n_fields) < 1:
+            raise ValueError("a batch holds at least one field")
+        if _is_level_bits(num_bits):
+            raise NotImplementedError("a bit depth per level in a batch is not built (DESIGN 7): use one num_bits for every field")
+        if num_bits is not None and not 1 <= int(num_bits) <= 8:
+            raise ValueError("num_bits in 1 .. 8 (the stored table is uint8), or None")
+        if int(hidden) != 64 or int(n_linear) != 3:
+            raise ValueError("the batched kernels decode with 3 Linear layers of 64 hidden units (hidden=64, n_linear=3)")
+        if int(groups_per_field) < 0 or int(groups_per_field) % 8:
+            raise ValueError(f"groups_per_field {groups_per_field}: 0 (automatic) or a multiple of 8")
+        self.field_size = (int(field_size),) * 2 if isinstance(field_size, int) else tuple(int(v) for v in field_size)
+        n_max = max(self.field_size) if finest_resolution is None else finest_resolution
+        self.geo = HashGeometry(self.field_size, tuple(level_resolutions(levels, base_resolution, n_max)), features, log2_table)
+        if not hash_fused_supported(self.geo, 64, 3):
+            raise ValueError("a batch needs a geometry of the fused set (nic_hash_fused_supported): dim 2 / 3, features 1 / 2 / 4 / 8, L F <= 64")
+        self.device = torch.device(device if device is not None else "cuda")
+        if self.device.type != "cuda":
+            raise RuntimeError("HashGridFieldBatch needs a HIP device: there is no CPU implementation of this path")
+        self.n_fields, self.hidden, self.n_linear = int(n_fields), 64, 3
+        self.num_bits = None if num_bits is None else int(num_bits)
+        self.noise_seed, self.groups_per_field = int(noise_seed), int(groups_per_field)
+        self._field_args = dict(levels=int(levels), features=int(features), log2_table=int(log2_table), base_resolution=base_resolution,
+                                finest_resolution=finest_resolution)
+        if seed is not None:
+            torch.manual_seed(seed)
+        b = self.n_fields
+        self.tables = torch.empty(b, *self.geo.table_shape(), dtype=torch.float32, device=self.device).uniform_(-1e-4, 1e-4).requires_grad_(True)
+        decoders = [ColorDecoder(self.geo.width, 64, 3).linear_params() for _ in range(b)]       # nn.Linear's default init, field by field
+        self.params = [torch.stack([d[k].detach() for d in decoders]).to(self.device).contiguous().requires_grad_(True) for k in range(6)]
+        self.optimizer = FusedAdam([{"params": [self.tables], "lr": 0.01}, {"params": self.params, "lr": 0.005}])
+        # the table gradient persists: the optimiser launch zeroes it after reading it, so a step needs no fill launch
+        self.tables.grad = torch.zeros_like(self.tables)
+        self.optimizer.zero_grad_in_step([self.tables])
+        self._gm = [torch.zeros_like(p) for p in self.params]
+        for p, g in zip(self.params, self._gm):
+            p.grad = g
+        self._grad_clean, self.scheduler, self.steps, self.frozen, self._pass_samples = True, None, 0, False, 0
+        if self.num_bits is not None:
+            self.optimizer.set_clamp([self.tables], *models._q_range(self.num_bits))
+
+    @property
+    def resolutions(self) -> Tuple[int, ...]:
+        return self.geo.resolutions
+
+    def set_schedule(self, num_epochs: int) -> None:
+        self.scheduler = CosineAnnealing(self.optimizer, T_max=num_epochs, eta_min=0)
+
+    def _groups(self, num_crops: int, extent: Sequence[int]) -> int:
+        """the constructor's ``groups_per_field`` for a launch on these crops: 0 stays automatic, a positive value is cut to the grid one
+        field's patches admit (the C entry refuses more)"""
+        if self.groups_per_field == 0:
+            return 0
+        return min(self.groups_per_field, (((_patches(self.geo, num_crops, extent) + 3) // 4) + 7) // 8 * 8)
+
+    def _check_field_index(self, b) -> int:
+        if not 0 <= int(b) < self.n_fields:
+            raise IndexError(f"field {b} of a batch of {self.n_fields}")
+        return int(b)
+
+    @torch.no_grad()
+    def train_step(self, coord, extent: Sequence[int], target: torch.Tensor, accumulate: bool = False, scale: float = 1.0, step: bool = True,
+                   noise: Optional[bool] = None) -> torch.Tensor:
+        """``HashGridField.train_step`` for every field at once; returns the [B] losses.  ``coord`` [num_crops, dim]: the crops of every field;
+        [B, num_crops, dim]: each field's own (validated per field).  ``target`` [B, N, 3].  ``accumulate`` / ``scale`` / ``step`` / ``noise``
+        are the single field's: the noise keys (seed, optimiser step, samples of this pass before this chunk + the row inside the field) are
+        the same for every field, so field b trains exactly as alone.  After ``freeze()`` only the decoders train."""
+        frozen = self.frozen
+        if isinstance(coord, torch.Tensor) and coord.is_cuda:
+            num_crops = coord.shape[-2] if coord.dim() >= 2 else 1
+        else:                                            # host origins: validated before anything else is touched
+            coord = _batch_origins(self.geo, coord, extent, self.n_fields, "cpu")
+            num_crops = coord.shape[1]
+        if len(extent) != self.geo.dim or any(int(e) < 1 for e in extent):
+            raise ValueError(f"extent {tuple(extent)} for a {self.geo.dim}D field")
+        n = _n_samples(num_crops, extent)
+        if not isinstance(target, torch.Tensor) or tuple(target.shape) != (self.n_fields, n, 3):
+            raise ValueError(f"target must be [{self.n_fields}, {n}, 3], got {tuple(target.shape) if isinstance(target, torch.Tensor) else type(target).__name__}")
+        if noise is None:
+            noise = self.num_bits is not None and not frozen
+        if noise and self.num_bits is None:
+            raise ValueError("noise needs num_bits: its amplitude is one quantisation step")
+        grad = None if frozen else self.tables.grad
+        if not accumulate:
+            if not frozen and not self._grad_clean:
+                grad.zero_()
+            self._pass_samples = 0
+        quant = (self.num_bits, self.noise_seed, self.steps, self._pass_samples) if noise else None
+        loss, _ = hash_batch_forward_backward(self.geo, self.tables, coord.to(self.device) if not coord.is_cuda else coord, extent, self.params, target,
+                                              self._gm, table_grads=grad, loss_scale=float(scale), quant=quant, add_grads=accumulate,
+                                              groups_per_field=self._groups(num_crops, extent))
+        self._pass_samples += n
+        if not frozen:
+            self._grad_clean = False
+        if step:
+            self.apply_step()
+        return loss
+
+    @torch.no_grad()
+    def apply_step(self) -> None:
+        """the optimiser half of ``train_step(step=True)``: ONE ``nic_adam_multi`` over the stacked tensors on the gradients the buffers hold
+        (the table gradient is zeroed by the same launch, the tables are clamped to the quantiser's range), then the schedule and the step count"""
+        grad = None if self.frozen else self.tables.grad
+        for p, g in zip(self.params, self._gm):
+            p.grad = g
+        self.optimizer.step()
+        if grad is not None:
+            self._grad_clean = self.optimizer.zeroed_in_last_step(grad)
+        if self.scheduler is not None:
+            self.scheduler.step()
+        self.steps += 1
+
+    @torch.no_grad()
+    def freeze(self) -> None:
+        """quantise every table in place (nic_quantize) and stop updating them: ``train_step`` then trains the decoders alone, without noise"""
+        if self.num_bits is None:
+            raise RuntimeError("freeze() needs num_bits: there is no quantiser without it")
+        if self.frozen:
+            return
+        t = self.tables.detach()
+        _lib.check(_lib.load().nic_quantize(_lib.ptr(t), _lib.ptr(t), t.numel(), self.num_bits, _lib.stream_ptr(t.device)), "nic_quantize")
+        self.tables.grad = None                      # FusedAdam skips a parameter without a gradient
+        self.tables.requires_grad_(False)
+        self.frozen = True
+
+    def fit(self, targets: torch.Tensor, epochs: int, chunk: Optional[int] = None, freeze_at: float = 0.95) -> List[List[float]]:
+        """``HashGridField.fit`` on ``targets`` [B, S_x, S_y(, S_z), 3]: ``epochs`` whole-field passes walked in slabs of ``chunk`` x-rows (one
+        optimiser step per pass, each slab's MSE weighted by its share); with ``num_bits`` noise while the epoch is below ``freeze_at`` *
+        epochs, then ``freeze()``.  Returns the per-pass losses, [epochs][B]."""
+        size = self.field_size
+        if not isinstance(targets, torch.Tensor) or tuple(targets.shape) != (self.n_fields, *size, 3):
+            raise ValueError(f"targets must be {(self.n_fields, *size, 3)}, got {tuple(targets.shape) if isinstance(targets, torch.Tensor) else type(targets).__name__}")
+        chunk = size[0] if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError("chunk >= 1")
+        starts = list(range(0, size[0], chunk))
+        slabs = [targets[:, x0:x0 + chunk].reshape(self.n_fields, -1, 3).contiguous() for x0 in starts]
+        total = sum(s.shape[1] for s in slabs)
+        freeze_epoch = math.ceil(freeze_at * epochs) if self.num_bits is not None else None
+        hist = []
+        for ep in range(epochs):
+            if freeze_epoch is not None and ep >= freeze_epoch and not self.frozen:
+                self.freeze()
+            tot = 0.0
+            for k, x0 in enumerate(starts):
+                ext = (min(chunk, size[0] - x0), *size[1:])
+                tot = tot + self.train_step([[x0] + [0] * (len(size) - 1)], ext, slabs[k], accumulate=k > 0, scale=slabs[k].shape[1] / total,
+                                            step=k == len(starts) - 1)
+            hist.append(tot)
+        return [[float(v) for v in h] for h in torch.stack(hist).tolist()] if hist else []
+
+    @torch.no_grad()
+    def decode(self, tile: int = 1024) -> torch.Tensor:
+        """every field whole, [B, S_x, S_y(, S_z), 3], in tiles of side <= ``tile``: one launch per tile for all fields"""
+        size = self.field_size
+        out = torch.empty(self.n_fields, *size, 3, dtype=torch.float32, device=self.device)
+        tables, params = self.tables.detach(), [p.detach() for p in self.params]
+        for o in itertools.product(*[range(0, s, tile) for s in size]):
+            ext = [min(tile, s - a) for s, a in zip(size, o)]
+            sl = (slice(None), *(slice(a, a + e) for a, e in zip(o, ext)))
+            out[sl] = hash_batch_forward(self.geo, tables, [o], ext, params, self._groups(1, ext)).reshape(self.n_fields, *ext, 3)
+        return out
+
+    def _adam_state(self, p: torch.Tensor):
+        st = self.optimizer.state.get(p)
+        return st if st else None
+
+    @torch.no_grad()
+    def extract(self, b: int) -> "HashGridField":
+        """an independent ``HashGridField(fused=True)`` holding copies of field b's table, decoder, codec state (``num_bits``, ``noise_seed``,
+        frozen or not), step count, learning rates and Adam moments: ``decode`` / ``query`` / ``resample`` / ``point_gradient`` /
+        ``save_compressed`` work on it, and later training of either side does not touch the other"""
+        b = self._check_field_index(b)
+        with torch.random.fork_rng(devices=[self.device]):                     # the constructor's random init is overwritten: leave the generators alone
+            f = HashGridField(self.field_size, hidden=64, n_linear=3, device=self.device, num_bits=self.num_bits, noise_seed=self.noise_seed, fused=True,
+                              **self._field_args)
+        if f.geo != self.geo or f.route != "fused":
+            raise RuntimeError("extract(): the single field's geometry differs from the batch's")
+        f.table.copy_(self.tables[b])
+        for q, p in zip(f.decoder.linear_params(), self.params):
+            q.copy_(p[b])
+        for gf, gb in zip(f.optimizer.param_groups, self.optimizer.param_groups):
+            gf["lr"] = gb["lr"]
+        for q, p in zip([f.table] + f.decoder.linear_params(), [self.tables] + self.params):
+            st = self._adam_state(p)
+            if st is not None:
+                f.optimizer.state[q] = {"step": st["step"].clone(), "exp_avg": st["exp_avg"][b].clone(), "exp_avg_sq": st["exp_avg_sq"][b].clone()}
+        f.steps = self.steps
+        if self.frozen:                              # the table is already quantised: take the state over without quantising again
+            f.table.grad = None
+            f.table.requires_grad_(False)
+            f.frozen = True
+        return f
+
+    @torch.no_grad()
+    def insert(self, b: int, field: "HashGridField") -> None:
+        """copies a compatible ``HashGridField`` into slot b: its table and decoder (and Adam moments, where both sides have them).  The
+        geometry, the decoder shape and the codec state (``num_bits``, no bit depth per level, frozen like the batch) must be the batch's, and
+        the field must hold an fp32 table (not one from ``load_compressed``): anything else is a ValueError"""
+        b = self._check_field_index(b)
+        if not isinstance(field, HashGridField):
+            raise TypeError("insert() takes a HashGridField")
+        if field.geo != self.geo:
+            raise ValueError(f"insert(): the field's geometry {field.geo} is not the batch's {self.geo}")
+        if field.hidden != 64 or field.n_linear != 3:
+            raise ValueError("insert(): the field's decoder is not 3 Linear layers of 64 hidden units")
+        if field.level_bits is not None or field.num_bits != self.num_bits:
+            raise ValueError(f"insert(): the field's codec (num_bits {field.num_bits}, level_bits {field.level_bits}) is not the batch's (num_bits {self.num_bits})")
+        if field.table is None:
+            raise ValueError("insert(): a field from load_compressed holds no fp32 table")
+        if bool(field.frozen) != bool(self.frozen):
+            raise ValueError(f"insert(): the field is {'frozen' if field.frozen else 'not frozen'}, the batch {'is' if self.frozen else 'is not'}")
+        self.tables[b].copy_(field.table.detach().to(self.device))
+        for p, q in zip(self.params, field.decoder.linear_params()):
+            p[b].copy_(q.detach().to(self.device))
+        if field.optimizer is not None:
+            for p, q in zip([self.tables] + self.params, [field.table] + field.decoder.linear_params()):
+                st, sf = self._adam_state(p), field.optimizer.state.get(q)
+                if st is not None and sf:
+                    st["exp_avg"][b].copy_(sf["exp_avg"])
+                    st["exp_avg_sq"][b].copy_(sf["exp_avg_sq"])
+
+    def save_compressed(self, paths: Sequence, packed: bool = False) -> None:
+        """one ordinary single-field file per field (``HashGridField.save_compressed`` of ``extract(b)``; ``HashGridField.load_compressed`` reads
+        each): no new format"""
+        if self.num_bits is None:
+            raise RuntimeError("save_compressed needs num_bits")
+        paths = list(paths)
+        if len(paths) != self.n_fields:
+            raise ValueError(f"{len(paths)} paths for {self.n_fields} fields")
+        for b, path in enumerate(paths):
+            self.extract(b).save_compressed(path, packed=packed)
