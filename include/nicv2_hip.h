@@ -826,6 +826,30 @@ int nic_hash_batch_forward_backward(const nic_hash_desc *desc, int n_fields, int
                                     float *table_grads, const nic_mlp_grads *mlp_grads, float *loss, float *y, int flags, void *workspace,
                                     size_t workspace_bytes, void *stream);
 
+/* ---- B STORED fields per launch, on the lattice or at points (hashgrid.py, HashGridFieldBatch.load_compressed / decode / query / resample,
+ *      hash_batch_forward_source; csrc/hashgrid_batch.hip).  Forward only: one launch, no atomics, no records - the same call
+ *      gives the same bits.  nic_hash_batch_forward_source is nic_hash_fused_forward / _u8 / _bits (origins) or nic_hash_fused_forward_points
+ *      (points) per field in ONE launch; workgroups belong to fields as above, the decoder is the stacked one of nic_hash_batch_forward.
+ *      Source: src->kind NIC_HASH_SRC_F32, _U8 or _BITS with the rules of nic_hash_encode_points (num_bits 0 for F32 and 1 .. 8 for U8 / BITS),
+ *      src->data the BASE of n_fields tables stacked without gaps: field b's table starts b x stride bytes after it, stride = levels x T x
+ *      features x 4 (F32), nic_hash_stored_bytes(desc) (U8) or nic_hash_packed_bytes(desc, num_bits) (BITS).  The BITS stride is 4 x sum + 8, a
+ *      multiple of 4: a 4-byte-aligned base (else NIC_E_ARG) aligns every field, and each field keeps its own 8 zero bytes.
+ *      Positions: exactly one of `origins` / `points` is non-null (else NIC_E_ARG), as in nic_hash_fused_forward_p16.  origins = [B, num_crops,
+ *      dim] int32 on the device (every field its own crops), y = [B, N, 3] in nic_hash_batch_forward's order; n_points is ignored.  points =
+ *      [B, n_points, dim] fp32 on the device in sample units with the clamping of nic_hash_encode_points (every field its own points), then
+ *      desc->extent is the FIELD size, desc->num_crops is 1 and 256 S_max < 2^30, and y = [B, n_points, 3].  One wave handles 64 consecutive
+ *      points of one field; a lane past the end decodes the field's last point and stores nothing.
+ *      groups_per_field = G as above, on the wave items of ONE field: its patches with origins, ceil(n_points / 64) with points (0: automatic;
+ *      a positive G must be a multiple of 8 and at most the grid a single-field launch over those items would use).
+ *      Host checks, all before any GPU work, in this order: null desc / mlp (NIC_E_NULL); the fused set (nic_hash_fused_supported's code); both
+ *      or neither of origins / points (NIC_E_ARG); the descriptor of that position source (points: num_crops == 1, NIC_E_SHAPE, and 256 S_max <
+ *      2^30, NIC_E_ARG; origins: 256 S_max < 2^30, NIC_E_ARG); n_fields in 1 .. 65535 (NIC_E_ARG); groups_per_field (NIC_E_ARG; for this check
+ *      alone n_points <= 0 counts as one wave item); null src, src->data, decoder layer or y (NIC_E_NULL); the source (NIC_E_ARG: kind,
+ *      num_bits, alignment, in nic_hash_encode_points' order); n_points < 0 with points (NIC_E_ARG); n_points == 0 with points is NIC_OK
+ *      without a launch. */
+int nic_hash_batch_forward_source(const nic_hash_desc *desc, int n_fields, int groups_per_field, const nic_hash_source *src,
+                                  const int32_t *origins, const float *points, int64_t n_points, const nic_mlp *mlp, float *y, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

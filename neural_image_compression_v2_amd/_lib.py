@@ -239,6 +239,7 @@ SIGNATURES = {
     "nic_hash_batch_forward": (_I, [ctypes.POINTER(NicHashDesc), _I, _I, _P, _P, _M, _P, _P]),
     "nic_hash_batch_forward_backward": (_I, [ctypes.POINTER(NicHashDesc), _I, _I, ctypes.POINTER(NicHashQuant), _P, _P, _M, _P, _F, _P, _G, _P, _P, _I,
                                              _P, _SZ, _P]),
+    "nic_hash_batch_forward_source": (_I, [ctypes.POINTER(NicHashDesc), _I, _I, ctypes.POINTER(NicHashSource), _P, _P, _L, _M, _P, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -12,7 +12,12 @@
 //   write_record to record (b, lb); a workgroup without a patch writes its all-zero record.  hash_batch_reduce_kernel is
 //   hash_fused_reduce_kernel's fixed-order sum with blockIdx.y = b, without the optimiser tail: one nic_adam_multi over the stacked tensors
 //   steps every field.
-// Every device helper is hash_common.hpp's; this unit holds the two kernels, their parameters and the host side.
+//   decoding from a stored table and at points (nic_hash_batch_forward_source): hash_batch_decode_kernel is the forward branch
+//   above with two sources added.  The table: field b's starts at base + b stride, fp32 [L, T, F], compact uint8 or bit-packed, the stride
+//   from the shared descriptor (a packed table is 4 sum + 8 bytes: every field of a 4-byte-aligned stack is aligned, and its 8 zero bytes keep
+//   the widest window of its last level inside the field).  The position: the lattice as above, or points [B, n, dim] through point_fixed,
+//   one wave item = 64 consecutive points of one field; a lane past the end decodes the field's last point and stores nothing.
+// Every device helper is hash_common.hpp's; this unit holds the three kernels, their parameters and the host side.
 #include "hash_common.hpp"
 
 namespace nic {
@@ -143,6 +148,88 @@ __global__ void __launch_bounds__(256) hash_batch_kernel(const BParams p) {
     }
 }
 
+// ---- forward only, from any table source, on the lattice or at points --------------------------------------------------------
+struct SParams {
+    nic_hash_desc d;          // one field's; at points extent[a] = S_a, num_crops = 1
+    int64_t stride;           // bytes from field b's table to field b + 1's
+    const int32_t* origins;   // [B, num_crops, dim], or
+    const float* points;      // [B, n, dim]
+    int64_t n;                // points of one field
+    const float* table;       // NIC_HASH_SRC_F32: the base of the stack (set_point_source fills the one of its kind)
+    const uint8_t* stored;    // NIC_HASH_SRC_U8
+    const uint32_t* packed;   // NIC_HASH_SRC_BITS, 4-byte aligned
+    float q_scale, q_bias;    // load4fp: (u - q_bias + 1) / q_scale
+    int32_t q_bits, q_tight;
+    const float *w1, *b1, *w2, *b2, *w3, *b3;      // bases of the stacked decoder
+    float* y;                 // [B, rows, 3]
+    int64_t n_items;          // wave items of one field: patches, or groups of 64 points
+    int64_t n_rows;           // rows of y per field
+    int32_t groups;           // G
+};
+
+// what encode_point reads of a stored source, for field b
+struct StoredSrc {
+    const nic_hash_desc& d;
+    const float* table;
+    const uint8_t* stored;
+    const uint32_t* packed;
+    float q_scale, q_bias;
+    int32_t q_bits, q_tight;
+};
+
+template <int D, int F, int SRC, bool POINTS>
+__global__ void __launch_bounds__(256) hash_batch_decode_kernel(const SParams p) {
+    __shared__ DecoderSmem sm;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 31, half = lane >> 5;
+    const int LF = p.d.levels * F;
+    const int b = (int)(blockIdx.x / (unsigned)p.groups), lb = (int)(blockIdx.x - (unsigned)b * (unsigned)p.groups);
+    load_decoder(sm, p.w1 + (int64_t)b * kH * LF, p.b1 + b * kH, p.w2 + (int64_t)b * kH * kH, p.b2 + b * kH, p.w3 + b * 3 * kH, p.b3 + b * 3, LF, tid);
+    __syncthreads();
+    float* xs = sm.x[wave];
+    float* xrow = xs + lane * XS;
+    const int64_t tab_off = (int64_t)b * p.stride;
+    const StoredSrc src_b{p.d,
+                          SRC == NIC_HASH_SRC_F32 ? reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(p.table) + tab_off) : nullptr,
+                          SRC == NIC_HASH_SRC_U8 ? p.stored + tab_off : nullptr,
+                          SRC == NIC_HASH_SRC_BITS ? reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(p.packed) + tab_off) : nullptr,
+                          p.q_scale, p.q_bias, p.q_bits, p.q_tight};
+    [[maybe_unused]] const int32_t* origins = POINTS ? nullptr : p.origins + (int64_t)b * p.d.num_crops * D;
+    [[maybe_unused]] const float* points = POINTS ? p.points + (int64_t)b * p.n * D : nullptr;
+    float* y = p.y + (int64_t)b * p.n_rows * 3;
+    const int ks1 = (LF + 1) >> 1;
+    const WaveRange wr = field_range(p.n_items, lb, p.groups);
+    for (int64_t g = wr.begin; g < wr.end; g += wr.step) {
+        const int64_t wv = 4 * g + wave;
+        if (wv >= p.n_items) continue;                          // wave-uniform; nothing below synchronises the workgroup
+        int64_t row;
+        uint32_t t[3];
+        bool live_lane;
+        if constexpr (POINTS) {
+            const int64_t n_raw = (wv << 6) + lane;
+            live_lane = n_raw < p.n;
+            row = live_lane ? n_raw : p.n - 1;                  // a lane past the end decodes the field's last point; its output is not stored
+            point_fixed<D>(p.d, points, row, t);
+        } else {
+            live_lane = lattice_position<D>(p.d, origins, wv, p.n_items, lane, row, t);
+        }
+        encode_point<D, F, SRC, false, false, false>(src_b, t, row, 0.f, xrow);
+        wave_sync();
+        const unsigned long long live_mask = __ballot(live_lane);
+#pragma unroll 1
+        for (int nt = 0; nt < 2; ++nt) {
+            const int src = 32 * nt + j;
+            const int64_t r = (int64_t)(uint32_t)__shfl((int)(uint32_t)row, src) | ((int64_t)__shfl((int)(row >> 32), src) << 32);
+            float yv[3];
+            decoder_forward_half(sm, xs, nt, j, half, ks1, yv);
+            if (half == 0 && ((live_mask >> src) & 1ull)) {
+#pragma unroll
+                for (int o = 0; o < 3; ++o) y[r * 3 + o] = yv[o];
+            }
+        }
+        wave_sync();
+    }
+}
+
 // hash_fused_reduce_kernel's fixed-order sum, field blockIdx.y: a block = 32 outputs x 8 slices of the field's G records, the slices combined
 // through LDS in slice order.  `g` holds the BASES of the stacked gradients, `loss` is [B].  No optimiser tail.
 __global__ void __launch_bounds__(256) hash_batch_reduce_kernel(const float* partials, int n_rec, int lf, nic_mlp_grads g, float* loss, float loss_mul,
@@ -190,14 +277,15 @@ static int check_batch_desc(const nic_hash_desc* d, int n_linear) {
 }
 // G: 0 = wg_cap() / B rounded up to a multiple of 8, at least 8, at most the single field's persistent grid; a positive value must be a
 // multiple of 8 within that grid.  -1: refused
-static int batch_groups(const nic_hash_desc* d, int n_fields, int groups_per_field) {
-    const int top = persistent_grid(count_patches(d));
+static int batch_groups_of(int64_t n_items, int n_fields, int groups_per_field) {
+    const int top = persistent_grid(n_items);
     if (groups_per_field < 0 || (groups_per_field & 7) || groups_per_field > top) return -1;
     if (groups_per_field > 0) return groups_per_field;
     int g = (wg_cap() / n_fields + 7) / 8 * 8;
     g = g < 8 ? 8 : g;
     return g < top ? g : top;
 }
+static int batch_groups(const nic_hash_desc* d, int n_fields, int groups_per_field) { return batch_groups_of(count_patches(d), n_fields, groups_per_field); }
 static bool mlp3_ok(const nic_mlp* m) {
     for (int i = 0; i < 3; ++i)
         if (!m->w[i] || !m->b[i]) return false;
@@ -217,6 +305,16 @@ static int launch(const BParams& p, int n_fields, void* stream) {
         constexpr int D = decltype(dim)::value, F = decltype(features)::value;
         if (p.d.levels * F > 32) hipLaunchKernelGGL((hash_batch_kernel<D, F, 2, MODE>), grid, dim3(256), 0, (hipStream_t)stream, p);
         else hipLaunchKernelGGL((hash_batch_kernel<D, F, 1, MODE>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    });
+}
+
+template <int SRC>
+static int launch_source(const SParams& p, int n_fields, void* stream) {
+    const dim3 grid((unsigned)n_fields * (unsigned)p.groups);
+    return dispatch_dim_features(p.d, [&](auto dim, auto features) {
+        constexpr int D = decltype(dim)::value, F = decltype(features)::value;
+        if (p.points != nullptr) hipLaunchKernelGGL((hash_batch_decode_kernel<D, F, SRC, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL((hash_batch_decode_kernel<D, F, SRC, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
     });
 }
 
@@ -247,6 +345,37 @@ int nic_hash_batch_forward(const nic_hash_desc* desc, int n_fields, int groups_p
     BParams p{};
     fill(p, desc, tables, origins, mlp, y, g);
     return launch<HB_FWD>(p, n_fields, stream);
+}
+
+int nic_hash_batch_forward_source(const nic_hash_desc* desc, int n_fields, int groups_per_field, const nic_hash_source* src, const int32_t* origins,
+                                  const float* points, int64_t n_points, const nic_mlp* mlp, float* y, void* stream) {
+    if (!desc || !mlp) return NIC_E_NULL;
+    int rc = nic_hash_fused_supported(desc, kH, mlp->n_linear);          // the only copy of the fused set (hash_fused.hip)
+    if (rc) return rc;
+    if ((origins != nullptr) == (points != nullptr)) return NIC_E_ARG;
+    if (points) {
+        if ((rc = check_point_desc(desc)) != NIC_OK) return rc;
+    } else if (256 * (int64_t)desc->S_max >= (int64_t(1) << 30)) {
+        return NIC_E_ARG;
+    }
+    if (n_fields < 1 || n_fields > kMaxFields) return NIC_E_ARG;
+    // G on the wave items of ONE field; a count of points that launches nothing (checked below) stands as one item here
+    const int64_t n_items = origins ? count_patches(desc) : (n_points > 0 ? (n_points + 63) >> 6 : 1);
+    const int g = batch_groups_of(n_items, n_fields, groups_per_field);
+    if (g < 0) return NIC_E_ARG;
+    if (!src || !src->data || !mlp3_ok(mlp) || !y) return NIC_E_NULL;
+    SParams p{};
+    p.d = *desc; p.origins = origins; p.points = points; p.y = y; p.groups = g; p.n_items = n_items;
+    p.n = origins ? 0 : n_points;
+    if ((rc = set_point_source(p, src)) != NIC_OK) return rc;
+    if (points && n_points < 0) return NIC_E_ARG;
+    if (points && n_points == 0) return NIC_OK;
+    p.stride = src->kind == NIC_HASH_SRC_F32 ? (((int64_t)desc->levels << desc->log2_table) * desc->features) * (int64_t)sizeof(float)
+             : src->kind == NIC_HASH_SRC_U8 ? nic_hash_stored_bytes(desc) : nic_hash_packed_bytes(desc, src->num_bits);
+    if (p.stride <= 0) return NIC_E_ARG;
+    p.n_rows = origins ? (int64_t)desc->num_crops * desc->extent[0] * desc->extent[1] * (desc->dim == 3 ? desc->extent[2] : 1) : n_points;
+    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
+    return dispatch_source(src->kind, [&](auto kind) { return launch_source<decltype(kind)::value>(p, n_fields, stream); });
 }
 
 int nic_hash_batch_forward_backward(const nic_hash_desc* desc, int n_fields, int groups_per_field, const nic_hash_quant* quant, const float* tables,

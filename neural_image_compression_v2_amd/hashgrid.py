@@ -74,7 +74,10 @@ into a position gradient, ``hash_fused_points_grad`` does gather, decoder, its b
 B fields per launch (include/nicv2_hip.h, nic_hash_batch_forward_backward; csrc/hashgrid_batch.hip): ``HashGridFieldBatch`` holds
 the stacked tables [B, L, T, F] and decoder tensors of B fields of one geometry; a workgroup of the batched kernel belongs to one field, a step is
 three launches whatever B is (the kernel, the reduction per field, one ``FusedAdam`` over the stacked tensors), ``decode`` one per tile.
-``hash_batch_forward`` / ``hash_batch_forward_backward`` are the functional forms; ``extract(b)`` / ``insert(b, field)`` move single fields out and in."""
+``hash_batch_forward`` / ``hash_batch_forward_backward`` are the functional forms; ``extract(b)`` / ``insert(b, field)`` move single fields out and in.
+The decoder side (nic_hash_batch_forward_source): ``HashGridFieldBatch.load_compressed(paths)`` stacks the uint8 or bit-packed tables of
+B stored files, ``decode`` / ``query`` / ``resample`` read whatever table a batch holds in one launch per tile for all fields;
+``hash_batch_forward_source`` is the functional form (fp32, uint8 or packed tables; crops or points)."""
 from __future__ import annotations
 
 import ctypes
@@ -653,6 +656,103 @@ def _point_source(geo: HashGeometry, data: torch.Tensor, kind: str, num_bits: Op
         if data.numel() != hash_stored_bytes(geo):
             raise ValueError(f"stored holds {data.numel()} bytes, the geometry needs {hash_stored_bytes(geo)}")
     return _lib.NicHashSource(POINT_SOURCES[kind], int(num_bits), data.data_ptr()), data
+
+
+def _batch_source_bytes(geo: HashGeometry, kind: str, num_bits: Optional[int]) -> int:
+    """bytes of ONE field's stored table of ``kind`` "u8" / "bits": the stride of a stack of them"""
+    if num_bits is None or isinstance(num_bits, bool) or _is_level_bits(num_bits) or not 1 <= int(num_bits) <= 8:
+        raise ValueError("a stored table needs its num_bits in 1 .. 8")
+    return hash_packed_bytes(geo, int(num_bits)) if kind == "bits" else hash_stored_bytes(geo)
+
+
+def _check_batch_source(geo: HashGeometry, data, kind: str, num_bits: Optional[int]) -> int:
+    """shape and dtype of the stacked tables of ``kind``: fp32 [B, L, T, F], or uint8 [B, bytes of one field]; returns B.  Host only."""
+    if kind not in POINT_SOURCES:
+        raise ValueError(f"table source {kind!r}: one of {sorted(POINT_SOURCES)}")
+    if not isinstance(data, torch.Tensor):
+        raise TypeError("data must be a torch.Tensor")
+    if kind == "f32":
+        if num_bits is not None:
+            raise ValueError("an fp32 table has no num_bits")
+        _check_batch_tables(geo, data, "data")
+        if data.dtype != torch.float32:
+            raise ValueError(f"data: fp32 tables for kind 'f32', got {data.dtype}")
+        return data.shape[0]
+    need = _batch_source_bytes(geo, kind, num_bits)
+    if data.dtype != torch.uint8 or data.dim() != 2 or data.shape[0] < 1 or data.shape[1] != need:
+        raise ValueError(f"data must be uint8 [B, {need}] = [fields, bytes of one {'bit-packed' if kind == 'bits' else 'compact uint8'} table] for kind "
+                         f"{kind!r}, got {data.dtype} {tuple(data.shape)}")
+    return data.shape[0]
+
+
+def _require_on_device(t: torch.Tensor, name: str) -> None:
+    """after every shape and dtype check: on a HIP device and contiguous - the kernel reads the fields in place, at the strides of the geometry"""
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} lives on {t.device}: this package only runs on a HIP device (no CPU path)")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous: the kernel reads the fields at the strides of the geometry")
+
+
+@fused._on_tensor_device
+def hash_batch_forward_source(geo: HashGeometry, data: torch.Tensor, params: Sequence[torch.Tensor], kind: str = "f32", num_bits: Optional[int] = None,
+                              coord=None, extent: Optional[Sequence[int]] = None, points: Optional[torch.Tensor] = None, groups_per_field: int = 0,
+                              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[B, N, 3]: B stacked fields of one geometry decoded in ONE launch from the table they hold (nic_hash_batch_forward_source).
+    ``data``: kind "f32" = fp32 [B, L, T, F]; "u8" / "bits" = contiguous uint8 [B, bytes] on the device, bytes = ``hash_stored_bytes`` /
+    ``hash_packed_bytes`` of ``num_bits``.  ``params``: the six stacked decoder tensors.  Exactly one position source: the crops ``coord``
+    ([num_crops, dim] shared or [B, num_crops, dim] per field) of ``extent``, or ``points`` ([N, dim] shared by all fields or [B, N, dim] per
+    field; fp32, sample units, clamped by the kernel like ``hash_fused_forward_points``).  Every shape and dtype is checked on the host first."""
+    n_fields = _check_batch_source(geo, data, kind, num_bits)
+    data = data.detach()
+    params = _check_batch_decoder(geo, [q.detach() if isinstance(q, torch.Tensor) else q for q in params], n_fields)
+    if any(q.dtype != torch.float32 for q in params):
+        raise ValueError("params: fp32 tensors")
+    if (coord is None) == (points is None):
+        raise ValueError("exactly one of coord (with extent) and points")
+    if 256 * geo.s_max >= 2 ** 30:
+        raise ValueError(f"a field of {geo.s_max} samples per axis is too large for the batched entry points: 256 * S_max < 2^30")
+    if points is not None:
+        if extent is not None:
+            raise ValueError("extent belongs to coord: points carry their own positions")
+        if not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or points.dim() not in (2, 3) or points.shape[-1] != geo.dim or (
+                points.dim() == 3 and points.shape[0] != n_fields):
+            raise ValueError(f"points must be fp32 [N, {geo.dim}] (shared) or [{n_fields}, N, {geo.dim}] (per field), got "
+                             f"{(points.dtype, tuple(points.shape)) if isinstance(points, torch.Tensor) else type(points).__name__}")
+        n = points.shape[-2]
+        org = None
+    else:
+        if extent is None:
+            raise ValueError("coord needs the extent of its crops")
+        org = _batch_origins(geo, coord, extent, n_fields, "cpu" if not (isinstance(coord, torch.Tensor) and coord.is_cuda) else coord.device)
+        n = _n_samples(org.shape[1], extent)
+    if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n_fields, n, 3)):
+        raise ValueError(f"out must be a contiguous fp32 tensor [{n_fields}, {n}, 3]")
+    # ---- the device, after every refusal the host can make
+    _require_on_device(data, "data")
+    for q in params:
+        _require_on_device(q, "params")
+    if kind == "bits" and data.data_ptr() % 4:
+        raise ValueError("data must start on a 4-byte boundary: the packed gather reads aligned dwords")
+    if out is not None:
+        _require_on_device(out, "out")
+    y = torch.empty(n_fields, n, 3, dtype=torch.float32, device=data.device) if out is None else out
+    if points is not None:
+        if not points.is_cuda:
+            raise RuntimeError(f"points live on {points.device}: this package only runs on a HIP device (no CPU path)")
+        if n == 0:
+            return y
+        pts = points.detach()
+        pts = (pts if pts.dim() == 3 else pts.unsqueeze(0).expand(n_fields, -1, -1)).contiguous()
+        d = _point_desc(geo)
+    else:
+        pts = None
+        org = org.to(data.device, non_blocking=True)
+        d = geo.to_desc(org.shape[1], extent)
+    src, m = _lib.NicHashSource(POINT_SOURCES[kind], 0 if kind == "f32" else int(num_bits), data.data_ptr()), fused._mlp_struct(params)
+    _lib.check(_lib.load().nic_hash_batch_forward_source(ctypes.byref(d), n_fields, int(groups_per_field), ctypes.byref(src), _lib.ptr(org), _lib.ptr(pts),
+                                                         n if pts is not None else 0, ctypes.byref(m), _lib.ptr(y), _lib.stream_ptr(data.device)),
+               "nic_hash_batch_forward_source")
+    return y
 
 
 def _lod_args(geo: HashGeometry, lod, n: int, device):
@@ -2062,8 +2162,13 @@ class HashGridFieldBatch:
     1 .. 8 for every field (the codec of ``HashGridField``); ``groups_per_field``: the workgroups a field gets per launch (0: automatic,
     ``hash_batch_groups``; a positive value is cut to the grid one field's crops admit).
 
-    Not built: batched ``query`` / ``train_points``, a level of detail, ``precision=``, a bit depth per level, decoding from the
-    stored (uint8 / bit-packed) tables, fields of differing geometry in one batch, a ``load_compressed`` that builds a batch."""
+    The decoder side: ``load_compressed(paths)`` builds a decode-only batch from B ``save_compressed`` files - stacked uint8 or
+    bit-packed tables [B, bytes] as stored, no fp32 table, no optimiser - and ``decode`` / ``query`` / ``resample`` read whatever table a batch
+    holds in one launch per tile for all fields (nic_hash_batch_forward_source); ``extract(b)`` of such a batch is what
+    ``HashGridField.load_compressed(fused=True)`` makes, ``save_compressed`` re-saves it in either format.
+
+    Not built: batched ``train_points``, a level of detail, ``precision=``, a bit depth per level (a ``/2`` file is read and
+    refused), fields of differing geometry in one batch, a container format that holds several fields in one file."""
 
     def __init__(self, n_fields: int, field_size: Union[int, Sequence[int]], levels: int = 16, features: int = 2, log2_table: int = 19,
                  base_resolution: float = 16, finest_resolution: Optional[float] = None, device=None, seed: Optional[int] = None,
@@ -2095,6 +2200,7 @@ class HashGridFieldBatch:
         if seed is not None:
             torch.manual_seed(seed)
         b = self.n_fields
+        self.stored = self.packed = None             # a decode-only batch (load_compressed) holds one of these instead of ``tables``
         self.tables = torch.empty(b, *self.geo.table_shape(), dtype=torch.float32, device=self.device).uniform_(-1e-4, 1e-4).requires_grad_(True)
         decoders = [ColorDecoder(self.geo.width, 64, 3).linear_params() for _ in range(b)]       # nn.Linear's default init, field by field
         self.params = [torch.stack([d[k].detach() for d in decoders]).to(self.device).contiguous().requires_grad_(True) for k in range(6)]
@@ -2128,6 +2234,89 @@ class HashGridFieldBatch:
             raise IndexError(f"field {b} of a batch of {self.n_fields}")
         return int(b)
 
+    @property
+    def decode_only(self) -> bool:
+        """a batch from ``load_compressed``: stored tables, no fp32 tables, no optimiser"""
+        return getattr(self, "tables", False) is None
+
+    def _refuse_decode_only(self, what: str) -> None:
+        if self.decode_only:
+            raise RuntimeError(f"{what}: a batch from load_compressed is decode-only (it holds the stored tables, no fp32 tables and no optimiser)")
+
+    @staticmethod
+    def _read_compressed(path) -> dict:
+        """what one ``save_compressed`` file says about itself, checked on the host: format, geometry, num_bits, decoder shape, table, decoder"""
+        d = torch.load(path, map_location="cpu", weights_only=True)
+        if not isinstance(d, dict) or d.get("format") not in (COMPRESSED_FORMAT, PACKED_FORMAT, MIXED_FORMAT):
+            raise ValueError(f"{path}: not a {COMPRESSED_FORMAT}, {PACKED_FORMAT} or {MIXED_FORMAT} file")
+        if d["format"] == MIXED_FORMAT:
+            raise NotImplementedError(f"{path}: a bit depth per level ({MIXED_FORMAT}) in a batch is not built (DESIGN 7): load it with "
+                                      "HashGridField.load_compressed")
+        field_size = tuple(int(v) for v in d["field_size"])
+        geo = HashGeometry(field_size, tuple(int(r) for r in d["resolutions"]), int(d["features"]), int(d["log2_table"]))
+        num_bits = int(d["num_bits"])
+        if not 1 <= num_bits <= 8:
+            raise ValueError(f"{path}: num_bits {num_bits}")
+        return {"format": d["format"], "geo": geo, "num_bits": num_bits, "decoder_shape": (int(d["hidden"]), int(d["n_linear"])), "table": d["table"],
+                "decoder": d["decoder"]}
+
+    @classmethod
+    def load_compressed(cls, paths: Sequence, device=None, groups_per_field: int = 0) -> "HashGridFieldBatch":
+        """a decode-only batch from B ``save_compressed`` files of ONE format (uint8 or bit-packed, uniform depth), geometry, ``num_bits`` and
+        decoder shape - anything else is a ValueError naming the first path that differs; a ``/2`` (bit depth per level) file raises
+        NotImplementedError.  The tables stay as stored, stacked [B, bytes] on the device; ``decode`` / ``query`` / ``resample`` gather from
+        them in one launch per tile for all fields.  There is no new file format: each file is ``HashGridField.load_compressed``'s."""
+        paths = list(paths)
+        if not paths:
+            raise ValueError("load_compressed: no paths (a batch holds at least one field)")
+        if int(groups_per_field) < 0 or int(groups_per_field) % 8:
+            raise ValueError(f"groups_per_field {groups_per_field}: 0 (automatic) or a multiple of 8")
+        first, tables, decoders = None, [], []
+        for path in paths:
+            f = cls._read_compressed(path)
+            if first is None:
+                first = f
+                if f["decoder_shape"] != (64, 3):
+                    raise ValueError(f"{path}: hidden {f['decoder_shape'][0]}, n_linear {f['decoder_shape'][1]}: the batched kernels decode with 3 Linear "
+                                     "layers of 64 hidden units (hidden=64, n_linear=3)")
+                if not hash_fused_supported(f["geo"], 64, 3):
+                    raise ValueError(f"{path}: a batch needs a geometry of the fused set (nic_hash_fused_supported): dim 2 / 3, features 1 / 2 / 4 / 8, "
+                                     "L F <= 64")
+                is_packed = f["format"] == PACKED_FORMAT
+                need = hash_packed_bytes(f["geo"], f["num_bits"]) if is_packed else hash_stored_bytes(f["geo"])
+            for key, name in (("format", "format"), ("geo", "geometry"), ("num_bits", "num_bits"), ("decoder_shape", "decoder shape (hidden, n_linear)")):
+                if f[key] != first[key]:
+                    raise ValueError(f"{path}: its {name} {f[key]} is not {first[key]}, that of {paths[0]}: the files of a batch agree in all four")
+            t = f["table"]
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.numel() != need:
+                raise ValueError(f"{path}: the table holds {t.numel()} {t.dtype} values, a {f['format']} file of this geometry needs {need} bytes")
+            dec = ColorDecoder(first["geo"].width, 64, 3)
+            dec.load_state_dict(f["decoder"])
+            tables.append(t)
+            decoders.append([q.detach() for q in dec.linear_params()])
+        device = torch.device(device if device is not None else "cuda")
+        if device.type != "cuda":
+            raise RuntimeError("HashGridFieldBatch needs a HIP device: there is no CPU implementation of this path")
+        self = cls.__new__(cls)
+        self.geo, self.field_size, self.device = first["geo"], first["geo"].field_size, device
+        self.n_fields, self.hidden, self.n_linear, self.num_bits = len(paths), 64, 3, first["num_bits"]
+        self.noise_seed, self.groups_per_field = 0, int(groups_per_field)
+        stack = torch.stack(tables).to(device).contiguous()
+        self.stored, self.packed = (None, stack) if is_packed else (stack, None)
+        self.tables = None
+        self.params = [torch.stack([d[k] for d in decoders]).to(device).contiguous() for k in range(6)]
+        self.optimizer = self.scheduler = self._gm = None
+        self._grad_clean, self.steps, self.frozen, self._pass_samples = True, 0, True, 0
+        return self
+
+    def _table_source(self) -> Tuple[torch.Tensor, str, Optional[int]]:
+        """the stacked tables this batch holds as a launch source: (data, kind, num_bits) - never converted"""
+        if self.tables is not None:
+            return self.tables.detach(), "f32", None
+        if self.packed is not None:
+            return self.packed, "bits", self.num_bits
+        return self.stored, "u8", self.num_bits
+
     @torch.no_grad()
     def train_step(self, coord, extent: Sequence[int], target: torch.Tensor, accumulate: bool = False, scale: float = 1.0, step: bool = True,
                    noise: Optional[bool] = None) -> torch.Tensor:
@@ -2135,6 +2324,7 @@ class HashGridFieldBatch:
         [B, num_crops, dim]: each field's own (validated per field).  ``target`` [B, N, 3].  ``accumulate`` / ``scale`` / ``step`` / ``noise``
         are the single field's: the noise keys (seed, optimiser step, samples of this pass before this chunk + the row inside the field) are
         the same for every field, so field b trains exactly as alone.  After ``freeze()`` only the decoders train."""
+        self._refuse_decode_only("train_step")
         frozen = self.frozen
         if isinstance(coord, torch.Tensor) and coord.is_cuda:
             num_crops = coord.shape[-2] if coord.dim() >= 2 else 1
@@ -2170,6 +2360,7 @@ class HashGridFieldBatch:
     def apply_step(self) -> None:
         """the optimiser half of ``train_step(step=True)``: ONE ``nic_adam_multi`` over the stacked tensors on the gradients the buffers hold
         (the table gradient is zeroed by the same launch, the tables are clamped to the quantiser's range), then the schedule and the step count"""
+        self._refuse_decode_only("apply_step")
         grad = None if self.frozen else self.tables.grad
         for p, g in zip(self.params, self._gm):
             p.grad = g
@@ -2183,6 +2374,7 @@ class HashGridFieldBatch:
     @torch.no_grad()
     def freeze(self) -> None:
         """quantise every table in place (nic_quantize) and stop updating them: ``train_step`` then trains the decoders alone, without noise"""
+        self._refuse_decode_only("freeze")
         if self.num_bits is None:
             raise RuntimeError("freeze() needs num_bits: there is no quantiser without it")
         if self.frozen:
@@ -2197,6 +2389,7 @@ class HashGridFieldBatch:
         """``HashGridField.fit`` on ``targets`` [B, S_x, S_y(, S_z), 3]: ``epochs`` whole-field passes walked in slabs of ``chunk`` x-rows (one
         optimiser step per pass, each slab's MSE weighted by its share); with ``num_bits`` noise while the epoch is below ``freeze_at`` *
         epochs, then ``freeze()``.  Returns the per-pass losses, [epochs][B]."""
+        self._refuse_decode_only("fit")
         size = self.field_size
         if not isinstance(targets, torch.Tensor) or tuple(targets.shape) != (self.n_fields, *size, 3):
             raise ValueError(f"targets must be {(self.n_fields, *size, 3)}, got {tuple(targets.shape) if isinstance(targets, torch.Tensor) else type(targets).__name__}")
@@ -2221,14 +2414,50 @@ class HashGridFieldBatch:
 
     @torch.no_grad()
     def decode(self, tile: int = 1024) -> torch.Tensor:
-        """every field whole, [B, S_x, S_y(, S_z), 3], in tiles of side <= ``tile``: one launch per tile for all fields"""
+        """every field whole, [B, S_x, S_y(, S_z), 3], in tiles of side <= ``tile``: one launch per tile for all fields, from whatever table the
+        batch holds - the fp32 tables (nic_hash_batch_forward, the launches a trained batch always made), or a decode-only batch's uint8 or
+        bit-packed ones as stored (nic_hash_batch_forward_source)"""
         size = self.field_size
         out = torch.empty(self.n_fields, *size, 3, dtype=torch.float32, device=self.device)
-        tables, params = self.tables.detach(), [p.detach() for p in self.params]
+        params = [p.detach() for p in self.params]
+        data, kind, bits = self._table_source()
         for o in itertools.product(*[range(0, s, tile) for s in size]):
             ext = [min(tile, s - a) for s, a in zip(size, o)]
             sl = (slice(None), *(slice(a, a + e) for a, e in zip(o, ext)))
-            out[sl] = hash_batch_forward(self.geo, tables, [o], ext, params, self._groups(1, ext)).reshape(self.n_fields, *ext, 3)
+            if kind == "f32":
+                y = hash_batch_forward(self.geo, data, [o], ext, params, self._groups(1, ext))
+            else:
+                y = hash_batch_forward_source(self.geo, data, params, kind, bits, coord=[o], extent=ext, groups_per_field=self._groups(1, ext))
+            out[sl] = y.reshape(self.n_fields, *ext, 3)
+        return out
+
+    def _point_groups(self, n: int) -> int:
+        """``_groups`` for a launch at ``n`` points per field: a positive ``groups_per_field`` is cut to the grid their wave items admit"""
+        if self.groups_per_field == 0:
+            return 0
+        return min(self.groups_per_field, ((((int(n) + 63) // 64 + 3) // 4) + 7) // 8 * 8)
+
+    @torch.no_grad()
+    def query(self, points: torch.Tensor) -> torch.Tensor:
+        """[B, N, 3] colours at ``points`` - [N, dim] shared by all fields, or [B, N, dim], each field its own - in ONE launch, from whatever
+        table the batch holds (nic_hash_batch_forward_source).  fp32, sample units, clamped like ``HashGridField.query``."""
+        data, kind, bits = self._table_source()
+        n = points.shape[-2] if isinstance(points, torch.Tensor) and points.dim() >= 2 else 0
+        return hash_batch_forward_source(self.geo, data, [p.detach() for p in self.params], kind, bits, points=points,
+                                         groups_per_field=self._point_groups(max(n, 1)))
+
+    @torch.no_grad()
+    def resample(self, size: Union[int, Sequence[int]], tile: int = 1024) -> torch.Tensor:
+        """every field decoded on a regular grid of ANY size, [B, *size, 3]: ``HashGridField.resample``'s sample positions (its
+        ``_resample_points``, generated once per tile and shared by all fields), one launch per tile for all fields"""
+        size = (int(size),) * self.geo.dim if isinstance(size, int) else tuple(int(v) for v in size)
+        if len(size) != self.geo.dim or any(v < 1 for v in size):
+            raise ValueError(f"size {size} for a {self.geo.dim}D field")
+        out = torch.empty(self.n_fields, *size, 3, dtype=torch.float32, device=self.device)
+        for o in itertools.product(*[range(0, s, tile) for s in size]):
+            ext = [min(tile, s - a) for s, a in zip(size, o)]
+            sl = (slice(None), *(slice(a, a + e) for a, e in zip(o, ext)))
+            out[sl] = self.query(HashGridField._resample_points(self, size, o, ext)).reshape(self.n_fields, *ext, 3)
         return out
 
     def _adam_state(self, p: torch.Tensor):
@@ -2239,8 +2468,24 @@ class HashGridFieldBatch:
     def extract(self, b: int) -> "HashGridField":
         """an independent ``HashGridField(fused=True)`` holding copies of field b's table, decoder, codec state (``num_bits``, ``noise_seed``,
         frozen or not), step count, learning rates and Adam moments: ``decode`` / ``query`` / ``resample`` / ``point_gradient`` /
-        ``save_compressed`` work on it, and later training of either side does not touch the other"""
+        ``save_compressed`` work on it, and later training of either side does not touch the other.  From a decode-only batch: the
+        decode-only field ``HashGridField.load_compressed(path, fused=True)`` makes of field b's file, on copies of its table and decoder"""
         b = self._check_field_index(b)
+        if self.decode_only:
+            f = HashGridField.__new__(HashGridField)
+            f.field_size, f.geo, f.hidden, f.n_linear, f._lod_fade = self.field_size, self.geo, 64, 3, None
+            f.num_bits, f.level_bits, f.device = self.num_bits, None, self.device
+            f.stored = None if self.stored is None else self.stored[b].clone()
+            f.packed = None if self.packed is None else self.packed[b].clone()
+            f.table = None
+            with torch.random.fork_rng(devices=[]):  # the default init is overwritten: leave the generator alone
+                f.decoder = ColorDecoder(self.geo.width, 64, 3).to(self.device)
+            for q, p in zip(f.decoder.linear_params(), self.params):
+                q.copy_(p[b])
+            f.optimizer = f.scheduler = None
+            f.noise_seed, f.steps, f.frozen, f._pass_samples, f._grad_clean = 0, 0, True, 0, True
+            f._set_route(True)
+            return f
         with torch.random.fork_rng(devices=[self.device]):                     # the constructor's random init is overwritten: leave the generators alone
             f = HashGridField(self.field_size, hidden=64, n_linear=3, device=self.device, num_bits=self.num_bits, noise_seed=self.noise_seed, fused=True,
                               **self._field_args)
@@ -2267,6 +2512,7 @@ class HashGridFieldBatch:
         """copies a compatible ``HashGridField`` into slot b: its table and decoder (and Adam moments, where both sides have them).  The
         geometry, the decoder shape and the codec state (``num_bits``, no bit depth per level, frozen like the batch) must be the batch's, and
         the field must hold an fp32 table (not one from ``load_compressed``): anything else is a ValueError"""
+        self._refuse_decode_only("insert")
         b = self._check_field_index(b)
         if not isinstance(field, HashGridField):
             raise TypeError("insert() takes a HashGridField")
