@@ -16,7 +16,8 @@ def library_path() -> str:
     return _lib.LIB_PATH
 
 
-_HASHGRID_NAMES = ("HashGeometry", "HashGridField", "HashGridFieldBatch", "hash_batch_forward", "hash_batch_forward_backward", "hash_batch_forward_source", "hash_batch_groups")
+_HASHGRID_NAMES = ("HashGeometry", "HashGridField", "HashGridFieldBatch", "hash_batch_forward", "hash_batch_forward_backward", "hash_batch_forward_source", "hash_batch_groups",
+                   "hash_batch_forward_p16", "hash_batch_groups_p16")
 
 
 def __getattr__(name):

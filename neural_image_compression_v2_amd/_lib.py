@@ -241,6 +241,10 @@ SIGNATURES = {
                                              _P, _SZ, _P]),
     "nic_hash_batch_forward_source": (_I, [ctypes.POINTER(NicHashDesc), _I, _I, ctypes.POINTER(NicHashSource), _P, _P, _L, _M, _P, _P]),
 }
+# the entries of include/nicv2_hip_ext.h: those added after the 86 of the main header; bound by load() in the same loop
+EXT_SIGNATURES = {
+    "nic_hash_batch_forward_p16": (_I, [ctypes.POINTER(NicHashDesc), _I, _I, ctypes.POINTER(NicHashSource), _P, _P, _L, _M, _I, _P, _P]),
+}
 
 _lib: Optional[ctypes.CDLL] = None
 _lock = threading.Lock()
@@ -258,7 +262,7 @@ def load() -> ctypes.CDLL:
                     f"{LIB_PATH} is missing - the HIP extension is the only implementation of this path. "
                     "Build it with `python -m neural_image_compression_v2_amd._build` (hipcc, gfx950).")
             lib = ctypes.CDLL(LIB_PATH)
-            for name, (res, args) in SIGNATURES.items():
+            for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES}.items():
                 fn = getattr(lib, name)          # AttributeError if the build is stale: loud by design
                 fn.restype = res
                 fn.argtypes = args

@@ -17,8 +17,10 @@
 //   from the shared descriptor (a packed table is 4 sum + 8 bytes: every field of a 4-byte-aligned stack is aligned, and its 8 zero bytes keep
 //   the widest window of its last level inside the field).  The position: the lattice as above, or points [B, n, dim] through point_fixed,
 //   one wave item = 64 consecutive points of one field; a lane past the end decodes the field's last point and stores nothing.
-// Every device helper is hash_common.hpp's; this unit holds the three kernels, their parameters and the host side.
+// Every device helper is hash_common.hpp's; this unit holds the three kernels, their parameters and the host side.  What the 16-bit batched
+// kernel (hashgrid_fused16.hip) shares with them - field_range, SParams, StoredSrc, the rules on B and G - is hashgrid_batch.hpp's.
 #include "hash_common.hpp"
+#include "hashgrid_batch.hpp"
 
 namespace nic {
 namespace hbatch {
@@ -48,14 +50,6 @@ struct FieldSrc {
     const NoiseSrc& noise;
     uint64_t sample_base;
 };
-
-// xcd_range on (lb, G) instead of (blockIdx.x, gridDim.x): each XCD (local blocks x, x + 8, ..) walks one contiguous range of groups of 4 patches
-__device__ __forceinline__ WaveRange field_range(int64_t n_waves, int lb, int G) {
-    const int xcd = lb & 7;
-    const int64_t n_groups = (n_waves + 3) >> 2, chunk = (n_groups + 7) >> 3;
-    const int64_t g_begin = xcd * chunk;
-    return WaveRange{g_begin + (lb >> 3), g_begin + chunk < n_groups ? g_begin + chunk : n_groups, G >> 3};
-}
 
 // the sample of lane `lane` in patch `wv` of a field: its row inside the field (targets, outputs, noise keys) and its fixed-point position.  A
 // lane on the rim of a patch gets the position of a real sample; it stores and adds nothing.
@@ -149,34 +143,7 @@ __global__ void __launch_bounds__(256) hash_batch_kernel(const BParams p) {
 }
 
 // ---- forward only, from any table source, on the lattice or at points --------------------------------------------------------
-struct SParams {
-    nic_hash_desc d;          // one field's; at points extent[a] = S_a, num_crops = 1
-    int64_t stride;           // bytes from field b's table to field b + 1's
-    const int32_t* origins;   // [B, num_crops, dim], or
-    const float* points;      // [B, n, dim]
-    int64_t n;                // points of one field
-    const float* table;       // NIC_HASH_SRC_F32: the base of the stack (set_point_source fills the one of its kind)
-    const uint8_t* stored;    // NIC_HASH_SRC_U8
-    const uint32_t* packed;   // NIC_HASH_SRC_BITS, 4-byte aligned
-    float q_scale, q_bias;    // load4fp: (u - q_bias + 1) / q_scale
-    int32_t q_bits, q_tight;
-    const float *w1, *b1, *w2, *b2, *w3, *b3;      // bases of the stacked decoder
-    float* y;                 // [B, rows, 3]
-    int64_t n_items;          // wave items of one field: patches, or groups of 64 points
-    int64_t n_rows;           // rows of y per field
-    int32_t groups;           // G
-};
-
-// what encode_point reads of a stored source, for field b
-struct StoredSrc {
-    const nic_hash_desc& d;
-    const float* table;
-    const uint8_t* stored;
-    const uint32_t* packed;
-    float q_scale, q_bias;
-    int32_t q_bits, q_tight;
-};
-
+// SParams, StoredSrc: hashgrid_batch.hpp
 template <int D, int F, int SRC, bool POINTS>
 __global__ void __launch_bounds__(256) hash_batch_decode_kernel(const SParams p) {
     __shared__ DecoderSmem sm;
@@ -266,31 +233,14 @@ __global__ void __launch_bounds__(256) hash_batch_reduce_kernel(const float* par
     *dst = add_grads ? acc + *dst : acc;
 }
 
-// ---- host side (the checks and grid rules are hash_common.hpp's) -----------------------------------------------------------------------------
-constexpr int kMaxFields = 65535;                 // the reduction's blockIdx.y
-
+// ---- host side (the checks and grid rules are hash_common.hpp's; kMaxFields, batch_groups_of, mlp3_ok: hashgrid_batch.hpp) ------------------------
 // the lattice goes through the fixed-point cell: 256 S_max < 2^30, as in every unit that reads a crop through lattice_fixed
 static int check_batch_desc(const nic_hash_desc* d, int n_linear) {
     const int rc = nic_hash_fused_supported(d, kH, n_linear);            // the only copy of the fused set (hash_fused.hip)
     if (rc) return rc;
     return 256 * (int64_t)d->S_max >= (int64_t(1) << 30) ? NIC_E_ARG : NIC_OK;
 }
-// G: 0 = wg_cap() / B rounded up to a multiple of 8, at least 8, at most the single field's persistent grid; a positive value must be a
-// multiple of 8 within that grid.  -1: refused
-static int batch_groups_of(int64_t n_items, int n_fields, int groups_per_field) {
-    const int top = persistent_grid(n_items);
-    if (groups_per_field < 0 || (groups_per_field & 7) || groups_per_field > top) return -1;
-    if (groups_per_field > 0) return groups_per_field;
-    int g = (wg_cap() / n_fields + 7) / 8 * 8;
-    g = g < 8 ? 8 : g;
-    return g < top ? g : top;
-}
 static int batch_groups(const nic_hash_desc* d, int n_fields, int groups_per_field) { return batch_groups_of(count_patches(d), n_fields, groups_per_field); }
-static bool mlp3_ok(const nic_mlp* m) {
-    for (int i = 0; i < 3; ++i)
-        if (!m->w[i] || !m->b[i]) return false;
-    return true;
-}
 static void fill(BParams& p, const nic_hash_desc* d, const float* tables, const int32_t* origins, const nic_mlp* mlp, float* y, int groups) {
     p.d = *d; p.tables = tables; p.origins = origins; p.y = y; p.groups = groups;
     p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];

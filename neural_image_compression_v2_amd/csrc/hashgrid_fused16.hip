@@ -11,8 +11,14 @@
 //   the loop-invariant weights live in LDS as bf16 hi / lo images in natural [unit][k] order (an A fragment is two 8-byte reads of a row): L F
 //   is a launch value, so the layer-1 fragments cannot sit in registers under a compile-time index, and images of at most 36 KB beside row tiles
 //   of L F <= 32 columns (WIDE = false) leave the workgroup at 61 KB of LDS - two workgroups per CU, a second wave per SIMD for the gathers.
+// B fields of one geometry per launch (include/nicv2_hip_ext.h: nic_hash_batch_forward_p16; hashgrid.py, HashGridFieldBatch.decode / query /
+// resample(precision=)): hash_batch16_kernel is the kernel above in hash_batch_decode_kernel's shape (hashgrid_batch.hip) - a
+// workgroup belongs to field b = blockIdx.x / G, stages field b's decoder once and walks field b's wave items (field_range); the table, the
+// origins or points and y at the field's strides.  Per sample the same encode_point and decoder16_half in the same order: the single kernel's bits.
 #include "hash_common.hpp"
 #include "fused_kernel.hpp"
+#include "hashgrid_batch.hpp"
+#include "../../include/nicv2_hip_ext.h"
 
 namespace nic {
 namespace hf16 {
@@ -47,10 +53,20 @@ struct Smem16 {
     __attribute__((aligned(8))) __bf16 w3[2][4 * LD2];       // rows 0 .. 2 and a zero row for the lanes of output rows 3 .. 31
 };
 
+// what position16 and load_decoder16 read of P16Params, for field b of a batch: the shared descriptor by reference, the field's own positions and
+// decoder
+struct Field16 {
+    const nic_hash_desc& d;
+    const int32_t* origins;   // [num_crops, dim]; null = the samples are `points`
+    const float* points;      // [n, dim]
+    int64_t n, n_waves;
+    const float *w1, *b1, *w2, *b2, *w3, *b3;
+};
+
 // the sample lane `lane` of wave item `wv` handles: its row of y and its fixed-point position.  A lane without a sample (the rim of a patch,
-// past the last point) gets the position of a real one; it stores nothing.
-template <int D>
-__device__ __forceinline__ bool position16(const P16Params& p, int64_t wv, int lane, int64_t& row, uint32_t (&t)[3]) {
+// past the last point) gets the position of a real one; it stores nothing.  P: P16Params, or Field16
+template <int D, class P>
+__device__ __forceinline__ bool position16(const P& p, int64_t wv, int lane, int64_t& row, uint32_t (&t)[3]) {
     if (p.origins != nullptr) {
         const PatchSample<D> s = patch_sample<D>(p.d, wv, p.n_waves, lane);
         lattice_fixed<D>(p.d, p.origins, s, t);
@@ -74,8 +90,8 @@ __device__ __forceinline__ void put8(__bf16* hi, __bf16* lo, const float (&v)[8]
     *reinterpret_cast<s16x4*>(lo + 4) = s16x4{l[4], l[5], l[6], l[7]};
 }
 // the decoder's weights as bf16 images (columns past L F zero), the biases, and the wave's row tile cleared; the caller synchronises after it
-template <bool WIDE>
-__device__ __forceinline__ void load_decoder16(Smem16<WIDE>& sm, const P16Params& p, int LF, int tid) {
+template <bool WIDE, class P>
+__device__ __forceinline__ void load_decoder16(Smem16<WIDE>& sm, const P& p, int LF, int tid) {
     using S = Smem16<WIDE>;
     for (int e = tid; e < kH * (S::KP / 8); e += 256) {
         const int h = e / (S::KP / 8), k0 = 8 * (e - h * (S::KP / 8));
@@ -202,6 +218,57 @@ __global__ void __launch_bounds__(256) hash_fused16_kernel(const P16Params p) {
     }
 }
 
+// the same per field (hash_batch_decode_kernel's shape, hashgrid_batch.hip): workgroup (b, lb) of G per field stages field b's decoder and walks
+// field b's wave items; a workgroup without one does nothing after its prologue.  Nothing synchronises across workgroups.
+template <int D, int F, int SRC, int MODE, bool WIDE>
+__global__ void __launch_bounds__(256) hash_batch16_kernel(const hbatch::SParams p) {
+    using S = Smem16<WIDE>;
+    __shared__ S sm;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 31, half = lane >> 5;
+    const int LF = p.d.levels * F, ks1 = (LF + 15) >> 4;
+    const int b = (int)(blockIdx.x / (unsigned)p.groups), lb = (int)(blockIdx.x - (unsigned)b * (unsigned)p.groups);
+    const Field16 fb{p.d,
+                     p.origins != nullptr ? p.origins + (int64_t)b * p.d.num_crops * D : nullptr,
+                     p.origins != nullptr ? nullptr : p.points + (int64_t)b * p.n * D,
+                     p.n, p.n_items,
+                     p.w1 + (int64_t)b * kH * LF, p.b1 + b * kH, p.w2 + (int64_t)b * kH * kH, p.b2 + b * kH, p.w3 + b * 3 * kH, p.b3 + b * 3};
+    load_decoder16<WIDE>(sm, fb, LF, tid);
+    __syncthreads();
+    float* xs = sm.x[wave];
+    float* xrow = xs + lane * S::XS16;
+    const int64_t tab_off = (int64_t)b * p.stride;
+    const hbatch::StoredSrc src_b{p.d,
+                                  SRC == NIC_HASH_SRC_F32 ? reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(p.table) + tab_off) : nullptr,
+                                  SRC == NIC_HASH_SRC_U8 ? p.stored + tab_off : nullptr,
+                                  SRC == NIC_HASH_SRC_BITS ? reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(p.packed) + tab_off) : nullptr,
+                                  p.q_scale, p.q_bias, p.q_bits, p.q_tight};
+    float* y = p.y + (int64_t)b * p.n_rows * 3;
+    const WaveRange wr = hbatch::field_range(p.n_items, lb, p.groups);
+    for (int64_t g = wr.begin; g < wr.end; g += wr.step) {
+        const int64_t wv = 4 * g + wave;
+        if (wv >= p.n_items) continue;                          // wave-uniform; nothing below synchronises the workgroup
+        int64_t row;
+        uint32_t t[3];
+        const bool live_lane = position16<D>(fb, wv, lane, row, t);
+        encode_point<D, F, SRC, false, false, false>(src_b, t, row, 0.f, xrow);
+        wave_sync();
+        const unsigned long long live_mask = __ballot(live_lane);
+#pragma unroll 1
+        for (int nt = 0; nt < 2; ++nt) {
+            if (((live_mask >> (32 * nt)) & 0xFFFFFFFFull) == 0ull) continue;      // a half tile without a sample (wave-uniform)
+            const int src = 32 * nt + j;
+            const int64_t r = (int64_t)(uint32_t)__shfl((int)(uint32_t)row, src) | ((int64_t)__shfl((int)(row >> 32), src) << 32);
+            float yv[3];
+            decoder16_half<MODE, WIDE>(sm, xs + src * S::XS16, j, half, ks1, yv);
+            if (half == 0 && ((live_mask >> src) & 1ull)) {
+#pragma unroll
+                for (int o = 0; o < 3; ++o) y[r * 3 + o] = yv[o];
+            }
+        }
+        wave_sync();
+    }
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
 // the lattice route goes through the fixed-point cell too: 256 S_max < 2^30, as at points
 static int p16_check_desc(const nic_hash_desc* d, bool at_points) {
@@ -222,6 +289,17 @@ static int launch16(const P16Params& p, void* stream) {
         const hipStream_t s = (hipStream_t)stream;
         if (p.d.levels * F > 32) hipLaunchKernelGGL((hash_fused16_kernel<D, F, SRC, MODE, true>), dim3(p16_grid(p.n_waves, true)), dim3(256), 0, s, p);
         else hipLaunchKernelGGL((hash_fused16_kernel<D, F, SRC, MODE, false>), dim3(p16_grid(p.n_waves, false)), dim3(256), 0, s, p);
+    });
+}
+
+template <int SRC, int MODE>
+static int launch_batch16(const hbatch::SParams& p, int n_fields, void* stream) {
+    const dim3 grid((unsigned)n_fields * (unsigned)p.groups);
+    return dispatch_dim_features(p.d, [&](auto dim, auto features) {
+        constexpr int D = decltype(dim)::value, F = decltype(features)::value;
+        const hipStream_t s = (hipStream_t)stream;
+        if (p.d.levels * F > 32) hipLaunchKernelGGL((hash_batch16_kernel<D, F, SRC, MODE, true>), grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((hash_batch16_kernel<D, F, SRC, MODE, false>), grid, dim3(256), 0, s, p);
     });
 }
 
@@ -255,6 +333,38 @@ int nic_hash_fused_forward_p16(const nic_hash_desc* desc, const nic_hash_source*
     return dispatch_source(src->kind, [&](auto kind) {
         constexpr int SRC = decltype(kind)::value;
         return precision == NIC_HASH_PREC_SPLIT ? launch16<SRC, P16_SPLIT>(p, stream) : launch16<SRC, P16_BF16>(p, stream);
+    });
+}
+
+int nic_hash_batch_forward_p16(const nic_hash_desc* desc, int n_fields, int groups_per_field, const nic_hash_source* src, const int32_t* origins,
+                               const float* points, int64_t n_points, const nic_mlp* mlp, int precision, float* y, void* stream) {
+    if (!desc || !mlp) return NIC_E_NULL;
+    int rc = nic_hash_fused_supported(desc, kH, mlp->n_linear);          // the only copy of the fused set (hash_fused.hip)
+    if (rc) return rc;
+    if ((origins != nullptr) == (points != nullptr)) return NIC_E_ARG;
+    if ((rc = p16_check_desc(desc, points != nullptr)) != NIC_OK) return rc;
+    if (n_fields < 1 || n_fields > hbatch::kMaxFields) return NIC_E_ARG;
+    // G on the wave items of ONE field under this kernel's cap (p16_grid); a count of points that launches nothing stands as one item here
+    const int64_t n_items = origins ? count_patches(desc) : (n_points > 0 ? (n_points + 63) >> 6 : 1);
+    const bool wide = desc->levels * desc->features > 32;
+    const int g = hbatch::batch_groups_in(p16_grid(n_items, wide), wg_cap() * (wide ? 1 : 2), n_fields, groups_per_field);
+    if (g < 0) return NIC_E_ARG;
+    if (!src || !src->data || !hbatch::mlp3_ok(mlp) || !y) return NIC_E_NULL;
+    hbatch::SParams p{};
+    p.d = *desc; p.origins = origins; p.points = points; p.y = y; p.groups = g; p.n_items = n_items;
+    p.n = origins ? 0 : n_points;
+    if ((rc = set_point_source(p, src)) != NIC_OK) return rc;
+    if (precision != NIC_HASH_PREC_SPLIT && precision != NIC_HASH_PREC_BF16) return NIC_E_ARG;
+    if (points && n_points < 0) return NIC_E_ARG;
+    if (points && n_points == 0) return NIC_OK;
+    p.stride = src->kind == NIC_HASH_SRC_F32 ? (((int64_t)desc->levels << desc->log2_table) * desc->features) * (int64_t)sizeof(float)
+             : src->kind == NIC_HASH_SRC_U8 ? nic_hash_stored_bytes(desc) : nic_hash_packed_bytes(desc, src->num_bits);
+    if (p.stride <= 0) return NIC_E_ARG;
+    p.n_rows = origins ? (int64_t)desc->num_crops * desc->extent[0] * desc->extent[1] * (desc->dim == 3 ? desc->extent[2] : 1) : n_points;
+    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
+    return dispatch_source(src->kind, [&](auto kind) {
+        constexpr int SRC = decltype(kind)::value;
+        return precision == NIC_HASH_PREC_SPLIT ? launch_batch16<SRC, P16_SPLIT>(p, n_fields, stream) : launch_batch16<SRC, P16_BF16>(p, n_fields, stream);
     });
 }
 

@@ -497,7 +497,15 @@ def hash_batch_groups(n_fields: int, patches: int, cap: int, groups_per_field: i
     return min(max((int(cap) // n_fields + 7) // 8 * 8, 8), top)
 
 
-BATCH_DECODER_SHAPES = ((64, None), (64,), (64, 64), (64,), (3, 64), (3,))     # None: L F
+def hash_batch_groups_p16(n_fields: int, items: int, cap: int, wide: bool, groups_per_field: int = 0) -> int:
+    """G of a batched launch on the 16-bit matrix pipe (nic_hash_batch_forward_p16): ``hash_batch_groups`` on that kernel's workgroup cap.
+    ``items``: the wave items of ONE field (its patches, or ceil(points / 64)); ``cap``: one workgroup per CU, a multiple of 8; ``wide``:
+    levels * features > 32.  Where it is not, the kernel's 61 KB of LDS let two workgroups share a CU and the cap doubles - for the automatic G
+    and for the single-field grid that bounds an explicit one."""
+    return hash_batch_groups(n_fields, items, int(cap) * (1 if wide else 2), groups_per_field)
+
+
+BATCH_DECODER_SHAPES =((64, None), (64,), (64, 64), (64,), (3, 64), (3,))     # None: L F
 
 
 def _check_batch_tables(geo: HashGeometry, tables: torch.Tensor, name: str = "tables") -> None:
@@ -693,15 +701,9 @@ def _require_on_device(t: torch.Tensor, name: str) -> None:
         raise ValueError(f"{name} must be contiguous: the kernel reads the fields at the strides of the geometry")
 
 
-@fused._on_tensor_device
-def hash_batch_forward_source(geo: HashGeometry, data: torch.Tensor, params: Sequence[torch.Tensor], kind: str = "f32", num_bits: Optional[int] = None,
-                              coord=None, extent: Optional[Sequence[int]] = None, points: Optional[torch.Tensor] = None, groups_per_field: int = 0,
-                              out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """[B, N, 3]: B stacked fields of one geometry decoded in ONE launch from the table they hold (nic_hash_batch_forward_source; DESIGN 4.7.14).
-    ``data``: kind "f32" = fp32 [B, L, T, F]; "u8" / "bits" = contiguous uint8 [B, bytes] on the device, bytes = ``hash_stored_bytes`` /
-    ``hash_packed_bytes`` of ``num_bits``.  ``params``: the six stacked decoder tensors.  Exactly one position source: the crops ``coord``
-    ([num_crops, dim] shared or [B, num_crops, dim] per field) of ``extent``, or ``points`` ([N, dim] shared by all fields or [B, N, dim] per
-    field; fp32, sample units, clamped by the kernel like ``hash_fused_forward_points``).  Every shape and dtype is checked on the host first."""
+def _batch_forward_source(geo, data, params, kind, num_bits, coord, extent, points, groups_per_field, out, precision):
+    """``hash_batch_forward_source`` (``precision`` None) and ``hash_batch_forward_p16`` ("split" / "bf16"): one set of refusals, one launch"""
+    prec = None if precision is None else _check_precision(precision)
     n_fields = _check_batch_source(geo, data, kind, num_bits)
     data = data.detach()
     params = _check_batch_decoder(geo, [q.detach() if isinstance(q, torch.Tensor) else q for q in params], n_fields)
@@ -749,10 +751,36 @@ def hash_batch_forward_source(geo: HashGeometry, data: torch.Tensor, params: Seq
         org = org.to(data.device, non_blocking=True)
         d = geo.to_desc(org.shape[1], extent)
     src, m = _lib.NicHashSource(POINT_SOURCES[kind], 0 if kind == "f32" else int(num_bits), data.data_ptr()), fused._mlp_struct(params)
-    _lib.check(_lib.load().nic_hash_batch_forward_source(ctypes.byref(d), n_fields, int(groups_per_field), ctypes.byref(src), _lib.ptr(org), _lib.ptr(pts),
-                                                         n if pts is not None else 0, ctypes.byref(m), _lib.ptr(y), _lib.stream_ptr(data.device)),
-               "nic_hash_batch_forward_source")
+    head = (ctypes.byref(d), n_fields, int(groups_per_field), ctypes.byref(src), _lib.ptr(org), _lib.ptr(pts), n if pts is not None else 0, ctypes.byref(m))
+    if prec is None:
+        _lib.check(_lib.load().nic_hash_batch_forward_source(*head, _lib.ptr(y), _lib.stream_ptr(data.device)), "nic_hash_batch_forward_source")
+    else:
+        _lib.check(_lib.load().nic_hash_batch_forward_p16(*head, prec, _lib.ptr(y), _lib.stream_ptr(data.device)), "nic_hash_batch_forward_p16")
     return y
+
+
+@fused._on_tensor_device
+def hash_batch_forward_source(geo: HashGeometry, data: torch.Tensor, params: Sequence[torch.Tensor], kind: str = "f32", num_bits: Optional[int] = None,
+                              coord=None, extent: Optional[Sequence[int]] = None, points: Optional[torch.Tensor] = None, groups_per_field: int = 0,
+                              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[B, N, 3]: B stacked fields of one geometry decoded in ONE launch from the table they hold (nic_hash_batch_forward_source; DESIGN 4.7.14).
+    ``data``: kind "f32" = fp32 [B, L, T, F]; "u8" / "bits" = contiguous uint8 [B, bytes] on the device, bytes = ``hash_stored_bytes`` /
+    ``hash_packed_bytes`` of ``num_bits``.  ``params``: the six stacked decoder tensors.  Exactly one position source: the crops ``coord``
+    ([num_crops, dim] shared or [B, num_crops, dim] per field) of ``extent``, or ``points`` ([N, dim] shared by all fields or [B, N, dim] per
+    field; fp32, sample units, clamped by the kernel like ``hash_fused_forward_points``).  Every shape and dtype is checked on the host first."""
+    return _batch_forward_source(geo, data, params, kind, num_bits, coord, extent, points, groups_per_field, out, None)
+
+
+@fused._on_tensor_device
+def hash_batch_forward_p16(geo: HashGeometry, data: torch.Tensor, params: Sequence[torch.Tensor], precision: str, kind: str = "f32",
+                           num_bits: Optional[int] = None, coord=None, extent: Optional[Sequence[int]] = None, points: Optional[torch.Tensor] = None,
+                           groups_per_field: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[B, N, 3]: ``hash_batch_forward_source`` with the decoder's products on the 16-bit matrix pipe (nic_hash_batch_forward_p16; DESIGN
+    4.7.15) - ``hash_fused_forward_p16`` of every field in ONE launch, bit for bit.  ``precision`` "split" (within 5e-6 of the fp32 route) or
+    "bf16" (1e-3 at default initialisation); every other argument and every refusal is ``hash_batch_forward_source``'s.  ``groups_per_field``
+    follows ``hash_batch_groups_p16``: two workgroups share a CU at levels * features <= 32."""
+    _check_precision(precision)
+    return _batch_forward_source(geo, data, params, kind, num_bits, coord, extent, points, groups_per_field, out, precision)
 
 
 def _lod_args(geo: HashGeometry, lod, n: int, device):
@@ -2167,7 +2195,10 @@ class HashGridFieldBatch:
     holds in one launch per tile for all fields (nic_hash_batch_forward_source); ``extract(b)`` of such a batch is what
     ``HashGridField.load_compressed(fused=True)`` makes, ``save_compressed`` re-saves it in either format.
 
-    Not built: batched ``train_points``, a level of detail, ``precision=``, a bit depth per level (a ``/2`` file is read and
+    The 16-bit matrix pipe: ``decode`` / ``query`` / ``resample(precision="split" | "bf16")`` run every tile or point set through
+    ``hash_batch_forward_p16`` from the same table - ``HashGridField``'s ``precision=`` per field, bit for bit, in one launch.  Forward only.
+
+    Not built: batched ``train_points``, a level of detail, 16-bit training, a bit depth per level (a ``/2`` file is read and
     refused), fields of differing geometry in one batch, a container format that holds several fields in one file."""
 
     def __init__(self, n_fields: int, field_size: Union[int, Sequence[int]], levels: int = 16, features: int = 2, log2_table: int = 19,
@@ -2413,10 +2444,13 @@ class HashGridFieldBatch:
         return [[float(v) for v in h] for h in torch.stack(hist).tolist()] if hist else []
 
     @torch.no_grad()
-    def decode(self, tile: int = 1024) -> torch.Tensor:
+    def decode(self, tile: int = 1024, precision: Optional[str] = None) -> torch.Tensor:
         """every field whole, [B, S_x, S_y(, S_z), 3], in tiles of side <= ``tile``: one launch per tile for all fields, from whatever table the
         batch holds - the fp32 tables (nic_hash_batch_forward, the launches a trained batch always made), or a decode-only batch's uint8 or
-        bit-packed ones as stored (nic_hash_batch_forward_source)"""
+        bit-packed ones as stored (nic_hash_batch_forward_source).  ``precision``: None (those launches, unchanged), or "split" / "bf16" -
+        every tile through ``hash_batch_forward_p16`` from the same table, ``HashGridField.decode(precision=)``'s bits per field"""
+        if precision is not None:
+            _check_precision(precision)
         size = self.field_size
         out = torch.empty(self.n_fields, *size, 3, dtype=torch.float32, device=self.device)
         params = [p.detach() for p in self.params]
@@ -2424,7 +2458,9 @@ class HashGridFieldBatch:
         for o in itertools.product(*[range(0, s, tile) for s in size]):
             ext = [min(tile, s - a) for s, a in zip(size, o)]
             sl = (slice(None), *(slice(a, a + e) for a, e in zip(o, ext)))
-            if kind == "f32":
+            if precision is not None:
+                y = hash_batch_forward_p16(self.geo, data, params, precision, kind, bits, coord=[o], extent=ext, groups_per_field=self._groups(1, ext))
+            elif kind == "f32":
                 y = hash_batch_forward(self.geo, data, [o], ext, params, self._groups(1, ext))
             else:
                 y = hash_batch_forward_source(self.geo, data, params, kind, bits, coord=[o], extent=ext, groups_per_field=self._groups(1, ext))
@@ -2438,18 +2474,26 @@ class HashGridFieldBatch:
         return min(self.groups_per_field, ((((int(n) + 63) // 64 + 3) // 4) + 7) // 8 * 8)
 
     @torch.no_grad()
-    def query(self, points: torch.Tensor) -> torch.Tensor:
+    def query(self, points: torch.Tensor, precision: Optional[str] = None) -> torch.Tensor:
         """[B, N, 3] colours at ``points`` - [N, dim] shared by all fields, or [B, N, dim], each field its own - in ONE launch, from whatever
-        table the batch holds (nic_hash_batch_forward_source).  fp32, sample units, clamped like ``HashGridField.query``."""
+        table the batch holds (nic_hash_batch_forward_source).  fp32, sample units, clamped like ``HashGridField.query``.  ``precision``: None,
+        or "split" / "bf16" - the same launch through ``hash_batch_forward_p16``."""
+        if precision is not None:
+            _check_precision(precision)
         data, kind, bits = self._table_source()
         n = points.shape[-2] if isinstance(points, torch.Tensor) and points.dim() >= 2 else 0
-        return hash_batch_forward_source(self.geo, data, [p.detach() for p in self.params], kind, bits, points=points,
-                                         groups_per_field=self._point_groups(max(n, 1)))
+        params, groups = [p.detach() for p in self.params], self._point_groups(max(n, 1))
+        if precision is not None:
+            return hash_batch_forward_p16(self.geo, data, params, precision, kind, bits, points=points, groups_per_field=groups)
+        return hash_batch_forward_source(self.geo, data, params, kind, bits, points=points, groups_per_field=groups)
 
     @torch.no_grad()
-    def resample(self, size: Union[int, Sequence[int]], tile: int = 1024) -> torch.Tensor:
+    def resample(self, size: Union[int, Sequence[int]], tile: int = 1024, precision: Optional[str] = None) -> torch.Tensor:
         """every field decoded on a regular grid of ANY size, [B, *size, 3]: ``HashGridField.resample``'s sample positions (its
-        ``_resample_points``, generated once per tile and shared by all fields), one launch per tile for all fields"""
+        ``_resample_points``, generated once per tile and shared by all fields), one launch per tile for all fields; ``precision`` as in
+        ``query``"""
+        if precision is not None:
+            _check_precision(precision)
         size = (int(size),) * self.geo.dim if isinstance(size, int) else tuple(int(v) for v in size)
         if len(size) != self.geo.dim or any(v < 1 for v in size):
             raise ValueError(f"size {size} for a {self.geo.dim}D field")
@@ -2457,7 +2501,7 @@ class HashGridFieldBatch:
         for o in itertools.product(*[range(0, s, tile) for s in size]):
             ext = [min(tile, s - a) for s, a in zip(size, o)]
             sl = (slice(None), *(slice(a, a + e) for a, e in zip(o, ext)))
-            out[sl] = self.query(HashGridField._resample_points(self, size, o, ext)).reshape(self.n_fields, *ext, 3)
+            out[sl] = self.query(HashGridField._resample_points(self, size, o, ext), precision).reshape(self.n_fields, *ext, 3)
         return out
 
     def _adam_state(self, p: torch.Tensor):
