@@ -33,6 +33,38 @@ int nic_hash_batch_forward_p16(const nic_hash_desc *desc, int n_fields, int grou
                                const int32_t *origins, const float *points, int64_t n_points, const nic_mlp *mlp, int precision, float *y,
                                void *stream);
 
+/* ---- B hash-grid fields per launch TRAINED at their own points (hashgrid.py, hash_batch_forward_backward_points, HashGridFieldBatch.train_points /
+ *      fit_points; csrc/hashgrid_batch.hip, hash_batch_points_kernel).  nic_hash_batch_forward_backward_points is
+ *      nic_hash_fused_forward_backward_points per field in TWO launches whatever n_fields is (the training kernel and the fixed-order reduction
+ *      of its records): the contract of nic_hash_batch_forward_backward - stacked tables / table_grads [B, L, T, F], the stacked decoder and its
+ *      gradients, loss [B], table_grads ADDED to with fp32 atomics (null: frozen tables, no scatter), the decoder gradients and loss overwritten
+ *      or added to under flags = NIC_HASH_FUSED_ADD_GRADS | NIC_HASH_FUSED_ADD_LOSS, no optimiser tail, nic_mark_kernel_end honoured - with the
+ *      position source of nic_hash_batch_forward_source(points=): desc->extent is the FIELD size and desc->num_crops is 1; points =
+ *      [B, n_points, dim] fp32 on the device in sample units with the clamping of nic_hash_encode_points; target and y (y may be null) =
+ *      [B, n_points, 3].
+ *      Point sets are ragged: counts is null (every field has n_points points) or int32 [B] on the device, field b's own count n_b, clamped to
+ *      [0, n_points].  Field b reads the first n_b rows of its points and targets only; rows of y at or past n_b are NOT written; loss[b] =
+ *      loss_scale mean((y_b - target_b)^2) over ITS n_b points.  A field with n_b = 0 has loss 0 and decoder gradients written as 0 (both
+ *      unchanged under the ADD flags); its table gradient is untouched.
+ *      order is null or int32 [B, n_points] of field-LOCAL row indices: wave w of field b takes the rows order[b, 64 w ..].  Only the first n_b
+ *      of a row of order are read, each clamped to [0, n_b - 1].  Targets, outputs and the noise of `quant` stay keyed by the row (sample_base
+ *      + the row inside the field, and the column): field b sees the noise of a single-field call with the same quant, whatever the order.
+ *      groups_per_field = G on the wave items of one field's padded row, ceil(n_points / 64), with nic_hash_batch_forward_source's rule.
+ *      workspace >= nic_hash_batch_points_workspace_bytes (n_fields x G records; 0: one of the checks below refuses).
+ *      Host checks, all before any GPU work, in nic_hash_batch_forward_backward's order, then the points': null desc / mlp (NIC_E_NULL); the
+ *      fused set (nic_hash_fused_supported's code; then 256 S_max < 2^30, NIC_E_ARG); n_fields in 1 .. 65535 (NIC_E_ARG); groups_per_field
+ *      (NIC_E_ARG; for this check alone n_points <= 0 counts as one wave item); null tables, points, decoder layer, target, mlp_grads, loss or
+ *      workspace (NIC_E_NULL; counts, order, table_grads and y may be null); flags (NIC_E_ARG); quant (nic_hash_fused_forward_backward's
+ *      rules); the workspace (NIC_E_WORKSPACE); the descriptor of a point source (num_crops == 1, NIC_E_SHAPE); n_points < 0 or >= 2^31
+ *      (NIC_E_ARG); n_points == 0 is NIC_OK without a launch, nothing written. */
+size_t nic_hash_batch_points_workspace_bytes(const nic_hash_desc *desc, int n_fields, int groups_per_field, int64_t n_points,
+                                             const nic_mlp *mlp);   /* 0: refused */
+int nic_hash_batch_forward_backward_points(const nic_hash_desc *desc, int n_fields, int groups_per_field, const nic_hash_quant *quant,
+                                           const float *tables, const float *points, int64_t n_points, const int32_t *counts,
+                                           const int32_t *order, const nic_mlp *mlp, const float *target, float loss_scale, float *table_grads,
+                                           const nic_mlp_grads *mlp_grads, float *loss, float *y, int flags, void *workspace,
+                                           size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

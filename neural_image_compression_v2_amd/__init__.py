@@ -17,7 +17,7 @@ def library_path() -> str:
 
 
 _HASHGRID_NAMES = ("HashGeometry", "HashGridField", "HashGridFieldBatch", "hash_batch_forward", "hash_batch_forward_backward", "hash_batch_forward_source", "hash_batch_groups",
-                   "hash_batch_forward_p16", "hash_batch_groups_p16")
+                   "hash_batch_forward_p16", "hash_batch_groups_p16", "hash_batch_forward_backward_points", "hash_batch_point_order")
 
 
 def __getattr__(name):

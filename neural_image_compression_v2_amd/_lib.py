@@ -244,6 +244,9 @@ SIGNATURES = {
 # the entries of include/nicv2_hip_ext.h: those added after the 86 of the main header; bound by load() in the same loop
 EXT_SIGNATURES = {
     "nic_hash_batch_forward_p16": (_I, [ctypes.POINTER(NicHashDesc), _I, _I, ctypes.POINTER(NicHashSource), _P, _P, _L, _M, _I, _P, _P]),
+    "nic_hash_batch_points_workspace_bytes": (_SZ, [ctypes.POINTER(NicHashDesc), _I, _I, _L, _M]),
+    "nic_hash_batch_forward_backward_points": (_I, [ctypes.POINTER(NicHashDesc), _I, _I, ctypes.POINTER(NicHashQuant), _P, _P, _L, _P, _P, _M, _P, _F, _P,
+                                                    _G, _P, _P, _I, _P, _SZ, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

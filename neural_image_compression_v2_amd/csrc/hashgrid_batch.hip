@@ -17,10 +17,15 @@
 //   from the shared descriptor (a packed table is 4 sum + 8 bytes: every field of a 4-byte-aligned stack is aligned, and its 8 zero bytes keep
 //   the widest window of its last level inside the field).  The position: the lattice as above, or points [B, n, dim] through point_fixed,
 //   one wave item = 64 consecutive points of one field; a lane past the end decodes the field's last point and stores nothing.
-// Every device helper is hash_common.hpp's; this unit holds the three kernels, their parameters and the host side.  What the 16-bit batched
+//   training at points (nic_hash_batch_forward_backward_points): hash_batch_points_kernel is the training branch above with the
+//   sample source of hash_points_fused_train_kernel (hash_points_train.hip), per field: points / target / y [B, n, ..], order [B, n] of field-LOCAL
+//   rows, and a count n_b <= n per field (counts [B], null = n) - real point sets are ragged.  Field b walks ceil(n_b / 64) wave items, divides
+//   its loss by ITS n_b, and leaves rows at or past n_b alone; the reduction takes the same counts.
+// Every device helper is hash_common.hpp's; this unit holds the four kernels, their parameters and the host side.  What the 16-bit batched
 // kernel (hashgrid_fused16.hip) shares with them - field_range, SParams, StoredSrc, the rules on B and G - is hashgrid_batch.hpp's.
 #include "hash_common.hpp"
 #include "hashgrid_batch.hpp"
+#include "../../include/nicv2_hip_ext.h"
 
 namespace nic {
 namespace hbatch {
@@ -142,6 +147,83 @@ __global__ void __launch_bounds__(256) hash_batch_kernel(const BParams p) {
     }
 }
 
+// ---- training at points, a count per field -------------------------------------------------------------------------------------
+struct PParams {
+    nic_hash_desc d;          // one field's; extent[a] = S_a, num_crops = 1
+    const float* tables;      // [B, L, T, F]
+    const float* points;      // [B, n, dim]
+    const int32_t* counts;    // null (every field has n points), or [B], clamped to [0, n]
+    const int32_t* order;     // null, or [B, n] field-local row indices: the first n_b of a row are read, clamped to [0, n_b - 1]
+    const float *w1, *b1, *w2, *b2, *w3, *b3;      // bases of the stacked decoder
+    const float* target;      // [B, n, 3]
+    float* y;                 // [B, n, 3] (may be null); rows at or past n_b are not written
+    float* grads;             // [B, L, T, F] (null: frozen tables, no scatter)
+    float* partials;          // [B, G, rec]
+    NoiseSrc noise;           // mode NIC_NOISE_NONE / NIC_NOISE_KERNEL
+    uint64_t sample_base;
+    float loss_scale;         // dscale = 2 field_loss_mul(loss_scale, n_b), per field
+    int64_t n;                // the padded width: points of one field's row
+    int32_t groups;           // G
+};
+
+// hash_batch_kernel's training branch on hash_points_fused_train_kernel's samples: wave item wv of field b = the points at positions 64 wv ..
+// of the field's order.  The noise is keyed by the field-local ROW, so field b sees the noise of a single-field call whatever the order.
+template <int D, int F, int KT, bool NOISE>
+__global__ void __launch_bounds__(256) hash_batch_points_kernel(const PParams p) {
+    __shared__ TrainSmem sm;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 31, half = lane >> 5;
+    const int LF = p.d.levels * F;
+    const int b = (int)(blockIdx.x / (unsigned)p.groups), lb = (int)(blockIdx.x - (unsigned)b * (unsigned)p.groups);
+    const int64_t tab_off = (((int64_t)b * p.d.levels) << p.d.log2_table) * F, row_off = (int64_t)b * p.n * 3;
+    load_decoder(sm, p.w1 + (int64_t)b * kH * LF, p.b1 + b * kH, p.w2 + (int64_t)b * kH * kH, p.b2 + b * kH, p.w3 + b * 3 * kH, p.b3 + b * 3, LF, tid);
+    __syncthreads();
+    float* xs = sm.x[wave];
+    float* xrow = xs + lane * XS;
+    float* P = sm.p[wave];
+    float* Q = sm.q[wave];
+    const int64_t n_b = field_count(p.counts, b, p.n);          // workgroup-uniform
+    const float dscale = n_b > 0 ? 2.0f * field_loss_mul(p.loss_scale, n_b) : 0.f;
+    const float* points = p.points + (int64_t)b * p.n * D;
+    const int32_t* order = p.order != nullptr ? p.order + (int64_t)b * p.n : nullptr;
+    const FieldSrc src_b{p.d, p.tables + tab_off, p.noise, p.sample_base};
+    float* grad = p.grads != nullptr ? p.grads + tab_off : nullptr;
+    const float* target = p.target + row_off;
+    float* y = p.y != nullptr ? p.y + row_off : nullptr;
+    const int ks1 = (LF + 1) >> 1;
+    const int64_t n_waves = (n_b + 63) >> 6;
+    const WaveRange wr = field_range(n_waves, lb, p.groups);
+    TrainAcc<KT> A;
+    A.clear();
+    for (int64_t g = wr.begin; g < wr.end; g += wr.step) {
+        const int64_t wv = 4 * g + wave;
+        if (wv >= n_waves) continue;                            // wave-uniform; nothing below synchronises the workgroup
+        const int64_t pos = (wv << 6) + lane;
+        const bool live_lane = pos < n_b;
+        const int64_t row = ordered_row(order, n_b, live_lane ? pos : n_b - 1);      // a lane past the end takes the field's last point; it stores and adds nothing
+        uint32_t t[3];
+        point_fixed<D>(p.d, points, row, t);
+        encode_point<D, F, NIC_HASH_SRC_F32, NOISE, false, false>(src_b, t, row, 0.f, xrow);
+        wave_sync();
+        const unsigned long long live_mask = __ballot(live_lane);
+#pragma unroll 1
+        for (int nt = 0; nt < 2; ++nt) {
+            const int src = 32 * nt + j;
+            const bool mine = half == 0 && ((live_mask >> src) & 1ull);
+            const int r = __shfl((int)row, src);                // row < n_b <= n < 2^31
+            decoder_train_half<KT>(sm, xs, P, Q, nt, j, half, ks1, mine, target + (int64_t)r * 3, y != nullptr ? y + (int64_t)r * 3 : nullptr, dscale,
+                                   grad != nullptr, A);
+        }
+        wave_sync();
+        if (grad != nullptr)
+            scatter_point<D, F, false>(p.d, t, grad, nullptr, 0.f, live_lane, lane, [&](int l, float (&gv)[F]) {
+#pragma unroll
+                for (int f = 0; f < F; ++f) gv[f] = xrow[l * F + f];
+            });
+        wave_sync();
+    }
+    write_record<KT>(sm, A, LF, p.partials + (int64_t)blockIdx.x * RecLayout(LF).rec, tid);      // record (b, lb); all zero without an item (n_b = 0 too)
+}
+
 // ---- forward only, from any table source, on the lattice or at points --------------------------------------------------------
 // SParams, StoredSrc: hashgrid_batch.hpp
 template <int D, int F, int SRC, bool POINTS>
@@ -198,9 +280,10 @@ __global__ void __launch_bounds__(256) hash_batch_decode_kernel(const SParams p)
 }
 
 // hash_fused_reduce_kernel's fixed-order sum, field blockIdx.y: a block = 32 outputs x 8 slices of the field's G records, the slices combined
-// through LDS in slice order.  `g` holds the BASES of the stacked gradients, `loss` is [B].  No optimiser tail.
+// through LDS in slice order.  `g` holds the BASES of the stacked gradients, `loss` is [B].  No optimiser tail.  `counts` null: field b's summed
+// error times `loss_mul`, the crop route's; else times field_loss_mul(loss_scale, n_b) of its own count (clamped to [0, n_points]; 0 at n_b = 0).
 __global__ void __launch_bounds__(256) hash_batch_reduce_kernel(const float* partials, int n_rec, int lf, nic_mlp_grads g, float* loss, float loss_mul,
-                                                                int add_grads, int add_loss) {
+                                                                int add_grads, int add_loss, const int32_t* counts, int64_t n_points, float loss_scale) {
     __shared__ float red[8][32];
     const RecLayout rl(lf);
     const int64_t b = blockIdx.y;
@@ -223,6 +306,10 @@ __global__ void __launch_bounds__(256) hash_batch_reduce_kernel(const float* par
 #pragma unroll
     for (int k = 1; k < 8; ++k) acc += red[k][threadIdx.x];
     if (e == rl.loss) {
+        if (counts != nullptr) {
+            const int64_t n_b = field_count(counts, (int)b, n_points);
+            loss_mul = n_b > 0 ? field_loss_mul(loss_scale, n_b) : 0.f;
+        }
         if (loss) loss[b] = add_loss ? loss[b] + acc * loss_mul : acc * loss_mul;
         return;
     }
@@ -266,6 +353,20 @@ static int launch_source(const SParams& p, int n_fields, void* stream) {
         if (p.points != nullptr) hipLaunchKernelGGL((hash_batch_decode_kernel<D, F, SRC, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
         else hipLaunchKernelGGL((hash_batch_decode_kernel<D, F, SRC, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
     });
+}
+
+template <bool NOISE>
+static int launch_points(const PParams& p, int n_fields, void* stream) {
+    const dim3 grid((unsigned)n_fields * (unsigned)p.groups);
+    return dispatch_dim_features(p.d, [&](auto dim, auto features) {
+        constexpr int D = decltype(dim)::value, F = decltype(features)::value;
+        if (p.d.levels * F > 32) hipLaunchKernelGGL((hash_batch_points_kernel<D, F, 2, NOISE>), grid, dim3(256), 0, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL((hash_batch_points_kernel<D, F, 1, NOISE>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    });
+}
+// G at points: on the wave items of ONE field's padded row; a count that launches nothing stands as one item (nic_hash_batch_forward_source's rule)
+static int point_groups(int64_t n_points, int n_fields, int groups_per_field) {
+    return batch_groups_of(n_points > 0 ? (n_points + 63) >> 6 : 1, n_fields, groups_per_field);
 }
 
 }  // namespace hbatch
@@ -348,13 +449,55 @@ int nic_hash_batch_forward_backward(const nic_hash_desc* desc, int n_fields, int
     const int lf = desc->levels * desc->features;
     const RecLayout rl(lf);
     if (workspace_bytes < (size_t)n_fields * g * rl.rec * sizeof(float)) return NIC_E_WORKSPACE;
-    const float loss_mul = (float)((double)loss_scale / (3.0 * (double)p.n_samples));
+    const float loss_mul = field_loss_mul(loss_scale, p.n_samples);
     p.dscale = 2.0f * loss_mul;
     p.partials = (float*)workspace;
     if ((rc = p.noise.mode == NIC_NOISE_KERNEL ? launch<HB_TRAIN_NOISY>(p, n_fields, stream) : launch<HB_TRAIN>(p, n_fields, stream)) != NIC_OK) return rc;
     kernel_end_mark((hipStream_t)stream);
     hipLaunchKernelGGL(hash_batch_reduce_kernel, dim3((unsigned)((rl.rec + 31) / 32), (unsigned)n_fields), dim3(256), 0, (hipStream_t)stream, p.partials, g,
-                       lf, *mlp_grads, loss, loss_mul, (flags & NIC_HASH_FUSED_ADD_GRADS) ? 1 : 0, (flags & NIC_HASH_FUSED_ADD_LOSS) ? 1 : 0);
+                       lf, *mlp_grads, loss, loss_mul, (flags & NIC_HASH_FUSED_ADD_GRADS) ? 1 : 0, (flags & NIC_HASH_FUSED_ADD_LOSS) ? 1 : 0,
+                       (const int32_t*)nullptr, (int64_t)0, loss_scale);
+    return (int)hipGetLastError();
+}
+
+size_t nic_hash_batch_points_workspace_bytes(const nic_hash_desc* desc, int n_fields, int groups_per_field, int64_t n_points, const nic_mlp* mlp) {
+    if (!desc || !mlp || check_batch_desc(desc, mlp->n_linear) != NIC_OK || n_fields < 1 || n_fields > kMaxFields) return 0;
+    const int g = point_groups(n_points, n_fields, groups_per_field);
+    if (g < 0 || check_point_desc(desc) != NIC_OK || n_points < 0 || n_points >= (int64_t(1) << 31)) return 0;
+    return (size_t)n_fields * g * RecLayout(desc->levels * desc->features).rec * sizeof(float);
+}
+
+int nic_hash_batch_forward_backward_points(const nic_hash_desc* desc, int n_fields, int groups_per_field, const nic_hash_quant* quant, const float* tables,
+                                           const float* points, int64_t n_points, const int32_t* counts, const int32_t* order, const nic_mlp* mlp,
+                                           const float* target, float loss_scale, float* table_grads, const nic_mlp_grads* mlp_grads, float* loss,
+                                           float* y, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+    const KernelEndDrop end;
+    if (!desc || !mlp) return NIC_E_NULL;
+    int rc = check_batch_desc(desc, mlp->n_linear);
+    if (rc) return rc;
+    if (n_fields < 1 || n_fields > kMaxFields) return NIC_E_ARG;
+    const int g = point_groups(n_points, n_fields, groups_per_field);
+    if (g < 0) return NIC_E_ARG;
+    if (!tables || !points || !mlp3_ok(mlp) || !target || !mlp_grads || !loss || !workspace) return NIC_E_NULL;
+    if (flags & ~(NIC_HASH_FUSED_ADD_GRADS | NIC_HASH_FUSED_ADD_LOSS)) return NIC_E_ARG;
+    PParams p{};
+    p.d = *desc; p.tables = tables; p.points = points; p.counts = counts; p.order = order; p.target = target; p.y = y; p.grads = table_grads;
+    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
+    p.n = n_points; p.groups = g; p.loss_scale = loss_scale;
+    p.noise.mode = NIC_NOISE_NONE;
+    if ((rc = set_noise(quant, true, p.noise, p.sample_base)) != NIC_OK) return rc;
+    const int lf = desc->levels * desc->features;
+    const RecLayout rl(lf);
+    if (workspace_bytes < (size_t)n_fields * g * rl.rec * sizeof(float)) return NIC_E_WORKSPACE;
+    if ((rc = check_point_desc(desc)) != NIC_OK) return rc;
+    if (n_points < 0 || n_points >= (int64_t(1) << 31)) return NIC_E_ARG;
+    if (n_points == 0) return NIC_OK;                                   // nothing to launch: loss and every gradient stay as they are
+    p.partials = (float*)workspace;
+    if ((rc = p.noise.mode == NIC_NOISE_KERNEL ? launch_points<true>(p, n_fields, stream) : launch_points<false>(p, n_fields, stream)) != NIC_OK) return rc;
+    kernel_end_mark((hipStream_t)stream);
+    hipLaunchKernelGGL(hash_batch_reduce_kernel, dim3((unsigned)((rl.rec + 31) / 32), (unsigned)n_fields), dim3(256), 0, (hipStream_t)stream, p.partials, g,
+                       lf, *mlp_grads, loss, counts ? 0.f : field_loss_mul(loss_scale, n_points), (flags & NIC_HASH_FUSED_ADD_GRADS) ? 1 : 0,
+                       (flags & NIC_HASH_FUSED_ADD_LOSS) ? 1 : 0, counts, n_points, loss_scale);
     return (int)hipGetLastError();
 }
 

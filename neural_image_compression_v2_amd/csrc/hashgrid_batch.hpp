@@ -16,6 +16,16 @@ __device__ __forceinline__ WaveRange field_range(int64_t n_waves, int lb, int G)
     return WaveRange{g_begin + (lb >> 3), g_begin + chunk < n_groups ? g_begin + chunk : n_groups, G >> 3};
 }
 
+// what a field's summed squared error is multiplied by for its loss, loss_scale / (3 n), n = the field's OWN samples: the single-field entries'
+// expression, in double on either side.  The training kernels' dscale is twice this.  n > 0
+__host__ __device__ inline float field_loss_mul(float loss_scale, int64_t n) { return (float)((double)loss_scale / (3.0 * (double)n)); }
+// field b's count of points: counts null = every field has n, else counts[b] clamped to [0, n]
+__device__ __forceinline__ int64_t field_count(const int32_t* counts, int b, int64_t n) {
+    if (counts == nullptr) return n;
+    const int64_t c = counts[b];
+    return c < 0 ? 0 : (c > n ? n : c);
+}
+
 // ---- forward only, from any table source, on the lattice or at points --------------------------------------------------------
 struct SParams {
     nic_hash_desc d;          // one field's; at points extent[a] = S_a, num_crops = 1

@@ -77,13 +77,17 @@ three launches whatever B is (the kernel, the reduction per field, one ``FusedAd
 ``hash_batch_forward`` / ``hash_batch_forward_backward`` are the functional forms; ``extract(b)`` / ``insert(b, field)`` move single fields out and in.
 The decoder side (nic_hash_batch_forward_source): ``HashGridFieldBatch.load_compressed(paths)`` stacks the uint8 or bit-packed tables of
 B stored files, ``decode`` / ``query`` / ``resample`` read whatever table a batch holds in one launch per tile for all fields;
-``hash_batch_forward_source`` is the functional form (fp32, uint8 or packed tables; crops or points)."""
+``hash_batch_forward_source`` is the functional form (fp32, uint8 or packed tables; crops or points).
+Training at points (include/nicv2_hip_ext.h, nic_hash_batch_forward_backward_points): ``HashGridFieldBatch.train_points`` /
+``fit_points`` train every field at its own (point, colour) samples with a count per field, ``hash_batch_forward_backward_points`` and
+``hash_batch_point_order`` are the functional forms."""
 from __future__ import annotations
 
 import ctypes
 import functools
 import itertools
 import math
+import numbers
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple, Union
 
@@ -856,6 +860,147 @@ def hash_point_order(geo: HashGeometry, points: torch.Tensor) -> torch.Tensor:
     if keys.shape[0] >= 2 ** 31:
         raise ValueError("an order indexes fewer than 2^31 points")
     return torch.sort(keys, stable=True).indices.to(torch.int32)
+
+
+# ---- B fields trained at their own points per launch (include/nicv2_hip_ext.h, nic_hash_batch_forward_backward_points) -------------
+def _check_batch_points(geo: HashGeometry, points, n_fields: int) -> int:
+    """the shape and dtype of a batch's points - fp32 [N, dim] shared by all fields or [B, N, dim], each field its own; returns N.  Host only."""
+    if not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or points.dim() not in (2, 3) or points.shape[-1] != geo.dim or (
+            points.dim() == 3 and points.shape[0] != n_fields):
+        raise ValueError(f"points must be fp32 [N, {geo.dim}] (shared) or [{n_fields}, N, {geo.dim}] (per field), got "
+                         f"{(points.dtype, tuple(points.shape)) if isinstance(points, torch.Tensor) else type(points).__name__}")
+    return int(points.shape[-2])
+
+
+def _check_batch_counts(counts, n_fields: int, n: int):
+    """``counts``: None, a sequence of B ints or an integer tensor [B] - a host one is validated to 0 <= n_b <= n and becomes an int32 CPU
+    tensor, a device one must be int32 and contiguous and is taken as is (the kernels clamp it; validating it would sync)"""
+    if counts is None:
+        return None
+    if isinstance(counts, torch.Tensor) and counts.is_cuda:
+        if counts.dtype != torch.int32 or tuple(counts.shape) != (n_fields,) or not counts.is_contiguous():
+            raise ValueError(f"counts on the device must be a contiguous int32 tensor [{n_fields}], got {counts.dtype} {tuple(counts.shape)}")
+        return counts
+    if isinstance(counts, torch.Tensor):
+        if counts.dtype not in (torch.int32, torch.int64) or tuple(counts.shape) != (n_fields,):
+            raise ValueError(f"counts must be an integer tensor [{n_fields}], got {counts.dtype} {tuple(counts.shape)}")
+        values = [int(v) for v in counts.tolist()]
+    else:
+        values = list(counts)
+        if len(values) != n_fields or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in values):
+            raise ValueError(f"counts must be {n_fields} ints, one per field, got {counts!r}")
+        values = [int(v) for v in values]
+    if any(not 0 <= v <= n for v in values):
+        raise ValueError(f"counts must lie in 0 .. {n} (the points a field's row holds), got {values}")
+    return torch.tensor(values, dtype=torch.int32)
+
+
+def _check_batch_order(order, n_fields: int, n: int):
+    """an int32 [B, N] tensor of field-local row indices (``hash_batch_point_order``); its values are the kernel's business (it clamps them)"""
+    if order is None:
+        return None
+    if not isinstance(order, torch.Tensor) or order.dtype != torch.int32 or tuple(order.shape) != (n_fields, n):
+        raise ValueError(f"order must be an int32 tensor [{n_fields}, {n}] of field-local rows (hash_batch_point_order), got "
+                         f"{(order.dtype, tuple(order.shape)) if isinstance(order, torch.Tensor) else type(order).__name__}")
+    return order
+
+
+def _stack_points(points: torch.Tensor, n_fields: int) -> torch.Tensor:
+    pts = points.detach()
+    return (pts if pts.dim() == 3 else pts.unsqueeze(0).expand(n_fields, -1, -1)).contiguous()
+
+
+@fused._on_tensor_device
+def hash_batch_point_order(geo: HashGeometry, points: torch.Tensor, counts=None) -> torch.Tensor:
+    """int32 [B, N]: row b is ``hash_point_order`` of field b's first ``counts[b]`` points (all N without ``counts``), field-local; what a row
+    holds past its count is the remaining indices in row order (the kernels never read them).  ONE ``hash_point_keys`` launch over the
+    flattened points - the keys depend on the geometry only -, the keys at or past a field's count set to the largest int64, one stable
+    ``torch.sort`` along dim 1."""
+    if not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or points.dim() != 3 or points.shape[2] != geo.dim or points.shape[0] < 1:
+        raise ValueError(f"points must be fp32 [B, N, {geo.dim}], got {(points.dtype, tuple(points.shape)) if isinstance(points, torch.Tensor) else type(points).__name__}")
+    b, n = int(points.shape[0]), int(points.shape[1])
+    counts = _check_batch_counts(counts, b, n)
+    if n >= 2 ** 31:
+        raise ValueError("an order indexes fewer than 2^31 points")
+    keys = hash_point_keys(geo, points.detach().reshape(b * n, geo.dim)).reshape(b, n)
+    if counts is not None:
+        past = torch.arange(n, device=keys.device).unsqueeze(0) >= counts.to(keys.device).unsqueeze(1)
+        keys = keys.masked_fill(past, torch.iinfo(torch.int64).max)
+    return torch.sort(keys, dim=1, stable=True).indices.to(torch.int32)
+
+
+@fused._on_tensor_device
+def hash_batch_forward_backward_points(geo: HashGeometry, tables: torch.Tensor, points: torch.Tensor, params: Sequence[torch.Tensor],
+                                       target: torch.Tensor, mlp_grads: Sequence[torch.Tensor], table_grads: Optional[torch.Tensor] = None,
+                                       order: Optional[torch.Tensor] = None, counts=None, loss: Optional[torch.Tensor] = None,
+                                       loss_scale: float = 1.0, want_y=False, quant=None, add_grads: bool = False, add_loss: bool = False,
+                                       groups_per_field: int = 0):
+    """``hash_fused_forward_backward_points`` of B stacked fields, each at ITS OWN points, in TWO launches whatever B is
+    (nic_hash_batch_forward_backward_points).  ``points`` fp32 [B, N, dim] (or [N, dim], shared), ``target`` [B, N, 3].
+    ``counts``: None, B ints or an int32 [B] tensor - field b trains on its first ``counts[b]`` rows only (a host value is validated to
+    0 .. N, a device tensor is clamped by the kernel), and loss[b] = mean((y_b - target_b)^2) * loss_scale over THOSE rows; a field with no
+    point has loss 0, decoder gradients 0 and an untouched table gradient.  ``order``: None or int32 [B, N] of field-local rows
+    (``hash_batch_point_order``) - wave w of field b takes rows order[b, 64 w ..]; targets, outputs and noise keys stay at the caller's rows.
+    ``want_y``: True, or a contiguous fp32 [B, N, 3] device tensor to write into; rows at or past a field's count are not written (zero in
+    the tensor ``want_y=True`` allocates).  Everything else as ``hash_batch_forward_backward``.  Returns (loss [B], y or None)."""
+    t = tables.detach() if isinstance(tables, torch.Tensor) else tables
+    _check_batch_tables(geo, t)
+    n_fields = t.shape[0]
+    params = _check_batch_decoder(geo, [q.detach() if isinstance(q, torch.Tensor) else q for q in params], n_fields)
+    mlp_grads = _check_batch_decoder(geo, mlp_grads, n_fields, "mlp_grads")
+    if table_grads is not None:
+        _check_batch_tables(geo, table_grads, "table_grads")
+        if table_grads.shape[0] != n_fields:
+            raise ValueError(f"table_grads holds {table_grads.shape[0]} fields, tables {n_fields}")
+    n = _check_batch_points(geo, points, n_fields)
+    if n < 1:
+        raise ValueError("no points")
+    if n >= 2 ** 31:
+        raise ValueError("a field's row holds fewer than 2^31 points")
+    if not isinstance(target, torch.Tensor) or tuple(target.shape) != (n_fields, n, 3):
+        raise ValueError(f"target must be [{n_fields}, {n}, 3], got {tuple(target.shape) if isinstance(target, torch.Tensor) else type(target).__name__}")
+    counts = _check_batch_counts(counts, n_fields, n)
+    order = _check_batch_order(order, n_fields, n)
+    y_out = want_y if isinstance(want_y, torch.Tensor) else None
+    if y_out is not None and not (y_out.dtype == torch.float32 and y_out.is_contiguous() and tuple(y_out.shape) == (n_fields, n, 3)):
+        raise ValueError(f"want_y as a tensor must be contiguous fp32 [{n_fields}, {n}, 3]")
+    if loss is not None and not (isinstance(loss, torch.Tensor) and loss.dtype == torch.float32 and loss.is_contiguous() and tuple(loss.shape) == (n_fields,)):
+        raise ValueError(f"loss must be a contiguous fp32 device tensor [{n_fields}]")
+    _point_desc(geo)
+    # ---- the device, after every refusal the host can make
+    _require_stacked([t], "tables")
+    _require_stacked(params, "params")
+    _require_stacked(mlp_grads, "mlp_grads")
+    if table_grads is not None:
+        _require_stacked([table_grads], "table_grads")
+    _require_on_device(points, "points")
+    target = _lib.require_cuda_f32(target, "target")
+    for x, name in ((order, "order"), (y_out, "want_y"), (loss, "loss")):
+        if x is not None:
+            _require_on_device(x, name)
+    pts = _stack_points(points, n_fields)
+    counts = None if counts is None else counts.to(t.device, non_blocking=True)
+    loss = torch.empty(n_fields, dtype=torch.float32, device=t.device) if loss is None else loss
+    if y_out is not None:
+        y = y_out
+    elif want_y:
+        y = (torch.empty if counts is None else torch.zeros)(n_fields, n, 3, dtype=torch.float32, device=t.device)
+    else:
+        y = None
+    lib = _lib.load()
+    d, m, gs = _point_desc(geo), fused._mlp_struct(params), fused._grads_struct(list(mlp_grads))
+    q = _quant_struct(quant)
+    nbytes = int(lib.nic_hash_batch_points_workspace_bytes(ctypes.byref(d), n_fields, int(groups_per_field), n, ctypes.byref(m)))
+    if nbytes == 0:          # refused: the entry point below names the reason with its code, and launches nothing on a 16-byte workspace
+        nbytes = 16
+    ws = _lib.workspace(t.device, nbytes)
+    flags = (_lib.NIC_HASH_FUSED_ADD_GRADS if add_grads else 0) | (_lib.NIC_HASH_FUSED_ADD_LOSS if add_loss else 0)
+    _lib.check(lib.nic_hash_batch_forward_backward_points(ctypes.byref(d), n_fields, int(groups_per_field), None if q is None else ctypes.byref(q),
+                                                          _lib.ptr(t), _lib.ptr(pts), n, _lib.ptr(counts), _lib.ptr(order), ctypes.byref(m),
+                                                          _lib.ptr(target), float(loss_scale), _lib.ptr(table_grads), ctypes.byref(gs), _lib.ptr(loss),
+                                                          _lib.ptr(y), flags, _lib.ptr(ws), nbytes, _lib.stream_ptr(t.device)),
+               "nic_hash_batch_forward_backward_points")
+    return loss, y
 
 
 def _encode_points_backward(geo, points, dx, table_grad, order, lod):
@@ -2198,8 +2343,13 @@ class HashGridFieldBatch:
     The 16-bit matrix pipe: ``decode`` / ``query`` / ``resample(precision="split" | "bf16")`` run every tile or point set through
     ``hash_batch_forward_p16`` from the same table - ``HashGridField``'s ``precision=`` per field, bit for bit, in one launch.  Forward only.
 
-    Not built: batched ``train_points``, a level of detail, 16-bit training, a bit depth per level (a ``/2`` file is read and
-    refused), fields of differing geometry in one batch, a container format that holds several fields in one file."""
+    Training at points: ``train_points`` / ``fit_points`` train every field at ITS OWN samples - masked images, importance
+    samples, point clouds - in the same three launches (nic_hash_batch_forward_backward_points), ``counts`` giving each field's own number of
+    points: rows past it are padding that is never read and never trains.  Field b's arithmetic is ``HashGridField.train_points(fused=True)``'s.
+
+    Not built: at points, passes in chunks with ragged counts, a level of detail, ``dpoints`` and the 16-bit modes; 16-bit
+    training; a bit depth per level (a ``/2`` file is read and refused), fields of differing geometry in one batch, a container format that
+    holds several fields in one file."""
 
     def __init__(self, n_fields: int, field_size: Union[int, Sequence[int]], levels: int = 16, features: int = 2, log2_table: int = 19,
                  base_resolution: float = 16, finest_resolution: Optional[float] = None, device=None, seed: Optional[int] = None,
@@ -2386,6 +2536,87 @@ class HashGridFieldBatch:
         if step:
             self.apply_step()
         return loss
+
+    def _check_train_points(self, points, target, counts, order):
+        """every host refusal of ``train_points`` / ``fit_points``, nothing set: (N, the counts as ``_check_batch_counts`` leaves them, the order
+        - None, "cell" or the checked tensor)"""
+        n = _check_batch_points(self.geo, points, self.n_fields)
+        if n < 1:
+            raise ValueError("no points")
+        if not isinstance(target, torch.Tensor) or tuple(target.shape) != (self.n_fields, n, 3):
+            raise ValueError(f"target must be [{self.n_fields}, {n}, 3], got {tuple(target.shape) if isinstance(target, torch.Tensor) else type(target).__name__}")
+        counts = _check_batch_counts(counts, self.n_fields, n)
+        if isinstance(order, str):
+            if order != "cell":
+                raise ValueError(f"order {order!r}: None, 'cell' or an int32 [{self.n_fields}, {n}] tensor")
+        else:
+            order = _check_batch_order(order, self.n_fields, n)
+        _point_desc(self.geo)
+        return n, counts, order
+
+    @torch.no_grad()
+    def train_points(self, points: torch.Tensor, target: torch.Tensor, counts=None, accumulate: bool = False, scale: float = 1.0, step: bool = True,
+                     noise: Optional[bool] = None, order=None) -> torch.Tensor:
+        """``HashGridField.train_points(fused=True)`` for every field at once, each at its own samples; returns the [B] losses.
+        ``points`` as ``query`` takes them - [N, dim] shared or [B, N, dim] per field, fp32, sample units -, ``target`` [B, N, 3].  ``counts``:
+        None, B ints or an int32 [B] tensor - real point sets are ragged: field b trains on its first ``counts[b]`` rows and its loss is the
+        mean over those; the rest of its row is padding that is never read.  ``order``: None, "cell" (``hash_batch_point_order`` of these
+        points, computed for this call) or a precomputed int32 [B, N] tensor of it.  ``accumulate`` / ``scale`` / ``step`` / ``noise`` and
+        the bookkeeping are ``train_step``'s: the noise keys (seed, optimiser step, samples of this pass before this chunk + the row inside
+        the field) are the same for every field, and a chunk advances the pass by the padded width N.  After ``freeze()`` only the decoders
+        train."""
+        self._refuse_decode_only("train_points")
+        frozen = self.frozen
+        n, counts, order = self._check_train_points(points, target, counts, order)
+        if noise is None:
+            noise = self.num_bits is not None and not frozen
+        if noise and self.num_bits is None:
+            raise ValueError("noise needs num_bits: its amplitude is one quantisation step")
+        _require_on_device(points, "points")
+        pts = _stack_points(points, self.n_fields)
+        if isinstance(order, str):
+            order = hash_batch_point_order(self.geo, pts, counts)
+        grad = None if frozen else self.tables.grad
+        if not accumulate:
+            if not frozen and not self._grad_clean:
+                grad.zero_()
+            self._pass_samples = 0
+        quant = (self.num_bits, self.noise_seed, self.steps, self._pass_samples) if noise else None
+        loss, _ = hash_batch_forward_backward_points(self.geo, self.tables, pts, self.params, target, self._gm, table_grads=grad, order=order, counts=counts,
+                                                     loss_scale=float(scale), quant=quant, add_grads=accumulate, groups_per_field=self._point_groups(n))
+        self._pass_samples += n
+        if not frozen:
+            self._grad_clean = False
+        if step:
+            self.apply_step()
+        return loss
+
+    def fit_points(self, points: torch.Tensor, target: torch.Tensor, epochs: int, counts=None, order="cell", freeze_at: float = 0.95) -> List[List[float]]:
+        """``HashGridField.fit_points(fused=True)`` for every field on its own fixed sample set: ``epochs`` passes over ``points`` / ``target`` /
+        ``counts`` (``train_points``'), one call and one optimiser step per pass.  ``order``: "cell" (default), None or an int32 [B, N]
+        tensor; it is computed once and every field's set is laid out in it once (its real rows first, in order, then its padding), so the
+        passes walk contiguous memory without an index.  With ``num_bits``: noise while the epoch is below ``freeze_at`` * epochs, then
+        ``freeze()`` - ``fit``'s schedule.  Returns the per-pass losses, [epochs][B]."""
+        self._refuse_decode_only("fit_points")
+        n, counts, order = self._check_train_points(points, target, counts, order)
+        _require_on_device(points, "points")
+        target = _lib.require_cuda_f32(target, "target")
+        pts = _stack_points(points, self.n_fields)
+        if order is not None:
+            idx = (hash_batch_point_order(self.geo, pts, counts) if isinstance(order, str) else order.to(pts.device)).to(torch.int64)
+            top = torch.full((self.n_fields, 1), n, dtype=torch.int64, device=pts.device) if counts is None else counts.to(pts.device, torch.int64).clamp(0, n).unsqueeze(1)
+            real = torch.arange(n, device=pts.device).unsqueeze(0) < top          # the kernel's rule: the first n_b entries name rows below n_b
+            idx = torch.minimum(idx, torch.where(real, top - 1, torch.full_like(top, n - 1))).clamp_(min=0)
+            pts = torch.gather(pts, 1, idx.unsqueeze(2).expand(-1, -1, self.geo.dim)).contiguous()
+            target = torch.gather(target, 1, idx.unsqueeze(2).expand(-1, -1, 3)).contiguous()
+        counts = None if counts is None else counts.to(pts.device)          # once: a device tensor is taken as it is by every pass
+        freeze_epoch = math.ceil(freeze_at * epochs) if self.num_bits is not None else None
+        hist = []
+        for ep in range(epochs):
+            if freeze_epoch is not None and ep >= freeze_epoch and not self.frozen:
+                self.freeze()
+            hist.append(self.train_points(pts, target, counts=counts))
+        return [[float(v) for v in h] for h in torch.stack(hist).tolist()] if hist else []
 
     @torch.no_grad()
     def apply_step(self) -> None:
