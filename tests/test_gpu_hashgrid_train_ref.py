@@ -21,6 +21,7 @@ import pytest
 import torch
 
 from oracle import hashgrid_train_ref as T
+from oracle.hashgrid_fit_ref import step_bound
 from tests import test_hashgrid_train_ref_cpu as C
 from tests.test_hashgrid_train_ref_cpu import LOSS_SCALE, NAMES, SHAPES, TOL_G, TOL_Y, shape_id
 
@@ -303,15 +304,9 @@ def _ulp32(x):
 
 
 def _step_bound(gmax, m_max, lr, betas, eps, step):
-    """the Lipschitz constant of Adam's update in the gradient, times TOL_G gmax (see ``StepCase``)"""
-    b1, b2 = betas
-    bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
-    gp = gmax * (1 + TOL_G)
-    s0 = math.sqrt(b2) * 0.1 * gmax                      # sqrt(v') >= sqrt(beta2 v) >= sqrt(beta2) 0.1 gmax, whatever g is
-    d0 = s0 / math.sqrt(bc2) + eps
-    m1 = b1 * m_max + (1 - b1) * gp                      # |m'| <= this
-    lip = lr / bc1 * ((1 - b1) / d0 + m1 * (1 - b2) * gp / (s0 * math.sqrt(bc2) * d0 * d0))
-    return lip * TOL_G * gmax
+    """the Lipschitz constant of Adam's update in the gradient, times TOL_G gmax (see ``StepCase``): ``step_bound`` of
+    oracle/hashgrid_fit_ref.py with this file's floor, sqrt(v') >= sqrt(beta2 v) >= sqrt(beta2) 0.1 gmax whatever g is"""
+    return step_bound(gmax, m_max, lr, betas, eps, step, s0=math.sqrt(betas[1]) * 0.1 * gmax)
 
 
 class Moments:
