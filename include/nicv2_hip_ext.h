@@ -65,6 +65,42 @@ int nic_hash_batch_forward_backward_points(const nic_hash_desc *desc, int n_fiel
                                            const nic_mlp_grads *mlp_grads, float *loss, float *y, int flags, void *workspace,
                                            size_t workspace_bytes, void *stream);
 
+/* ---- B hash-grid fields per launch with a level of detail PER POINT, decoded and trained (hashgrid.py, hash_batch_forward_points_lod,
+ *      hash_batch_forward_backward_points_lod, HashGridFieldBatch.query / resample / train_points / fit_points(lod=), decode_mip, fit_mips;
+ *      csrc/hashgrid_batch.hip, hash_batch_decode_lod_kernel and hash_batch_points_lod_kernel).  The nic_hash_lod section of
+ *      nicv2_hip.h holds for every field of the launch, word for word: lambda of point n of field b = (lod ? lod[b, n] : 0) + lod_uniform in
+ *      fp32, NaN becomes 0, the sum clamped to [0, 32]; a_l = min(max((fade[l] - lambda) + 1.0f, 0), 1); column l F + f of the row is
+ *      fl(a_l r); a level of weight 0 is not read, gets no noise and no atomic, and a level no lane of a wave weighs above 0 costs that wave
+ *      no gather; the backward is straight-through, fl(a_l dx) goes where the entry without _lod sends dx.  One nic_hash_lod (fade and
+ *      lod_uniform) serves all fields.  lod is NULL or fp32 [B, n_points] on the device (the host never reads it), field b's slice its
+ *      n_points values; it is read at the field-local ROW, as the point is: with an `order`, at order[b, pos] clamped to [0, n_b - 1].
+ *      Everything else is the sibling's, argument for argument:
+ *      nic_hash_batch_forward_points_lod = nic_hash_batch_forward_source with points (no origins: a level of detail is served at points only) -
+ *      the stacked source of any of the three kinds, the stacked decoder, points [B, n_points, dim], y [B, n_points, 3], groups_per_field on
+ *      ceil(n_points / 64) wave items; one launch, no atomics, the same call gives the same bits; y of field b is
+ *      nic_hash_fused_forward_points_lod's on field b's tensors bit for bit.
+ *      nic_hash_batch_forward_backward_points_lod = nic_hash_batch_forward_backward_points - counts, order, records, the fixed-order
+ *      reduction, flags, noise keys (sample_base + the row inside the field), loss[b] over ITS n_b points, rows of y at or past n_b not
+ *      written, nic_mark_kernel_end honoured; the workspace query is nic_hash_batch_points_workspace_bytes.
+ *      Host checks, all before any GPU work, in the sibling's order and with its codes; on top of them lodp == NULL is NIC_E_NULL (with the
+ *      other pointers), and right after the pointers a fade[l] (l < levels) that is not finite or is negative, a lod_uniform that is not
+ *      finite, or reserved != 0 is NIC_E_ARG.  In full, forward: null desc / mlp (NIC_E_NULL); the fused set (nic_hash_fused_supported's
+ *      code); the descriptor of a point source (num_crops == 1, NIC_E_SHAPE, and 256 S_max < 2^30, NIC_E_ARG); n_fields in 1 .. 65535
+ *      (NIC_E_ARG); groups_per_field (NIC_E_ARG; n_points <= 0 counts as one wave item); null lodp, src, src->data, points, decoder layer or
+ *      y (NIC_E_NULL); the nic_hash_lod (NIC_E_ARG); the source (NIC_E_ARG: kind, num_bits, alignment); n_points < 0 (NIC_E_ARG); n_points ==
+ *      0 is NIC_OK without a launch.  Training: null desc / mlp; the fused set, then 256 S_max < 2^30; n_fields; groups_per_field; null
+ *      lodp, tables, points, decoder layer, target, mlp_grads, loss or workspace (lod, counts, order, table_grads and y may be null); the
+ *      nic_hash_lod; flags; quant; the workspace (NIC_E_WORKSPACE); num_crops == 1 (NIC_E_SHAPE); n_points < 0 or >= 2^31 (NIC_E_ARG);
+ *      n_points == 0 is NIC_OK without a launch, nothing written. */
+int nic_hash_batch_forward_points_lod(const nic_hash_desc *desc, int n_fields, int groups_per_field, const nic_hash_lod *lodp,
+                                      const nic_hash_source *src, const float *points, const float *lod, int64_t n_points, const nic_mlp *mlp,
+                                      float *y, void *stream);
+int nic_hash_batch_forward_backward_points_lod(const nic_hash_desc *desc, int n_fields, int groups_per_field, const nic_hash_lod *lodp,
+                                               const nic_hash_quant *quant, const float *tables, const float *points, const float *lod,
+                                               int64_t n_points, const int32_t *counts, const int32_t *order, const nic_mlp *mlp,
+                                               const float *target, float loss_scale, float *table_grads, const nic_mlp_grads *mlp_grads,
+                                               float *loss, float *y, int flags, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

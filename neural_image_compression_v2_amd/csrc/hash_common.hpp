@@ -900,7 +900,8 @@ inline int check_lod(const nic_hash_desc* d, const nic_hash_lod* lp) {
     if (!std::isfinite(lp->lod_uniform) || lp->reserved != 0) return NIC_E_ARG;
     return NIC_OK;
 }
-inline void set_lod(LodParams& p, const nic_hash_lod* lp, const float* lod) {
+template <class Params>      // LodParams, and the batch unit's parameter structs with the same three fields
+inline void set_lod(Params& p, const nic_hash_lod* lp, const float* lod) {
     for (int l = 0; l < NIC_HASH_MAX_LEVELS; ++l) p.fade[l] = l < p.d.levels ? lp->fade[l] : 0.f;
     p.lod_uniform = lp->lod_uniform;
     p.lod = lod;

@@ -21,7 +21,10 @@
 //   sample source of hash_points_fused_train_kernel (hash_points_train.hip), per field: points / target / y [B, n, ..], order [B, n] of field-LOCAL
 //   rows, and a count n_b <= n per field (counts [B], null = n) - real point sets are ragged.  Field b walks ceil(n_b / 64) wave items, divides
 //   its loss by ITS n_b, and leaves rows at or past n_b alone; the reduction takes the same counts.
-// Every device helper is hash_common.hpp's; this unit holds the four kernels, their parameters and the host side.  What the 16-bit batched
+//   with a level of detail per point (nic_hash_batch_forward_points_lod, nic_hash_batch_forward_backward_points_lod):
+//   hash_batch_decode_lod_kernel and hash_batch_points_lod_kernel are the two kernels at points with hash_common.hpp's LOD level loop and
+//   scatter, lod [B, n] read at the field-local row; kernels of their own, so that the plain ones keep their code.
+// Every device helper is hash_common.hpp's; this unit holds the six kernels, their parameters and the host side.  What the 16-bit batched
 // kernel (hashgrid_fused16.hip) shares with them - field_range, SParams, StoredSrc, the rules on B and G - is hashgrid_batch.hpp's.
 #include "hash_common.hpp"
 #include "hashgrid_batch.hpp"
@@ -279,6 +282,130 @@ __global__ void __launch_bounds__(256) hash_batch_decode_kernel(const SParams p)
     }
 }
 
+// ---- with a level of detail per point (nic_hash_batch_forward_points_lod, nic_hash_batch_forward_backward_points_lod) -----------
+// The two kernels at points above with hash_common.hpp's LOD level loop and scatter: lambda of a lane = point_lambda(field b's [n] slice of lod or
+// null, lod_uniform, the lane's field-local ROW) - with an order the row order[b, pos] clamped to the field's count, as the point is read -, the
+// fade shared by every field of the launch.  Kernels of their own beside the plain ones, whose code they leave as it was.
+struct PLParams : PParams {
+    float fade[NIC_HASH_MAX_LEVELS];
+    float lod_uniform;
+    const float* lod;         // null, or [B, n]
+};
+struct SLParams : SParams {   // points only: origins is null
+    float fade[NIC_HASH_MAX_LEVELS];
+    float lod_uniform;
+    const float* lod;         // null, or [B, n]
+};
+// FieldSrc / StoredSrc with what the LOD level loop reads on top: the launch's fade
+struct LodFieldSrc : FieldSrc {
+    const float (&fade)[NIC_HASH_MAX_LEVELS];
+};
+struct LodStoredSrc : StoredSrc {
+    const float (&fade)[NIC_HASH_MAX_LEVELS];
+};
+
+template <int D, int F, int KT, bool NOISE>
+__global__ void __launch_bounds__(256) hash_batch_points_lod_kernel(const PLParams p) {
+    __shared__ TrainSmem sm;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 31, half = lane >> 5;
+    const int LF = p.d.levels * F;
+    const int b = (int)(blockIdx.x / (unsigned)p.groups), lb = (int)(blockIdx.x - (unsigned)b * (unsigned)p.groups);
+    const int64_t tab_off = (((int64_t)b * p.d.levels) << p.d.log2_table) * F, row_off = (int64_t)b * p.n * 3;
+    load_decoder(sm, p.w1 + (int64_t)b * kH * LF, p.b1 + b * kH, p.w2 + (int64_t)b * kH * kH, p.b2 + b * kH, p.w3 + b * 3 * kH, p.b3 + b * 3, LF, tid);
+    __syncthreads();
+    float* xs = sm.x[wave];
+    float* xrow = xs + lane * XS;
+    float* P = sm.p[wave];
+    float* Q = sm.q[wave];
+    const int64_t n_b = field_count(p.counts, b, p.n);          // workgroup-uniform
+    const float dscale = n_b > 0 ? 2.0f * field_loss_mul(p.loss_scale, n_b) : 0.f;
+    const float* points = p.points + (int64_t)b * p.n * D;
+    const float* lod_b = p.lod != nullptr ? p.lod + (int64_t)b * p.n : nullptr;
+    const int32_t* order = p.order != nullptr ? p.order + (int64_t)b * p.n : nullptr;
+    const LodFieldSrc src_b{{p.d, p.tables + tab_off, p.noise, p.sample_base}, p.fade};
+    float* grad = p.grads != nullptr ? p.grads + tab_off : nullptr;
+    const float* target = p.target + row_off;
+    float* y = p.y != nullptr ? p.y + row_off : nullptr;
+    const int ks1 = (LF + 1) >> 1;
+    const int64_t n_waves = (n_b + 63) >> 6;
+    const WaveRange wr = field_range(n_waves, lb, p.groups);
+    TrainAcc<KT> A;
+    A.clear();
+    for (int64_t g = wr.begin; g < wr.end; g += wr.step) {
+        const int64_t wv = 4 * g + wave;
+        if (wv >= n_waves) continue;                            // wave-uniform; nothing below synchronises the workgroup
+        const int64_t pos = (wv << 6) + lane;
+        const bool live_lane = pos < n_b;
+        const int64_t row = ordered_row(order, n_b, live_lane ? pos : n_b - 1);      // a lane past the end takes the field's last point; it stores and adds nothing
+        const float lam = point_lambda(lod_b, p.lod_uniform, row);                   // at the ROW, as the point
+        uint32_t t[3];
+        point_fixed<D>(p.d, points, row, t);
+        encode_point<D, F, NIC_HASH_SRC_F32, NOISE, false, true>(src_b, t, row, lam, xrow);
+        wave_sync();
+        const unsigned long long live_mask = __ballot(live_lane);
+#pragma unroll 1
+        for (int nt = 0; nt < 2; ++nt) {
+            const int src = 32 * nt + j;
+            const bool mine = half == 0 && ((live_mask >> src) & 1ull);
+            const int r = __shfl((int)row, src);                // row < n_b <= n < 2^31
+            decoder_train_half<KT>(sm, xs, P, Q, nt, j, half, ks1, mine, target + (int64_t)r * 3, y != nullptr ? y + (int64_t)r * 3 : nullptr, dscale,
+                                   grad != nullptr, A);
+        }
+        wave_sync();
+        if (grad != nullptr)
+            scatter_point<D, F, true>(p.d, t, grad, p.fade, lam, live_lane, lane, [&](int l, float (&gv)[F]) {
+#pragma unroll
+                for (int f = 0; f < F; ++f) gv[f] = xrow[l * F + f];
+            });
+        wave_sync();
+    }
+    write_record<KT>(sm, A, LF, p.partials + (int64_t)blockIdx.x * RecLayout(LF).rec, tid);      // record (b, lb); all zero without an item (n_b = 0 too)
+}
+
+template <int D, int F, int SRC>
+__global__ void __launch_bounds__(256) hash_batch_decode_lod_kernel(const SLParams p) {
+    __shared__ DecoderSmem sm;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 31, half = lane >> 5;
+    const int LF = p.d.levels * F;
+    const int b = (int)(blockIdx.x / (unsigned)p.groups), lb = (int)(blockIdx.x - (unsigned)b * (unsigned)p.groups);
+    load_decoder(sm, p.w1 + (int64_t)b * kH * LF, p.b1 + b * kH, p.w2 + (int64_t)b * kH * kH, p.b2 + b * kH, p.w3 + b * 3 * kH, p.b3 + b * 3, LF, tid);
+    __syncthreads();
+    float* xs = sm.x[wave];
+    float* xrow = xs + lane * XS;
+    const int64_t tab_off = (int64_t)b * p.stride;
+    const LodStoredSrc src_b{{p.d,
+                              SRC == NIC_HASH_SRC_F32 ? reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(p.table) + tab_off) : nullptr,
+                              SRC == NIC_HASH_SRC_U8 ? p.stored + tab_off : nullptr,
+                              SRC == NIC_HASH_SRC_BITS ? reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(p.packed) + tab_off) : nullptr,
+                              p.q_scale, p.q_bias, p.q_bits, p.q_tight},
+                             p.fade};
+    const float* points = p.points + (int64_t)b * p.n * D;
+    const float* lod_b = p.lod != nullptr ? p.lod + (int64_t)b * p.n : nullptr;
+    float* y = p.y + (int64_t)b * p.n_rows * 3;
+    const int ks1 = (LF + 1) >> 1;
+    const WaveRange wr = field_range(p.n_items, lb, p.groups);
+    for (int64_t g = wr.begin; g < wr.end; g += wr.step) {
+        const int64_t wv = 4 * g + wave;
+        if (wv >= p.n_items) continue;                          // wave-uniform; nothing below synchronises the workgroup
+        const int64_t n0 = wv << 6, n_raw = n0 + lane, row = n_raw < p.n ? n_raw : p.n - 1;
+        uint32_t t[3];
+        point_fixed<D>(p.d, points, row, t);                    // a lane past the end decodes the field's last point; its output is not stored
+        encode_point<D, F, SRC, false, false, true>(src_b, t, row, point_lambda(lod_b, p.lod_uniform, row), xrow);
+        wave_sync();
+#pragma unroll 1
+        for (int nt = 0; nt < 2; ++nt) {
+            const int64_t r = n0 + 32 * nt + j;
+            float yv[3];
+            decoder_forward_half(sm, xs, nt, j, half, ks1, yv);
+            if (half == 0 && r < p.n) {
+#pragma unroll
+                for (int o = 0; o < 3; ++o) y[r * 3 + o] = yv[o];
+            }
+        }
+        wave_sync();
+    }
+}
+
 // hash_fused_reduce_kernel's fixed-order sum, field blockIdx.y: a block = 32 outputs x 8 slices of the field's G records, the slices combined
 // through LDS in slice order.  `g` holds the BASES of the stacked gradients, `loss` is [B].  No optimiser tail.  `counts` null: field b's summed
 // error times `loss_mul`, the crop route's; else times field_loss_mul(loss_scale, n_b) of its own count (clamped to [0, n_points]; 0 at n_b = 0).
@@ -367,6 +494,25 @@ static int launch_points(const PParams& p, int n_fields, void* stream) {
 // G at points: on the wave items of ONE field's padded row; a count that launches nothing stands as one item (nic_hash_batch_forward_source's rule)
 static int point_groups(int64_t n_points, int n_fields, int groups_per_field) {
     return batch_groups_of(n_points > 0 ? (n_points + 63) >> 6 : 1, n_fields, groups_per_field);
+}
+
+// with a level of detail per point: the same grids, the _lod kernels
+template <int SRC>
+static int launch_source_lod(const SLParams& p, int n_fields, void* stream) {
+    const dim3 grid((unsigned)n_fields * (unsigned)p.groups);
+    return dispatch_dim_features(p.d, [&](auto dim, auto features) {
+        constexpr int D = decltype(dim)::value, F = decltype(features)::value;
+        hipLaunchKernelGGL((hash_batch_decode_lod_kernel<D, F, SRC>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    });
+}
+template <bool NOISE>
+static int launch_points_lod(const PLParams& p, int n_fields, void* stream) {
+    const dim3 grid((unsigned)n_fields * (unsigned)p.groups);
+    return dispatch_dim_features(p.d, [&](auto dim, auto features) {
+        constexpr int D = decltype(dim)::value, F = decltype(features)::value;
+        if (p.d.levels * F > 32) hipLaunchKernelGGL((hash_batch_points_lod_kernel<D, F, 2, NOISE>), grid, dim3(256), 0, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL((hash_batch_points_lod_kernel<D, F, 1, NOISE>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    });
 }
 
 }  // namespace hbatch
@@ -494,6 +640,70 @@ int nic_hash_batch_forward_backward_points(const nic_hash_desc* desc, int n_fiel
     if (n_points == 0) return NIC_OK;                                   // nothing to launch: loss and every gradient stay as they are
     p.partials = (float*)workspace;
     if ((rc = p.noise.mode == NIC_NOISE_KERNEL ? launch_points<true>(p, n_fields, stream) : launch_points<false>(p, n_fields, stream)) != NIC_OK) return rc;
+    kernel_end_mark((hipStream_t)stream);
+    hipLaunchKernelGGL(hash_batch_reduce_kernel, dim3((unsigned)((rl.rec + 31) / 32), (unsigned)n_fields), dim3(256), 0, (hipStream_t)stream, p.partials, g,
+                       lf, *mlp_grads, loss, counts ? 0.f : field_loss_mul(loss_scale, n_points), (flags & NIC_HASH_FUSED_ADD_GRADS) ? 1 : 0,
+                       (flags & NIC_HASH_FUSED_ADD_LOSS) ? 1 : 0, counts, n_points, loss_scale);
+    return (int)hipGetLastError();
+}
+
+// ---- with a level of detail per point: the siblings' checks in their order, lodp with the other pointers, check_lod right after them
+int nic_hash_batch_forward_points_lod(const nic_hash_desc* desc, int n_fields, int groups_per_field, const nic_hash_lod* lodp, const nic_hash_source* src,
+                                      const float* points, const float* lod, int64_t n_points, const nic_mlp* mlp, float* y, void* stream) {
+    if (!desc || !mlp) return NIC_E_NULL;
+    int rc = nic_hash_fused_supported(desc, kH, mlp->n_linear);          // the only copy of the fused set (hash_fused.hip)
+    if (rc) return rc;
+    if ((rc = check_point_desc(desc)) != NIC_OK) return rc;
+    if (n_fields < 1 || n_fields > kMaxFields) return NIC_E_ARG;
+    const int64_t n_items = n_points > 0 ? (n_points + 63) >> 6 : 1;     // a count that launches nothing (checked below) stands as one item here
+    const int g = batch_groups_of(n_items, n_fields, groups_per_field);
+    if (g < 0) return NIC_E_ARG;
+    if (!lodp || !src || !src->data || !points || !mlp3_ok(mlp) || !y) return NIC_E_NULL;
+    if ((rc = check_lod(desc, lodp)) != NIC_OK) return rc;
+    SLParams p{};
+    p.d = *desc; p.points = points; p.y = y; p.groups = g; p.n_items = n_items; p.n = n_points; p.n_rows = n_points;
+    set_lod(p, lodp, lod);
+    if ((rc = set_point_source(p, src)) != NIC_OK) return rc;
+    if (n_points < 0) return NIC_E_ARG;
+    if (n_points == 0) return NIC_OK;
+    p.stride = src->kind == NIC_HASH_SRC_F32 ? (((int64_t)desc->levels << desc->log2_table) * desc->features) * (int64_t)sizeof(float)
+             : src->kind == NIC_HASH_SRC_U8 ? nic_hash_stored_bytes(desc) : nic_hash_packed_bytes(desc, src->num_bits);
+    if (p.stride <= 0) return NIC_E_ARG;
+    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
+    return dispatch_source(src->kind, [&](auto kind) { return launch_source_lod<decltype(kind)::value>(p, n_fields, stream); });
+}
+
+int nic_hash_batch_forward_backward_points_lod(const nic_hash_desc* desc, int n_fields, int groups_per_field, const nic_hash_lod* lodp,
+                                               const nic_hash_quant* quant, const float* tables, const float* points, const float* lod, int64_t n_points,
+                                               const int32_t* counts, const int32_t* order, const nic_mlp* mlp, const float* target, float loss_scale,
+                                               float* table_grads, const nic_mlp_grads* mlp_grads, float* loss, float* y, int flags, void* workspace,
+                                               size_t workspace_bytes, void* stream) {
+    const KernelEndDrop end;
+    if (!desc || !mlp) return NIC_E_NULL;
+    int rc = check_batch_desc(desc, mlp->n_linear);
+    if (rc) return rc;
+    if (n_fields < 1 || n_fields > kMaxFields) return NIC_E_ARG;
+    const int g = point_groups(n_points, n_fields, groups_per_field);
+    if (g < 0) return NIC_E_ARG;
+    if (!lodp || !tables || !points || !mlp3_ok(mlp) || !target || !mlp_grads || !loss || !workspace) return NIC_E_NULL;
+    if ((rc = check_lod(desc, lodp)) != NIC_OK) return rc;
+    if (flags & ~(NIC_HASH_FUSED_ADD_GRADS | NIC_HASH_FUSED_ADD_LOSS)) return NIC_E_ARG;
+    PLParams p{};
+    p.d = *desc; p.tables = tables; p.points = points; p.counts = counts; p.order = order; p.target = target; p.y = y; p.grads = table_grads;
+    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
+    p.n = n_points; p.groups = g; p.loss_scale = loss_scale;
+    set_lod(p, lodp, lod);
+    p.noise.mode = NIC_NOISE_NONE;
+    if ((rc = set_noise(quant, true, p.noise, p.sample_base)) != NIC_OK) return rc;
+    const int lf = desc->levels * desc->features;
+    const RecLayout rl(lf);
+    if (workspace_bytes < (size_t)n_fields * g * rl.rec * sizeof(float)) return NIC_E_WORKSPACE;
+    if ((rc = check_point_desc(desc)) != NIC_OK) return rc;
+    if (n_points < 0 || n_points >= (int64_t(1) << 31)) return NIC_E_ARG;
+    if (n_points == 0) return NIC_OK;                                   // nothing to launch: loss and every gradient stay as they are
+    p.partials = (float*)workspace;
+    if ((rc = p.noise.mode == NIC_NOISE_KERNEL ? launch_points_lod<true>(p, n_fields, stream) : launch_points_lod<false>(p, n_fields, stream)) != NIC_OK)
+        return rc;
     kernel_end_mark((hipStream_t)stream);
     hipLaunchKernelGGL(hash_batch_reduce_kernel, dim3((unsigned)((rl.rec + 31) / 32), (unsigned)n_fields), dim3(256), 0, (hipStream_t)stream, p.partials, g,
                        lf, *mlp_grads, loss, counts ? 0.f : field_loss_mul(loss_scale, n_points), (flags & NIC_HASH_FUSED_ADD_GRADS) ? 1 : 0,

@@ -705,8 +705,31 @@ def _require_on_device(t: torch.Tensor, name: str) -> None:
         raise ValueError(f"{name} must be contiguous: the kernel reads the fields at the strides of the geometry")
 
 
-def _batch_forward_source(geo, data, params, kind, num_bits, coord, extent, points, groups_per_field, out, precision):
-    """``hash_batch_forward_source`` (``precision`` None) and ``hash_batch_forward_p16`` ("split" / "bf16"): one set of refusals, one launch"""
+def _check_batch_lod(lod, n_fields: int, n: int):
+    """None, or the level of detail per point of a batch: an fp32 tensor [N] shared by all fields or [B, N], each field its own; the values
+    are the kernel's business (it clamps).  Host only: the device is asked after every shape."""
+    if lod is None:
+        return None
+    if not isinstance(lod, torch.Tensor) or lod.dtype != torch.float32 or tuple(lod.shape) not in ((n,), (n_fields, n)):
+        raise ValueError(f"lod must be fp32 [{n}] (shared) or [{n_fields}, {n}] (per field), one value per point, got "
+                         f"{(lod.dtype, tuple(lod.shape)) if isinstance(lod, torch.Tensor) else type(lod).__name__}")
+    return lod.detach()
+
+
+def _stack_lod(lod: Optional[torch.Tensor], n_fields: int, device) -> Optional[torch.Tensor]:
+    """the checked ``lod`` as the contiguous [B, N] the entry reads, on the device of the points"""
+    if lod is None:
+        return None
+    if not lod.is_cuda:
+        raise RuntimeError(f"lod lives on {lod.device}: this package only runs on a HIP device (no CPU path)")
+    if lod.device != device:
+        raise ValueError(f"lod lives on {lod.device}, the points on {device}")
+    return (lod if lod.dim() == 2 else lod.unsqueeze(0).expand(n_fields, -1)).contiguous()
+
+
+def _batch_forward_source(geo, data, params, kind, num_bits, coord, extent, points, groups_per_field, out, precision, lod=None):
+    """``hash_batch_forward_source`` (``precision`` None) and ``hash_batch_forward_p16`` ("split" / "bf16"): one set of refusals, one launch;
+    with ``lod`` = (lod, lod_uniform, fade) ``hash_batch_forward_points_lod`` (points, and no ``precision``)"""
     prec = None if precision is None else _check_precision(precision)
     n_fields = _check_batch_source(geo, data, kind, num_bits)
     data = data.detach()
@@ -726,6 +749,8 @@ def _batch_forward_source(geo, data, params, kind, num_bits, coord, extent, poin
                              f"{(points.dtype, tuple(points.shape)) if isinstance(points, torch.Tensor) else type(points).__name__}")
         n = points.shape[-2]
         org = None
+        lp = None if lod is None else _lod_struct(geo, lod[2], lod[1])
+        lod_t = None if lod is None else _check_batch_lod(lod[0], n_fields, n)
     else:
         if extent is None:
             raise ValueError("coord needs the extent of its crops")
@@ -750,6 +775,13 @@ def _batch_forward_source(geo, data, params, kind, num_bits, coord, extent, poin
         pts = points.detach()
         pts = (pts if pts.dim() == 3 else pts.unsqueeze(0).expand(n_fields, -1, -1)).contiguous()
         d = _point_desc(geo)
+        if lod is not None:
+            lod_t, m = _stack_lod(lod_t, n_fields, pts.device), fused._mlp_struct(params)
+            src = _lib.NicHashSource(POINT_SOURCES[kind], 0 if kind == "f32" else int(num_bits), data.data_ptr())
+            _lib.check(_lib.load().nic_hash_batch_forward_points_lod(ctypes.byref(d), n_fields, int(groups_per_field), ctypes.byref(lp), ctypes.byref(src),
+                                                                     _lib.ptr(pts), _lib.ptr(lod_t), n, ctypes.byref(m), _lib.ptr(y),
+                                                                     _lib.stream_ptr(data.device)), "nic_hash_batch_forward_points_lod")
+            return y
     else:
         pts = None
         org = org.to(data.device, non_blocking=True)
@@ -785,6 +817,19 @@ def hash_batch_forward_p16(geo: HashGeometry, data: torch.Tensor, params: Sequen
     follows ``hash_batch_groups_p16``: two workgroups share a CU at levels * features <= 32."""
     _check_precision(precision)
     return _batch_forward_source(geo, data, params, kind, num_bits, coord, extent, points, groups_per_field, out, precision)
+
+
+@fused._on_tensor_device
+def hash_batch_forward_points_lod(geo: HashGeometry, data: torch.Tensor, points: torch.Tensor, params: Sequence[torch.Tensor],
+                                  lod: Optional[torch.Tensor] = None, lod_uniform: float = 0.0, fade=None, kind: str = "f32",
+                                  num_bits: Optional[int] = None, groups_per_field: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[B, N, 3]: ``hash_batch_forward_source(points=)`` with a level of detail per point (nic_hash_batch_forward_points_lod) -
+    ``hash_fused_forward_points_lod`` of every field in ONE launch, bit for bit.  ``lod``: None, or fp32 [N] shared by all fields or [B, N],
+    each field its own; ``lod_uniform`` and ``fade`` (None: ``hash_lod_fade(geo)``) serve every field.  Every other argument and refusal is
+    ``hash_batch_forward_source``'s."""
+    if points is None:
+        raise ValueError("points must be given: a level of detail is served at points only")
+    return _batch_forward_source(geo, data, params, kind, num_bits, None, None, points, groups_per_field, out, None, (lod, lod_uniform, fade))
 
 
 def _lod_args(geo: HashGeometry, lod, n: int, device):
@@ -929,20 +974,9 @@ def hash_batch_point_order(geo: HashGeometry, points: torch.Tensor, counts=None)
     return torch.sort(keys, dim=1, stable=True).indices.to(torch.int32)
 
 
-@fused._on_tensor_device
-def hash_batch_forward_backward_points(geo: HashGeometry, tables: torch.Tensor, points: torch.Tensor, params: Sequence[torch.Tensor],
-                                       target: torch.Tensor, mlp_grads: Sequence[torch.Tensor], table_grads: Optional[torch.Tensor] = None,
-                                       order: Optional[torch.Tensor] = None, counts=None, loss: Optional[torch.Tensor] = None,
-                                       loss_scale: float = 1.0, want_y=False, quant=None, add_grads: bool = False, add_loss: bool = False,
-                                       groups_per_field: int = 0):
-    """``hash_fused_forward_backward_points`` of B stacked fields, each at ITS OWN points, in TWO launches whatever B is
-    (nic_hash_batch_forward_backward_points; DESIGN 4.7.18).  ``points`` fp32 [B, N, dim] (or [N, dim], shared), ``target`` [B, N, 3].
-    ``counts``: None, B ints or an int32 [B] tensor - field b trains on its first ``counts[b]`` rows only (a host value is validated to
-    0 .. N, a device tensor is clamped by the kernel), and loss[b] = mean((y_b - target_b)^2) * loss_scale over THOSE rows; a field with no
-    point has loss 0, decoder gradients 0 and an untouched table gradient.  ``order``: None or int32 [B, N] of field-local rows
-    (``hash_batch_point_order``) - wave w of field b takes rows order[b, 64 w ..]; targets, outputs and noise keys stay at the caller's rows.
-    ``want_y``: True, or a contiguous fp32 [B, N, 3] device tensor to write into; rows at or past a field's count are not written (zero in
-    the tensor ``want_y=True`` allocates).  Everything else as ``hash_batch_forward_backward``.  Returns (loss [B], y or None)."""
+def _batch_forward_backward_points(geo, tables, points, params, target, mlp_grads, table_grads, order, counts, loss, loss_scale, want_y, quant, add_grads,
+                                   add_loss, groups_per_field, lod):
+    """``hash_batch_forward_backward_points`` (``lod`` None) and ``hash_batch_forward_backward_points_lod`` (``lod`` = (lod, lod_uniform, fade))"""
     t = tables.detach() if isinstance(tables, torch.Tensor) else tables
     _check_batch_tables(geo, t)
     n_fields = t.shape[0]
@@ -961,6 +995,8 @@ def hash_batch_forward_backward_points(geo: HashGeometry, tables: torch.Tensor, 
         raise ValueError(f"target must be [{n_fields}, {n}, 3], got {tuple(target.shape) if isinstance(target, torch.Tensor) else type(target).__name__}")
     counts = _check_batch_counts(counts, n_fields, n)
     order = _check_batch_order(order, n_fields, n)
+    lod_t = None if lod is None else _check_batch_lod(lod[0], n_fields, n)
+    lp = None if lod is None else _lod_struct(geo, lod[2], lod[1])
     y_out = want_y if isinstance(want_y, torch.Tensor) else None
     if y_out is not None and not (y_out.dtype == torch.float32 and y_out.is_contiguous() and tuple(y_out.shape) == (n_fields, n, 3)):
         raise ValueError(f"want_y as a tensor must be contiguous fp32 [{n_fields}, {n}, 3]")
@@ -979,6 +1015,7 @@ def hash_batch_forward_backward_points(geo: HashGeometry, tables: torch.Tensor, 
         if x is not None:
             _require_on_device(x, name)
     pts = _stack_points(points, n_fields)
+    lod_t = _stack_lod(lod_t, n_fields, pts.device)
     counts = None if counts is None else counts.to(t.device, non_blocking=True)
     loss = torch.empty(n_fields, dtype=torch.float32, device=t.device) if loss is None else loss
     if y_out is not None:
@@ -995,12 +1032,50 @@ def hash_batch_forward_backward_points(geo: HashGeometry, tables: torch.Tensor, 
         nbytes = 16
     ws = _lib.workspace(t.device, nbytes)
     flags = (_lib.NIC_HASH_FUSED_ADD_GRADS if add_grads else 0) | (_lib.NIC_HASH_FUSED_ADD_LOSS if add_loss else 0)
-    _lib.check(lib.nic_hash_batch_forward_backward_points(ctypes.byref(d), n_fields, int(groups_per_field), None if q is None else ctypes.byref(q),
-                                                          _lib.ptr(t), _lib.ptr(pts), n, _lib.ptr(counts), _lib.ptr(order), ctypes.byref(m),
-                                                          _lib.ptr(target), float(loss_scale), _lib.ptr(table_grads), ctypes.byref(gs), _lib.ptr(loss),
-                                                          _lib.ptr(y), flags, _lib.ptr(ws), nbytes, _lib.stream_ptr(t.device)),
-               "nic_hash_batch_forward_backward_points")
+    qp = None if q is None else ctypes.byref(q)
+    tail = (_lib.ptr(counts), _lib.ptr(order), ctypes.byref(m), _lib.ptr(target), float(loss_scale), _lib.ptr(table_grads), ctypes.byref(gs), _lib.ptr(loss),
+            _lib.ptr(y), flags, _lib.ptr(ws), nbytes, _lib.stream_ptr(t.device))
+    if lp is None:
+        _lib.check(lib.nic_hash_batch_forward_backward_points(ctypes.byref(d), n_fields, int(groups_per_field), qp, _lib.ptr(t), _lib.ptr(pts), n, *tail),
+                   "nic_hash_batch_forward_backward_points")
+    else:
+        _lib.check(lib.nic_hash_batch_forward_backward_points_lod(ctypes.byref(d), n_fields, int(groups_per_field), ctypes.byref(lp), qp, _lib.ptr(t),
+                                                                  _lib.ptr(pts), _lib.ptr(lod_t), n, *tail), "nic_hash_batch_forward_backward_points_lod")
     return loss, y
+
+
+@fused._on_tensor_device
+def hash_batch_forward_backward_points(geo: HashGeometry, tables: torch.Tensor, points: torch.Tensor, params: Sequence[torch.Tensor],
+                                       target: torch.Tensor, mlp_grads: Sequence[torch.Tensor], table_grads: Optional[torch.Tensor] = None,
+                                       order: Optional[torch.Tensor] = None, counts=None, loss: Optional[torch.Tensor] = None,
+                                       loss_scale: float = 1.0, want_y=False, quant=None, add_grads: bool = False, add_loss: bool = False,
+                                       groups_per_field: int = 0):
+    """``hash_fused_forward_backward_points`` of B stacked fields, each at ITS OWN points, in TWO launches whatever B is
+    (nic_hash_batch_forward_backward_points; DESIGN 4.7.18).  ``points`` fp32 [B, N, dim] (or [N, dim], shared), ``target`` [B, N, 3].
+    ``counts``: None, B ints or an int32 [B] tensor - field b trains on its first ``counts[b]`` rows only (a host value is validated to
+    0 .. N, a device tensor is clamped by the kernel), and loss[b] = mean((y_b - target_b)^2) * loss_scale over THOSE rows; a field with no
+    point has loss 0, decoder gradients 0 and an untouched table gradient.  ``order``: None or int32 [B, N] of field-local rows
+    (``hash_batch_point_order``) - wave w of field b takes rows order[b, 64 w ..]; targets, outputs and noise keys stay at the caller's rows.
+    ``want_y``: True, or a contiguous fp32 [B, N, 3] device tensor to write into; rows at or past a field's count are not written (zero in
+    the tensor ``want_y=True`` allocates).  Everything else as ``hash_batch_forward_backward``.  Returns (loss [B], y or None)."""
+    return _batch_forward_backward_points(geo, tables, points, params, target, mlp_grads, table_grads, order, counts, loss, loss_scale, want_y, quant,
+                                          add_grads, add_loss, groups_per_field, None)
+
+
+@fused._on_tensor_device
+def hash_batch_forward_backward_points_lod(geo: HashGeometry, tables: torch.Tensor, points: torch.Tensor, params: Sequence[torch.Tensor],
+                                           target: torch.Tensor, mlp_grads: Sequence[torch.Tensor], lod: Optional[torch.Tensor] = None,
+                                           lod_uniform: float = 0.0, fade=None, table_grads: Optional[torch.Tensor] = None,
+                                           order: Optional[torch.Tensor] = None, counts=None, loss: Optional[torch.Tensor] = None,
+                                           loss_scale: float = 1.0, want_y=False, quant=None, add_grads: bool = False, add_loss: bool = False,
+                                           groups_per_field: int = 0):
+    """``hash_batch_forward_backward_points`` with a level of detail per point (nic_hash_batch_forward_backward_points_lod):
+    the same two launches, every field's row weighed as in ``hash_encode_points_lod`` and its gradient weighed again before the scatter -
+    ``hash_fused_forward_backward_points_lod`` per field.  ``lod``: None, or fp32 [N] shared by all fields or [B, N], each field its own,
+    read at the row the point is read at (with an ``order``: at ``order[b, pos]``); ``lod_uniform`` and ``fade`` (None:
+    ``hash_lod_fade(geo)``) serve every field.  Returns (loss [B], y or None)."""
+    return _batch_forward_backward_points(geo, tables, points, params, target, mlp_grads, table_grads, order, counts, loss, loss_scale, want_y, quant,
+                                          add_grads, add_loss, groups_per_field, (lod, lod_uniform, fade))
 
 
 def _encode_points_backward(geo, points, dx, table_grad, order, lod):
@@ -2347,7 +2422,12 @@ class HashGridFieldBatch:
     samples, point clouds - in the same three launches (nic_hash_batch_forward_backward_points), ``counts`` giving each field's own number of
     points: rows past it are padding that is never read and never trains.  Field b's arithmetic is ``HashGridField.train_points(fused=True)``'s.
 
-    Not built: at points, passes in chunks with ragged counts, a level of detail, ``dpoints`` and the 16-bit modes; 16-bit
+    A level of detail per point: ``query_lod`` / ``train_points_lod`` / ``fit_points_lod``, ``resample_lod``, ``decode_mip(m)``
+    and ``fit_mips`` are ``HashGridField``'s ``lod=`` calls per field - the levels finer than a sample's footprint fade out before the decoder and are not
+    gathered - in the batch's launches (nic_hash_batch_forward_points_lod, nic_hash_batch_forward_backward_points_lod), from the fp32 tables
+    and from stored ones.  ``lod_fade``: the fade start of every level, shared by all fields (``hash_lod_fade(geo)`` unless assigned).
+
+    Not built: at points, passes in chunks with ragged counts, ``dpoints`` and the 16-bit modes with ``lod``; 16-bit
     training; a bit depth per level (a ``/2`` file is read and refused), fields of differing geometry in one batch, a container format that
     holds several fields in one file."""
 
@@ -2375,7 +2455,7 @@ class HashGridFieldBatch:
             raise RuntimeError("HashGridFieldBatch needs a HIP device: there is no CPU implementation of this path")
         self.n_fields, self.hidden, self.n_linear = int(n_fields), 64, 3
         self.num_bits = None if num_bits is None else int(num_bits)
-        self.noise_seed, self.groups_per_field = int(noise_seed), int(groups_per_field)
+        self.noise_seed, self.groups_per_field, self._lod_fade = int(noise_seed), int(groups_per_field), None
         self._field_args = dict(levels=int(levels), features=int(features), log2_table=int(log2_table), base_resolution=base_resolution,
                                 finest_resolution=finest_resolution)
         if seed is not None:
@@ -2402,6 +2482,33 @@ class HashGridFieldBatch:
 
     def set_schedule(self, num_epochs: int) -> None:
         self.scheduler = CosineAnnealing(self.optimizer, T_max=num_epochs, eta_min=0)
+
+    @property
+    def lod_fade(self) -> Tuple[float, ...]:
+        """the fade start of every level for the ``_lod`` calls, shared by all fields: ``hash_lod_fade(geo)`` unless one was
+        assigned (``batch.lod_fade = [...]``: ``levels`` finite values >= 0, or None for the default); ``extract(b)`` hands it to the field"""
+        fade = getattr(self, "_lod_fade", None)
+        return fade if fade is not None else hash_lod_fade(self.geo)
+
+    @lod_fade.setter
+    def lod_fade(self, fade) -> None:
+        self._lod_fade = None if fade is None else _check_fade(self.geo.levels, fade)
+
+    @staticmethod
+    def _lod_args(lod) -> Tuple[Optional[torch.Tensor], float]:
+        """``lod`` of a call - a finite float, or a tensor [N] / [B, N] - as (per-point tensor or None, launch-wide value); the tensor is
+        checked against the points by ``_check_batch_lod``"""
+        if isinstance(lod, torch.Tensor) and lod.dim() > 0:
+            return lod, 0.0
+        if isinstance(lod, (str, bytes)):
+            raise ValueError(f"lod is a float or a [N] / [B, N] tensor, got {lod!r}")
+        try:
+            v = float(lod)
+        except (TypeError, ValueError):
+            raise ValueError(f"lod is a float or a [N] / [B, N] tensor, got {lod!r}") from None
+        if not math.isfinite(v):
+            raise ValueError(f"lod {lod!r} is not finite")
+        return None, v
 
     def _groups(self, num_crops: int, extent: Sequence[int]) -> int:
         """the constructor's ``groups_per_field`` for a launch on these crops: 0 stays automatic, a positive value is cut to the grid one
@@ -2479,6 +2586,7 @@ class HashGridFieldBatch:
         if device.type != "cuda":
             raise RuntimeError("HashGridFieldBatch needs a HIP device: there is no CPU implementation of this path")
         self = cls.__new__(cls)
+        self._lod_fade = None                        # the files hold no fade: ``lod_fade`` may be assigned
         self.geo, self.field_size, self.device = first["geo"], first["geo"].field_size, device
         self.n_fields, self.hidden, self.n_linear, self.num_bits = len(paths), 64, 3, first["num_bits"]
         self.noise_seed, self.groups_per_field = 0, int(groups_per_field)
@@ -2564,10 +2672,28 @@ class HashGridFieldBatch:
         points, computed for this call) or a precomputed int32 [B, N] tensor of it.  ``accumulate`` / ``scale`` / ``step`` / ``noise`` and
         the bookkeeping are ``train_step``'s: the noise keys (seed, optimiser step, samples of this pass before this chunk + the row inside
         the field) are the same for every field, and a chunk advances the pass by the padded width N.  After ``freeze()`` only the decoders
-        train."""
+        train.  With a level of detail: ``train_points_lod``."""
+        return self._train_points(points, target, counts, accumulate, scale, step, noise, order, None)
+
+    @torch.no_grad()
+    def train_points_lod(self, points: torch.Tensor, target: torch.Tensor, lod, counts=None, accumulate: bool = False, scale: float = 1.0,
+                         step: bool = True, noise: Optional[bool] = None, order=None) -> torch.Tensor:
+        """``train_points`` with a level of detail for these samples - ``HashGridField.train_points(fused=True, lod=)`` for
+        every field at once, in the same three launches (nic_hash_batch_forward_backward_points_lod).  ``lod``: a finite float, a tensor [N]
+        shared by all fields or [B, N], each field its own; it fades the finer levels out of a sample's row and of its gradient (fade starts
+        ``lod_fade``) and is read at the row the point is read at.  Every other argument is ``train_points``'."""
+        if lod is None:
+            raise ValueError("lod is a float or a [N] / [B, N] tensor: without a level of detail call train_points")
+        return self._train_points(points, target, counts, accumulate, scale, step, noise, order, lod)
+
+    @torch.no_grad()
+    def _train_points(self, points, target, counts, accumulate, scale, step, noise, order, lod) -> torch.Tensor:
+        """``train_points`` (``lod`` None: exactly the calls it always made) and ``train_points_lod``"""
         self._refuse_decode_only("train_points")
         frozen = self.frozen
+        lod_t, lod_u = (None, 0.0) if lod is None else self._lod_args(lod)
         n, counts, order = self._check_train_points(points, target, counts, order)
+        lod_t = _check_batch_lod(lod_t, self.n_fields, n)
         if noise is None:
             noise = self.num_bits is not None and not frozen
         if noise and self.num_bits is None:
@@ -2582,8 +2708,14 @@ class HashGridFieldBatch:
                 grad.zero_()
             self._pass_samples = 0
         quant = (self.num_bits, self.noise_seed, self.steps, self._pass_samples) if noise else None
-        loss, _ = hash_batch_forward_backward_points(self.geo, self.tables, pts, self.params, target, self._gm, table_grads=grad, order=order, counts=counts,
-                                                     loss_scale=float(scale), quant=quant, add_grads=accumulate, groups_per_field=self._point_groups(n))
+        if lod is None:
+            loss, _ = hash_batch_forward_backward_points(self.geo, self.tables, pts, self.params, target, self._gm, table_grads=grad, order=order,
+                                                         counts=counts, loss_scale=float(scale), quant=quant, add_grads=accumulate,
+                                                         groups_per_field=self._point_groups(n))
+        else:
+            loss, _ = hash_batch_forward_backward_points_lod(self.geo, self.tables, pts, self.params, target, self._gm, lod_t, lod_u, self.lod_fade,
+                                                             table_grads=grad, order=order, counts=counts, loss_scale=float(scale), quant=quant,
+                                                             add_grads=accumulate, groups_per_field=self._point_groups(n))
         self._pass_samples += n
         if not frozen:
             self._grad_clean = False
@@ -2596,12 +2728,27 @@ class HashGridFieldBatch:
         ``counts`` (``train_points``'), one call and one optimiser step per pass.  ``order``: "cell" (default), None or an int32 [B, N]
         tensor; it is computed once and every field's set is laid out in it once (its real rows first, in order, then its padding), so the
         passes walk contiguous memory without an index.  With ``num_bits``: noise while the epoch is below ``freeze_at`` * epochs, then
-        ``freeze()`` - ``fit``'s schedule.  Returns the per-pass losses, [epochs][B]."""
+        ``freeze()`` - ``fit``'s schedule.  Returns the per-pass losses, [epochs][B].  With a level of detail: ``fit_points_lod``."""
+        return self._fit_points(points, target, epochs, counts, order, freeze_at, None)
+
+    def fit_points_lod(self, points: torch.Tensor, target: torch.Tensor, epochs: int, lod, counts=None, order="cell",
+                       freeze_at: float = 0.95) -> List[List[float]]:
+        """``fit_points`` with ``train_points_lod``'s level of detail: a ``lod`` tensor is laid out in the order with the points
+        and targets, once.  Every other argument is ``fit_points``'."""
+        if lod is None:
+            raise ValueError("lod is a float or a [N] / [B, N] tensor: without a level of detail call fit_points")
+        return self._fit_points(points, target, epochs, counts, order, freeze_at, lod)
+
+    def _fit_points(self, points, target, epochs, counts, order, freeze_at, lod) -> List[List[float]]:
+        """``fit_points`` (``lod`` None) and ``fit_points_lod``"""
         self._refuse_decode_only("fit_points")
+        lod_t, lod_u = (None, None) if lod is None else self._lod_args(lod)
         n, counts, order = self._check_train_points(points, target, counts, order)
+        lod_t = _check_batch_lod(lod_t, self.n_fields, n)
         _require_on_device(points, "points")
         target = _lib.require_cuda_f32(target, "target")
         pts = _stack_points(points, self.n_fields)
+        lod_t = _stack_lod(lod_t, self.n_fields, pts.device)
         if order is not None:
             idx = (hash_batch_point_order(self.geo, pts, counts) if isinstance(order, str) else order.to(pts.device)).to(torch.int64)
             top = torch.full((self.n_fields, 1), n, dtype=torch.int64, device=pts.device) if counts is None else counts.to(pts.device, torch.int64).clamp(0, n).unsqueeze(1)
@@ -2609,14 +2756,43 @@ class HashGridFieldBatch:
             idx = torch.minimum(idx, torch.where(real, top - 1, torch.full_like(top, n - 1))).clamp_(min=0)
             pts = torch.gather(pts, 1, idx.unsqueeze(2).expand(-1, -1, self.geo.dim)).contiguous()
             target = torch.gather(target, 1, idx.unsqueeze(2).expand(-1, -1, 3)).contiguous()
+            lod_t = None if lod_t is None else torch.gather(lod_t, 1, idx).contiguous()
         counts = None if counts is None else counts.to(pts.device)          # once: a device tensor is taken as it is by every pass
         freeze_epoch = math.ceil(freeze_at * epochs) if self.num_bits is not None else None
         hist = []
         for ep in range(epochs):
             if freeze_epoch is not None and ep >= freeze_epoch and not self.frozen:
                 self.freeze()
-            hist.append(self.train_points(pts, target, counts=counts))
+            if lod is None:
+                hist.append(self.train_points(pts, target, counts=counts))
+            else:
+                hist.append(self.train_points_lod(pts, target, lod_u if lod_t is None else lod_t, counts=counts))
         return [[float(v) for v in h] for h in torch.stack(hist).tolist()] if hist else []
+
+    def _mip_size(self, m: int) -> Tuple[int, ...]:
+        return HashGridField._mip_size(self, m)
+
+    def fit_mips(self, targets: torch.Tensor, epochs: int, mips: int = 2, order="cell", freeze_at: float = 0.95) -> List[List[float]]:
+        """``HashGridField.fit_mips`` for every field at once on ``targets`` [B, S_x, S_y(, S_z), 3]: mip m = the mean over blocks of 2^m
+        samples per axis (m = 0 .. ``mips``), its samples at ``decode_mip(m)``'s points with level of detail m.  The points and their ``lod``
+        are built once and shared by all fields, the colours are each field's; the sets of all mips go to ONE ``fit_points_lod`` call, so cell
+        order and the freeze schedule are that method's.  Returns the per-pass losses, [epochs][B]."""
+        self._refuse_decode_only("fit_mips")
+        size, dim, b = self.field_size, self.geo.dim, self.n_fields
+        if not isinstance(targets, torch.Tensor) or tuple(targets.shape) != (b, *size, 3):
+            raise ValueError(f"targets must be {(b, *size, 3)}, got {tuple(targets.shape) if isinstance(targets, torch.Tensor) else type(targets).__name__}")
+        if int(mips) < 0:
+            raise ValueError("mips >= 0")
+        sizes = [self._mip_size(m) for m in range(int(mips) + 1)]
+        targets = _lib.require_cuda_f32(targets, "targets")
+        pts, lods, cols = [], [], []
+        for m, sz in enumerate(sizes):
+            blocks = targets.reshape(b, *[v for s in sz for v in (s, 1 << m)], 3)
+            cols.append(blocks.mean(dim=tuple(range(2, 2 * dim + 1, 2))).reshape(b, -1, 3))
+            pts.append(HashGridField._resample_points(self, sz, [0] * dim, sz))
+            lods.append(torch.full((pts[-1].shape[0],), float(m), dtype=torch.float32, device=self.device))
+        return self.fit_points_lod(torch.cat(pts).contiguous(), torch.cat(cols, dim=1).contiguous(), epochs, torch.cat(lods).contiguous(), order=order,
+                                   freeze_at=freeze_at)
 
     @torch.no_grad()
     def apply_step(self) -> None:
@@ -2708,32 +2884,82 @@ class HashGridFieldBatch:
     def query(self, points: torch.Tensor, precision: Optional[str] = None) -> torch.Tensor:
         """[B, N, 3] colours at ``points`` - [N, dim] shared by all fields, or [B, N, dim], each field its own - in ONE launch, from whatever
         table the batch holds (nic_hash_batch_forward_source).  fp32, sample units, clamped like ``HashGridField.query``.  ``precision``: None,
-        or "split" / "bf16" - the same launch through ``hash_batch_forward_p16``."""
+        or "split" / "bf16" - the same launch through ``hash_batch_forward_p16``.  With a level of detail: ``query_lod``."""
+        return self._query(points, precision, None)
+
+    @torch.no_grad()
+    def query_lod(self, points: torch.Tensor, lod, precision: Optional[str] = None) -> torch.Tensor:
+        """``query`` with the level of detail of the query - ``HashGridField.query(lod=)`` of every field in the ONE launch
+        (nic_hash_batch_forward_points_lod), from whatever table the batch holds.  ``lod``: a finite float, a tensor [N] shared by all fields or
+        [B, N], each field its own: the levels finer than the footprint fade out before the decoder and are not gathered (fade starts
+        ``lod_fade``).  ``precision`` other than None is refused, as on the single field."""
+        if lod is None:
+            raise ValueError("lod is a float or a [N] / [B, N] tensor: without a level of detail call query")
+        return self._query(points, precision, lod)
+
+    @torch.no_grad()
+    def _query(self, points, precision, lod) -> torch.Tensor:
+        """``query`` (``lod`` None: exactly the calls it always made) and ``query_lod``"""
         if precision is not None:
             _check_precision(precision)
+            if lod is not None:
+                raise NotImplementedError("precision= with a level of detail is not built (DESIGN 7): call without lod, or without precision")
+        lod_t, lod_u = (None, 0.0) if lod is None else self._lod_args(lod)
         data, kind, bits = self._table_source()
         n = points.shape[-2] if isinstance(points, torch.Tensor) and points.dim() >= 2 else 0
         params, groups = [p.detach() for p in self.params], self._point_groups(max(n, 1))
         if precision is not None:
             return hash_batch_forward_p16(self.geo, data, params, precision, kind, bits, points=points, groups_per_field=groups)
+        if lod is not None:
+            return hash_batch_forward_points_lod(self.geo, data, points, params, lod_t, lod_u, self.lod_fade, kind, bits, groups_per_field=groups)
         return hash_batch_forward_source(self.geo, data, params, kind, bits, points=points, groups_per_field=groups)
 
     @torch.no_grad()
     def resample(self, size: Union[int, Sequence[int]], tile: int = 1024, precision: Optional[str] = None) -> torch.Tensor:
         """every field decoded on a regular grid of ANY size, [B, *size, 3]: ``HashGridField.resample``'s sample positions (its
         ``_resample_points``, generated once per tile and shared by all fields), one launch per tile for all fields; ``precision`` as in
-        ``query``"""
+        ``query``.  With a level of detail: ``resample_lod``."""
+        return self._resample(size, tile, precision, None)
+
+    @torch.no_grad()
+    def resample_lod(self, size: Union[int, Sequence[int]], lod="auto", tile: int = 1024, precision: Optional[str] = None) -> torch.Tensor:
+        """``resample`` with ``HashGridField.resample(lod=)``'s level of detail for every sample: a float, or "auto" =
+        max(0, log2(max_a S_a / size_a)), the footprint of an output sample in octaves.  ``precision`` other than None is refused."""
+        if lod is None:
+            raise ValueError("lod is 'auto' or a float: without a level of detail call resample")
+        return self._resample(size, tile, precision, lod)
+
+    @torch.no_grad()
+    def _resample(self, size, tile, precision, lod) -> torch.Tensor:
+        """``resample`` (``lod`` None) and ``resample_lod``"""
         if precision is not None:
             _check_precision(precision)
+            if lod is not None:
+                raise NotImplementedError("precision= with a level of detail is not built (DESIGN 7): call without lod, or without precision")
         size = (int(size),) * self.geo.dim if isinstance(size, int) else tuple(int(v) for v in size)
         if len(size) != self.geo.dim or any(v < 1 for v in size):
             raise ValueError(f"size {size} for a {self.geo.dim}D field")
+        if isinstance(lod, str):
+            if lod != "auto":
+                raise ValueError(f"lod {lod!r}: None, 'auto' or a float")
+            lod = max(0.0, math.log2(max(s / v for s, v in zip(self.field_size, size))))
+        if lod is not None:
+            if isinstance(lod, torch.Tensor) and lod.dim() > 0:
+                raise ValueError("resample takes one level of detail for the whole grid: None, 'auto' or a float")
+            lod = self._lod_args(lod)[1]
         out = torch.empty(self.n_fields, *size, 3, dtype=torch.float32, device=self.device)
         for o in itertools.product(*[range(0, s, tile) for s in size]):
             ext = [min(tile, s - a) for s, a in zip(size, o)]
             sl = (slice(None), *(slice(a, a + e) for a, e in zip(o, ext)))
-            out[sl] = self.query(HashGridField._resample_points(self, size, o, ext), precision).reshape(self.n_fields, *ext, 3)
+            pts = HashGridField._resample_points(self, size, o, ext)
+            out[sl] = (self.query(pts, precision) if lod is None else self.query_lod(pts, lod, precision)).reshape(self.n_fields, *ext, 3)
         return out
+
+    @torch.no_grad()
+    def decode_mip(self, m: int, tile: int = 1024) -> torch.Tensor:
+        """mip ``m`` of every field, [B, S_x / 2^m, S_y / 2^m(, S_z / 2^m), 3]: ``HashGridField.decode_mip``'s points and level of detail m,
+        one launch per tile for all fields"""
+        return self.resample_lod(self._mip_size(m), float(int(m)), tile=tile)
 
     def _adam_state(self, p: torch.Tensor):
         st = self.optimizer.state.get(p)
@@ -2748,7 +2974,7 @@ class HashGridFieldBatch:
         b = self._check_field_index(b)
         if self.decode_only:
             f = HashGridField.__new__(HashGridField)
-            f.field_size, f.geo, f.hidden, f.n_linear, f._lod_fade = self.field_size, self.geo, 64, 3, None
+            f.field_size, f.geo, f.hidden, f.n_linear, f._lod_fade = self.field_size, self.geo, 64, 3, getattr(self, "_lod_fade", None)
             f.num_bits, f.level_bits, f.device = self.num_bits, None, self.device
             f.stored = None if self.stored is None else self.stored[b].clone()
             f.packed = None if self.packed is None else self.packed[b].clone()
@@ -2763,7 +2989,7 @@ class HashGridFieldBatch:
             return f
         with torch.random.fork_rng(devices=[self.device]):                     # the constructor's random init is overwritten: leave the generators alone
             f = HashGridField(self.field_size, hidden=64, n_linear=3, device=self.device, num_bits=self.num_bits, noise_seed=self.noise_seed, fused=True,
-                              **self._field_args)
+                              lod_fade=getattr(self, "_lod_fade", None), **self._field_args)
         if f.geo != self.geo or f.route != "fused":
             raise RuntimeError("extract(): the single field's geometry differs from the batch's")
         f.table.copy_(self.tables[b])
