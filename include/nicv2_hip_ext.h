@@ -101,6 +101,54 @@ int nic_hash_batch_forward_backward_points_lod(const nic_hash_desc *desc, int n_
                                                const float *target, float loss_scale, float *table_grads, const nic_mlp_grads *mlp_grads,
                                                float *loss, float *y, int flags, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- B hash-grid fields per launch with the gradient with respect to the POINT COORDINATES, alone and in the training step (hashgrid.py,
+ *      hash_batch_points_grad, hash_batch_forward_backward_points_grad, HashGridFieldBatch.point_gradient / jacobian / query_differentiable /
+ *      train_points_grad / train_points_differentiable; csrc/hashgrid_batch_grad.hip, hash_batch_points_grad_kernel; csrc/hashgrid_batch.hip,
+ *      hash_batch_points_joint_kernel).  Both take a NULLABLE nic_hash_lod, as nic_hash_fused_forward_backward_points_grad
+ *      does: lodp == NULL is the plain call (and lod != NULL is then NIC_E_ARG), else the nic_hash_lod section of nicv2_hip.h holds for every
+ *      field as in the _lod entries above, lod NULL or fp32 [B, n_points] read at the field-local ROW.  dpoints = [B, n_points, dim] fp32: the
+ *      derivative of the multilinear interpolant at the rounded position the forward uses, in sample units; an axis whose floating-point
+ *      clamp moved the point (or a NaN) gets exactly 0.0f; noise and level weights are constants.  counts and order as in
+ *      nic_hash_batch_forward_backward_points: counts null or int32 [B] clamped to [0, n_points], order null or int32 [B, n_points] of
+ *      field-local rows, the first n_b read, each clamped to [0, n_b - 1].  Row order[b, pos] of y and dpoints is written once, by the lane
+ *      that handles it - overwritten, never added to; rows at or past n_b, and rows an order does not name, are NOT written; a field with
+ *      n_b = 0 walks nothing and writes nothing.
+ *      nic_hash_batch_points_grad = nic_hash_fused_points_grad per field in ONE launch: no atomics, no workspace, no reduction (tables and
+ *      decoders are constants), the same call gives the same bits, and with dy field b's rows are nic_hash_fused_points_grad's on field b's
+ *      tensors bit for bit.  The stacked source of any of the three kinds under nic_hash_batch_forward_source's contract and alignment rules,
+ *      the stacked decoder, points [B, n_points, dim], exactly one of dy / target [B, n_points, 3], y [B, n_points, 3] or null.  With target,
+ *      field b's output gradient is 2 (y - target) loss_scale / (3 n_b), n_b its OWN count.  groups_per_field on ceil(n_points / 64) wave
+ *      items, nic_hash_batch_forward_source's rule.
+ *      Host checks, all before any GPU work: null desc / mlp (NIC_E_NULL); the fused set (nic_hash_fused_supported's code); the descriptor
+ *      of a point source (num_crops == 1, NIC_E_SHAPE, and 256 S_max < 2^30, NIC_E_ARG); n_fields in 1 .. 65535 (NIC_E_ARG);
+ *      groups_per_field (NIC_E_ARG; n_points <= 0 counts as one wave item); null src, src->data, points, decoder layer or dpoints
+ *      (NIC_E_NULL; lodp, lod, counts, order, dy, target and y may be null); the source (NIC_E_ARG: kind, num_bits, alignment); lod without
+ *      lodp, then the nic_hash_lod (NIC_E_ARG); both or neither of dy / target (NIC_E_ARG); n_points < 0 or >= 2^31 (NIC_E_ARG); n_points
+ *      == 0 is NIC_OK without a launch, nothing written.
+ *      nic_hash_batch_forward_backward_points_grad = nic_hash_batch_forward_backward_points with lodp == NULL, otherwise
+ *      nic_hash_batch_forward_backward_points_lod, argument for argument, in the same TWO launches: their records and fixed-order reduction
+ *      without a tail, their flags and workspace (nic_hash_batch_points_workspace_bytes), noise keyed by sample_base + the row,
+ *      nic_mark_kernel_end honoured, table_grads == NULL frozen tables (no scatter; dpoints and the decoder records are still produced).
+ *      On top of their outputs it writes dpoints, the derivative of the loss the call returns for field b taken at the parameters the
+ *      forward used - nic_hash_batch_points_grad's with target on the same tables when there is no noise, bit for bit -, overwritten
+ *      whatever NIC_HASH_FUSED_ADD_GRADS says.
+ *      Host checks, all before any GPU work, in the siblings' order: null desc / mlp (NIC_E_NULL); the fused set, then 256 S_max < 2^30
+ *      (NIC_E_ARG); n_fields in 1 .. 65535 (NIC_E_ARG); groups_per_field (NIC_E_ARG; n_points <= 0 counts as one wave item); null tables,
+ *      points, decoder layer, target, mlp_grads, loss, dpoints or workspace (NIC_E_NULL; lodp, lod, counts, order, table_grads and y may be
+ *      null); lod without lodp, then the nic_hash_lod (NIC_E_ARG); flags (NIC_E_ARG); quant (nic_hash_fused_forward_backward's rules); the
+ *      workspace (NIC_E_WORKSPACE); num_crops == 1 (NIC_E_SHAPE); n_points < 0 or >= 2^31 (NIC_E_ARG); n_points == 0 is NIC_OK without a
+ *      launch, nothing written. */
+int nic_hash_batch_points_grad(const nic_hash_desc *desc, int n_fields, int groups_per_field, const nic_hash_lod *lodp,
+                               const nic_hash_source *src, const float *points, const float *lod, int64_t n_points,
+                               const int32_t *counts, const int32_t *order, const nic_mlp *mlp, const float *dy,
+                               const float *target, float loss_scale, float *y, float *dpoints, void *stream);
+int nic_hash_batch_forward_backward_points_grad(const nic_hash_desc *desc, int n_fields, int groups_per_field,
+                                                const nic_hash_lod *lodp, const nic_hash_quant *quant, const float *tables,
+                                                const float *points, const float *lod, int64_t n_points, const int32_t *counts,
+                                                const int32_t *order, const nic_mlp *mlp, const float *target, float loss_scale,
+                                                float *table_grads, const nic_mlp_grads *mlp_grads, float *loss, float *y, float *dpoints,
+                                                int flags, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

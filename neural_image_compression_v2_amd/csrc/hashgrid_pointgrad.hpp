@@ -1,5 +1,6 @@
-// The position-gradient walk of the hash-grid point kernels, the one copy of it: hashgrid_pointgrad.hip (the field's
-// parameters constant) and hashgrid_points_joint.hip (the training step that also hands back d loss / d points) include this header.  `s` is
+// The position-gradient walk of the hash-grid point kernels, the one copy of it: hashgrid_pointgrad.hip (the
+// field's parameters constant), hashgrid_points_joint.hip (the training step that also hands back d loss / d points) and their batched forms
+// (hashgrid_batch_grad.hip, hashgrid_batch.hip's joint kernel) include this header; so is the decoder's backward to the input alone.  `s` is
 // whatever holds the source - a kernel's parameter struct: d, the table of SRC, with LOD fade - and each field is read where the loop uses it,
 // as in encode_point_levels (hash_common.hpp).  Everything is force-inlined.
 #pragma once
@@ -105,6 +106,120 @@ template <int D>
 __device__ __forceinline__ void store_point_grad(float* dpoints, int64_t n, uint32_t kept, const float (&g)[D]) {
 #pragma unroll
     for (int a = 0; a < D; ++a) dpoints[n * D + a] = ((kept >> a) & 1u) ? g[a] : 0.0f;
+}
+
+
+// ---- the decoder's backward to the input alone -----------------------------------------------------------------------------------------------
+// decoder_train_half (hash_common.hpp) without its three weight-gradient passes and without TrainAcc, the same products in the same order:
+// forward of the 32 samples `32 nt + j` of the row tile `xs` keeping the two GELU derivative tiles, dZ3 = dy y (1 - y), dA2 = W3^T dZ3,
+// dZ2 = dA2 gelu', dA1 = W2^T dZ2, dZ1 = dA1 gelu', dX = W1^T dZ1 written over the rows of this half.  `mine`: this lane (half 0) owns a live
+// sample; its dy is read at `dyrow`, or formed from `trow` as dscale (y - target); y goes to `yrow` when that is not null.
+template <int KT>
+__device__ __forceinline__ void decoder_dx_half(const DecoderSmem& sm, float* xs, int nt, int j, int half, int ks1, bool mine, const float* dyrow,
+                                                const float* trow, float* yrow, float dscale) {
+    const int src = 32 * nt + j;
+    const float* xb = xs + src * XS;
+    // ---- layer 1
+    f32x16 a1[2] = {f32x16{}, f32x16{}};
+    f32x16 d1[2];
+    for (int k = 0; k < ks1; ++k) {
+        const float b = xb[2 * k + half];
+        a1[0] = mfma(sm.w1[j * XS + 2 * k + half], b, a1[0]);
+        a1[1] = mfma(sm.w1[(32 + j) * XS + 2 * k + half], b, a1[1]);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float av, dv;
+            gelu_and_grad(a1[t][r] + sm.b1[32 * t + row_of(r, half)], av, dv);
+            a1[t][r] = av;
+            d1[t][r] = dv;
+        }
+    // ---- layer 2
+    f32x16 a2[2] = {f32x16{}, f32x16{}};
+    f32x16 d2[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int k = 32 * t + row_of(r, half);
+            a2[0] = mfma(sm.w2[j * XS + k], a1[t][r], a2[0]);
+            a2[1] = mfma(sm.w2[(32 + j) * XS + k], a1[t][r], a2[1]);
+        }
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float av, dv;
+            gelu_and_grad(a2[t][r] + sm.b2[32 * t + row_of(r, half)], av, dv);
+            a2[t][r] = av;
+            d2[t][r] = dv;
+        }
+    // ---- output layer: rows 0 .. 2 of one tile (registers 0 .. 2 of half 0)
+    f32x16 z3 = f32x16{};
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int k = 32 * t + row_of(r, half);
+            z3 = mfma(j < 3 ? sm.w3[j * kH + k] : 0.f, a2[t][r], z3);
+        }
+    float yv[3];
+#pragma unroll
+    for (int o = 0; o < 3; ++o) yv[o] = sigmoid_f(z3[o] + sm.b3[o]);
+    if (mine && yrow != nullptr) {
+#pragma unroll
+        for (int o = 0; o < 3; ++o) yrow[o] = yv[o];
+    }
+    // ---- dZ3 = dy y (1 - y); with a target dy = 2 (y - t) loss_scale / (3 N)
+    float dz3[3] = {0.f, 0.f, 0.f};
+    if (mine) {
+#pragma unroll
+        for (int o = 0; o < 3; ++o) {
+            if (dyrow != nullptr) dz3[o] = dyrow[o] * yv[o] * (1.0f - yv[o]);
+            else dz3[o] = dscale * (yv[o] - trow[o]) * yv[o] * (1.0f - yv[o]);
+        }
+    }
+    // dA2 = W3^T dZ3 (k-steps: o = s of half 0; half 1 carries zeros), dZ2 = dA2 gelu'
+    f32x16 dz2[2] = {f32x16{}, f32x16{}};
+#pragma unroll
+    for (int o = 0; o < 3; ++o) {
+        const float b = half == 0 ? dz3[o] : 0.f;
+        dz2[0] = mfma(half == 0 ? sm.w3[o * kH + j] : 0.f, b, dz2[0]);
+        dz2[1] = mfma(half == 0 ? sm.w3[o * kH + 32 + j] : 0.f, b, dz2[1]);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) dz2[t] *= d2[t];
+    // dA1 = W2^T dZ2, dZ1 = dA1 gelu'
+    f32x16 dz1[2] = {f32x16{}, f32x16{}};
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int k = 32 * t + row_of(r, half);
+            dz1[0] = mfma(sm.w2[k * XS + j], dz2[t][r], dz1[0]);
+            dz1[1] = mfma(sm.w2[k * XS + 32 + j], dz2[t][r], dz1[1]);
+        }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) dz1[t] *= d1[t];
+    // dX = W1^T dZ1 over the rows of this half (their X is spent: every lane of the wave has issued its layer-1 reads)
+    f32x16 dx[KT];
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) dx[kt] = f32x16{};
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int h = 32 * t + row_of(r, half);
+#pragma unroll
+            for (int kt = 0; kt < KT; ++kt) dx[kt] = mfma(sm.w1[h * XS + 32 * kt + j], dz1[t][r], dx[kt]);
+        }
+    float* xw = xs + src * XS;
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) xw[32 * kt + row_of(r, half)] = dx[kt][r];
 }
 
 }  // namespace hcommon

@@ -975,8 +975,9 @@ def hash_batch_point_order(geo: HashGeometry, points: torch.Tensor, counts=None)
 
 
 def _batch_forward_backward_points(geo, tables, points, params, target, mlp_grads, table_grads, order, counts, loss, loss_scale, want_y, quant, add_grads,
-                                   add_loss, groups_per_field, lod):
-    """``hash_batch_forward_backward_points`` (``lod`` None) and ``hash_batch_forward_backward_points_lod`` (``lod`` = (lod, lod_uniform, fade))"""
+                                   add_loss, groups_per_field, lod, dpoints=False):
+    """``hash_batch_forward_backward_points`` (``lod`` None) and ``hash_batch_forward_backward_points_lod`` (``lod`` = (lod, lod_uniform, fade));
+    with ``dpoints`` - None for a fresh tensor, or the tensor to fill - ``hash_batch_forward_backward_points_grad``, which returns it too"""
     t = tables.detach() if isinstance(tables, torch.Tensor) else tables
     _check_batch_tables(geo, t)
     n_fields = t.shape[0]
@@ -1002,6 +1003,8 @@ def _batch_forward_backward_points(geo, tables, points, params, target, mlp_grad
         raise ValueError(f"want_y as a tensor must be contiguous fp32 [{n_fields}, {n}, 3]")
     if loss is not None and not (isinstance(loss, torch.Tensor) and loss.dtype == torch.float32 and loss.is_contiguous() and tuple(loss.shape) == (n_fields,)):
         raise ValueError(f"loss must be a contiguous fp32 device tensor [{n_fields}]")
+    if dpoints is not False and dpoints is not None:
+        _check_batch_dpoints_shape(geo, n_fields, n, dpoints)
     _point_desc(geo)
     # ---- the device, after every refusal the host can make
     _require_stacked([t], "tables")
@@ -1035,6 +1038,16 @@ def _batch_forward_backward_points(geo, tables, points, params, target, mlp_grad
     qp = None if q is None else ctypes.byref(q)
     tail = (_lib.ptr(counts), _lib.ptr(order), ctypes.byref(m), _lib.ptr(target), float(loss_scale), _lib.ptr(table_grads), ctypes.byref(gs), _lib.ptr(loss),
             _lib.ptr(y), flags, _lib.ptr(ws), nbytes, _lib.stream_ptr(t.device))
+    if dpoints is not False:
+        if dpoints is None:      # rows at or past a field's count, and rows an order does not name, are not written: zero in a fresh tensor
+            dpoints = (torch.empty if counts is None and order is None else torch.zeros)(n_fields, n, geo.dim, dtype=torch.float32, device=t.device)
+        else:
+            _check_batch_dpoints_device(dpoints, pts.device)
+        _lib.check(lib.nic_hash_batch_forward_backward_points_grad(
+            ctypes.byref(d), n_fields, int(groups_per_field), None if lp is None else ctypes.byref(lp), qp, _lib.ptr(t), _lib.ptr(pts), _lib.ptr(lod_t), n,
+            _lib.ptr(counts), _lib.ptr(order), ctypes.byref(m), _lib.ptr(target), float(loss_scale), _lib.ptr(table_grads), ctypes.byref(gs), _lib.ptr(loss),
+            _lib.ptr(y), _lib.ptr(dpoints), flags, _lib.ptr(ws), nbytes, _lib.stream_ptr(t.device)), "nic_hash_batch_forward_backward_points_grad")
+        return loss, y, dpoints
     if lp is None:
         _lib.check(lib.nic_hash_batch_forward_backward_points(ctypes.byref(d), n_fields, int(groups_per_field), qp, _lib.ptr(t), _lib.ptr(pts), n, *tail),
                    "nic_hash_batch_forward_backward_points")
@@ -1392,6 +1405,129 @@ def hash_fused_points_grad(geo: HashGeometry, data: torch.Tensor, points: torch.
     return y, out
 
 
+# ---- B fields per launch with the gradient with respect to the point coordinates (include/nicv2_hip_ext.h) ------------------------
+def _check_batch_dpoints_shape(geo: HashGeometry, n_fields: int, n: int, dpoints) -> None:
+    """``_check_dpoints`` for a batch, the part the host decides: an fp32 [B, N, dim] tensor, contiguous - the kernel writes it in place"""
+    if not isinstance(dpoints, torch.Tensor):
+        raise TypeError("dpoints must be a torch.Tensor")
+    if tuple(dpoints.shape) != (n_fields, n, geo.dim):
+        raise ValueError(f"dpoints must be [{n_fields}, {n}, {geo.dim}], one row per point of every field, got {tuple(dpoints.shape)}")
+    if dpoints.dtype != torch.float32:
+        raise ValueError(f"dpoints has dtype {dpoints.dtype}; the kernel writes fp32")
+    if not dpoints.is_contiguous():
+        raise ValueError("dpoints must be contiguous: the kernel writes it in place")
+
+
+def _check_batch_dpoints_device(dpoints: torch.Tensor, device) -> None:
+    """``_check_dpoints``' device part: on the points' HIP device"""
+    if not dpoints.is_cuda:
+        raise RuntimeError(f"dpoints lives on {dpoints.device}: this package only runs on a HIP device (no CPU path)")
+    if dpoints.device != device:
+        raise ValueError(f"dpoints lives on {dpoints.device}, the points on {device}")
+
+
+def _plain_lod(lod, lod_uniform, fade) -> bool:
+    """no level of detail at all - ``lod`` None, ``lod_uniform`` 0 and ``fade`` None: the gradient entries' plain launch (``_grad_lod``)"""
+    return lod is None and fade is None and float(lod_uniform) == 0.0
+
+
+def _batch_points_grad(geo, data, points, params, dy, target, loss_scale, counts, order, want_y, kind, num_bits, lod, lod_uniform, fade, groups_per_field,
+                       dpoints=None):
+    """``hash_batch_points_grad``; ``dpoints``: None for a fresh tensor, or the fp32 [B, N, dim] device tensor to fill"""
+    n_fields = _check_batch_source(geo, data, kind, num_bits)
+    data = data.detach()
+    params = _check_batch_decoder(geo, [q.detach() if isinstance(q, torch.Tensor) else q for q in params], n_fields)
+    if any(q.dtype != torch.float32 for q in params):
+        raise ValueError("params: fp32 tensors")
+    n = _check_batch_points(geo, points, n_fields)
+    if n >= 2 ** 31:
+        raise ValueError("a field's row holds fewer than 2^31 points")
+    if (dy is None) == (target is None):
+        raise ValueError("exactly one of dy and target: the gradient of the output, or the colours of a mean squared error")
+    for name, v in (("dy", dy), ("target", target)):
+        if v is not None and (not isinstance(v, torch.Tensor) or tuple(v.shape) != (n_fields, n, 3)):
+            raise ValueError(f"{name} must be [{n_fields}, {n}, 3], got {tuple(v.shape) if isinstance(v, torch.Tensor) else type(v).__name__}")
+    counts = _check_batch_counts(counts, n_fields, n)
+    order = _check_batch_order(order, n_fields, n)
+    plain = _plain_lod(lod, lod_uniform, fade)
+    lod_t = None if plain else _check_batch_lod(lod, n_fields, n)
+    lp = None if plain else _lod_struct(geo, fade, lod_uniform)
+    y_out = want_y if isinstance(want_y, torch.Tensor) else None
+    if y_out is not None and not (y_out.dtype == torch.float32 and y_out.is_contiguous() and tuple(y_out.shape) == (n_fields, n, 3)):
+        raise ValueError(f"want_y as a tensor must be contiguous fp32 [{n_fields}, {n}, 3]")
+    if dpoints is not None:
+        _check_batch_dpoints_shape(geo, n_fields, n, dpoints)
+    d = _point_desc(geo)
+    # ---- the device, after every refusal the host can make
+    _require_on_device(data, "data")
+    for q in params:
+        _require_on_device(q, "params")
+    if kind == "bits" and data.data_ptr() % 4:
+        raise ValueError("data must start on a 4-byte boundary: the packed gather reads aligned dwords")
+    _require_on_device(points, "points")
+    dy = None if dy is None else _lib.require_cuda_f32(dy.detach(), "dy")
+    target = None if target is None else _lib.require_cuda_f32(target.detach(), "target")
+    for x, name in ((order, "order"), (y_out, "want_y")):
+        if x is not None:
+            _require_on_device(x, name)
+    pts = _stack_points(points, n_fields)
+    lod_t = _stack_lod(lod_t, n_fields, pts.device)
+    counts = None if counts is None else counts.to(data.device, non_blocking=True)
+    fresh = torch.empty if counts is None and order is None else torch.zeros      # rows a field does not own, or an order does not name, are not written
+    if y_out is not None:
+        y = y_out
+    else:
+        y = fresh(n_fields, n, 3, dtype=torch.float32, device=data.device) if want_y else None
+    if dpoints is None:
+        dpoints = fresh(n_fields, n, geo.dim, dtype=torch.float32, device=data.device)
+    else:
+        _check_batch_dpoints_device(dpoints, pts.device)
+    if n == 0:
+        return y, dpoints
+    src, m = _lib.NicHashSource(POINT_SOURCES[kind], 0 if kind == "f32" else int(num_bits), data.data_ptr()), fused._mlp_struct(params)
+    _lib.check(_lib.load().nic_hash_batch_points_grad(
+        ctypes.byref(d), n_fields, int(groups_per_field), None if lp is None else ctypes.byref(lp), ctypes.byref(src), _lib.ptr(pts), _lib.ptr(lod_t), n,
+        _lib.ptr(counts), _lib.ptr(order), ctypes.byref(m), _lib.ptr(dy), _lib.ptr(target), float(loss_scale), _lib.ptr(y), _lib.ptr(dpoints),
+        _lib.stream_ptr(data.device)), "nic_hash_batch_points_grad")
+    return y, dpoints
+
+
+@fused._on_tensor_device
+def hash_batch_points_grad(geo: HashGeometry, data: torch.Tensor, points: torch.Tensor, params: Sequence[torch.Tensor],
+                           dy: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None, loss_scale: float = 1.0, counts=None,
+                           order: Optional[torch.Tensor] = None, want_y=True, kind: str = "f32", num_bits: Optional[int] = None,
+                           lod: Optional[torch.Tensor] = None, lod_uniform: float = 0.0, fade=None,
+                           groups_per_field: int = 0) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+    """(y [B, N, 3] or None, dpoints [B, N, dim]): ``hash_fused_points_grad`` of B stacked fields, each at ITS OWN points, in ONE launch
+    (nic_hash_batch_points_grad).  ``data`` / ``kind`` / ``num_bits`` / ``params`` / ``points`` as ``hash_batch_forward_source``
+    takes them (fp32, uint8 or bit-packed stacks); exactly one of ``dy`` / ``target`` [B, N, 3]: the output gradient, or the colours of
+    loss_b = mean((y_b - target_b)^2) * ``loss_scale`` over field b's OWN ``counts[b]`` rows.  ``counts`` / ``order`` as
+    ``hash_batch_forward_backward_points``: rows at or past a field's count, and rows an ``order`` does not name, are not written (zero in
+    the tensors this call allocates).  ``want_y``: True, False, or a contiguous fp32 [B, N, 3] device tensor to write into.  Any of ``lod``
+    ([N] shared or [B, N]) / ``lod_uniform`` / ``fade`` makes it the call with a level of detail per point.  Tables and decoders are
+    constants: nothing is added anywhere, the same call gives the same bits."""
+    return _batch_points_grad(geo, data, points, params, dy, target, loss_scale, counts, order, want_y, kind, num_bits, lod, lod_uniform, fade,
+                              groups_per_field)
+
+
+@fused._on_tensor_device
+def hash_batch_forward_backward_points_grad(geo: HashGeometry, tables: torch.Tensor, points: torch.Tensor, params: Sequence[torch.Tensor],
+                                            target: torch.Tensor, mlp_grads: Sequence[torch.Tensor], lod: Optional[torch.Tensor] = None,
+                                            lod_uniform: float = 0.0, fade=None, table_grads: Optional[torch.Tensor] = None,
+                                            order: Optional[torch.Tensor] = None, counts=None, loss: Optional[torch.Tensor] = None,
+                                            loss_scale: float = 1.0, want_y=False, quant=None, add_grads: bool = False, add_loss: bool = False,
+                                            groups_per_field: int = 0, dpoints: Optional[torch.Tensor] = None):
+    """``hash_batch_forward_backward_points`` - with any of ``lod`` / ``lod_uniform`` / ``fade``, ``hash_batch_forward_backward_points_lod`` -
+    that also writes d loss_b / d points of the loss it returns for field b (nic_hash_batch_forward_backward_points_grad):
+    the same two launches, losses, y and gradients; the position gradient is ``hash_batch_points_grad``'s with ``target``, taken at the
+    parameters the forward used, noise and level weights constant; frozen tables (``table_grads`` None) still give it.  ``dpoints``: None
+    for a fresh tensor, or an fp32 [B, N, dim] device tensor that is overwritten (never added to, whatever ``add_grads`` says) at the rows
+    each field owns.  Returns (loss [B], y or None, dpoints)."""
+    return _batch_forward_backward_points(geo, tables, points, params, target, mlp_grads, table_grads, order, counts, loss, loss_scale, want_y, quant,
+                                          add_grads, add_loss, groups_per_field, None if _plain_lod(lod, lod_uniform, fade) else (lod, lod_uniform, fade),
+                                          dpoints=dpoints)
+
+
 @fused._on_tensor_device
 def hash_pack_bits_levels(geo: HashGeometry, table: torch.Tensor, level_bits, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """format /2 of an fp32 [L, T, F] table (nic_hash_pack_bits_levels): ``hash_pack_bits`` with ``level_bits[l]`` bits per value inside level
@@ -1647,6 +1783,42 @@ class _TrainPointsFunction(torch.autograd.Function):
     def backward(ctx, g):
         dp, = ctx.saved_tensors
         return g.reshape(()) * dp, None, None, None
+
+
+class _BatchQueryPointsFunction(torch.autograd.Function):
+    """``HashGridFieldBatch.query`` / ``query_lod`` as a differentiable op of the points (``query_differentiable``): backward =
+    ``point_gradient`` with the output gradient, summed over the fields for shared [N, dim] points; nothing for the fields' parameters"""
+
+    @staticmethod
+    def forward(ctx, points, batch, lod):
+        ctx.batch, ctx.lod = batch, lod
+        ctx.save_for_backward(points)
+        return batch.query(points) if lod is None else batch.query_lod(points, lod)
+
+    @staticmethod
+    def backward(ctx, dy):
+        points, = ctx.saved_tensors
+        dp = ctx.batch.point_gradient(points, dy=dy.contiguous(), lod=ctx.lod)[1]
+        return (dp.sum(0) if points.dim() == 2 else dp), None, None
+
+
+class _BatchTrainPointsFunction(torch.autograd.Function):
+    """``HashGridFieldBatch.train_points_grad`` as a differentiable op of the points (``train_points_differentiable``): the forward trains
+    the fields and keeps d loss_b / d points, the backward hands upstream[b] * dpoints[b] to the points (summed over the fields for shared
+    [N, dim] points)"""
+
+    @staticmethod
+    def forward(ctx, points, batch, target, kwargs):
+        loss, dp = batch.train_points_grad(points.detach(), target, **kwargs)
+        ctx.save_for_backward(dp)
+        ctx.shared = points.dim() == 2
+        return loss.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        dp, = ctx.saved_tensors
+        out = g.reshape(-1, 1, 1) * dp
+        return (out.sum(0) if ctx.shared else out), None, None, None
 
 
 def _table_of_u8(geo: HashGeometry, stored: torch.Tensor, num_bits: int) -> torch.Tensor:
@@ -2427,9 +2599,15 @@ class HashGridFieldBatch:
     gathered - in the batch's launches (nic_hash_batch_forward_points_lod, nic_hash_batch_forward_backward_points_lod), from the fp32 tables
     and from stored ones.  ``lod_fade``: the fade start of every level, shared by all fields (``hash_lod_fade(geo)`` unless assigned).
 
-    Not built: at points, passes in chunks with ragged counts, ``dpoints`` and the 16-bit modes with ``lod``; 16-bit
-    training; a bit depth per level (a ``/2`` file is read and refused), fields of differing geometry in one batch, a container format that
-    holds several fields in one file."""
+    Gradients to the point positions: ``point_gradient`` / ``jacobian`` / ``query_differentiable`` give d y / d points of
+    every field in ONE launch (nic_hash_batch_points_grad) from whatever tables the batch holds, and ``train_points_grad`` /
+    ``train_points_differentiable`` are ``train_points`` / ``train_points_lod`` that also return d loss_b / d points
+    (nic_hash_batch_forward_backward_points_grad) - ``HashGridField.train_points(fused=True, dpoints=)`` per field in the batch's three
+    launches: the frames of a jittered clip or the tiles of a scan are registered while they are fitted.
+
+    Not built (DESIGN 7): at points, passes in chunks with ragged counts, and the 16-bit modes with ``lod`` or with position gradients;
+    ``fit_points`` with positions; a gradient with respect to the level of detail; 16-bit training; a bit depth per level (a ``/2`` file is
+    read and refused), fields of differing geometry in one batch, a container format that holds several fields in one file."""
 
     def __init__(self, n_fields: int, field_size: Union[int, Sequence[int]], levels: int = 16, features: int = 2, log2_table: int = 19,
                  base_resolution: float = 16, finest_resolution: Optional[float] = None, device=None, seed: Optional[int] = None,
@@ -2687,8 +2865,9 @@ class HashGridFieldBatch:
         return self._train_points(points, target, counts, accumulate, scale, step, noise, order, lod)
 
     @torch.no_grad()
-    def _train_points(self, points, target, counts, accumulate, scale, step, noise, order, lod) -> torch.Tensor:
-        """``train_points`` (``lod`` None: exactly the calls it always made) and ``train_points_lod``"""
+    def _train_points(self, points, target, counts, accumulate, scale, step, noise, order, lod, dpoints=False):
+        """``train_points`` (``lod`` None: exactly the calls it always made) and ``train_points_lod``; with ``dpoints`` - None or the tensor
+        to fill - ``train_points_grad``: the same bookkeeping around the joint entry, and (loss, dpoints) back"""
         self._refuse_decode_only("train_points")
         frozen = self.frozen
         lod_t, lod_u = (None, 0.0) if lod is None else self._lod_args(lod)
@@ -2708,7 +2887,12 @@ class HashGridFieldBatch:
                 grad.zero_()
             self._pass_samples = 0
         quant = (self.num_bits, self.noise_seed, self.steps, self._pass_samples) if noise else None
-        if lod is None:
+        if dpoints is not False:
+            loss, _, dpoints = hash_batch_forward_backward_points_grad(
+                self.geo, self.tables, pts, self.params, target, self._gm, lod_t, lod_u, None if lod is None else self.lod_fade, table_grads=grad,
+                order=order, counts=counts, loss_scale=float(scale), quant=quant, add_grads=accumulate, groups_per_field=self._point_groups(n),
+                dpoints=dpoints)
+        elif lod is None:
             loss, _ = hash_batch_forward_backward_points(self.geo, self.tables, pts, self.params, target, self._gm, table_grads=grad, order=order,
                                                          counts=counts, loss_scale=float(scale), quant=quant, add_grads=accumulate,
                                                          groups_per_field=self._point_groups(n))
@@ -2721,7 +2905,38 @@ class HashGridFieldBatch:
             self._grad_clean = False
         if step:
             self.apply_step()
-        return loss
+        return loss if dpoints is False else (loss, dpoints)
+
+    @torch.no_grad()
+    def train_points_grad(self, points: torch.Tensor, target: torch.Tensor, dpoints: Optional[torch.Tensor] = None, lod=None, counts=None,
+                          accumulate: bool = False, scale: float = 1.0, step: bool = True, noise: Optional[bool] = None, order=None):
+        """``train_points`` (with ``lod``: ``train_points_lod``) that also returns d loss_b / d points of every field's loss -
+        ``HashGridField.train_points(fused=True, dpoints=)`` for every field at once, in the same three launches
+        (nic_hash_batch_forward_backward_points_grad): the fields step as they always do, and the positions - the shift of a frame, the offset
+        of a tile, a pose - can be stepped from the same forward.  Returns (loss [B], dpoints [B, N, dim]); ``dpoints``: None for a fresh
+        tensor (zero at the rows a field does not own), or a contiguous fp32 [B, N, dim] device tensor that is overwritten at the rows each
+        field owns, whatever ``accumulate`` says: each chunk of an accumulated pass fills its own.  The gradient is taken at the parameters
+        the forward used (before this call's optimiser step), the noise and the level weights constant; after ``freeze()`` it still comes.
+        Every other argument, the bookkeeping and the noise keys are ``train_points``'."""
+        self._refuse_decode_only("train_points_grad")
+        if dpoints is not None:
+            n, _, _ = self._check_train_points(points, target, counts, order)
+            _check_batch_dpoints_shape(self.geo, self.n_fields, n, dpoints)
+        return self._train_points(points, target, counts, accumulate, scale, step, noise, order, lod, dpoints=dpoints)
+
+    def train_points_differentiable(self, points: torch.Tensor, target: torch.Tensor, **kwargs) -> torch.Tensor:
+        """``train_points_grad(points, target, **kwargs)`` as a differentiable op of ``points``: the call steps the fields as
+        it always does and returns the [B] losses, whose backward hands upstream[b] * d loss_b / d points[b] to ``points`` - summed over the
+        fields when ``points`` is the shared [N, dim] - so a torch optimiser on whatever produced the positions (a shift per frame, an
+        offset per tile) steps from the same forward.  No gradient reaches the fields' parameters through autograd: their step is the
+        call's own.  Without ``points.requires_grad``, or under ``torch.no_grad()``, it is plain ``train_points`` / ``train_points_lod``."""
+        if "dpoints" in kwargs:
+            raise TypeError("train_points_differentiable keeps dpoints for the backward: call train_points_grad for the tensor itself")
+        if not (isinstance(points, torch.Tensor) and points.requires_grad and torch.is_grad_enabled()):
+            kwargs = dict(kwargs)
+            lod = kwargs.pop("lod", None)
+            return self.train_points(points, target, **kwargs) if lod is None else self.train_points_lod(points, target, lod, **kwargs)
+        return _BatchTrainPointsFunction.apply(points, self, target, kwargs)
 
     def fit_points(self, points: torch.Tensor, target: torch.Tensor, epochs: int, counts=None, order="cell", freeze_at: float = 0.95) -> List[List[float]]:
         """``HashGridField.fit_points(fused=True)`` for every field on its own fixed sample set: ``epochs`` passes over ``points`` / ``target`` /
@@ -2913,6 +3128,60 @@ class HashGridFieldBatch:
         if lod is not None:
             return hash_batch_forward_points_lod(self.geo, data, points, params, lod_t, lod_u, self.lod_fade, kind, bits, groups_per_field=groups)
         return hash_batch_forward_source(self.geo, data, params, kind, bits, points=points, groups_per_field=groups)
+
+    @torch.no_grad()
+    def point_gradient(self, points: torch.Tensor, dy: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None, scale: float = 1.0,
+                       counts=None, order=None, lod=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(y [B, N, 3], dpoints [B, N, dim]): ``query(points)`` (``query_lod`` with ``lod``) and the gradient with respect to the point
+        COORDINATES - ``HashGridField.point_gradient`` of every field in ONE launch (nic_hash_batch_points_grad), from
+        whatever tables the batch holds: a batch from ``load_compressed`` works.  ``points`` [N, dim] shared or [B, N, dim]; exactly one of
+        ``dy`` [B, N, 3] (the gradient of sum(y * dy)) and ``target`` [B, N, 3] (of mean((y_b - target_b)^2) * ``scale`` over field b's own
+        rows).  ``counts`` / ``order`` (None, "cell" or an int32 [B, N] tensor) as ``train_points``: rows at or past a field's count are zero
+        in both outputs.  ``lod``: a finite float, a tensor [N] or [B, N].  The fields' parameters are constants here: no ``.grad`` is
+        touched and no optimiser state moves."""
+        n = _check_batch_points(self.geo, points, self.n_fields)
+        if (dy is None) == (target is None):
+            raise ValueError("exactly one of dy and target: the gradient of the output, or the colours of a mean squared error")
+        for name, v in (("dy", dy), ("target", target)):
+            if v is not None and (not isinstance(v, torch.Tensor) or tuple(v.shape) != (self.n_fields, n, 3)):
+                raise ValueError(f"{name} must be [{self.n_fields}, {n}, 3], got {tuple(v.shape) if isinstance(v, torch.Tensor) else type(v).__name__}")
+        counts = _check_batch_counts(counts, self.n_fields, n)
+        if isinstance(order, str):
+            if order != "cell":
+                raise ValueError(f"order {order!r}: None, 'cell' or an int32 [{self.n_fields}, {n}] tensor")
+        else:
+            order = _check_batch_order(order, self.n_fields, n)
+        lod_t, lod_u = (None, 0.0) if lod is None else self._lod_args(lod)
+        lod_t = _check_batch_lod(lod_t, self.n_fields, n)
+        _point_desc(self.geo)
+        _require_on_device(points, "points")
+        pts = _stack_points(points, self.n_fields)
+        if isinstance(order, str):
+            order = hash_batch_point_order(self.geo, pts, counts)
+        data, kind, bits = self._table_source()
+        return hash_batch_points_grad(self.geo, data, pts, [p.detach() for p in self.params], dy=dy, target=target, loss_scale=float(scale), counts=counts,
+                                      order=order, want_y=True, kind=kind, num_bits=bits, lod=lod_t, lod_uniform=lod_u,
+                                      fade=None if lod is None else self.lod_fade, groups_per_field=self._point_groups(max(n, 1)))
+
+    def jacobian(self, points: torch.Tensor, lod=None) -> torch.Tensor:
+        """[B, N, 3, dim]: d y[b, n, o] / d points[b, n, a], as three ``point_gradient`` calls with a one-hot ``dy``"""
+        n = _check_batch_points(self.geo, points, self.n_fields)
+        rows = []
+        for o in range(3):
+            dy = torch.zeros(self.n_fields, n, 3, dtype=torch.float32, device=points.device)
+            dy[..., o] = 1.0
+            rows.append(self.point_gradient(points, dy=dy, lod=lod)[1])
+        return torch.stack(rows, dim=2)
+
+    def query_differentiable(self, points: torch.Tensor, lod=None) -> torch.Tensor:
+        """``query(points)`` (``query_lod`` with ``lod``) as a differentiable op of ``points``: the backward hands the output gradient to
+        ``point_gradient`` - for shared [N, dim] points summed over the fields - so ``points.requires_grad_()`` works with any torch loss
+        and optimiser on the positions or on whatever produced them.  No gradient reaches the fields' parameters through it.  Without
+        ``points.requires_grad``, or under ``torch.no_grad()``, it is the plain call."""
+        if not (isinstance(points, torch.Tensor) and points.requires_grad and torch.is_grad_enabled()):
+            return self.query(points) if lod is None else self.query_lod(points, lod)
+        _check_batch_points(self.geo, points, self.n_fields)
+        return _BatchQueryPointsFunction.apply(points, self, lod)
 
     @torch.no_grad()
     def resample(self, size: Union[int, Sequence[int]], tile: int = 1024, precision: Optional[str] = None) -> torch.Tensor:
