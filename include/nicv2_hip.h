@@ -750,7 +750,7 @@ int nic_hash_fused_forward_p16(const nic_hash_desc *desc, const nic_hash_source 
  *      - noise is additive on the row and does not enter.
  *      - level of detail: lodp == NULL is none (then lod must be NULL too, else NIC_E_ARG); else a_l is nic_hash_encode_points_lod's and depends
  *        on lambda only: a level of weight 0 is not gathered and adds nothing, a level no lane of a wave weighs is skipped by the wave.  There is
- *        no gradient with respect to lambda.
+ *        no gradient with respect to lambda from these two entries: the _grad_lod entries of nicv2_hip_ext.h give it next to dpoints.
  *      - outputs are WRITTEN, not added; row n belongs to point n; there are no atomics: the same call gives the same bits.
  *      nic_hash_encode_points_grad: dx = [n_points, L F] (d loss / d row), dpoints = [n_points, dim]; one lane per point; the three sources,
  *        dim 2 / 3, features 1 / 2 / 4 / 8.

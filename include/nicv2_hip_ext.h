@@ -149,6 +149,39 @@ int nic_hash_batch_forward_backward_points_grad(const nic_hash_desc *desc, int n
                                                 float *table_grads, const nic_mlp_grads *mlp_grads, float *loss, float *y, float *dpoints,
                                                 int flags, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- The gradient with respect to the LEVEL OF DETAIL of a point, next to the one with respect to its coordinates (hashgrid.py,
+ *      hash_encode_points_grad_lod, hash_fused_points_grad_lod, HashGridField.point_gradient_lod / jacobian_lod / query_differentiable_lod;
+ *      csrc/hashgrid_lodgrad.hip).  nic_hash_encode_points_grad_lod is nic_hash_encode_points_grad and
+ *      nic_hash_fused_points_grad_lod is nic_hash_fused_points_grad, argument for argument, with dlod after dpoints: the same gathers, y and
+ *      dpoints of the siblings called with the same nic_hash_lod bit for bit, one launch, no atomics - the same call gives the same bits.
+ *      Notation of nic_hash_encode_points_lod: lambda_raw = (lod ? lod[n] : 0) + lod_uniform in fp32; lambda is lambda_raw with NaN -> 0,
+ *      clamped to [0, 32]; a_raw = (fade[l] - lambda) + 1.0f in fp32, in exactly that order (the level weight before its clamp).  Level l is
+ *      ON THE RAMP iff 0 < a_raw <= 1 - the right-hand derivative, "what happens when the footprint grows": a level exactly at its fade start
+ *      (a_raw == 1) has slope -1, a level exactly at its end (a_raw == 0) has slope 0 and is not gathered.  An integer lambda with the
+ *      default fades hits these kinks exactly; the convention is part of the contract.
+ *          dlod[n] = - sum_{l on the ramp} sum_f g[n, l F + f] r[n, l, f]
+ *      g = d loss / d row, the gradient of the WEIGHED column (dx of the layer-wise entry; the decoder's backward of the fused one);
+ *      r = the unweighed blend sum_c prod_a cw_a(c) value[l, idx(v + c), f] from the fp32, uint8 or bit-packed table.  Noise does not
+ *      enter: these entries have no quant.  dlod[n] is exactly 0.0f when lambda_raw < 0, lambda_raw >= 32 or lambda_raw is NaN (the
+ *      right-hand derivative of the clamp); lambda_raw == 0 passes the gradient through.  Positions enter only through r, taken at the
+ *      rounded and clamped position the forward uses: a clamped axis does not zero dlod.  dlod = [n_points] fp32 on the device, row n
+ *      WRITTEN (never added to) by the lane of point n; nothing past n_points is touched.  The gradient for lod_uniform is the sum of dlod;
+ *      the caller forms it.  There is no gradient with respect to fade, no second derivative and no batched or training-step form.
+ *      Host checks, all before any GPU work, are the siblings' in the siblings' order with two changes: lodp == NULL is NIC_E_NULL,
+ *      reported with the other pointers (these are _lod entries), and dlod == NULL is NIC_E_NULL.  Layer-wise: the descriptor of a point
+ *      source (check of nic_hash_encode_points: NIC_E_NULL / NIC_E_ARG / NIC_E_SHAPE); null lodp, src, src->data, points, dx, dpoints or
+ *      dlod (NIC_E_NULL; lod may be null); the source (NIC_E_ARG: kind, num_bits, alignment); the nic_hash_lod (NIC_E_ARG: a fade[l], l <
+ *      levels, not finite or negative, lod_uniform not finite, reserved != 0); n_points < 0 (NIC_E_ARG); n_points == 0 is NIC_OK without a
+ *      launch.  Fused: null desc / mlp (NIC_E_NULL); the fused set (nic_hash_fused_supported's code); the descriptor of a point source;
+ *      null lodp, src, src->data, points, dpoints or dlod, then a null decoder layer (NIC_E_NULL; lod, dy, target and y may be null); the
+ *      source; the nic_hash_lod; both or neither of dy / target (NIC_E_ARG); n_points < 0 (NIC_E_ARG); n_points == 0 is NIC_OK without a
+ *      launch. */
+int nic_hash_encode_points_grad_lod(const nic_hash_desc *desc, const nic_hash_lod *lodp, const nic_hash_source *src, const float *points,
+                                    const float *lod, int64_t n_points, const float *dx, float *dpoints, float *dlod, void *stream);
+int nic_hash_fused_points_grad_lod(const nic_hash_desc *desc, const nic_hash_lod *lodp, const nic_hash_source *src, const float *points,
+                                   const float *lod, int64_t n_points, const nic_mlp *mlp, const float *dy, const float *target,
+                                   float loss_scale, float *y, float *dpoints, float *dlod, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,12 @@ interpolant at the rounded position, 0 on an axis where the point lies outside t
 into a position gradient, ``hash_fused_points_grad`` does gather, decoder, its backward to the row and the position gradient in one launch;
 ``HashGridField.point_gradient`` / ``jacobian`` / ``query_differentiable`` are the surface.  The field's parameters are constants there.
 
+Gradients with respect to the level of detail (include/nicv2_hip_ext.h, nic_hash_encode_points_grad_lod; csrc/hashgrid_lodgrad.hip):
+column l F + f is a_l r[l, f] with a_l = clamp((fade[l] - lambda) + 1, 0, 1), so dlod[n] = - sum over the levels on the ramp 0 < a_raw <= 1 of
+sum_f g[n, l F + f] r[n, l, f] - the right-hand derivative, one more accumulator on the position gradient's walk, exactly 0 where lambda itself
+is clamped.  ``hash_encode_points_grad_lod`` / ``hash_fused_points_grad_lod`` return it next to dpoints; ``HashGridField.point_gradient_lod`` /
+``jacobian_lod`` / ``query_differentiable_lod`` are the surface.
+
 B fields per launch (include/nicv2_hip.h, nic_hash_batch_forward_backward; csrc/hashgrid_batch.hip): ``HashGridFieldBatch`` holds
 the stacked tables [B, L, T, F] and decoder tensors of B fields of one geometry; a workgroup of the batched kernel belongs to one field, a step is
 three launches whatever B is (the kernel, the reduction per field, one ``FusedAdam`` over the stacked tensors), ``decode`` one per tile.
@@ -1405,6 +1411,68 @@ def hash_fused_points_grad(geo: HashGeometry, data: torch.Tensor, points: torch.
     return y, out
 
 
+# ---- the gradient with respect to the level of detail, next to the one with respect to the points (include/nicv2_hip_ext.h) ------
+@fused._on_tensor_device
+def hash_encode_points_grad_lod(geo: HashGeometry, data: torch.Tensor, points: torch.Tensor, dx: torch.Tensor, kind: str = "f32",
+                                num_bits: Optional[int] = None, lod: Optional[torch.Tensor] = None, lod_uniform: float = 0.0,
+                                fade=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(dpoints [N, dim], dlod [N]) for the [N, L F] gradient ``dx`` of ``hash_encode_points_lod`` (nic_hash_encode_points_grad_lod; DESIGN
+    4.7.22): ``dpoints`` is ``hash_encode_points_grad``'s with the same level of detail bit for bit; ``dlod[n]`` = - sum over the levels on
+    the ramp 0 < (fade[l] - lambda) + 1 <= 1 of sum_f dx[n, l F + f] r[n, l, f], r the unweighed blend - the right-hand derivative with
+    respect to lambda_n, exactly 0 where lambda_raw < 0, >= 32 or NaN.  Always a level-of-detail launch: ``lod`` None, ``lod_uniform`` 0 and
+    ``fade`` None is lambda = 0 with the default fades.  Written, not added; the gradient for ``lod_uniform`` is ``dlod.sum()``."""
+    src, data = _point_source(geo, data, kind, num_bits)
+    pts = _check_points(geo, points)
+    n = pts.shape[0]
+    dx = _lib.require_cuda_f32(dx.detach() if isinstance(dx, torch.Tensor) else dx, "dx")
+    if tuple(dx.shape) != (n, geo.width):
+        raise ValueError(f"dx must be [{n}, {geo.width}], got {tuple(dx.shape)}")
+    lod_t = _check_lod(lod, n, pts.device)
+    lp = _lod_struct(geo, fade, lod_uniform)
+    d = _point_desc(geo)
+    out = torch.empty(n, geo.dim, dtype=torch.float32, device=data.device)
+    dlod = torch.empty(n, dtype=torch.float32, device=data.device)
+    if n == 0:
+        return out, dlod
+    _lib.check(_lib.load().nic_hash_encode_points_grad_lod(ctypes.byref(d), ctypes.byref(lp), ctypes.byref(src), _lib.ptr(pts), _lib.ptr(lod_t), n,
+                                                           _lib.ptr(dx), _lib.ptr(out), _lib.ptr(dlod), _lib.stream_ptr(data.device)),
+               "nic_hash_encode_points_grad_lod")
+    return out, dlod
+
+
+@fused._on_tensor_device
+def hash_fused_points_grad_lod(geo: HashGeometry, data: torch.Tensor, points: torch.Tensor, params: Sequence[torch.Tensor],
+                               dy: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None, loss_scale: float = 1.0,
+                               want_y: bool = True, kind: str = "f32", num_bits: Optional[int] = None, lod: Optional[torch.Tensor] = None,
+                               lod_uniform: float = 0.0, fade=None) -> Tuple[Optional[torch.Tensor], torch.Tensor, torch.Tensor]:
+    """(y [N, 3] or None, dpoints [N, dim], dlod [N]) in one launch (nic_hash_fused_points_grad_lod): ``hash_fused_points_grad``
+    with the same level of detail - y and dpoints bit for bit - and the gradient with respect to lambda_n of ``hash_encode_points_grad_lod``
+    for the row gradient the decoder's backward leaves on the chip.  Always a level-of-detail launch."""
+    n = points.shape[0] if isinstance(points, torch.Tensor) and points.dim() == 2 else -1
+    if n >= 0:
+        _check_dy_target(dy, target, n)
+    src, data = _point_source(geo, data, kind, num_bits)
+    params = _check_fused_decoder(geo, [q.detach() for q in params])
+    pts = _check_points(geo, points)
+    n = pts.shape[0]
+    _check_dy_target(dy, target, n)
+    dy = None if dy is None else _lib.require_cuda_f32(dy.detach(), "dy")
+    target = None if target is None else _lib.require_cuda_f32(target.detach(), "target")
+    lod_t = _check_lod(lod, n, pts.device)
+    lp = _lod_struct(geo, fade, lod_uniform)
+    d, m = _point_desc(geo), fused._mlp_struct(params)
+    y = torch.empty(n, 3, dtype=torch.float32, device=data.device) if want_y else None
+    out = torch.empty(n, geo.dim, dtype=torch.float32, device=data.device)
+    dlod = torch.empty(n, dtype=torch.float32, device=data.device)
+    if n == 0:
+        return y, out, dlod
+    _lib.check(_lib.load().nic_hash_fused_points_grad_lod(ctypes.byref(d), ctypes.byref(lp), ctypes.byref(src), _lib.ptr(pts), _lib.ptr(lod_t), n,
+                                                          ctypes.byref(m), _lib.ptr(dy), _lib.ptr(target), float(loss_scale), _lib.ptr(y),
+                                                          _lib.ptr(out), _lib.ptr(dlod), _lib.stream_ptr(data.device)),
+               "nic_hash_fused_points_grad_lod")
+    return y, out, dlod
+
+
 # ---- B fields per launch with the gradient with respect to the point coordinates (DESIGN 4.7.21; include/nicv2_hip_ext.h) ------------------------
 def _check_batch_dpoints_shape(geo: HashGeometry, n_fields: int, n: int, dpoints) -> None:
     """``_check_dpoints`` for a batch, the part the host decides: an fp32 [B, N, dim] tensor, contiguous - the kernel writes it in place"""
@@ -1765,6 +1833,29 @@ class _QueryPointsFunction(torch.autograd.Function):
     def backward(ctx, dy):
         points, = ctx.saved_tensors
         return ctx.field.point_gradient(points, dy=dy.contiguous(), lod=ctx.lod)[1], None, None
+
+
+class _QueryPointsLodFunction(torch.autograd.Function):
+    """``HashGridField.query(points, lod)`` as a differentiable op of the points and of the level of detail (``query_differentiable_lod``):
+    backward = ``point_gradient_lod`` with the output gradient - ``dlod`` for a per-point ``lod``, its sum for a 0-dim one; nothing for the
+    field's parameters"""
+
+    @staticmethod
+    def forward(ctx, points, lod, field):
+        ctx.field = field
+        ctx.lod = None if isinstance(lod, torch.Tensor) else lod
+        ctx.save_for_backward(points, *([lod] if isinstance(lod, torch.Tensor) else []))
+        return field.query(points, lod=lod)
+
+    @staticmethod
+    def backward(ctx, dy):
+        points, *rest = ctx.saved_tensors
+        lod = rest[0] if rest else ctx.lod
+        _, dpoints, dlod = ctx.field.point_gradient_lod(points, lod, dy=dy.contiguous())
+        glod = None
+        if rest and ctx.needs_input_grad[1]:
+            glod = (dlod if lod.dim() > 0 else dlod.sum()).to(lod.dtype).reshape(lod.shape)
+        return (dpoints if ctx.needs_input_grad[0] else None), glod, None
 
 
 class _TrainPointsFunction(torch.autograd.Function):
@@ -2501,6 +2592,71 @@ class HashGridField:
         if not (isinstance(points, torch.Tensor) and points.requires_grad and torch.is_grad_enabled()):
             return self.query(points, lod=lod)
         return _QueryPointsFunction.apply(points, self, lod)
+
+    def point_gradient_lod(self, points: torch.Tensor, lod, dy: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None,
+                           scale: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(y [N, 3], dpoints [N, dim], dlod [N]): ``point_gradient(points, dy, target, scale, lod=lod)`` - y and dpoints bit for bit - and
+        the gradient of the same loss with respect to the LEVEL OF DETAIL of each point, ``lod`` a float or a [N] tensor as in
+        ``query``.  ``dlod[n]`` = - sum over the levels on the ramp (0 < (fade[l] - lambda_n) + 1 <= 1, the right-hand derivative: a level
+        exactly at its fade start counts, one exactly at its end does not) of the row gradient times the unweighed blend of the level;
+        exactly 0 where lambda_n < 0, >= 32 or NaN; a point outside the field has the clamped point's.  The gradient for a launch-wide
+        ``lod`` is ``dlod.sum()``.  One launch on the fused route (nic_hash_fused_points_grad_lod); encode, general decoder forward and
+        backward and nic_hash_encode_points_grad_lod on the layer-wise one.  Reads whichever table the field holds; the field's parameters
+        are constants: no ``.grad`` is touched and no optimiser state moves."""
+        if self.level_bits is not None:
+            raise NotImplementedError("gradients with respect to the level of detail with a bit depth per level are not built (DESIGN 7): use a "
+                                      "uniform num_bits")
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != self.geo.dim:
+            raise ValueError(f"points must be [N, {self.geo.dim}] for a {self.geo.dim}D field, got "
+                             f"{tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__}")
+        n = points.shape[0]
+        _check_dy_target(dy, target, n)
+        if lod is None:
+            raise ValueError("lod is a float or a [N] tensor: the level of detail the gradient is taken at")
+        lod_t, lod_u = self._lod_args(lod)
+        fade = self.lod_fade
+        pts = _check_points(self.geo, points)
+        data, kind, bits = self._point_table()
+        params = [p.detach() for p in self.decoder.linear_params()]
+        if self.route == "fused":
+            return hash_fused_points_grad_lod(self.geo, data, pts, params, dy=dy, target=target, loss_scale=scale, want_y=True, kind=kind,
+                                              num_bits=bits, lod=lod_t, lod_uniform=lod_u, fade=fade)
+        if n == 0:
+            return (torch.empty(0, 3, dtype=torch.float32, device=self.device), torch.empty(0, self.geo.dim, dtype=torch.float32, device=self.device),
+                    torch.empty(0, dtype=torch.float32, device=self.device))
+        x = hash_encode_points_lod(self.geo, data, pts, lod_t, lod_u, fade, kind, bits)
+        with torch.enable_grad():
+            x.requires_grad_(True)
+            y = fused.DecoderFunction.apply(x, *params)
+            if dy is None:
+                g = (y.detach() - _lib.require_cuda_f32(target.detach(), "target")) * (2.0 * float(scale) / (3.0 * n))
+            else:
+                g = _lib.require_cuda_f32(dy.detach(), "dy")
+            dx, = torch.autograd.grad(y, x, g)
+        dpoints, dlod = hash_encode_points_grad_lod(self.geo, data, pts, dx, kind, bits, lod=lod_t, lod_uniform=lod_u, fade=fade)
+        return y.detach(), dpoints, dlod
+
+    def jacobian_lod(self, points: torch.Tensor, lod) -> torch.Tensor:
+        """[N, 3]: d y[n, o] / d lambda_n, as three ``point_gradient_lod`` calls with a one-hot ``dy``"""
+        cols = []
+        for o in range(3):
+            dy = torch.zeros(points.shape[0], 3, dtype=torch.float32, device=points.device)
+            dy[:, o] = 1.0
+            cols.append(self.point_gradient_lod(points, lod, dy=dy)[2])
+        return torch.stack(cols, dim=1)
+
+    def query_differentiable_lod(self, points: torch.Tensor, lod) -> torch.Tensor:
+        """``query(points, lod)`` as a differentiable op of ``points`` and / or ``lod`` - a [N] tensor, or a 0-dim tensor (one level of detail
+        for the launch, whose gradient is the sum of the per-point ones): the backward hands the output gradient to ``point_gradient_lod``, so
+        a zoom, a blur or a mip bias can be descended on with any torch loss and optimiser.  With nothing that requires a gradient, or under
+        ``no_grad``, it is the plain ``query`` call.  No gradient reaches the field's parameters through it."""
+        if self.level_bits is not None:
+            raise NotImplementedError("gradients with respect to the level of detail with a bit depth per level are not built (DESIGN 7): use a "
+                                      "uniform num_bits")
+        wants = any(isinstance(t, torch.Tensor) and t.requires_grad for t in (points, lod))
+        if not (wants and torch.is_grad_enabled()):
+            return self.query(points, lod=lod)
+        return _QueryPointsLodFunction.apply(points, lod, self)
 
     def _resample_points(self, size: Sequence[int], origin: Sequence[int], extent: Sequence[int]) -> torch.Tensor:
         """[prod(extent), dim] fp32 points of the block ``origin`` .. ``origin + extent`` of a regular grid of ``size`` samples over the field,
