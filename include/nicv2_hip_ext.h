@@ -182,6 +182,51 @@ int nic_hash_fused_points_grad_lod(const nic_hash_desc *desc, const nic_hash_lod
                                    const float *lod, int64_t n_points, const nic_mlp *mlp, const float *dy, const float *target,
                                    float loss_scale, float *y, float *dpoints, float *dlod, void *stream);
 
+/* ---- The gradient with respect to the LEVEL OF DETAIL from the TRAINING STEP (hashgrid.py, hash_fused_forward_backward_points_grad_lod,
+ *      hash_encode_points_grad_lod_noisy, HashGridField.train_points_grad_lod / train_points_differentiable_lod; csrc/hashgrid_lodtrain.hip;
+ *      DESIGN 4.7.23).  Notation of the section above: lambda_raw, lambda, a_raw = (fade[l] - lambda) + 1.0f in fp32 in that order; level l is
+ *      ON THE RAMP iff 0 < a_raw <= 1; passes(n) iff 0 <= lambda_raw < 32.  The row a training step decodes carries the codec noise INSIDE
+ *      the weighed column - column l F + f is a_l (r[n, l, f] + nz[n, l F + f]) - so the slope on the ramp is -(r + nz), not -r:
+ *          dlod[n] = passes(n) ? - sum_{l on the ramp} sum_f g[n, l F + f] (r[n, l, f] + nz[n, l F + f]) : 0
+ *      g = d loss / d row of the loss the call returns, loss_scale mean((y - target)^2), taken at the parameters the forward used, before
+ *      the tail's step (the layer-wise entry: dx); r = the unweighed blend at the rounded, clamped position; nz = exactly the noise value
+ *      the forward added to that column: the same key sample_base + n with n the CALLER'S ROW (order[pos] with an order), the same generator
+ *      block, the same byte of it; nz is 0 without noise.  The kink rules of the section above hold unchanged: the right-hand derivative,
+ *      a_raw == 1 has slope -1, a_raw == 0 has slope 0 and is not gathered, dlod is exactly 0.0f where lambda is clamped or NaN, a clamped
+ *      axis zeroes its dpoints and not dlod.  Row n of dpoints and dlod is WRITTEN once by its lane - with an order that is row order[pos] -,
+ *      never added to and touched by no atomic, whatever NIC_HASH_FUSED_ADD_GRADS says; nothing past n_points is touched, and a call with
+ *      n_points == 0 touches nothing.
+ *      nic_hash_fused_forward_backward_points_grad_lod is nic_hash_fused_forward_backward_points_grad, argument for argument, with dlod
+ *      [n_points] after dpoints and a level of detail always on: lodp == NULL and dlod == NULL are NIC_E_NULL among the pointers.  Everything
+ *      else is the sibling's called with the same nic_hash_lod: the same two launches, records, fixed-order reduction, flags, tail,
+ *      nic_mark_kernel_end, workspace (nic_hash_fused_points_workspace_bytes), noise, loss, y, decoder gradients and table gradient;
+ *      table_grad == NULL (a frozen table) still produces dpoints, dlod and the decoder records; dpoints is the sibling's bit for bit, and
+ *      without noise dlod is nic_hash_fused_points_grad_lod's with target on the same table bit for bit.
+ *      Host checks, all before any GPU work, in the sibling's order with its codes: null desc / mlp (NIC_E_NULL); the fused set
+ *      (nic_hash_fused_supported's code); the descriptor of a point source (NIC_E_SHAPE / NIC_E_ARG); null lodp, table, points, decoder
+ *      layer, target, mlp_grads, loss, dpoints, dlod or workspace (NIC_E_NULL; quant, lod, order, table_grad, y and tail may be null); flags
+ *      (NIC_E_ARG); the nic_hash_lod (NIC_E_ARG); quant (num_bits 1 .. 8, sample_base >= 0, noise_mode: NIC_E_ARG; NIC_NOISE_TENSOR is
+ *      NIC_E_UNSUPPORTED); n_points < 0, or >= 2^31 with an order (NIC_E_ARG); the workspace (NIC_E_WORKSPACE); the tail (its codes);
+ *      n_points == 0 is NIC_OK with nothing written.
+ *      nic_hash_encode_points_grad_lod_noisy is the layer-wise sibling for the fp32 table, since training reads nothing else:
+ *      nic_hash_encode_points_grad_lod from `table` [L, T, F] fp32 with a NULLABLE nic_hash_quant checked as the training entries check it.
+ *      With quant == NULL or noise_mode NIC_NOISE_NONE its dpoints and dlod are nic_hash_encode_points_grad_lod's from an fp32 source bit
+ *      for bit; with NIC_NOISE_KERNEL dpoints stays that (noise is a constant of the positions) and dlod gains the nz term.  One launch, no
+ *      atomics, the same call gives the same bits.
+ *      Host checks: the descriptor of a point source; null lodp, table, points, dx, dpoints or dlod (NIC_E_NULL; quant and lod may be
+ *      null); the nic_hash_lod (NIC_E_ARG); quant (as above); n_points < 0 (NIC_E_ARG); n_points == 0 is NIC_OK without a launch.
+ *      There is no batched form, no bit depth per level, no 16-bit precision mode, no stored table, no second derivative and no gradient
+ *      with respect to fade. */
+int nic_hash_encode_points_grad_lod_noisy(const nic_hash_desc *desc, const nic_hash_lod *lodp, const nic_hash_quant *quant, const float *table,
+                                          const float *points, const float *lod, int64_t n_points, const float *dx, float *dpoints,
+                                          float *dlod, void *stream);
+int nic_hash_fused_forward_backward_points_grad_lod(const nic_hash_desc *desc, const nic_hash_lod *lodp, const nic_hash_quant *quant,
+                                                    const float *table, const float *points, const float *lod, int64_t n_points,
+                                                    const int32_t *order, const nic_mlp *mlp, const float *target, float loss_scale,
+                                                    float *table_grad, const nic_mlp_grads *mlp_grads, float *loss, float *y, float *dpoints,
+                                                    float *dlod, int flags, void *workspace, size_t workspace_bytes,
+                                                    const nic_step_tail *tail, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,11 +18,11 @@ OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libnicv2_hip.so")
 SOURCES = ["simple_kernels.hip", "decoder_general.hip", "fused_capi.hip", "fused_m1.hip", "fused_m2.hip", "fused_m3.hip", "fused_m4.hip", "fused_t16.hip", "fused_mlpn.hip", "fused_q1.hip", "fused_q2.hip", "fused_q3.hip", "fused_q4.hip",
            "hash_grid.hip", "hash_fused.hip", "hash_points.hip", "hash_points_train.hip", "hash_mixed.hip", "hashgrid_fused16.hip", "hashgrid_pointgrad.hip", "hashgrid_points_joint.hip", "hashgrid_batch.hip",
-           "hashgrid_batch_grad.hip", "hashgrid_lodgrad.hip"]
+           "hashgrid_batch_grad.hip", "hashgrid_lodgrad.hip", "hashgrid_lodtrain.hip"]
 # the lists of csrc/fused_capi.hip (NIC_CP_LIST, NIC_ML_LIST): one object per entry, compiled from one source with the entry as NIC_ENTRY
 LISTED = {"NIC_CP_LIST": ("fused_qc.hip", "fused_qc_{}_{}_{}.o"),        # (layout, C, P): non-default channel counts on the plain-bf16 kernels
           "NIC_ML_LIST": ("fused_ml.hip", "fused_ml_{}_{}_{}.o")}        # (levels, C, n_linear): multi-level layouts (fused_q16.hpp::QML)
-HEADERS = ["nic_device.hpp", "nic_adam.hpp", "fused_kernel.hpp", "fused_dispatch.hpp", "fused_launch.hpp", "fused_train16.hpp", "fused_mlpn.hpp", "fused_q16.hpp", "fused_q16_launch.hpp", "hash_common.hpp", "hashgrid_pointgrad.hpp", "hashgrid_lodgrad.hpp", "hashgrid_batch.hpp", os.path.join("..", "..", "include", "nicv2_hip.h"),
+HEADERS = ["nic_device.hpp", "nic_adam.hpp", "fused_kernel.hpp", "fused_dispatch.hpp", "fused_launch.hpp", "fused_train16.hpp", "fused_mlpn.hpp", "fused_q16.hpp", "fused_q16_launch.hpp", "hash_common.hpp", "hashgrid_pointgrad.hpp", "hashgrid_lodgrad.hpp", "hashgrid_lodtrain.hpp", "hashgrid_batch.hpp", os.path.join("..", "..", "include", "nicv2_hip.h"),
            os.path.join("..", "..", "include", "nicv2_hip_ext.h")]
 # -amdgpu-mfma-vgpr-form: MFMA results that vector instructions consume may live in the architectural VGPRs instead of bouncing
 # through v_accvgpr_read / write (split training kernel: 656 -> 423 of them, -0.7 %; fp32 2D 18 -> 0 spills; 3D 170 -> 115 / 135 -> 85)

@@ -75,7 +75,9 @@ Gradients with respect to the level of detail (include/nicv2_hip_
 column l F + f is a_l r[l, f] with a_l = clamp((fade[l] - lambda) + 1, 0, 1), so dlod[n] = - sum over the levels on the ramp 0 < a_raw <= 1 of
 sum_f g[n, l F + f] r[n, l, f] - the right-hand derivative, one more accumulator on the position gradient's walk, exactly 0 where lambda itself
 is clamped.  ``hash_encode_points_grad_lod`` / ``hash_fused_points_grad_lod`` return it next to dpoints; ``HashGridField.point_gradient_lod`` /
-``jacobian_lod`` / ``query_differentiable_lod`` are the surface.
+``jacobian_lod`` / ``query_differentiable_lod`` are the surface.  From the training step (csrc/hashgrid_lodtrain.hip) the row
+carries the codec noise inside the weighed column, a_l (r + nz), and the slope counts it: ``hash_fused_forward_backward_points_grad_lod`` /
+``hash_encode_points_grad_lod_noisy``, ``HashGridField.train_points_grad_lod`` / ``train_points_differentiable_lod``.
 
 B fields per launch (include/nicv2_hip.h, nic_hash_batch_forward_backward; csrc/hashgrid_batch.hip): ``HashGridFieldBatch`` holds
 the stacked tables [B, L, T, F] and decoder tensors of B fields of one geometry; a workgroup of the batched kernel belongs to one field, a step is
@@ -1161,9 +1163,10 @@ def hash_fused_forward_points(geo: HashGeometry, data: torch.Tensor, points: tor
 
 
 def _fused_forward_backward_points(geo, table, points, params, target, mlp_grads, table_grad, order, loss, loss_scale, want_y, quant, add_grads,
-                                   add_loss, tail, lod, dpoints=None):
+                                   add_loss, tail, lod, dpoints=None, dlod=None):
     """``hash_fused_forward_backward_points`` (``lod`` None) and ``hash_fused_forward_backward_points_lod`` (``lod`` = (lod, lod_uniform, fade));
-    with ``dpoints`` (checked by the caller) ``hash_fused_forward_backward_points_grad``, which takes either"""
+    with ``dpoints`` (checked by the caller) ``hash_fused_forward_backward_points_grad``, which takes either; with ``dlod`` on top (checked by
+    the caller; ``lod`` is then required) ``hash_fused_forward_backward_points_grad_lod``"""
     t = _check_table(geo, table.detach())
     params = _check_fused_decoder(geo, [q.detach() for q in params])
     pts = _check_points(geo, points)
@@ -1193,6 +1196,8 @@ def _fused_forward_backward_points(geo, table, points, params, target, mlp_grads
     if dpoints is not None:                                # the one entry with a nullable nic_hash_lod, and the gradient after y
         head, where = (ctypes.byref(d), None if lp is None else ctypes.byref(lp)), (_lib.ptr(pts), _lib.ptr(lod_tensor), n)
         name, out = "nic_hash_fused_forward_backward_points_grad", (_lib.ptr(y), _lib.ptr(dpoints))
+    if dlod is not None:                                   # the same entry with a level of detail always on, and dlod after dpoints
+        name, out = "nic_hash_fused_forward_backward_points_grad_lod", (_lib.ptr(y), _lib.ptr(dpoints), _lib.ptr(dlod))
     _lib.check(getattr(lib, name)(*head, qp, _lib.ptr(t), *where, _lib.ptr(order), ctypes.byref(m), _lib.ptr(target), float(loss_scale),
                                   _lib.ptr(table_grad), ctypes.byref(gs), _lib.ptr(loss), *out, flags, _lib.ptr(ws), ws.numel(),
                                   None if tail is None else ctypes.byref(tail.struct), _lib.stream_ptr(t.device)), name)
@@ -1471,6 +1476,79 @@ def hash_fused_points_grad_lod(geo: HashGeometry, data: torch.Tensor, points: to
                                                           _lib.ptr(out), _lib.ptr(dlod), _lib.stream_ptr(data.device)),
                "nic_hash_fused_points_grad_lod")
     return y, out, dlod
+
+
+# ---- the gradient with respect to the level of detail from the training step (include/nicv2_hip_ext.h) ----------------------------
+def _check_dlod(points, dlod, device: bool = True) -> torch.Tensor:
+    """the second output of a joint step: an fp32 [N] tensor on the points' HIP device, contiguous - the kernel writes it in place (``points``
+    is a [N, dim] tensor).  ``device`` False: type, shape, dtype and layout only, what the host decides"""
+    if not isinstance(dlod, torch.Tensor):
+        raise TypeError("dlod must be a torch.Tensor")
+    if tuple(dlod.shape) != (points.shape[0],):
+        raise ValueError(f"dlod must be [{points.shape[0]}], one value per point, got {tuple(dlod.shape)}")
+    if dlod.dtype != torch.float32:
+        raise ValueError(f"dlod has dtype {dlod.dtype}; the kernel writes fp32")
+    if not dlod.is_contiguous():
+        raise ValueError("dlod must be contiguous: the kernel writes it in place")
+    if not device:
+        return dlod
+    if not dlod.is_cuda:
+        raise RuntimeError(f"dlod lives on {dlod.device}: this package only runs on a HIP device (no CPU path)")
+    if dlod.device != points.device:
+        raise ValueError(f"dlod lives on {dlod.device}, the points on {points.device}")
+    return dlod
+
+
+@fused._on_tensor_device
+def hash_fused_forward_backward_points_grad_lod(geo: HashGeometry, table: torch.Tensor, points: torch.Tensor, params: Sequence[torch.Tensor],
+                                                target: torch.Tensor, mlp_grads: Sequence[torch.Tensor], lod: Optional[torch.Tensor] = None,
+                                                lod_uniform: float = 0.0, fade=None, table_grad: Optional[torch.Tensor] = None,
+                                                order: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None, loss_scale: float = 1.0,
+                                                want_y: bool = False, quant=None, add_grads: bool = False, add_loss: bool = False, tail=None,
+                                                dpoints: Optional[torch.Tensor] = None, dlod: Optional[torch.Tensor] = None):
+    """``hash_fused_forward_backward_points_grad`` that also writes d loss / d lambda of the loss it returns
+    (nic_hash_fused_forward_backward_points_grad_lod): the same two launches, loss, y, gradients and ``dpoints``; ``dlod[n]`` =
+    - sum over the levels on the ramp of sum_f g[n, l F + f] (r[n, l, f] + nz[n, l F + f]) - g the row gradient the step has on the chip, r the
+    unweighed blend, nz the noise this step's forward added under ``quant`` (0 without) -, exactly 0 where lambda_raw < 0, >= 32 or NaN.
+    Always a level-of-detail launch: ``lod`` None, ``lod_uniform`` 0 and ``fade`` None is lambda = 0 with the default fades.  ``dpoints``
+    / ``dlod``: None for fresh tensors, or fp32 [N, dim] / [N] device tensors that are overwritten (never added to).  Returns (loss [1], y or
+    None, dpoints, dlod)."""
+    if dpoints is None:
+        pts = _check_points(geo, points)
+        dpoints = torch.empty(pts.shape[0], geo.dim, dtype=torch.float32, device=pts.device)
+    else:
+        dpoints = _check_dpoints(geo, points, dpoints)
+    dlod = torch.empty(dpoints.shape[0], dtype=torch.float32, device=dpoints.device) if dlod is None else _check_dlod(dpoints, dlod)
+    loss, y = _fused_forward_backward_points(geo, table, points, params, target, mlp_grads, table_grad, order, loss, loss_scale, want_y, quant,
+                                             add_grads, add_loss, tail, (lod, lod_uniform, fade), dpoints=dpoints, dlod=dlod)
+    return loss, y, dpoints, dlod
+
+
+@fused._on_tensor_device
+def hash_encode_points_grad_lod_noisy(geo: HashGeometry, table: torch.Tensor, points: torch.Tensor, dx: torch.Tensor,
+                                      lod: Optional[torch.Tensor] = None, lod_uniform: float = 0.0, fade=None,
+                                      quant=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(dpoints [N, dim], dlod [N]) for the [N, L F] gradient ``dx`` of ``hash_encode_points_lod(table, .., quant=quant)`` from the fp32
+    ``table`` (nic_hash_encode_points_grad_lod_noisy): ``hash_encode_points_grad_lod`` whose ``dlod`` counts the noise the
+    forward added inside the weighed column - the slope of column l F + f on the ramp is -(r + nz).  ``quant``: None, or the forward's
+    (num_bits, seed, offset, sample_base); with None both outputs are ``hash_encode_points_grad_lod``'s bit for bit."""
+    t = _check_table(geo, table.detach())
+    pts = _check_points(geo, points)
+    n = pts.shape[0]
+    dx = _lib.require_cuda_f32(dx.detach() if isinstance(dx, torch.Tensor) else dx, "dx")
+    if tuple(dx.shape) != (n, geo.width):
+        raise ValueError(f"dx must be [{n}, {geo.width}], got {tuple(dx.shape)}")
+    lod_t = _check_lod(lod, n, pts.device)
+    lp = _lod_struct(geo, fade, lod_uniform)
+    d, q = _point_desc(geo), _quant_struct(quant)
+    out = torch.empty(n, geo.dim, dtype=torch.float32, device=t.device)
+    dlod = torch.empty(n, dtype=torch.float32, device=t.device)
+    if n == 0:
+        return out, dlod
+    _lib.check(_lib.load().nic_hash_encode_points_grad_lod_noisy(ctypes.byref(d), ctypes.byref(lp), None if q is None else ctypes.byref(q), _lib.ptr(t),
+                                                                 _lib.ptr(pts), _lib.ptr(lod_t), n, _lib.ptr(dx), _lib.ptr(out), _lib.ptr(dlod),
+                                                                 _lib.stream_ptr(t.device)), "nic_hash_encode_points_grad_lod_noisy")
+    return out, dlod
 
 
 # ---- B fields per launch with the gradient with respect to the point coordinates (DESIGN 4.7.21; include/nicv2_hip_ext.h) ------------------------
@@ -1876,6 +1954,30 @@ class _TrainPointsFunction(torch.autograd.Function):
         return g.reshape(()) * dp, None, None, None
 
 
+class _TrainPointsLodFunction(torch.autograd.Function):
+    """``HashGridField.train_points_grad_lod`` as a differentiable op of the points and of the level of detail
+    (``train_points_differentiable_lod``): the forward trains the field and keeps d loss / d points and d loss / d lambda of the loss it
+    returns, the backward hands upstream * dpoints and upstream * dlod (its sum for a 0-dim ``lod``) to whichever requires a gradient"""
+
+    @staticmethod
+    def forward(ctx, points, lod, field, target, kwargs):
+        with torch.enable_grad():                      # the layer-wise step runs its own backward
+            loss, dp, dl = field.train_points_grad_lod(points.detach(), target, lod.detach() if isinstance(lod, torch.Tensor) else lod, **kwargs)
+        ctx.lod_shape = (lod.shape, lod.dtype) if isinstance(lod, torch.Tensor) else None
+        ctx.save_for_backward(dp, dl)
+        return loss.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        dp, dl = ctx.saved_tensors
+        g = g.reshape(())
+        glod = None
+        if ctx.lod_shape is not None and ctx.needs_input_grad[1]:
+            shape, dtype = ctx.lod_shape
+            glod = (g * (dl if len(shape) > 0 else dl.sum())).to(dtype).reshape(shape)
+        return (g * dp if ctx.needs_input_grad[0] else None), glod, None, None, None
+
+
 class _BatchQueryPointsFunction(torch.autograd.Function):
     """``HashGridFieldBatch.query`` / ``query_lod`` as a differentiable op of the points (``query_differentiable``): backward =
     ``point_gradient`` with the output gradient, summed over the fields for shared [N, dim] points; nothing for the fields' parameters"""
@@ -2093,6 +2195,51 @@ class HashGridField:
         moves them), noise and level weights constant - registration while fitting, in the step's own launches (``fused=True``:
         nic_hash_fused_forward_backward_points_grad; layer-wise: nic_hash_encode_points_grad on the row gradient the step has anyway, also
         after ``freeze()``).  Each chunk of an ``accumulate`` pass fills its own ``dpoints``."""
+        return self._train_points(points, target, accumulate, scale, step, noise, order, fused, lod, dpoints, None)
+
+    def train_points_grad_lod(self, points: torch.Tensor, target: torch.Tensor, lod, dpoints: Optional[torch.Tensor] = None,
+                              dlod: Optional[torch.Tensor] = None, accumulate: bool = False, scale: float = 1.0, step: bool = True,
+                              noise: Optional[bool] = None, order=None, fused: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(loss, dpoints [N, dim], dlod [N]): ``train_points(points, target, lod=lod, dpoints=...)`` that also fills ``dlod`` with d loss / d
+        lambda_n of the loss it returns, taken like ``dpoints`` at the parameters this step's forward used, in the step's own
+        launches - for a level of detail that comes from parameters optimised while the field is fitted (a zoom ``lambda = log2 s + bias``, a
+        mip bias per view).  ``lod`` is required: a float, a 0-dim tensor or one value per point [N]; the gradient for a launch-wide value is
+        ``dlod.sum()``.  ``dlod[n]`` = - sum over the levels on the ramp (0 < (fade[l] - lambda_n) + 1 <= 1, the right-hand derivative) of
+        sum_f g[n, l F + f] (r[n, l, f] + nz[n, l F + f]): with a codec the step's forward adds its noise INSIDE the weighed column, and the
+        slope counts it - ``point_gradient_lod(target=)`` in front of the step cannot.  Exactly 0 where lambda_n < 0, >= 32 or NaN.
+        ``dpoints`` / ``dlod``: None for fresh tensors, or fp32 contiguous device tensors [N, dim] / [N] that are OVERWRITTEN.  ``fused=True``:
+        nic_hash_fused_forward_backward_points_grad_lod inside ``train_points``' bookkeeping; layer-wise:
+        nic_hash_encode_points_grad_lod_noisy on the row gradient the step has anyway, with the step's noise key, before the optimiser moves
+        the table, also after ``freeze()``.  Everything else - ``accumulate`` / ``scale`` / ``step`` / ``noise`` / ``order``, the noise keys
+        of a chunked pass - is ``train_points``'."""
+        if self.table is None:
+            raise RuntimeError("a field from load_compressed decodes only")
+        if self.level_bits is not None:
+            raise NotImplementedError("gradients with respect to the level of detail with a bit depth per level are not built (DESIGN 7): use a "
+                                      "uniform num_bits")
+        if lod is None:
+            raise ValueError("lod is a float or a [N] tensor: the level of detail the gradient is taken at")
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != self.geo.dim:
+            raise ValueError(f"points must be [N, {self.geo.dim}] for a {self.geo.dim}D field, got "
+                             f"{tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__}")
+        # the two tensors: type, shape, dtype and layout of both, then where they live
+        if dlod is not None:
+            _check_dlod(points, dlod, device=False)
+        if dpoints is not None:
+            dpoints = _check_dpoints(self.geo, points, dpoints)
+        if dlod is not None:
+            dlod = _check_dlod(points, dlod)
+        if not points.is_cuda:
+            raise RuntimeError(f"points live on {points.device}: this package only runs on a HIP device (no CPU path)")
+        if dpoints is None:
+            dpoints = torch.empty(points.shape[0], self.geo.dim, dtype=torch.float32, device=points.device)
+        if dlod is None:
+            dlod = torch.empty(points.shape[0], dtype=torch.float32, device=points.device)
+        loss = self._train_points(points, target, accumulate, scale, step, noise, order, fused, lod, dpoints, dlod)
+        return loss, dpoints, dlod
+
+    def _train_points(self, points, target, accumulate, scale, step, noise, order, fused, lod, dpoints, dlod) -> torch.Tensor:
+        """``train_points`` (``dlod`` None) and ``train_points_grad_lod`` (``dlod`` a checked [N] tensor; ``lod`` and ``dpoints`` are then given)"""
         if self.table is None:
             raise RuntimeError("a field from load_compressed decodes only")
         if dpoints is not None:
@@ -2125,7 +2272,7 @@ class HashGridField:
         if isinstance(order, str):
             order = hash_point_order(self.geo, pts)
         if fused:
-            return self._fused_train_points(pts, target, accumulate, scale, step, noise, order, None if lod is None else (lod_t, lod_u), dpoints)
+            return self._fused_train_points(pts, target, accumulate, scale, step, noise, order, None if lod is None else (lod_t, lod_u), dpoints, dlod)
         if not accumulate:
             for p in params:
                 p.grad = None
@@ -2145,7 +2292,11 @@ class HashGridField:
         y = DecoderFunction.apply(x, *params)          # `fused` is this call's argument here
         loss = ((y - target) ** 2).mean() * scale
         loss.backward()
-        if dpoints is not None:                        # before the optimiser moves the table: the derivative at the forward's parameters
+        if dlod is not None:                           # both gradients from one walk, with the noise this forward added
+            dp, dl = hash_encode_points_grad_lod_noisy(self.geo, self.table, pts, x.grad, lod_t, lod_u, self.lod_fade, quant=quant)
+            dpoints.copy_(dp)
+            dlod.copy_(dl)
+        elif dpoints is not None:                      # before the optimiser moves the table: the derivative at the forward's parameters
             dpoints.copy_(hash_encode_points_grad(self.geo, self.table, pts, x.grad, lod=lod_t, lod_uniform=lod_u,
                                                   fade=None if lod is None else self.lod_fade))
         if not frozen and lod is not None:
@@ -2165,10 +2316,11 @@ class HashGridField:
         return loss.detach()
 
     @torch.no_grad()
-    def _fused_train_points(self, pts, target, accumulate, scale, step, noise, order, lod=None, dpoints=None) -> torch.Tensor:
+    def _fused_train_points(self, pts, target, accumulate, scale, step, noise, order, lod=None, dpoints=None, dlod=None) -> torch.Tensor:
         """``train_points`` as two launches, with ``_fused_train_step``'s bookkeeping: persistent decoder-gradient buffers, the chunks of a
         pass adding into them and into the table gradient, the optimiser riding on the last chunk's reduction.  The arguments are checked.
-        ``lod``: None or (per-point tensor or None, launch-wide value).  ``dpoints``: None, or the tensor the joint entry overwrites."""
+        ``lod``: None or (per-point tensor or None, launch-wide value).  ``dpoints``: None, or the tensor the joint entry overwrites;
+        ``dlod`` (with ``lod`` and ``dpoints``): the tensor the entry with the gradient for the level of detail overwrites."""
         params = self.decoder.linear_params()
         frozen = self.frozen
         grad = None if frozen else self.table.grad
@@ -2185,7 +2337,11 @@ class HashGridField:
         tail = None
         if step:
             tail = self.optimizer.step_tail([] if frozen else [(self.table, grad)], list(zip(params, gm)))
-        if dpoints is not None:
+        if dlod is not None:
+            loss, _, _, _ = hash_fused_forward_backward_points_grad_lod(self.geo, self.table, pts, params, target, gm, lod[0], lod[1], self.lod_fade,
+                                                                        table_grad=grad, order=order, loss_scale=float(scale), quant=quant,
+                                                                        add_grads=accumulate, tail=tail, dpoints=dpoints, dlod=dlod)
+        elif dpoints is not None:
             loss, _, _ = hash_fused_forward_backward_points_grad(self.geo, self.table, pts, params, target, gm, *((None, 0.0, None) if lod is None else
                                                                  (lod[0], lod[1], self.lod_fade)), table_grad=grad, order=order,
                                                                  loss_scale=float(scale), quant=quant, add_grads=accumulate, tail=tail, dpoints=dpoints)
@@ -2224,6 +2380,19 @@ class HashGridField:
         if not (isinstance(points, torch.Tensor) and points.requires_grad and torch.is_grad_enabled()):
             return self.train_points(points, target, **kwargs)
         return _TrainPointsFunction.apply(points, self, target, kwargs)
+
+    def train_points_differentiable_lod(self, points: torch.Tensor, lod, target: torch.Tensor, **kwargs) -> torch.Tensor:
+        """``train_points(points, target, lod=lod, **kwargs)`` as a differentiable op of ``points`` and / or ``lod`` - ``lod`` a
+        [N] tensor, or a 0-dim tensor (one level of detail for the launch, whose gradient is the sum of the per-point ones): the call steps
+        the field as it always does, and the loss it returns has a backward that hands upstream * d loss / d points and upstream * d loss / d
+        lambda (``train_points_grad_lod``'s, the step's noise counted) to whichever requires a gradient.  With nothing that requires one, or
+        under ``torch.no_grad()``, it is plain ``train_points``.  No gradient reaches the field's parameters through autograd."""
+        if "dpoints" in kwargs or "dlod" in kwargs:
+            raise TypeError("train_points_differentiable_lod keeps dpoints and dlod for the backward: call train_points_grad_lod for the tensors")
+        wants = any(isinstance(t, torch.Tensor) and t.requires_grad for t in (points, lod))
+        if not (wants and torch.is_grad_enabled()):
+            return self.train_points(points, target, lod=lod, **kwargs)
+        return _TrainPointsLodFunction.apply(points, lod, self, target, kwargs)
 
     def fit_points(self, points: torch.Tensor, target: torch.Tensor, epochs: int, batch: Optional[int] = None, order="cell",
                    fused: Optional[bool] = None, freeze_at: float = 0.95, lod=None) -> List[float]:
