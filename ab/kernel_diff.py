@@ -1,11 +1,13 @@
 """Kernel-by-kernel comparison of two `hipcc -S --cuda-device-only` outputs of one unit, and the resource table of a
 `-Rpass-analysis=kernel-resource-usage` log (profiles/hashgrid_batch_lod_disasm.txt, profiles/hashgrid_batch_lod_resources.txt).
 
-    python ab/kernel_diff.py diff parent.s new.s
+    python ab/kernel_diff.py diff parent.s new.s [--commute]
     python ab/kernel_diff.py resources remarks.txt [name filter ...]
 
 A kernel's text runs from its label to the end of its "Kernel info" comment block; its own mangled name, the function index of local labels
-(.LBBn_ / BBn_) and of .Lfunc_endN, and runs of blanks are normalised.  Lines that name __hip_cuid are dropped."""
+(.LBBn_ / BBn_) and of .Lfunc_endN, and runs of blanks are normalised.  Lines that name __hip_cuid are dropped.  --commute: a kernel that is
+the parent's once the two source operands of its commutative two-operand instructions are put in one order - the same opcodes in the same order
+on the same registers, the same resource block - is counted as "operands"  and the swapped lines are counted."""
 import re
 import subprocess
 import sys
@@ -47,10 +49,22 @@ def kernels(path):
     return out
 
 
-def diff(parent, new):
+COMMUTATIVE = re.compile(r"^([vs]_(?:xor|or|and|add_u32|mul_f32|add_f32|min|max)\w*) ([^,]+), ([^,]+), ([^,]+)$")
+
+
+def commuted(ln):
+    """the line with the two source operands of a commutative two-operand instruction sorted"""
+    m = COMMUTATIVE.match(ln)
+    if not m or m.group(1).startswith(("v_add_u32_sdwa", "v_mul_f32_sdwa")) or "dpp" in m.group(1):
+        return ln
+    x, y = sorted((m.group(3), m.group(4)))
+    return f"{m.group(1)} {m.group(2)}, {x}, {y}"
+
+
+def diff(parent, new, commute=False):
     a, b = kernels(parent), kernels(new)
     names = demangle(sorted(set(a) | set(b)))
-    same = moved = 0
+    same = moved = swapped = swapped_lines = 0
     rows = []
     for m in sorted(names, key=lambda k: names[k]):
         n = short(names[m])
@@ -61,11 +75,17 @@ def diff(parent, new):
         elif a[m] == b[m]:
             same += 1
             rows.append(f"identical {len(a[m]):>7} {len(b[m]):>7}  {n}")
+        elif commute and len(a[m]) == len(b[m]) and [commuted(ln) for ln in a[m]] == [commuted(ln) for ln in b[m]]:
+            k = sum(x != y for x, y in zip(a[m], b[m]))
+            swapped += 1
+            swapped_lines += k
+            rows.append(f"operands  {len(a[m]):>7} {len(b[m]):>7}  {n}  ({k} line{'s' if k > 1 else ''})")
         else:
             moved += 1
             rows.append(f"DIFFERENT {len(a[m]):>7} {len(b[m]):>7}  {n}")
-    print(f"{len(a)} kernels at the parent, {len(b)} now; of the parent's: identical {same}, different {moved}, gone {len(set(a) - set(b))}; "
-          f"new {len(set(b) - set(a))}")
+    print(f"{len(a)} kernels at the parent, {len(b)} now; of the parent's: identical {same}, "
+          + (f"operand order only {swapped} ({swapped_lines} lines), " if commute else "")
+          + f"different {moved}, gone {len(set(a) - set(b))}; new {len(set(b) - set(a))}")
     print("\n".join(rows))
     return moved + len(set(a) - set(b))
 
@@ -96,5 +116,5 @@ def resources(path, filters):
 
 if __name__ == "__main__":
     if sys.argv[1] == "diff":
-        sys.exit(1 if diff(sys.argv[2], sys.argv[3]) else 0)
+        sys.exit(1 if diff(sys.argv[2], sys.argv[3], "--commute" in sys.argv[4:]) else 0)
     resources(sys.argv[2], sys.argv[3:])

@@ -22,7 +22,7 @@ SOURCES = ["simple_kernels.hip", "decoder_general.hip", "fused_capi.hip", "fused
 # the lists of csrc/fused_capi.hip (NIC_CP_LIST, NIC_ML_LIST): one object per entry, compiled from one source with the entry as NIC_ENTRY
 LISTED = {"NIC_CP_LIST": ("fused_qc.hip", "fused_qc_{}_{}_{}.o"),        # (layout, C, P): non-default channel counts on the plain-bf16 kernels
           "NIC_ML_LIST": ("fused_ml.hip", "fused_ml_{}_{}_{}.o")}        # (levels, C, n_linear): multi-level layouts (fused_q16.hpp::QML)
-HEADERS = ["nic_device.hpp", "nic_adam.hpp", "fused_kernel.hpp", "fused_dispatch.hpp", "fused_launch.hpp", "fused_train16.hpp", "fused_mlpn.hpp", "fused_q16.hpp", "fused_q16_launch.hpp", "hash_common.hpp", "hashgrid_pointgrad.hpp", "hashgrid_lodgrad.hpp", "hashgrid_lodtrain.hpp", "hashgrid_batch.hpp", os.path.join("..", "..", "include", "nicv2_hip.h"),
+HEADERS = ["nic_device.hpp", "nic_adam.hpp", "fused_kernel.hpp", "fused_dispatch.hpp", "fused_launch.hpp", "fused_train16.hpp", "fused_mlpn.hpp", "fused_q16.hpp", "fused_q16_launch.hpp", "hash_common.hpp", "hashgrid_pointgrad.hpp", "hashgrid_batch.hpp", os.path.join("..", "..", "include", "nicv2_hip.h"),
            os.path.join("..", "..", "include", "nicv2_hip_ext.h")]
 # -amdgpu-mfma-vgpr-form: MFMA results that vector instructions consume may live in the architectural VGPRs instead of bouncing
 # through v_accvgpr_read / write (split training kernel: 656 -> 423 of them, -0.7 %; fp32 2D 18 -> 0 spills; 3D 170 -> 115 / 135 -> 85)

@@ -984,5 +984,51 @@ inline int finish_fused_step(const FusedTail& ft, const nic_mlp_grads* mlp_grads
                        ft.tl);
     return (int)hipGetLastError();
 }
+
+// ---- the fused training step at points, the same at its four entry points (hash_points_train.hip, hashgrid_points_joint.hip,
+// hashgrid_lodtrain.hip) -----------------------------------------------------------------------------------------------------------------------
+// the workspace of the step: one record per workgroup of the widest persistent launch
+inline size_t points_workspace_bytes(int lf) { return (size_t)wg_cap() * RecLayout(lf).rec * sizeof(float); }
+// The opening of an entry: the descriptor and the decoder.  Each entry follows it with its own null list, then `flags` and check_lod in the
+// order include/nicv2_hip.h states for it: _points has no level of detail; _points_lod asks check_lod, then flags; _points_grad flags, then
+// check_lod where lodp is given; _points_grad_lod flags, then check_lod.
+inline int open_fused_points(const nic_hash_desc* desc, const nic_mlp* mlp) {
+    if (!desc || !mlp) return NIC_E_NULL;
+    int rc = nic_hash_fused_supported(desc, kH, mlp->n_linear);          // the only copy of the fused set (hash_fused.hip)
+    if (rc) return rc;
+    if ((rc = check_point_desc(desc)) != NIC_OK) return rc;
+    for (int i = 0; i < 3; ++i)
+        if (!mlp->w[i] || !mlp->b[i]) return NIC_E_NULL;
+    return NIC_OK;
+}
+// what every parameter struct of the step holds, from the arguments every entry has
+template <class Params>
+inline void fill_fused_points(Params& p, const nic_hash_desc* desc, const float* points, int64_t n_points, const int32_t* order, const float* table,
+                              const float* target, float* table_grad, float* y, const nic_mlp* mlp) {
+    p.d = *desc; p.points = points; p.n = n_points; p.order = order; p.table = table; p.target = target; p.grad = table_grad; p.y = y;
+    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
+}
+// From the first check that needs the parameters on: the quantiser, the point count, the workspace, the tail, then the step.  `p` arrives with
+// everything but noise, dscale and partials set; `launch(noise, grid)` starts the entry's training kernel, `noise` a std::bool_constant
+template <class Params, class Launch>
+inline int points_fused_step(Params& p, const nic_hash_quant* quant, const int32_t* order, float loss_scale, const nic_mlp_grads* mlp_grads, float* loss,
+                             int flags, void* workspace, size_t workspace_bytes, const nic_step_tail* tail, void* stream, Launch launch) {
+    p.noise.mode = NIC_NOISE_NONE;
+    int rc = set_noise(quant, true, p.noise, p.sample_base);
+    if (rc) return rc;
+    if (p.n < 0 || (order && p.n >= (int64_t(1) << 31))) return NIC_E_ARG;
+    const int lf = p.d.levels * p.d.features;
+    if (workspace_bytes < points_workspace_bytes(lf)) return NIC_E_WORKSPACE;
+    FusedTail ft;
+    if ((rc = check_fused_tail(tail, mlp_grads, lf, ft)) != NIC_OK) return rc;
+    if (p.n == 0) return NIC_OK;                                      // nothing to launch: *loss and every gradient output stay as they are
+    const int grid = persistent_grid((p.n + 63) >> 6);
+    const float loss_mul = (float)((double)loss_scale / (3.0 * (double)p.n));
+    p.dscale = 2.0f * loss_mul;
+    p.partials = (float*)workspace;
+    return finish_fused_step(ft, mlp_grads, flags, lf, grid, loss_mul, loss, p.partials, stream, [&] {
+        return p.noise.mode == NIC_NOISE_KERNEL ? launch(std::true_type{}, grid) : launch(std::false_type{}, grid);
+    });
+}
 }  // namespace hcommon
 }  // namespace nic

@@ -152,29 +152,6 @@ static int launch(const Params& p, int nb, void* stream) {
     });
 }
 
-// what the two fused training entry points share from the first check that needs the parameters on: the quantiser, the point count, the
-// workspace, the tail, then the step.  `p` arrives with everything but noise, dscale and partials set
-template <class Params>
-static int fused_step(Params& p, const nic_hash_quant* quant, const int32_t* order, float loss_scale, const nic_mlp_grads* mlp_grads, float* loss,
-                      int flags, void* workspace, size_t workspace_bytes, const nic_step_tail* tail, void* stream) {
-    p.noise.mode = NIC_NOISE_NONE;
-    int rc = set_noise(quant, true, p.noise, p.sample_base);
-    if (rc) return rc;
-    if (p.n < 0 || (order && p.n >= (int64_t(1) << 31))) return NIC_E_ARG;
-    const int lf = p.d.levels * p.d.features;
-    if (workspace_bytes < (size_t)wg_cap() * RecLayout(lf).rec * sizeof(float)) return NIC_E_WORKSPACE;
-    FusedTail ft;
-    if ((rc = check_fused_tail(tail, mlp_grads, lf, ft)) != NIC_OK) return rc;
-    if (p.n == 0) return NIC_OK;                                      // nothing to launch: *loss and every gradient stay as they are
-    const int grid = persistent_grid((p.n + 63) >> 6);
-    const float loss_mul = (float)((double)loss_scale / (3.0 * (double)p.n));
-    p.dscale = 2.0f * loss_mul;
-    p.partials = (float*)workspace;
-    return finish_fused_step(ft, mlp_grads, flags, lf, grid, loss_mul, loss, p.partials, stream, [&] {
-        return p.noise.mode == NIC_NOISE_KERNEL ? launch<TK_TRAIN_NOISY>(p, grid, stream) : launch<TK_TRAIN>(p, grid, stream);
-    });
-}
-
 }  // namespace hptrain
 }  // namespace nic
 
@@ -216,7 +193,7 @@ int nic_hash_encode_points_backward_ordered(const nic_hash_desc* desc, const flo
 
 size_t nic_hash_fused_points_workspace_bytes(const nic_hash_desc* desc, const nic_mlp* mlp) {
     if (!desc || !mlp || nic_hash_fused_supported(desc, kH, mlp->n_linear) != NIC_OK || check_point_desc(desc) != NIC_OK) return 0;
-    return (size_t)wg_cap() * RecLayout(desc->levels * desc->features).rec * sizeof(float);
+    return points_workspace_bytes(desc->levels * desc->features);
 }
 
 int nic_hash_fused_forward_backward_points(const nic_hash_desc* desc, const nic_hash_quant* quant, const float* table, const float* points,
@@ -224,18 +201,14 @@ int nic_hash_fused_forward_backward_points(const nic_hash_desc* desc, const nic_
                                            float* table_grad, const nic_mlp_grads* mlp_grads, float* loss, float* y, int flags, void* workspace,
                                            size_t workspace_bytes, const nic_step_tail* tail, void* stream) {
     const KernelEndDrop end;
-    if (!desc || !mlp) return NIC_E_NULL;
-    int rc = nic_hash_fused_supported(desc, kH, mlp->n_linear);          // the only copy of the fused set (hash_fused.hip)
+    int rc = open_fused_points(desc, mlp);
     if (rc) return rc;
-    if ((rc = check_point_desc(desc)) != NIC_OK) return rc;
-    bool mlp_ok = true;
-    for (int i = 0; i < 3; ++i) mlp_ok = mlp_ok && mlp->w[i] && mlp->b[i];
-    if (!table || !points || !mlp_ok || !target || !mlp_grads || !loss || !workspace) return NIC_E_NULL;
+    if (!table || !points || !target || !mlp_grads || !loss || !workspace) return NIC_E_NULL;
     if (flags & ~(NIC_HASH_FUSED_ADD_GRADS | NIC_HASH_FUSED_ADD_LOSS)) return NIC_E_ARG;
     TParams p{};
-    p.d = *desc; p.points = points; p.n = n_points; p.order = order; p.table = table; p.target = target; p.grad = table_grad; p.y = y;
-    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
-    return fused_step(p, quant, order, loss_scale, mlp_grads, loss, flags, workspace, workspace_bytes, tail, stream);
+    fill_fused_points(p, desc, points, n_points, order, table, target, table_grad, y, mlp);
+    return points_fused_step(p, quant, order, loss_scale, mlp_grads, loss, flags, workspace, workspace_bytes, tail, stream,
+                             [&](auto noise, int grid) { return launch<decltype(noise)::value ? TK_TRAIN_NOISY : TK_TRAIN>(p, grid, stream); });
 }
 
 // ---- with a level of detail per point: the checks of the nic_hash_lod follow the null checks, the launches are the same ------
@@ -258,20 +231,16 @@ int nic_hash_fused_forward_backward_points_lod(const nic_hash_desc* desc, const 
                                                const float* target, float loss_scale, float* table_grad, const nic_mlp_grads* mlp_grads, float* loss,
                                                float* y, int flags, void* workspace, size_t workspace_bytes, const nic_step_tail* tail, void* stream) {
     const KernelEndDrop end;
-    if (!desc || !mlp) return NIC_E_NULL;
-    int rc = nic_hash_fused_supported(desc, kH, mlp->n_linear);          // the only copy of the fused set (hash_fused.hip)
+    int rc = open_fused_points(desc, mlp);
     if (rc) return rc;
-    if ((rc = check_point_desc(desc)) != NIC_OK) return rc;
-    bool mlp_ok = true;
-    for (int i = 0; i < 3; ++i) mlp_ok = mlp_ok && mlp->w[i] && mlp->b[i];
-    if (!lodp || !table || !points || !mlp_ok || !target || !mlp_grads || !loss || !workspace) return NIC_E_NULL;
+    if (!lodp || !table || !points || !target || !mlp_grads || !loss || !workspace) return NIC_E_NULL;
     if ((rc = check_lod(desc, lodp)) != NIC_OK) return rc;
     if (flags & ~(NIC_HASH_FUSED_ADD_GRADS | NIC_HASH_FUSED_ADD_LOSS)) return NIC_E_ARG;
     LodParams p{};
-    p.d = *desc; p.points = points; p.n = n_points; p.order = order; p.table = table; p.target = target; p.grad = table_grad; p.y = y;
-    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
+    fill_fused_points(p, desc, points, n_points, order, table, target, table_grad, y, mlp);
     set_lod(p, lodp, lod);
-    return fused_step(p, quant, order, loss_scale, mlp_grads, loss, flags, workspace, workspace_bytes, tail, stream);
+    return points_fused_step(p, quant, order, loss_scale, mlp_grads, loss, flags, workspace, workspace_bytes, tail, stream,
+                             [&](auto noise, int grid) { return launch<decltype(noise)::value ? TK_TRAIN_NOISY : TK_TRAIN>(p, grid, stream); });
 }
 
 }  // extern "C"

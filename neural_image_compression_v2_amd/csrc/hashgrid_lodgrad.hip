@@ -6,10 +6,10 @@
 //       dlod[n] = - sum_{l: 0 < a_raw <= 1} sum_f g[n, l F + f] r[n, l, f]
 //   with g = d loss / d row - the right-hand derivative: a level exactly at its fade start has slope -1, one exactly at its end slope 0 - and
 //   exactly 0.0f where the clamp of lambda itself is flat (lambda_raw < 0, >= 32 or NaN).  Both kernels are hashgrid_pointgrad.hip's with the
-//   combined walk of hashgrid_lodgrad.hpp in the place of point_grad: the same gathers, the same dpoints bit for bit, one more accumulator and one
+//   walk of hashgrid_pointgrad.hpp asked for d / d lambda too: the same gathers, the same dpoints bit for bit, one more accumulator and one
 //   more store per point.  Nothing is added anywhere: row n of every output is written once by the lane of point n.
 #include "hash_common.hpp"
-#include "hashgrid_lodgrad.hpp"
+#include "hashgrid_pointgrad.hpp"
 
 namespace nic {
 namespace hlgrad {
@@ -48,7 +48,7 @@ __global__ void __launch_bounds__(256) hash_points_grad_lod_kernel(const LodGrad
         const float lam = point_lambda(p.lod, p.lod_uniform, n);
         const float* drow = p.dx + n * LF;
         float g[D], gl;
-        point_grad_lod<D, F, SRC>(p, t, lam, [&](int l, float (&gv)[F]) { load_row<F>(drow + l * F, gv); }, g, gl);
+        point_walk<D, F, SRC, true, true, false>(p, t, n, lam, [&](int l, float (&gv)[F]) { load_row<F>(drow + l * F, gv); }, g, gl);
         store_point_grad<D>(p.dpoints, n, kept_axes<D>(p.d, p.points, n), g);
         p.dlod[n] = lambda_passes(p.lod, p.lod_uniform, n) ? gl : 0.0f;
     }
@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(256) hash_points_fused_grad_lod_kernel(const L
         }
         wave_sync();
         float gp[D], gl;
-        point_grad_lod<D, F, SRC>(p, t, lam, [&](int l, float (&gv)[F]) {
+        point_walk<D, F, SRC, true, true, false>(p, t, row, lam, [&](int l, float (&gv)[F]) {
 #pragma unroll
             for (int f = 0; f < F; ++f) gv[f] = xrow[l * F + f];
         }, gp, gl);

@@ -5,12 +5,12 @@
 //       dlod[n] = passes(n) ? - sum_{l: 0 < a_raw <= 1} sum_f g[n, l F + f] (r[n, l, f] + nz[n, l F + f]) : 0
 //   with g = d loss / d row of the loss the call returns, the conventions of hashgrid_lodgrad.hip (the right-hand derivative; exactly 0.0f where
 //   the clamp of lambda is flat) and nz the value the forward added - regenerated from the same key in the walk, not carried.
-//   The fused kernel is hash_points_joint_train_kernel (hashgrid_points_joint.hip) with a level of detail always on and the combined walk of
-//   hashgrid_lodtrain.hpp in the place of point_grad: the same gathers, the same records, the same scatter, the same dpoints bit for bit, one
+//   The fused kernel is hash_points_joint_train_kernel (hashgrid_points_joint.hip) with a level of detail always on and the walk of
+//   hashgrid_pointgrad.hpp asked for d / d lambda and the noise: the same gathers, the same records, the same scatter, the same dpoints bit for bit, one
 //   more accumulator and one more store per point.  The layer-wise kernel is hash_points_grad_lod_kernel (hashgrid_lodgrad.hip) from the fp32
 //   table with the same walk.  Rows of dpoints and dlod are written once by their lane; nothing is added to them.
 #include "hash_common.hpp"
-#include "hashgrid_lodtrain.hpp"
+#include "hashgrid_pointgrad.hpp"
 
 namespace nic {
 namespace hltrain {
@@ -33,7 +33,7 @@ __global__ void __launch_bounds__(256) hash_points_grad_lod_noisy_kernel(const L
         const float lam = point_lambda(s, n);
         const float* drow = s.dx + n * LF;
         float g[D], gl;
-        point_grad_lod_noisy<D, F, NOISE>(s, t, n, lam, [&](int l, float (&gv)[F]) { load_row<F>(drow + l * F, gv); }, g, gl);
+        point_walk<D, F, NIC_HASH_SRC_F32, true, true, NOISE>(s, t, n, lam, [&](int l, float (&gv)[F]) { load_row<F>(drow + l * F, gv); }, g, gl);
         store_point_grad<D>(p.dpoints, n, kept_axes<D>(s.d, s.points, n), g);
         p.dlod[n] = lambda_passes(s.lod, s.lod_uniform, n) ? gl : 0.0f;
     }
@@ -85,7 +85,7 @@ __global__ void __launch_bounds__(256) hash_points_lod_train_kernel(const LodTra
         };
         if (s.grad != nullptr) scatter_point<D, F, true>(s.d, t, s.grad, level_fade(s), lam, live_lane, lane, grow);
         float gp[D], gl;
-        point_grad_lod_noisy<D, F, NOISE>(s, t, row, lam, grow, gp, gl);
+        point_walk<D, F, NIC_HASH_SRC_F32, true, true, NOISE>(s, t, row, lam, grow, gp, gl);
         if (live_lane) {
             store_point_grad<D>(p.dpoints, row, kept_axes<D>(s.d, s.points, row), gp);
             p.dlod[row] = lambda_passes(s.lod, s.lod_uniform, row) ? gl : 0.0f;
@@ -133,8 +133,7 @@ int nic_hash_encode_points_grad_lod_noisy(const nic_hash_desc* desc, const nic_h
     return p.noise.mode == NIC_NOISE_KERNEL ? launch<false, true>(p, nb, stream) : launch<false, false>(p, nb, stream);
 }
 
-// nic_hash_fused_forward_backward_points_grad (hashgrid_points_joint.hip) with lodp != NULL, check for check; its joint_step line for line:
-// the quantiser, the point count, the workspace, the tail, then the two launches
+// nic_hash_fused_forward_backward_points_grad (hashgrid_points_joint.hip) with lodp != NULL, check for check
 int nic_hash_fused_forward_backward_points_grad_lod(const nic_hash_desc* desc, const nic_hash_lod* lodp, const nic_hash_quant* quant,
                                                     const float* table, const float* points, const float* lod, int64_t n_points,
                                                     const int32_t* order, const nic_mlp* mlp, const float* target, float loss_scale,
@@ -142,35 +141,17 @@ int nic_hash_fused_forward_backward_points_grad_lod(const nic_hash_desc* desc, c
                                                     float* dlod, int flags, void* workspace, size_t workspace_bytes, const nic_step_tail* tail,
                                                     void* stream) {
     const KernelEndDrop end;
-    if (!desc || !mlp) return NIC_E_NULL;
-    int rc = nic_hash_fused_supported(desc, kH, mlp->n_linear);          // the only copy of the fused set (hash_fused.hip)
+    int rc = open_fused_points(desc, mlp);
     if (rc) return rc;
-    if ((rc = check_point_desc(desc)) != NIC_OK) return rc;
-    bool mlp_ok = true;
-    for (int i = 0; i < 3; ++i) mlp_ok = mlp_ok && mlp->w[i] && mlp->b[i];
-    if (!lodp || !table || !points || !mlp_ok || !target || !mlp_grads || !loss || !dpoints || !dlod || !workspace) return NIC_E_NULL;
+    if (!lodp || !table || !points || !target || !mlp_grads || !loss || !dpoints || !dlod || !workspace) return NIC_E_NULL;
     if (flags & ~(NIC_HASH_FUSED_ADD_GRADS | NIC_HASH_FUSED_ADD_LOSS)) return NIC_E_ARG;
     if ((rc = check_lod(desc, lodp)) != NIC_OK) return rc;
     LodTrainParams p{};
-    p.d = *desc; p.points = points; p.n = n_points; p.order = order; p.table = table; p.target = target; p.grad = table_grad; p.y = y;
-    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
+    fill_fused_points(p, desc, points, n_points, order, table, target, table_grad, y, mlp);
     p.dpoints = dpoints; p.dlod = dlod;
     set_lod(p, lodp, lod);
-    p.noise.mode = NIC_NOISE_NONE;
-    if ((rc = set_noise(quant, true, p.noise, p.sample_base)) != NIC_OK) return rc;
-    if (p.n < 0 || (order && p.n >= (int64_t(1) << 31))) return NIC_E_ARG;
-    const int lf = p.d.levels * p.d.features;
-    if (workspace_bytes < (size_t)wg_cap() * RecLayout(lf).rec * sizeof(float)) return NIC_E_WORKSPACE;
-    FusedTail ft;
-    if ((rc = check_fused_tail(tail, mlp_grads, lf, ft)) != NIC_OK) return rc;
-    if (p.n == 0) return NIC_OK;                                      // nothing to launch: *loss, dpoints, dlod and every gradient stay as they are
-    const int grid = persistent_grid((p.n + 63) >> 6);
-    const float loss_mul = (float)((double)loss_scale / (3.0 * (double)p.n));
-    p.dscale = 2.0f * loss_mul;
-    p.partials = (float*)workspace;
-    return finish_fused_step(ft, mlp_grads, flags, lf, grid, loss_mul, loss, p.partials, stream, [&] {
-        return p.noise.mode == NIC_NOISE_KERNEL ? launch<true, true>(p, grid, stream) : launch<true, false>(p, grid, stream);
-    });
+    return points_fused_step(p, quant, order, loss_scale, mlp_grads, loss, flags, workspace, workspace_bytes, tail, stream,
+                             [&](auto noise, int grid) { return launch<true, decltype(noise)::value>(p, grid, stream); });
 }
 
 }  // extern "C"

@@ -40,7 +40,7 @@ struct GradParams {
     float dscale;             // 2 loss_scale / (3 N)
 };
 
-// kept_axes, point_grad (the level loop: point_cell<D>(t, R, S, fdiv, v, w), the 2^D corner rows, the D signed weights per corner) and
+// kept_axes, point_walk (the level loop: point_cell<D>(t, R, S, fdiv, v, w), the 2^D corner rows, the D signed weights per corner) and
 // store_point_grad live in hashgrid_pointgrad.hpp: the joint training kernel (hashgrid_points_joint.hip) walks the levels with the same code
 
 // ---- layer-wise: d loss / d row from memory, one lane per point ----------------------------------------------------------------------------
@@ -52,8 +52,8 @@ __global__ void __launch_bounds__(256) hash_points_grad_kernel(const GradParams 
         point_fixed<D>(p.d, p.points, n, t);
         const float lam = LOD ? point_lambda(p.lod, p.lod_uniform, n) : 0.f;
         const float* drow = p.dx + n * LF;
-        float g[D];
-        point_grad<D, F, SRC, LOD>(p, t, lam, [&](int l, float (&gv)[F]) { load_row<F>(drow + l * F, gv); }, g);
+        float g[D], unused;
+        point_walk<D, F, SRC, LOD, false, false>(p, t, n, lam, [&](int l, float (&gv)[F]) { load_row<F>(drow + l * F, gv); }, g, unused);
         store_point_grad<D>(p.dpoints, n, kept_axes<D>(p.d, p.points, n), g);
     }
 }
@@ -96,11 +96,11 @@ __global__ void __launch_bounds__(256) hash_points_fused_grad_kernel(const GradP
                                 p.y != nullptr ? p.y + r * 3 : nullptr, p.dscale);
         }
         wave_sync();
-        float gp[D];
-        point_grad<D, F, SRC, LOD>(p, t, lam, [&](int l, float (&gv)[F]) {
+        float gp[D], unused;
+        point_walk<D, F, SRC, LOD, false, false>(p, t, row, lam, [&](int l, float (&gv)[F]) {
 #pragma unroll
             for (int f = 0; f < F; ++f) gv[f] = xrow[l * F + f];
-        }, gp);
+        }, gp, unused);
         if (live_lane) store_point_grad<D>(p.dpoints, n_raw, kept_axes<D>(p.d, p.points, row), gp);
         wave_sync();
     }

@@ -5,9 +5,8 @@
 //   (ordered) points into its LDS tile, runs the decoder forward and backward on the fp32 matrix pipe and leaves d loss / d row in the tile,
 //   scatters it with the run sums, one record per workgroup for hash_fused_reduce_kernel - with two differences: the backward to the row is
 //   always taken (a frozen table still has positions to move), and after the scatter, the row gradient still untouched in the tile, the levels
-//   are walked once more for the position gradient: point_grad of hashgrid_pointgrad.hpp, the walk of hash_points_fused_grad_kernel, the same
-//   operations in the same order.  Row `row` of dpoints - the caller's numbering, order[pos] with an order - is written once by its lane;
-//   nothing is added to it.
+//   are walked once more for the position gradient: point_grad of hashgrid_pointgrad.hpp, the walk of hash_points_fused_grad_kernel.
+//   Row `row` of dpoints - the caller's numbering, order[pos] with an order - is written once by its lane; nothing is added to it.
 #include "hash_common.hpp"
 #include "hashgrid_pointgrad.hpp"
 
@@ -87,6 +86,8 @@ __global__ void __launch_bounds__(256) hash_points_joint_train_kernel(const Para
             for (int f = 0; f < F; ++f) gv[f] = xrow[l * F + f];
         };
         if (s.grad != nullptr) scatter_point<D, F, LOD>(s.d, t, s.grad, level_fade(s), lam, live_lane, lane, grow);
+        // through point_grad: with point_walk called from here and its unused `glam` a local of the kernel, every instantiation comes out with its
+        // MFMA accumulators in other registers
         float gp[D];
         point_grad<D, F, NIC_HASH_SRC_F32, LOD>(s, t, lam, grow, gp);
         if (live_lane) store_point_grad<D>(p.dpoints, row, kept_axes<D>(s.d, s.points, row), gp);
@@ -106,30 +107,6 @@ static int launch(const Params& p, int nb, void* stream) {
     });
 }
 
-// fused_step of hash_points_train.hip, line for line (static there; the two must stay in step - the CPU tests sweep both entries' codes):
-// the quantiser, the point count, the workspace, the tail, then the two launches.  `p` arrives with everything but noise, dscale and
-// partials set
-template <class Params>
-static int joint_step(Params& p, const nic_hash_quant* quant, const int32_t* order, float loss_scale, const nic_mlp_grads* mlp_grads, float* loss,
-                      int flags, void* workspace, size_t workspace_bytes, const nic_step_tail* tail, void* stream) {
-    p.noise.mode = NIC_NOISE_NONE;
-    int rc = set_noise(quant, true, p.noise, p.sample_base);
-    if (rc) return rc;
-    if (p.n < 0 || (order && p.n >= (int64_t(1) << 31))) return NIC_E_ARG;
-    const int lf = p.d.levels * p.d.features;
-    if (workspace_bytes < (size_t)wg_cap() * RecLayout(lf).rec * sizeof(float)) return NIC_E_WORKSPACE;
-    FusedTail ft;
-    if ((rc = check_fused_tail(tail, mlp_grads, lf, ft)) != NIC_OK) return rc;
-    if (p.n == 0) return NIC_OK;                                      // nothing to launch: *loss, dpoints and every gradient stay as they are
-    const int grid = persistent_grid((p.n + 63) >> 6);
-    const float loss_mul = (float)((double)loss_scale / (3.0 * (double)p.n));
-    p.dscale = 2.0f * loss_mul;
-    p.partials = (float*)workspace;
-    return finish_fused_step(ft, mlp_grads, flags, lf, grid, loss_mul, loss, p.partials, stream, [&] {
-        return p.noise.mode == NIC_NOISE_KERNEL ? launch<true>(p, grid, stream) : launch<false>(p, grid, stream);
-    });
-}
-
 }  // namespace hpjoint
 }  // namespace nic
 
@@ -144,32 +121,29 @@ int nic_hash_fused_forward_backward_points_grad(const nic_hash_desc* desc, const
                                                 float* y, float* dpoints, int flags, void* workspace, size_t workspace_bytes, const nic_step_tail* tail,
                                                 void* stream) {
     const KernelEndDrop end;
-    if (!desc || !mlp) return NIC_E_NULL;
-    int rc = nic_hash_fused_supported(desc, kH, mlp->n_linear);          // the only copy of the fused set (hash_fused.hip)
+    int rc = open_fused_points(desc, mlp);
     if (rc) return rc;
-    if ((rc = check_point_desc(desc)) != NIC_OK) return rc;
-    bool mlp_ok = true;
-    for (int i = 0; i < 3; ++i) mlp_ok = mlp_ok && mlp->w[i] && mlp->b[i];
-    if (!table || !points || !mlp_ok || !target || !mlp_grads || !loss || !dpoints || !workspace) return NIC_E_NULL;
+    if (!table || !points || !target || !mlp_grads || !loss || !dpoints || !workspace) return NIC_E_NULL;
     // flags, then the level of detail: the order include/nicv2_hip.h states for this entry (the _lod sibling asks check_lod first; both are
     // NIC_E_ARG, so no caller can tell)
     if (flags & ~(NIC_HASH_FUSED_ADD_GRADS | NIC_HASH_FUSED_ADD_LOSS)) return NIC_E_ARG;
     if (lodp && (rc = check_lod(desc, lodp)) != NIC_OK) return rc;
     if (!lodp && lod) return NIC_E_ARG;
-    auto fill = [&](auto& p) {
-        p.d = *desc; p.points = points; p.n = n_points; p.order = order; p.table = table; p.target = target; p.grad = table_grad; p.y = y;
-        p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
-        p.dpoints = dpoints;
+    auto step = [&](auto& p) {
+        return points_fused_step(p, quant, order, loss_scale, mlp_grads, loss, flags, workspace, workspace_bytes, tail, stream,
+                                 [&](auto noise, int grid) { return launch<decltype(noise)::value>(p, grid, stream); });
     };
     if (lodp) {
         JointParams<LodParams> p{};
-        fill(p);
+        fill_fused_points(p, desc, points, n_points, order, table, target, table_grad, y, mlp);
+        p.dpoints = dpoints;
         set_lod(p, lodp, lod);
-        return joint_step(p, quant, order, loss_scale, mlp_grads, loss, flags, workspace, workspace_bytes, tail, stream);
+        return step(p);
     }
     JointParams<PlainParams> p{};
-    fill(p);
-    return joint_step(p, quant, order, loss_scale, mlp_grads, loss, flags, workspace, workspace_bytes, tail, stream);
+    fill_fused_points(p, desc, points, n_points, order, table, target, table_grad, y, mlp);
+    p.dpoints = dpoints;
+    return step(p);
 }
 
 }  // extern "C"

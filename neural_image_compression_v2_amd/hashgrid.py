@@ -1345,10 +1345,10 @@ def hash_fused_forward_backward_points_grad(geo: HashGeometry, table: torch.Tens
     return loss, y, dpoints
 
 
-def _grad_lod(geo: HashGeometry, lod, lod_uniform, fade, n: int, device):
+def _grad_lod(geo: HashGeometry, lod, lod_uniform, fade, n: int, device, always: bool = False):
     """(``nic_hash_lod`` or None, the checked per-point tensor or None) of the gradient entries: no level of detail at all - ``lod`` None,
-    ``lod_uniform`` 0 and ``fade`` None - is the plain launch"""
-    if lod is None and fade is None and float(lod_uniform) == 0.0:
+    ``lod_uniform`` 0 and ``fade`` None - is the plain launch, unless the entry is ``always`` a level-of-detail launch"""
+    if not always and lod is None and fade is None and float(lod_uniform) == 0.0:
         return None, None
     per_point = _check_lod(lod, n, device)
     return _lod_struct(geo, fade, lod_uniform), per_point
@@ -1363,37 +1363,37 @@ def _check_dy_target(dy, target, n: int):
             raise ValueError(f"{name} must be [{n}, 3], got {tuple(v.shape) if isinstance(v, torch.Tensor) else type(v).__name__}")
 
 
-@fused._on_tensor_device
-def hash_encode_points_grad(geo: HashGeometry, data: torch.Tensor, points: torch.Tensor, dx: torch.Tensor, kind: str = "f32",
-                            num_bits: Optional[int] = None, lod: Optional[torch.Tensor] = None, lod_uniform: float = 0.0, fade=None) -> torch.Tensor:
-    """[N, dim] = d loss / d points for the [N, L F] gradient ``dx`` of ``hash_encode_points`` (``hash_encode_points_lod`` with any of ``lod`` /
-    ``lod_uniform`` / ``fade``) from the table ``data`` of ``kind`` (nic_hash_encode_points_grad; DESIGN 4.7.11): the derivative of the multilinear
-    interpolant at the rounded position, written (not added), 0 on an axis whose clamp moved the point.  The table is a constant."""
-    src, data = _point_source(geo, data, kind, num_bits)
+def _encode_points_grad(geo: HashGeometry, data: torch.Tensor, points, dx, lod, lod_uniform, fade, name: str, src=None, quant=None,
+                        dlod: bool = True):
+    """the three layer-wise gradient entries after the check of their table, which is the caller's: ``data`` is the checked table, ``src`` its
+    ``nic_hash_source`` or None for the entry that takes ``quant`` and the fp32 table; ``dlod`` False is the entry without d / d lambda, where no
+    level of detail at all is the plain launch.  Returns (dpoints, dlod or None)"""
     pts = _check_points(geo, points)
     n = pts.shape[0]
     dx = _lib.require_cuda_f32(dx.detach() if isinstance(dx, torch.Tensor) else dx, "dx")
     if tuple(dx.shape) != (n, geo.width):
         raise ValueError(f"dx must be [{n}, {geo.width}], got {tuple(dx.shape)}")
-    lp, lod_t = _grad_lod(geo, lod, lod_uniform, fade, n, pts.device)
+    lp, lod_t = _grad_lod(geo, lod, lod_uniform, fade, n, pts.device, always=dlod)
     d = _point_desc(geo)
+    if src is not None:
+        source = (ctypes.byref(src),)
+    else:
+        q = _quant_struct(quant)
+        source = (None if q is None else ctypes.byref(q), _lib.ptr(data))
     out = torch.empty(n, geo.dim, dtype=torch.float32, device=data.device)
+    dl = torch.empty(n, dtype=torch.float32, device=data.device) if dlod else None
     if n == 0:
-        return out
-    _lib.check(_lib.load().nic_hash_encode_points_grad(ctypes.byref(d), None if lp is None else ctypes.byref(lp), ctypes.byref(src), _lib.ptr(pts),
-                                                       _lib.ptr(lod_t), n, _lib.ptr(dx), _lib.ptr(out), _lib.stream_ptr(data.device)),
-               "nic_hash_encode_points_grad")
-    return out
+        return out, dl
+    outs = (_lib.ptr(out), _lib.ptr(dl)) if dlod else (_lib.ptr(out),)
+    _lib.check(getattr(_lib.load(), name)(ctypes.byref(d), None if lp is None else ctypes.byref(lp), *source, _lib.ptr(pts), _lib.ptr(lod_t), n,
+                                          _lib.ptr(dx), *outs, _lib.stream_ptr(data.device)), name)
+    return out, dl
 
 
-@fused._on_tensor_device
-def hash_fused_points_grad(geo: HashGeometry, data: torch.Tensor, points: torch.Tensor, params: Sequence[torch.Tensor],
-                           dy: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None, loss_scale: float = 1.0, want_y: bool = True,
-                           kind: str = "f32", num_bits: Optional[int] = None, lod: Optional[torch.Tensor] = None, lod_uniform: float = 0.0,
-                           fade=None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
-    """(y [N, 3] or None, dpoints [N, dim]) in one launch (nic_hash_fused_points_grad; DESIGN 4.7.11): y = ColorDecoder(hash_encode_points(...)),
-    then d loss / d points for the output gradient ``dy`` [N, 3], or for loss = mean((y - ``target``)^2) * ``loss_scale`` - exactly one of the
-    two.  Row and row gradient stay on the chip; table and decoder are constants."""
+def _fused_points_grad(geo: HashGeometry, data, points, params, dy, target, loss_scale, want_y, kind, num_bits, lod, lod_uniform, fade, name: str,
+                       dlod: bool):
+    """the two fused gradient entries; ``dlod`` False is the one without d / d lambda, where no level of detail at all is the plain launch.
+    Returns (y or None, dpoints, dlod or None)"""
     n = points.shape[0] if isinstance(points, torch.Tensor) and points.dim() == 2 else -1
     if n >= 0:
         _check_dy_target(dy, target, n)
@@ -1404,16 +1404,40 @@ def hash_fused_points_grad(geo: HashGeometry, data: torch.Tensor, points: torch.
     _check_dy_target(dy, target, n)
     dy = None if dy is None else _lib.require_cuda_f32(dy.detach(), "dy")
     target = None if target is None else _lib.require_cuda_f32(target.detach(), "target")
-    lp, lod_t = _grad_lod(geo, lod, lod_uniform, fade, n, pts.device)
+    lp, lod_t = _grad_lod(geo, lod, lod_uniform, fade, n, pts.device, always=dlod)
     d, m = _point_desc(geo), fused._mlp_struct(params)
     y = torch.empty(n, 3, dtype=torch.float32, device=data.device) if want_y else None
     out = torch.empty(n, geo.dim, dtype=torch.float32, device=data.device)
+    dl = torch.empty(n, dtype=torch.float32, device=data.device) if dlod else None
     if n == 0:
-        return y, out
-    _lib.check(_lib.load().nic_hash_fused_points_grad(ctypes.byref(d), None if lp is None else ctypes.byref(lp), ctypes.byref(src), _lib.ptr(pts),
-                                                      _lib.ptr(lod_t), n, ctypes.byref(m), _lib.ptr(dy), _lib.ptr(target), float(loss_scale),
-                                                      _lib.ptr(y), _lib.ptr(out), _lib.stream_ptr(data.device)), "nic_hash_fused_points_grad")
-    return y, out
+        return y, out, dl
+    outs = (_lib.ptr(out), _lib.ptr(dl)) if dlod else (_lib.ptr(out),)
+    _lib.check(getattr(_lib.load(), name)(ctypes.byref(d), None if lp is None else ctypes.byref(lp), ctypes.byref(src), _lib.ptr(pts), _lib.ptr(lod_t), n,
+                                          ctypes.byref(m), _lib.ptr(dy), _lib.ptr(target), float(loss_scale), _lib.ptr(y), *outs,
+                                          _lib.stream_ptr(data.device)), name)
+    return y, out, dl
+
+
+@fused._on_tensor_device
+def hash_encode_points_grad(geo: HashGeometry, data: torch.Tensor, points: torch.Tensor, dx: torch.Tensor, kind: str = "f32",
+                            num_bits: Optional[int] = None, lod: Optional[torch.Tensor] = None, lod_uniform: float = 0.0, fade=None) -> torch.Tensor:
+    """[N, dim] = d loss / d points for the [N, L F] gradient ``dx`` of ``hash_encode_points`` (``hash_encode_points_lod`` with any of ``lod`` /
+    ``lod_uniform`` / ``fade``) from the table ``data`` of ``kind`` (nic_hash_encode_points_grad; DESIGN 4.7.11): the derivative of the multilinear
+    interpolant at the rounded position, written (not added), 0 on an axis whose clamp moved the point.  The table is a constant."""
+    src, data = _point_source(geo, data, kind, num_bits)
+    return _encode_points_grad(geo, data, points, dx, lod, lod_uniform, fade, "nic_hash_encode_points_grad", src=src, dlod=False)[0]
+
+
+@fused._on_tensor_device
+def hash_fused_points_grad(geo: HashGeometry, data: torch.Tensor, points: torch.Tensor, params: Sequence[torch.Tensor],
+                           dy: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None, loss_scale: float = 1.0, want_y: bool = True,
+                           kind: str = "f32", num_bits: Optional[int] = None, lod: Optional[torch.Tensor] = None, lod_uniform: float = 0.0,
+                           fade=None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+    """(y [N, 3] or None, dpoints [N, dim]) in one launch (nic_hash_fused_points_grad; DESIGN 4.7.11): y = ColorDecoder(hash_encode_points(...)),
+    then d loss / d points for the output gradient ``dy`` [N, 3], or for loss = mean((y - ``target``)^2) * ``loss_scale`` - exactly one of the
+    two.  Row and row gradient stay on the chip; table and decoder are constants."""
+    return _fused_points_grad(geo, data, points, params, dy, target, loss_scale, want_y, kind, num_bits, lod, lod_uniform, fade,
+                              "nic_hash_fused_points_grad", dlod=False)[:2]
 
 
 # ---- the gradient with respect to the level of detail, next to the one with respect to the points (DESIGN 4.7.22; include/nicv2_hip_ext.h) ------
@@ -1427,22 +1451,7 @@ def hash_encode_points_grad_lod(geo: HashGeometry, data: torch.Tensor, points: t
     respect to lambda_n, exactly 0 where lambda_raw < 0, >= 32 or NaN.  Always a level-of-detail launch: ``lod`` None, ``lod_uniform`` 0 and
     ``fade`` None is lambda = 0 with the default fades.  Written, not added; the gradient for ``lod_uniform`` is ``dlod.sum()``."""
     src, data = _point_source(geo, data, kind, num_bits)
-    pts = _check_points(geo, points)
-    n = pts.shape[0]
-    dx = _lib.require_cuda_f32(dx.detach() if isinstance(dx, torch.Tensor) else dx, "dx")
-    if tuple(dx.shape) != (n, geo.width):
-        raise ValueError(f"dx must be [{n}, {geo.width}], got {tuple(dx.shape)}")
-    lod_t = _check_lod(lod, n, pts.device)
-    lp = _lod_struct(geo, fade, lod_uniform)
-    d = _point_desc(geo)
-    out = torch.empty(n, geo.dim, dtype=torch.float32, device=data.device)
-    dlod = torch.empty(n, dtype=torch.float32, device=data.device)
-    if n == 0:
-        return out, dlod
-    _lib.check(_lib.load().nic_hash_encode_points_grad_lod(ctypes.byref(d), ctypes.byref(lp), ctypes.byref(src), _lib.ptr(pts), _lib.ptr(lod_t), n,
-                                                           _lib.ptr(dx), _lib.ptr(out), _lib.ptr(dlod), _lib.stream_ptr(data.device)),
-               "nic_hash_encode_points_grad_lod")
-    return out, dlod
+    return _encode_points_grad(geo, data, points, dx, lod, lod_uniform, fade, "nic_hash_encode_points_grad_lod", src=src)
 
 
 @fused._on_tensor_device
@@ -1453,29 +1462,8 @@ def hash_fused_points_grad_lod(geo: HashGeometry, data: torch.Tensor, points: to
     """(y [N, 3] or None, dpoints [N, dim], dlod [N]) in one launch (nic_hash_fused_points_grad_lod): ``hash_fused_points_grad``
     with the same level of detail - y and dpoints bit for bit - and the gradient with respect to lambda_n of ``hash_encode_points_grad_lod``
     for the row gradient the decoder's backward leaves on the chip.  Always a level-of-detail launch."""
-    n = points.shape[0] if isinstance(points, torch.Tensor) and points.dim() == 2 else -1
-    if n >= 0:
-        _check_dy_target(dy, target, n)
-    src, data = _point_source(geo, data, kind, num_bits)
-    params = _check_fused_decoder(geo, [q.detach() for q in params])
-    pts = _check_points(geo, points)
-    n = pts.shape[0]
-    _check_dy_target(dy, target, n)
-    dy = None if dy is None else _lib.require_cuda_f32(dy.detach(), "dy")
-    target = None if target is None else _lib.require_cuda_f32(target.detach(), "target")
-    lod_t = _check_lod(lod, n, pts.device)
-    lp = _lod_struct(geo, fade, lod_uniform)
-    d, m = _point_desc(geo), fused._mlp_struct(params)
-    y = torch.empty(n, 3, dtype=torch.float32, device=data.device) if want_y else None
-    out = torch.empty(n, geo.dim, dtype=torch.float32, device=data.device)
-    dlod = torch.empty(n, dtype=torch.float32, device=data.device)
-    if n == 0:
-        return y, out, dlod
-    _lib.check(_lib.load().nic_hash_fused_points_grad_lod(ctypes.byref(d), ctypes.byref(lp), ctypes.byref(src), _lib.ptr(pts), _lib.ptr(lod_t), n,
-                                                          ctypes.byref(m), _lib.ptr(dy), _lib.ptr(target), float(loss_scale), _lib.ptr(y),
-                                                          _lib.ptr(out), _lib.ptr(dlod), _lib.stream_ptr(data.device)),
-               "nic_hash_fused_points_grad_lod")
-    return y, out, dlod
+    return _fused_points_grad(geo, data, points, params, dy, target, loss_scale, want_y, kind, num_bits, lod, lod_uniform, fade,
+                              "nic_hash_fused_points_grad_lod", dlod=True)
 
 
 # ---- the gradient with respect to the level of detail from the training step (DESIGN 4.7.23; include/nicv2_hip_ext.h) ----------------------------
@@ -1533,22 +1521,7 @@ def hash_encode_points_grad_lod_noisy(geo: HashGeometry, table: torch.Tensor, po
     forward added inside the weighed column - the slope of column l F + f on the ramp is -(r + nz).  ``quant``: None, or the forward's
     (num_bits, seed, offset, sample_base); with None both outputs are ``hash_encode_points_grad_lod``'s bit for bit."""
     t = _check_table(geo, table.detach())
-    pts = _check_points(geo, points)
-    n = pts.shape[0]
-    dx = _lib.require_cuda_f32(dx.detach() if isinstance(dx, torch.Tensor) else dx, "dx")
-    if tuple(dx.shape) != (n, geo.width):
-        raise ValueError(f"dx must be [{n}, {geo.width}], got {tuple(dx.shape)}")
-    lod_t = _check_lod(lod, n, pts.device)
-    lp = _lod_struct(geo, fade, lod_uniform)
-    d, q = _point_desc(geo), _quant_struct(quant)
-    out = torch.empty(n, geo.dim, dtype=torch.float32, device=t.device)
-    dlod = torch.empty(n, dtype=torch.float32, device=t.device)
-    if n == 0:
-        return out, dlod
-    _lib.check(_lib.load().nic_hash_encode_points_grad_lod_noisy(ctypes.byref(d), ctypes.byref(lp), None if q is None else ctypes.byref(q), _lib.ptr(t),
-                                                                 _lib.ptr(pts), _lib.ptr(lod_t), n, _lib.ptr(dx), _lib.ptr(out), _lib.ptr(dlod),
-                                                                 _lib.stream_ptr(t.device)), "nic_hash_encode_points_grad_lod_noisy")
-    return out, dlod
+    return _encode_points_grad(geo, t, points, dx, lod, lod_uniform, fade, "nic_hash_encode_points_grad_lod_noisy", quant=quant)
 
 
 # ---- B fields per launch with the gradient with respect to the point coordinates (DESIGN 4.7.21; include/nicv2_hip_ext.h) ------------------------

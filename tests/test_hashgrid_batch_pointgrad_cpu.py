@@ -254,13 +254,13 @@ def test_the_kernels_call_the_shared_helpers_and_restate_none():
         assert re.search(rf'^\s*#include\s+"{re.escape(inc)}"', grad, re.M) and re.search(rf'^\s*#include\s+"{re.escape(inc)}"', joint, re.M), inc
     assert re.search(r'^\s*#include\s+".*nicv2_hip_ext\.h"', grad, re.M)
     device = ["lattice_fixed", "load_decoder", "decoder_forward_half", "decoder_train_half", "write_record", "persistent_grid", "strided_grid", "field_range",
-              "field_loss_mul", "field_count", "decoder_dx_half", "point_grad", "point_grad_levels", "kept_axes", "store_point_grad"]
+              "field_loss_mul", "field_count", "decoder_dx_half", "point_grad", "point_walk", "point_walk_levels", "kept_axes", "store_point_grad"]
     for name in common.FUNCTIONS + list(common.OVERLOADS) + device:
         assert not any(common._function_re(name).match(ln) for ln in grad.splitlines()), name
     for name in common.STRUCTS + ["DecoderSmem", "TrainSmem", "TrainAcc", "SParams", "StoredSrc"]:
         assert not any(common._struct_re(name).match(ln) for ln in grad.splitlines()), name
     # the walk and the decoder's backward to the input: one definition each, in the shared header
-    for name in ("decoder_dx_half", "point_grad", "point_grad_levels", "kept_axes", "store_point_grad"):
+    for name in ("decoder_dx_half", "point_grad", "point_walk", "point_walk_levels", "kept_axes", "store_point_grad"):
         found = sorted(f for f, t in texts.items() if any(common._function_re(name).match(ln) for ln in t.splitlines()))
         assert found == [WALK], (name, found)
     assert "decoder_dx_half<KT>(" in texts["hashgrid_pointgrad.hip"]

@@ -83,3 +83,39 @@ def test_the_definition_pattern_sees_a_definition_and_not_a_call():
     assert not _function_re("hash_index").match("    return (int)hash_index(hash_level_dense(desc->dim, R, desc->log2_table), (uint32_t)R);")
     assert _function_re("patch_sample").match("__device__ __forceinline__ PatchSample<D> patch_sample(const nic_hash_desc& d, int64_t wv) {")
     assert _struct_re("PatchSample").match("struct PatchSample {") and not _struct_re("PatchSample").match("    PatchSample<D> s;")
+
+
+# ---- the second level walk and the host path of the fused step at points: one definition over all of csrc/  --------------------
+WALK_HEADER = "hashgrid_pointgrad.hpp"
+WALK_HELPERS = ["point_walk_levels", "point_walk", "lambda_passes", "kept_axes", "store_point_grad", "decoder_dx_half"]
+RETIRED = ["point_grad_levels", "point_grad_lod_levels", "point_grad_lod_noisy_levels", "fused_step", "joint_step"]
+POINT_GRAD_UNITS = ["hash_points_train.hip", "hashgrid_points_joint.hip", "hashgrid_lodtrain.hip", "hashgrid_pointgrad.hip", "hashgrid_lodgrad.hip"]
+
+
+def _all_sources():
+    out = {}
+    for p in sorted(glob.glob(os.path.join(_build.CSRC, "*"))):
+        if os.path.isfile(p):
+            with open(p) as f:
+                out[os.path.basename(p)] = f.read().splitlines()
+    return out
+
+
+def test_the_point_walk_and_the_step_host_path_are_defined_once_in_all_of_csrc():
+    src = _all_sources()
+    assert WALK_HEADER in src and HEADER in src and all(u in src for u in POINT_GRAD_UNITS)
+    assert WALK_HEADER in _build.HEADERS and all(u in _build.SOURCES for u in POINT_GRAD_UNITS)
+    for name in WALK_HELPERS:
+        found = _definitions(_function_re(name), src)
+        assert len(found) == 1 and found[0][0] == WALK_HEADER, (name, found)
+    found = _definitions(_function_re("points_fused_step"), src)
+    assert len(found) == 1 and found[0][0] == HEADER, found
+    for name in RETIRED:
+        assert _definitions(_function_re(name), src) == [], name
+    for u in POINT_GRAD_UNITS:
+        assert not any("atomicAdd" in ln for ln in src[u]), u
+    # the pattern sees the definitions it is asked about, and tells the shared step from the retired one
+    assert _function_re("point_walk").match("__device__ __forceinline__ void point_walk(const Src& s, const uint32_t (&t)[3], int64_t n) {")
+    assert not _function_re("point_walk").match("__device__ __forceinline__ void point_walk_levels(const Src& s, const uint32_t (&t)[3]) {")
+    assert _function_re("fused_step").match("static int fused_step(Params& p, const nic_hash_quant* quant) {")
+    assert not _function_re("fused_step").match("inline int points_fused_step(Params& p, const nic_hash_quant* quant) {")

@@ -34,7 +34,7 @@ ARGS = {ENC: ["desc", "lodp", "src", "points", "lod", "n_points", "dx", "dpoints
         FUSED: ["desc", "lodp", "src", "points", "lod", "n_points", "mlp", "dy", "target", "loss_scale", "y", "dpoints", "dlod", "stream"]}
 SIBLINGS = {ENC: "nic_hash_encode_points_grad", FUSED: "nic_hash_fused_points_grad"}
 PTR = ctypes.c_void_p
-UNIT, WALK = "hashgrid_lodgrad.hip", "hashgrid_lodgrad.hpp"
+UNIT, WALK = "hashgrid_lodgrad.hip", "hashgrid_pointgrad.hpp"
 F32 = np.float32
 TOL_G = 1e-4            # tests/test_gpu_hashgrid_pointgrad.py's: of the largest magnitude of the compared tensor
 
@@ -382,17 +382,17 @@ def test_the_unit_and_its_header_are_in_the_build_and_restate_no_shared_helper()
     for f in (UNIT, WALK):
         assert f.startswith("hashgrid_") and not f.startswith(("hash_", "lod_"))
     unit, walk = (open(os.path.join(_build.CSRC, f)).read() for f in (UNIT, WALK))
-    assert re.search(r'^\s*#include\s+"hashgrid_pointgrad\.hpp"', walk, re.M) and re.search(r'^\s*#include\s+"hashgrid_lodgrad\.hpp"', unit, re.M)
+    assert re.search(r'^\s*#include\s+"hash_common\.hpp"', walk, re.M) and re.search(r'^\s*#include\s+"hashgrid_pointgrad\.hpp"', unit, re.M)
+    walk_helpers = ["decoder_dx_half", "point_grad", "point_walk", "point_walk_levels", "kept_axes", "store_point_grad", "lambda_passes"]
     for text in (unit, walk):
-        for name in common.FUNCTIONS + list(common.OVERLOADS) + ["decoder_dx_half", "point_grad", "point_grad_levels", "kept_axes", "store_point_grad"]:
-            assert not any(common._function_re(name).match(ln) for ln in text.splitlines()), name
+        for name in common.FUNCTIONS + list(common.OVERLOADS) + walk_helpers:
+            # the walk header defines its own helpers once each; nothing else is restated anywhere
+            assert sum(bool(common._function_re(name).match(ln)) for ln in text.splitlines()) == (1 if text is walk and name in walk_helpers else 0), name
         for name in common.STRUCTS:
             assert not any(common._struct_re(name).match(ln) for ln in text.splitlines()), name
         assert "atomic" not in text
-    for name in ("point_grad_lod_levels", "point_grad_lod"):
-        assert sum(bool(common._function_re(name).match(ln)) for ln in walk.splitlines()) == 1, name
     for call in ("hash_points_grad_lod_kernel<D, F, SRC>", "hash_points_fused_grad_lod_kernel<D, F, SRC, 2>", "hash_points_fused_grad_lod_kernel<D, F, SRC, 1>",
-                 "p.d.levels * F > 32", "decoder_dx_half<KT>(", "encode_point<D, F, SRC, false, false, true>(p, t, 0, lam, xrow)", "point_grad_lod<D, F, SRC>("):
+                 "p.d.levels * F > 32", "decoder_dx_half<KT>(", "encode_point<D, F, SRC, false, false, true>(p, t, 0, lam, xrow)", "point_walk<D, F, SRC, true, true, false>("):
         assert call in unit, call
     assert "accl = fmaf(pw, dot, accl)" in walk and "glam = __fsub_rn(glam, accl)" in walk
 

@@ -38,7 +38,7 @@ ARGS = {FUSED: ["desc", "lodp", "quant", "table", "points", "lod", "n_points", "
                 "dpoints", "dlod", "flags", "workspace", "workspace_bytes", "tail", "stream"],
         ENC: ["desc", "lodp", "quant", "table", "points", "lod", "n_points", "dx", "dpoints", "dlod", "stream"]}
 PTR = ctypes.c_void_p
-UNIT, WALK = "hashgrid_lodtrain.hip", "hashgrid_lodtrain.hpp"
+UNIT, WALK = "hashgrid_lodtrain.hip", "hashgrid_pointgrad.hpp"
 
 # ------------------------------------------------------------------------------------------------------------------ shared with the GPU file
 # (bits, seed, offset, sample_base): sample_base != 0, a seed and an offset with both 32-bit halves in use
@@ -348,24 +348,27 @@ def test_the_unit_and_its_header_are_in_the_build_and_restate_no_shared_helper()
     for f in (UNIT, WALK):
         assert f.startswith("hashgrid_") and not f.startswith("hash_") and f not in common.UNITS
     unit, walk = (open(os.path.join(_build.CSRC, f)).read() for f in (UNIT, WALK))
-    assert re.search(r'^\s*#include\s+"hashgrid_lodgrad\.hpp"', walk, re.M) and re.search(r'^\s*#include\s+"hashgrid_lodtrain\.hpp"', unit, re.M)
+    assert re.search(r'^\s*#include\s+"hash_common\.hpp"', walk, re.M) and re.search(r'^\s*#include\s+"hashgrid_pointgrad\.hpp"', unit, re.M)
     shared = common.FUNCTIONS + list(common.OVERLOADS) + ["load_decoder", "decoder_train_half", "write_record", "persistent_grid", "strided_grid", "point_grad",
-                                                          "point_grad_levels", "kept_axes", "store_point_grad", "point_grad_lod", "point_grad_lod_levels",
-                                                          "lambda_passes", "noise_block", "noise_from_block"]
+                                                          "point_walk", "point_walk_levels", "kept_axes", "store_point_grad", "lambda_passes", "noise_block",
+                                                          "noise_from_block"]
+    own = ["point_grad", "point_walk", "point_walk_levels", "kept_axes", "store_point_grad", "lambda_passes"]      # the walk header's: once each
     for text in (unit, walk):
         for name in shared:
-            assert not any(common._function_re(name).match(ln) for ln in text.splitlines()), name
+            assert sum(bool(common._function_re(name).match(ln)) for ln in text.splitlines()) == (1 if text is walk and name in own else 0), name
         for name in common.STRUCTS + ["DecoderSmem", "TrainSmem", "TrainAcc"]:
             assert not any(common._struct_re(name).match(ln) for ln in text.splitlines()), name
         assert "atomicAdd" not in text                                         # the only atomics are scatter_point's, in the shared header
     for piece in ("hash_points_lod_train_kernel<D, F, 2, NOISE>", "hash_points_lod_train_kernel<D, F, 1, NOISE>", "hash_points_grad_lod_noisy_kernel<D, F, NOISE>",
                   "p.d.levels * F > 32", "load_decoder(", "encode_point<D, F, NIC_HASH_SRC_F32, NOISE, false, true>(s, t, row, lam, xrow)",
                   "decoder_train_half<KT>(", "scatter_point<D, F, true>(", "write_record<KT>(", "xcd_range(", "ordered_row(", "point_lambda(",
-                  "store_point_grad<D>(p.dpoints, row,", "kept_axes<D>(", "check_fused_tail(", "finish_fused_step(", "p.dlod[row] = lambda_passes("):
+                  "store_point_grad<D>(p.dpoints, row,", "kept_axes<D>(", "open_fused_points(", "fill_fused_points(", "points_fused_step(", "p.dlod[row] = lambda_passes(",
+                  "point_walk<D, F, NIC_HASH_SRC_F32, true, true, NOISE>(s, t, row, lam, grow, gp, gl)"):
         assert piece in unit, piece
-    # the walk regenerates the noise with the forward's key and subtracts it with the blend; without noise it is 4.7.22's walk itself
+    assert "check_fused_tail(" not in unit and "finish_fused_step(" not in unit      # the host path of the step is hash_common.hpp's
+    # the walk regenerates the noise with the forward's key and subtracts it with the blend; without noise it is 4.7.22's walk itself: one body
     for piece in ("noise_block(s.noise, s.sample_base + (uint64_t)n, nblk_id)", "noise_from_block(s.noise, nblk, (c0 + f) & 15)",
-                  "glam = __fsub_rn(glam, __fadd_rn(accl, nd))", "else point_grad_lod<D, F, NIC_HASH_SRC_F32>(s, t, lam, grow, g, glam)"):
+                  "glam = __fsub_rn(glam, __fadd_rn(accl, nd))", "glam = __fsub_rn(glam, accl)", "if constexpr (NOISE) {"):
         assert piece in walk, piece
 
 

@@ -137,15 +137,20 @@ def test_the_unit_is_in_the_build_and_the_walk_exists_once():
         for struct in common.STRUCTS + ["DecoderSmem", "TrainSmem", "TrainAcc"]:
             assert not any(common._struct_re(struct).match(ln) for ln in lines), (name, struct)
     # the walk: defined in the shared header, once, as templates on the struct they read, and in neither unit
-    for helper in ("kept_axes", "point_grad_levels", "point_grad", "store_point_grad"):
+    for helper in ("kept_axes", "point_walk_levels", "point_walk", "point_grad", "store_point_grad", "lambda_passes"):
         found = {name: sum(bool(common._function_re(helper).match(ln)) for ln in t.splitlines()) for name, t in text.items()}
         assert found == {UNIT: 0, SHARED: 1, "hashgrid_pointgrad.hip": 0}, (helper, found)
-    assert text[SHARED].count("const Src& s") == 2
+    assert text[SHARED].count("const Src& s") == 3                             # the walk, its q_tight dispatcher, the position-gradient wrapper
     joint = text[UNIT]
     for piece in ("hash_points_joint_train_kernel", "load_decoder(", "encode_point<", "decoder_train_half<KT>(", "scatter_point<", "write_record<KT>(",
-                  "xcd_range(", "ordered_row(", "point_lambda(", "point_grad<", "store_point_grad<D>(", "kept_axes<D>(", "check_fused_tail(",
-                  "finish_fused_step("):
+                  "xcd_range(", "ordered_row(", "point_lambda(", "point_grad<", "store_point_grad<D>(", "kept_axes<D>(", "open_fused_points(",
+                  "fill_fused_points(", "points_fused_step("):
         assert piece in joint, piece
+    # the host path of the step is hash_common.hpp's: the tail and the end of the step are called from there, in that order
+    step = open(os.path.join(_build.CSRC, common.HEADER)).read()
+    step = step[step.index("inline int points_fused_step("):]
+    assert 0 < step.index("set_noise(") < step.index("NIC_E_WORKSPACE") < step.index("check_fused_tail(") < step.index("finish_fused_step(")
+    assert "check_fused_tail(" not in joint and "finish_fused_step(" not in joint
     assert "atomicAdd" not in joint                                            # the only atomics are scatter_point's, in the shared header
 
 
