@@ -166,7 +166,8 @@ int nic_hash_batch_forward_backward_points_grad(const nic_hash_desc *desc, int n
  *      right-hand derivative of the clamp); lambda_raw == 0 passes the gradient through.  Positions enter only through r, taken at the
  *      rounded and clamped position the forward uses: a clamped axis does not zero dlod.  dlod = [n_points] fp32 on the device, row n
  *      WRITTEN (never added to) by the lane of point n; nothing past n_points is touched.  The gradient for lod_uniform is the sum of dlod;
- *      the caller forms it.  There is no gradient with respect to fade, no second derivative and no batched or training-step form.
+ *      the caller forms it.  There is no gradient with respect to fade and no second derivative; the training-step and batched forms are the
+ *      sections below.
  *      Host checks, all before any GPU work, are the siblings' in the siblings' order with two changes: lodp == NULL is NIC_E_NULL,
  *      reported with the other pointers (these are _lod entries), and dlod == NULL is NIC_E_NULL.  Layer-wise: the descriptor of a point
  *      source (check of nic_hash_encode_points: NIC_E_NULL / NIC_E_ARG / NIC_E_SHAPE); null lodp, src, src->data, points, dx, dpoints or
@@ -215,7 +216,7 @@ int nic_hash_fused_points_grad_lod(const nic_hash_desc *desc, const nic_hash_lod
  *      atomics, the same call gives the same bits.
  *      Host checks: the descriptor of a point source; null lodp, table, points, dx, dpoints or dlod (NIC_E_NULL; quant and lod may be
  *      null); the nic_hash_lod (NIC_E_ARG); quant (as above); n_points < 0 (NIC_E_ARG); n_points == 0 is NIC_OK without a launch.
- *      There is no batched form, no bit depth per level, no 16-bit precision mode, no stored table, no second derivative and no gradient
+ *      The batched form is the section below.  There is no bit depth per level, no 16-bit precision mode, no stored table, no second derivative and no gradient
  *      with respect to fade. */
 int nic_hash_encode_points_grad_lod_noisy(const nic_hash_desc *desc, const nic_hash_lod *lodp, const nic_hash_quant *quant, const float *table,
                                           const float *points, const float *lod, int64_t n_points, const float *dx, float *dpoints,
@@ -226,6 +227,39 @@ int nic_hash_fused_forward_backward_points_grad_lod(const nic_hash_desc *desc, c
                                                     float *table_grad, const nic_mlp_grads *mlp_grads, float *loss, float *y, float *dpoints,
                                                     float *dlod, int flags, void *workspace, size_t workspace_bytes,
                                                     const nic_step_tail *tail, void *stream);
+
+/* ---- B hash-grid fields per launch with the gradient with respect to the LEVEL OF DETAIL, alone and in the training step (hashgrid.py,
+ *      hash_batch_points_grad_lod, hash_batch_forward_backward_points_grad_lod, HashGridFieldBatch.point_gradient_lod / jacobian_lod /
+ *      query_differentiable_lod / train_points_grad_lod / train_points_differentiable_lod; csrc/hashgrid_batch_grad.hip,
+ *      hash_batch_points_grad_lod_kernel; csrc/hashgrid_batch.hip, hash_batch_points_joint_lod_kernel).
+ *      nic_hash_batch_points_grad_lod is nic_hash_batch_points_grad and nic_hash_batch_forward_backward_points_grad_lod is
+ *      nic_hash_batch_forward_backward_points_grad, argument for argument, with dlod after dpoints and a level of detail always on: the
+ *      same launches, gathers, records, reduction, flags, workspace, counts and order; y and dpoints (and loss and the decoder gradients
+ *      of the step) are the siblings' called with the same nic_hash_lod bit for bit.  dlod = [B, n_points] fp32 on the device; the
+ *      definitions are the two sections above, per field: dlod[b, n] = passes ? - sum_{l on the ramp} sum_f g[l F + f] (r[l, f] + nz[l F + f])
+ *      : 0 with lambda_raw = (lod ? lod[b, n] : 0) + lod_uniform read at the field-local ROW n, g = d loss_b / d row (with target the
+ *      output gradient is 2 (y - target) loss_scale / (3 n_b), n_b the field's OWN count), r the unweighed blend of field b's table at the
+ *      rounded, clamped position, nz the noise the step's forward added - keyed by sample_base + n, n the field-local row whatever the
+ *      order - and 0 in the gradient-only entry, which has no quant.  The right-hand derivative: a_raw == 1 has slope -1, a_raw == 0 slope 0;
+ *      exactly 0.0f where lambda_raw < 0, >= 32 or NaN; a clamped axis zeroes its dpoints and not dlod.  Row order[b, pos] of dlod is
+ *      WRITTEN once by the lane that handles it, never added to and touched by no atomic, whatever NIC_HASH_FUSED_ADD_GRADS says; rows at or
+ *      past n_b, and rows an order does not name, are NOT written; a field with n_b = 0 writes nothing.  Field b's rows are
+ *      nic_hash_fused_points_grad_lod's / nic_hash_fused_forward_backward_points_grad_lod's on field b's tensors bit for bit.  The gradient
+ *      for lod_uniform, or for a lod shared by the fields, is a sum of dlod; the caller forms it.
+ *      Host checks, all before any GPU work: the siblings' in the siblings' order with two changes - lodp == NULL is NIC_E_NULL, reported
+ *      with the other pointers (these are _lod entries; lod may be null), and dlod == NULL is NIC_E_NULL in the same check; the
+ *      nic_hash_lod is checked where the siblings check it.  n_points == 0 is NIC_OK without a launch, nothing written.
+ *      There is no 16-bit precision mode, no bit depth per level, no second derivative and no gradient with respect to fade. */
+int nic_hash_batch_points_grad_lod(const nic_hash_desc *desc, int n_fields, int groups_per_field, const nic_hash_lod *lodp,
+                                   const nic_hash_source *src, const float *points, const float *lod, int64_t n_points,
+                                   const int32_t *counts, const int32_t *order, const nic_mlp *mlp, const float *dy,
+                                   const float *target, float loss_scale, float *y, float *dpoints, float *dlod, void *stream);
+int nic_hash_batch_forward_backward_points_grad_lod(const nic_hash_desc *desc, int n_fields, int groups_per_field,
+                                                    const nic_hash_lod *lodp, const nic_hash_quant *quant, const float *tables,
+                                                    const float *points, const float *lod, int64_t n_points, const int32_t *counts,
+                                                    const int32_t *order, const nic_mlp *mlp, const float *target, float loss_scale,
+                                                    float *table_grads, const nic_mlp_grads *mlp_grads, float *loss, float *y, float *dpoints,
+                                                    float *dlod, int flags, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -20,7 +20,8 @@ _HASHGRID_NAMES = ("HashGeometry", "HashGridField", "HashGridFieldBatch", "hash_
                    "hash_batch_forward_p16", "hash_batch_groups_p16", "hash_batch_forward_backward_points", "hash_batch_point_order",
                    "hash_batch_forward_points_lod", "hash_batch_forward_backward_points_lod", "hash_batch_points_grad",
                    "hash_batch_forward_backward_points_grad", "hash_encode_points_grad_lod", "hash_fused_points_grad_lod",
-                   "hash_encode_points_grad_lod_noisy", "hash_fused_forward_backward_points_grad_lod")
+                   "hash_encode_points_grad_lod_noisy", "hash_fused_forward_backward_points_grad_lod", "hash_batch_points_grad_lod",
+                   "hash_batch_forward_backward_points_grad_lod")
 
 
 def __getattr__(name):

@@ -28,7 +28,9 @@
 //   hash_batch_points_joint_kernel, at the end of the unit, is the two training kernels at points with the two differences of
 //   hash_points_joint_train_kernel (hashgrid_points_joint.hip) - the backward to the row is always taken, and after the scatter the levels are
 //   walked once more for the position gradient (hashgrid_pointgrad.hpp), row `row` of field b's slice of dpoints written once by its lane.
-// Every device helper is hash_common.hpp's or hashgrid_pointgrad.hpp's; this unit holds the seven kernels, their parameters and the host side.  What the 16-bit batched
+//   the same step with d loss / d lambda on top (nic_hash_batch_forward_backward_points_grad_lod): hash_batch_points_joint_lod_kernel,
+//   after it, asks that walk for the level-of-detail accumulator and the noise term and stores dlod[b, row] beside dpoints.
+// Every device helper is hash_common.hpp's or hashgrid_pointgrad.hpp's; this unit holds the eight kernels, their parameters and the host side.  What the 16-bit batched
 // kernel (hashgrid_fused16.hip) shares with them - field_range, SParams, StoredSrc, the rules on B and G - is hashgrid_batch.hpp's.
 #include "hash_common.hpp"
 #include "hashgrid_batch.hpp"
@@ -602,6 +604,92 @@ static int launch_points_joint(const PJParams& p, int n_fields, void* stream) {
     });
 }
 
+// ---- the same step that also hands back d loss / d lambda (nic_hash_batch_forward_backward_points_grad_lod) ---------------------
+// hash_batch_points_joint_kernel<.., LOD = true> with the walk asked for d / d lambda and the noise (point_walk, hashgrid_pointgrad.hpp) where that
+// calls point_grad - hash_points_lod_train_kernel (hashgrid_lodtrain.hip) per field: the same gathers, records, scatter and dpoints bit for bit,
+// one more accumulator and one more store per point.  `row` is the field-local row the forward keyed its noise with (sample_base + row), so the
+// nz the walk regenerates is the value the forward added.  Row `row` of field b's slice of dlod is written once by its live lane, exactly 0.0f
+// where the clamp of lambda is flat; rows at or past n_b are not written, nothing is added.  A kernel of its own: the one above keeps its code.
+struct PJLParams : PJParams {
+    float* dlod;              // [B, n]
+};
+
+template <int D, int F, int KT, bool NOISE>
+__global__ void __launch_bounds__(256) hash_batch_points_joint_lod_kernel(const PJLParams p) {
+    __shared__ TrainSmem sm;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 31, half = lane >> 5;
+    const int LF = p.d.levels * F;
+    const int b = (int)(blockIdx.x / (unsigned)p.groups), lb = (int)(blockIdx.x - (unsigned)b * (unsigned)p.groups);
+    const int64_t tab_off = (((int64_t)b * p.d.levels) << p.d.log2_table) * F, row_off = (int64_t)b * p.n * 3;
+    load_decoder(sm, p.w1 + (int64_t)b * kH * LF, p.b1 + b * kH, p.w2 + (int64_t)b * kH * kH, p.b2 + b * kH, p.w3 + b * 3 * kH, p.b3 + b * 3, LF, tid);
+    __syncthreads();
+    float* xs = sm.x[wave];
+    float* xrow = xs + lane * XS;
+    float* P = sm.p[wave];
+    float* Q = sm.q[wave];
+    const int64_t n_b = field_count(p.counts, b, p.n);          // workgroup-uniform
+    const float dscale = n_b > 0 ? 2.0f * field_loss_mul(p.loss_scale, n_b) : 0.f;
+    const float* points = p.points + (int64_t)b * p.n * D;
+    const float* lod_b = p.lod != nullptr ? p.lod + (int64_t)b * p.n : nullptr;
+    const int32_t* order = p.order != nullptr ? p.order + (int64_t)b * p.n : nullptr;
+    const LodFieldSrc src_b{{p.d, p.tables + tab_off, p.noise, p.sample_base}, p.fade};
+    float* grad = p.grads != nullptr ? p.grads + tab_off : nullptr;
+    const float* target = p.target + row_off;
+    float* y = p.y != nullptr ? p.y + row_off : nullptr;
+    float* dpoints = p.dpoints + (int64_t)b * p.n * D;
+    float* dlod = p.dlod + (int64_t)b * p.n;
+    const int ks1 = (LF + 1) >> 1;
+    const int64_t n_waves = (n_b + 63) >> 6;
+    const WaveRange wr = field_range(n_waves, lb, p.groups);
+    TrainAcc<KT> A;
+    A.clear();
+    for (int64_t g = wr.begin; g < wr.end; g += wr.step) {
+        const int64_t wv = 4 * g + wave;
+        if (wv >= n_waves) continue;                            // wave-uniform; nothing below synchronises the workgroup
+        const int64_t pos = (wv << 6) + lane;
+        const bool live_lane = pos < n_b;
+        const int64_t row = ordered_row(order, n_b, live_lane ? pos : n_b - 1);      // a lane past the end takes the field's last point; it stores and adds nothing
+        const float lam = point_lambda(lod_b, p.lod_uniform, row);                   // at the ROW, as the point
+        uint32_t t[3];
+        point_fixed<D>(p.d, points, row, t);
+        encode_point<D, F, NIC_HASH_SRC_F32, NOISE, false, true>(src_b, t, row, lam, xrow);
+        wave_sync();
+        const unsigned long long live_mask = __ballot(live_lane);
+#pragma unroll 1
+        for (int nt = 0; nt < 2; ++nt) {
+            const int src = 32 * nt + j;
+            const bool mine = half == 0 && ((live_mask >> src) & 1ull);
+            const int r = __shfl((int)row, src);                // row < n_b <= n < 2^31
+            decoder_train_half<KT>(sm, xs, P, Q, nt, j, half, ks1, mine, target + (int64_t)r * 3, y != nullptr ? y + (int64_t)r * 3 : nullptr, dscale,
+                                   true, A);
+        }
+        wave_sync();
+        // d loss / d row of this lane's point is its row of the tile from here to the last wave_sync: the scatter and the walk only read it
+        auto grow = [&](int l, float (&gv)[F]) {
+#pragma unroll
+            for (int f = 0; f < F; ++f) gv[f] = xrow[l * F + f];
+        };
+        if (grad != nullptr) scatter_point<D, F, true>(p.d, t, grad, p.fade, lam, live_lane, lane, grow);
+        float gp[D], gl;
+        point_walk<D, F, NIC_HASH_SRC_F32, true, true, NOISE>(src_b, t, row, lam, grow, gp, gl);
+        if (live_lane) {
+            store_point_grad<D>(dpoints, row, kept_axes<D>(p.d, points, row), gp);
+            dlod[row] = lambda_passes(lod_b, p.lod_uniform, row) ? gl : 0.0f;
+        }
+        wave_sync();
+    }
+    write_record<KT>(sm, A, LF, p.partials + (int64_t)blockIdx.x * RecLayout(LF).rec, tid);      // record (b, lb); all zero without an item (n_b = 0 too)
+}
+template <bool NOISE>
+static int launch_points_joint_lod(const PJLParams& p, int n_fields, void* stream) {
+    const dim3 grid((unsigned)n_fields * (unsigned)p.groups);
+    return dispatch_dim_features(p.d, [&](auto dim, auto features) {
+        constexpr int D = decltype(dim)::value, F = decltype(features)::value;
+        if (p.d.levels * F > 32) hipLaunchKernelGGL((hash_batch_points_joint_lod_kernel<D, F, 2, NOISE>), grid, dim3(256), 0, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL((hash_batch_points_joint_lod_kernel<D, F, 1, NOISE>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    });
+}
+
 }  // namespace hbatch
 }  // namespace nic
 
@@ -833,6 +921,47 @@ int nic_hash_batch_forward_backward_points_grad(const nic_hash_desc* desc, int n
     const bool noisy = p.noise.mode == NIC_NOISE_KERNEL;
     rc = lodp ? (noisy ? launch_points_joint<true, true>(p, n_fields, stream) : launch_points_joint<false, true>(p, n_fields, stream))
               : (noisy ? launch_points_joint<true, false>(p, n_fields, stream) : launch_points_joint<false, false>(p, n_fields, stream));
+    if (rc != NIC_OK) return rc;
+    kernel_end_mark((hipStream_t)stream);
+    hipLaunchKernelGGL(hash_batch_reduce_kernel, dim3((unsigned)((rl.rec + 31) / 32), (unsigned)n_fields), dim3(256), 0, (hipStream_t)stream, p.partials, g,
+                       lf, *mlp_grads, loss, counts ? 0.f : field_loss_mul(loss_scale, n_points), (flags & NIC_HASH_FUSED_ADD_GRADS) ? 1 : 0,
+                       (flags & NIC_HASH_FUSED_ADD_LOSS) ? 1 : 0, counts, n_points, loss_scale);
+    return (int)hipGetLastError();
+}
+
+// ---- the same step that also writes d loss / d lambda: the entry above with a level of detail always on and dlod after dpoints -
+// its checks in its order, lodp and dlod with the other pointers, its records, reduction and flags
+int nic_hash_batch_forward_backward_points_grad_lod(const nic_hash_desc* desc, int n_fields, int groups_per_field, const nic_hash_lod* lodp,
+                                                    const nic_hash_quant* quant, const float* tables, const float* points, const float* lod,
+                                                    int64_t n_points, const int32_t* counts, const int32_t* order, const nic_mlp* mlp,
+                                                    const float* target, float loss_scale, float* table_grads, const nic_mlp_grads* mlp_grads,
+                                                    float* loss, float* y, float* dpoints, float* dlod, int flags, void* workspace,
+                                                    size_t workspace_bytes, void* stream) {
+    const KernelEndDrop end;
+    if (!desc || !mlp) return NIC_E_NULL;
+    int rc = check_batch_desc(desc, mlp->n_linear);
+    if (rc) return rc;
+    if (n_fields < 1 || n_fields > kMaxFields) return NIC_E_ARG;
+    const int g = point_groups(n_points, n_fields, groups_per_field);
+    if (g < 0) return NIC_E_ARG;
+    if (!lodp || !tables || !points || !mlp3_ok(mlp) || !target || !mlp_grads || !loss || !dpoints || !dlod || !workspace) return NIC_E_NULL;
+    if ((rc = check_lod(desc, lodp)) != NIC_OK) return rc;
+    if (flags & ~(NIC_HASH_FUSED_ADD_GRADS | NIC_HASH_FUSED_ADD_LOSS)) return NIC_E_ARG;
+    PJLParams p{};
+    p.d = *desc; p.tables = tables; p.points = points; p.counts = counts; p.order = order; p.target = target; p.y = y; p.grads = table_grads;
+    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
+    p.n = n_points; p.groups = g; p.loss_scale = loss_scale; p.dpoints = dpoints; p.dlod = dlod;
+    set_lod(p, lodp, lod);
+    p.noise.mode = NIC_NOISE_NONE;
+    if ((rc = set_noise(quant, true, p.noise, p.sample_base)) != NIC_OK) return rc;
+    const int lf = desc->levels * desc->features;
+    const RecLayout rl(lf);
+    if (workspace_bytes < (size_t)n_fields * g * rl.rec * sizeof(float)) return NIC_E_WORKSPACE;
+    if ((rc = check_point_desc(desc)) != NIC_OK) return rc;
+    if (n_points < 0 || n_points >= (int64_t(1) << 31)) return NIC_E_ARG;
+    if (n_points == 0) return NIC_OK;                                   // nothing to launch: loss, dpoints, dlod and every gradient stay as they are
+    p.partials = (float*)workspace;
+    rc = p.noise.mode == NIC_NOISE_KERNEL ? launch_points_joint_lod<true>(p, n_fields, stream) : launch_points_joint_lod<false>(p, n_fields, stream);
     if (rc != NIC_OK) return rc;
     kernel_end_mark((hipStream_t)stream);
     hipLaunchKernelGGL(hash_batch_reduce_kernel, dim3((unsigned)((rl.rec + 31) / 32), (unsigned)n_fields), dim3(256), 0, (hipStream_t)stream, p.partials, g,

@@ -983,9 +983,11 @@ def hash_batch_point_order(geo: HashGeometry, points: torch.Tensor, counts=None)
 
 
 def _batch_forward_backward_points(geo, tables, points, params, target, mlp_grads, table_grads, order, counts, loss, loss_scale, want_y, quant, add_grads,
-                                   add_loss, groups_per_field, lod, dpoints=False):
+                                   add_loss, groups_per_field, lod, dpoints=False, dlod=False):
     """``hash_batch_forward_backward_points`` (``lod`` None) and ``hash_batch_forward_backward_points_lod`` (``lod`` = (lod, lod_uniform, fade));
-    with ``dpoints`` - None for a fresh tensor, or the tensor to fill - ``hash_batch_forward_backward_points_grad``, which returns it too"""
+    with ``dpoints`` - None for a fresh tensor, or the tensor to fill - ``hash_batch_forward_backward_points_grad``, which returns it too; with
+    ``dlod`` on top (``lod`` and ``dpoints`` are then given) - None for a fresh tensor (zeros), or the fp32 [B, N] tensor to fill -
+    ``hash_batch_forward_backward_points_grad_lod``, which returns both"""
     t = tables.detach() if isinstance(tables, torch.Tensor) else tables
     _check_batch_tables(geo, t)
     n_fields = t.shape[0]
@@ -1013,6 +1015,8 @@ def _batch_forward_backward_points(geo, tables, points, params, target, mlp_grad
         raise ValueError(f"loss must be a contiguous fp32 device tensor [{n_fields}]")
     if dpoints is not False and dpoints is not None:
         _check_batch_dpoints_shape(geo, n_fields, n, dpoints)
+    if dlod is not False and dlod is not None:
+        _check_batch_dlod_shape(n_fields, n, dlod)
     _point_desc(geo)
     # ---- the device, after every refusal the host can make
     _require_stacked([t], "tables")
@@ -1051,6 +1055,17 @@ def _batch_forward_backward_points(geo, tables, points, params, target, mlp_grad
             dpoints = (torch.empty if counts is None and order is None else torch.zeros)(n_fields, n, geo.dim, dtype=torch.float32, device=t.device)
         else:
             _check_batch_dpoints_device(dpoints, pts.device)
+        if dlod is not False:
+            if dlod is None:
+                dlod = torch.zeros(n_fields, n, dtype=torch.float32, device=t.device)
+            else:
+                _check_batch_dlod_device(dlod, pts.device)
+            _lib.check(lib.nic_hash_batch_forward_backward_points_grad_lod(
+                ctypes.byref(d), n_fields, int(groups_per_field), ctypes.byref(lp), qp, _lib.ptr(t), _lib.ptr(pts), _lib.ptr(lod_t), n, _lib.ptr(counts),
+                _lib.ptr(order), ctypes.byref(m), _lib.ptr(target), float(loss_scale), _lib.ptr(table_grads), ctypes.byref(gs), _lib.ptr(loss), _lib.ptr(y),
+                _lib.ptr(dpoints), _lib.ptr(dlod), flags, _lib.ptr(ws), nbytes, _lib.stream_ptr(t.device)),
+                "nic_hash_batch_forward_backward_points_grad_lod")
+            return loss, y, dpoints, dlod
         _lib.check(lib.nic_hash_batch_forward_backward_points_grad(
             ctypes.byref(d), n_fields, int(groups_per_field), None if lp is None else ctypes.byref(lp), qp, _lib.ptr(t), _lib.ptr(pts), _lib.ptr(lod_t), n,
             _lib.ptr(counts), _lib.ptr(order), ctypes.byref(m), _lib.ptr(target), float(loss_scale), _lib.ptr(table_grads), ctypes.byref(gs), _lib.ptr(loss),
@@ -1545,14 +1560,36 @@ def _check_batch_dpoints_device(dpoints: torch.Tensor, device) -> None:
         raise ValueError(f"dpoints lives on {dpoints.device}, the points on {device}")
 
 
+def _check_batch_dlod_shape(n_fields: int, n: int, dlod) -> None:
+    """``_check_dlod`` for a batch, the part the host decides: an fp32 [B, N] tensor, contiguous - the kernel writes it in place"""
+    if not isinstance(dlod, torch.Tensor):
+        raise TypeError("dlod must be a torch.Tensor")
+    if tuple(dlod.shape) != (n_fields, n):
+        raise ValueError(f"dlod must be [{n_fields}, {n}], one value per point of every field, got {tuple(dlod.shape)}")
+    if dlod.dtype != torch.float32:
+        raise ValueError(f"dlod has dtype {dlod.dtype}; the kernel writes fp32")
+    if not dlod.is_contiguous():
+        raise ValueError("dlod must be contiguous: the kernel writes it in place")
+
+
+def _check_batch_dlod_device(dlod: torch.Tensor, device) -> None:
+    """``_check_dlod``'s device part: on the points' HIP device"""
+    if not dlod.is_cuda:
+        raise RuntimeError(f"dlod lives on {dlod.device}: this package only runs on a HIP device (no CPU path)")
+    if dlod.device != device:
+        raise ValueError(f"dlod lives on {dlod.device}, the points on {device}")
+
+
 def _plain_lod(lod, lod_uniform, fade) -> bool:
     """no level of detail at all - ``lod`` None, ``lod_uniform`` 0 and ``fade`` None: the gradient entries' plain launch (``_grad_lod``)"""
     return lod is None and fade is None and float(lod_uniform) == 0.0
 
 
 def _batch_points_grad(geo, data, points, params, dy, target, loss_scale, counts, order, want_y, kind, num_bits, lod, lod_uniform, fade, groups_per_field,
-                       dpoints=None):
-    """``hash_batch_points_grad``; ``dpoints``: None for a fresh tensor, or the fp32 [B, N, dim] device tensor to fill"""
+                       dpoints=None, dlod=False):
+    """``hash_batch_points_grad``; ``dpoints``: None for a fresh tensor, or the fp32 [B, N, dim] device tensor to fill.  With ``dlod`` - None
+    for a fresh tensor (zeros), or the fp32 [B, N] device tensor to fill - ``hash_batch_points_grad_lod``: always a level-of-detail launch,
+    and (y, dpoints, dlod) back"""
     n_fields = _check_batch_source(geo, data, kind, num_bits)
     data = data.detach()
     params = _check_batch_decoder(geo, [q.detach() if isinstance(q, torch.Tensor) else q for q in params], n_fields)
@@ -1568,7 +1605,7 @@ def _batch_points_grad(geo, data, points, params, dy, target, loss_scale, counts
             raise ValueError(f"{name} must be [{n_fields}, {n}, 3], got {tuple(v.shape) if isinstance(v, torch.Tensor) else type(v).__name__}")
     counts = _check_batch_counts(counts, n_fields, n)
     order = _check_batch_order(order, n_fields, n)
-    plain = _plain_lod(lod, lod_uniform, fade)
+    plain = dlod is False and _plain_lod(lod, lod_uniform, fade)
     lod_t = None if plain else _check_batch_lod(lod, n_fields, n)
     lp = None if plain else _lod_struct(geo, fade, lod_uniform)
     y_out = want_y if isinstance(want_y, torch.Tensor) else None
@@ -1576,6 +1613,8 @@ def _batch_points_grad(geo, data, points, params, dy, target, loss_scale, counts
         raise ValueError(f"want_y as a tensor must be contiguous fp32 [{n_fields}, {n}, 3]")
     if dpoints is not None:
         _check_batch_dpoints_shape(geo, n_fields, n, dpoints)
+    if dlod is not False and dlod is not None:
+        _check_batch_dlod_shape(n_fields, n, dlod)
     d = _point_desc(geo)
     # ---- the device, after every refusal the host can make
     _require_on_device(data, "data")
@@ -1601,9 +1640,19 @@ def _batch_points_grad(geo, data, points, params, dy, target, loss_scale, counts
         dpoints = fresh(n_fields, n, geo.dim, dtype=torch.float32, device=data.device)
     else:
         _check_batch_dpoints_device(dpoints, pts.device)
+    if dlod is None:                                  # a fresh one is zeros: rows a field does not own are not written
+        dlod = torch.zeros(n_fields, n, dtype=torch.float32, device=data.device)
+    elif dlod is not False:
+        _check_batch_dlod_device(dlod, pts.device)
     if n == 0:
-        return y, dpoints
+        return (y, dpoints) if dlod is False else (y, dpoints, dlod)
     src, m = _lib.NicHashSource(POINT_SOURCES[kind], 0 if kind == "f32" else int(num_bits), data.data_ptr()), fused._mlp_struct(params)
+    if dlod is not False:
+        _lib.check(_lib.load().nic_hash_batch_points_grad_lod(
+            ctypes.byref(d), n_fields, int(groups_per_field), ctypes.byref(lp), ctypes.byref(src), _lib.ptr(pts), _lib.ptr(lod_t), n, _lib.ptr(counts),
+            _lib.ptr(order), ctypes.byref(m), _lib.ptr(dy), _lib.ptr(target), float(loss_scale), _lib.ptr(y), _lib.ptr(dpoints), _lib.ptr(dlod),
+            _lib.stream_ptr(data.device)), "nic_hash_batch_points_grad_lod")
+        return y, dpoints, dlod
     _lib.check(_lib.load().nic_hash_batch_points_grad(
         ctypes.byref(d), n_fields, int(groups_per_field), None if lp is None else ctypes.byref(lp), ctypes.byref(src), _lib.ptr(pts), _lib.ptr(lod_t), n,
         _lib.ptr(counts), _lib.ptr(order), ctypes.byref(m), _lib.ptr(dy), _lib.ptr(target), float(loss_scale), _lib.ptr(y), _lib.ptr(dpoints),
@@ -1645,6 +1694,46 @@ def hash_batch_forward_backward_points_grad(geo: HashGeometry, tables: torch.Ten
     return _batch_forward_backward_points(geo, tables, points, params, target, mlp_grads, table_grads, order, counts, loss, loss_scale, want_y, quant,
                                           add_grads, add_loss, groups_per_field, None if _plain_lod(lod, lod_uniform, fade) else (lod, lod_uniform, fade),
                                           dpoints=dpoints)
+
+
+# ---- B fields per launch with the gradient with respect to the level of detail (include/nicv2_hip_ext.h) ---------------------------
+@fused._on_tensor_device
+def hash_batch_points_grad_lod(geo: HashGeometry, data: torch.Tensor, points: torch.Tensor, params: Sequence[torch.Tensor],
+                               lod: Optional[torch.Tensor] = None, lod_uniform: float = 0.0, fade=None, dy: Optional[torch.Tensor] = None,
+                               target: Optional[torch.Tensor] = None, loss_scale: float = 1.0, counts=None, order: Optional[torch.Tensor] = None,
+                               want_y=True, kind: str = "f32", num_bits: Optional[int] = None, groups_per_field: int = 0,
+                               dpoints: Optional[torch.Tensor] = None,
+                               dlod: Optional[torch.Tensor] = None) -> Tuple[Optional[torch.Tensor], torch.Tensor, torch.Tensor]:
+    """(y [B, N, 3] or None, dpoints [B, N, dim], dlod [B, N]): ``hash_fused_points_grad_lod`` of B stacked fields, each at ITS OWN points and
+    its own level of detail, in ONE launch (nic_hash_batch_points_grad_lod) - ``hash_batch_points_grad`` with the same level of
+    detail, y and dpoints bit for bit, and ``dlod[b, n]`` = - sum over the levels on the ramp 0 < (fade[l] - lambda) + 1 <= 1 of the row gradient
+    times the unweighed blend of field b's table: the right-hand derivative with respect to lambda_{b, n}, exactly 0 where lambda_raw < 0,
+    >= 32 or NaN.  ``lod``: None, fp32 [N] shared by all fields or [B, N]; always a level-of-detail launch (``lod`` None, ``lod_uniform`` 0
+    and ``fade`` None is lambda = 0 with the default fades).  With ``target`` field b's gradient is scaled by ITS count.  ``dpoints`` /
+    ``dlod``: None for fresh tensors (zero at the rows a field does not own), or contiguous fp32 [B, N, dim] / [B, N] device tensors that are
+    overwritten at the rows each field owns.  The gradient for a shared ``lod`` is ``dlod.sum(0)``, for ``lod_uniform`` ``dlod.sum()``.
+    Everything else is ``hash_batch_points_grad``'s."""
+    return _batch_points_grad(geo, data, points, params, dy, target, loss_scale, counts, order, want_y, kind, num_bits, lod, lod_uniform, fade,
+                              groups_per_field, dpoints=dpoints, dlod=dlod)
+
+
+@fused._on_tensor_device
+def hash_batch_forward_backward_points_grad_lod(geo: HashGeometry, tables: torch.Tensor, points: torch.Tensor, params: Sequence[torch.Tensor],
+                                                target: torch.Tensor, mlp_grads: Sequence[torch.Tensor], lod: Optional[torch.Tensor] = None,
+                                                lod_uniform: float = 0.0, fade=None, table_grads: Optional[torch.Tensor] = None,
+                                                order: Optional[torch.Tensor] = None, counts=None, loss: Optional[torch.Tensor] = None,
+                                                loss_scale: float = 1.0, want_y=False, quant=None, add_grads: bool = False, add_loss: bool = False,
+                                                groups_per_field: int = 0, dpoints: Optional[torch.Tensor] = None,
+                                                dlod: Optional[torch.Tensor] = None):
+    """``hash_batch_forward_backward_points_grad`` that also writes d loss_b / d lambda of the loss it returns for field b
+    (nic_hash_batch_forward_backward_points_grad_lod) - ``hash_fused_forward_backward_points_grad_lod`` per field in the same
+    two launches: losses, y, gradients and ``dpoints`` are the sibling's with the same level of detail bit for bit; ``dlod[b, n]`` counts the
+    noise this step's forward added under ``quant`` inside the weighed column (the slope on the ramp is -(r + nz), keyed by the field-local
+    row whatever the ``order``), exactly 0 where lambda_raw < 0, >= 32 or NaN.  Always a level-of-detail launch.  ``dpoints`` / ``dlod``: None
+    for fresh tensors, or contiguous fp32 [B, N, dim] / [B, N] device tensors that are overwritten (never added to, whatever ``add_grads``
+    says) at the rows each field owns.  Returns (loss [B], y or None, dpoints, dlod)."""
+    return _batch_forward_backward_points(geo, tables, points, params, target, mlp_grads, table_grads, order, counts, loss, loss_scale, want_y, quant,
+                                          add_grads, add_loss, groups_per_field, (lod, lod_uniform, fade), dpoints=dpoints, dlod=dlod)
 
 
 @fused._on_tensor_device
@@ -1985,6 +2074,59 @@ class _BatchTrainPointsFunction(torch.autograd.Function):
         dp, = ctx.saved_tensors
         out = g.reshape(-1, 1, 1) * dp
         return (out.sum(0) if ctx.shared else out), None, None, None
+
+
+def _batch_lod_grad(dlod: torch.Tensor, shape, dtype) -> torch.Tensor:
+    """the [B, N] gradient for the level of detail as the gradient of the ``lod`` the caller gave: itself for [B, N], summed over the fields
+    for a shared [N], summed over everything for a 0-dim tensor"""
+    g = dlod if len(shape) == 2 else dlod.sum(0) if len(shape) == 1 else dlod.sum()
+    return g.to(dtype).reshape(shape)
+
+
+class _BatchQueryPointsLodFunction(torch.autograd.Function):
+    """``HashGridFieldBatch.query_lod`` as a differentiable op of the points and of the level of detail (``query_differentiable_lod``):
+    backward = ``point_gradient_lod`` with the output gradient - ``dpoints`` summed over the fields for shared [N, dim] points, ``dlod`` for
+    a [B, N] ``lod``, its sum over the fields for a shared [N] one, over everything for a 0-dim one; nothing for the fields' parameters"""
+
+    @staticmethod
+    def forward(ctx, points, lod, batch):
+        ctx.batch = batch
+        ctx.lod = None if isinstance(lod, torch.Tensor) else lod
+        ctx.save_for_backward(points, *([lod] if isinstance(lod, torch.Tensor) else []))
+        return batch.query_lod(points, lod)
+
+    @staticmethod
+    def backward(ctx, dy):
+        points, *rest = ctx.saved_tensors
+        lod = rest[0] if rest else ctx.lod
+        _, dp, dl = ctx.batch.point_gradient_lod(points, lod, dy=dy.contiguous())
+        glod = _batch_lod_grad(dl, lod.shape, lod.dtype) if rest and ctx.needs_input_grad[1] else None
+        return ((dp.sum(0) if points.dim() == 2 else dp) if ctx.needs_input_grad[0] else None), glod, None
+
+
+class _BatchTrainPointsLodFunction(torch.autograd.Function):
+    """``HashGridFieldBatch.train_points_grad_lod`` as a differentiable op of the points and of the level of detail
+    (``train_points_differentiable_lod``): the forward trains the fields and keeps d loss_b / d points and d loss_b / d lambda, the backward
+    hands upstream[b] * dpoints[b] and upstream[b] * dlod[b] to whichever requires a gradient, summed as the shapes say"""
+
+    @staticmethod
+    def forward(ctx, points, lod, batch, target, kwargs):
+        loss, dp, dl = batch.train_points_grad_lod(points.detach(), target, lod.detach() if isinstance(lod, torch.Tensor) else lod, **kwargs)
+        ctx.lod_shape = (lod.shape, lod.dtype) if isinstance(lod, torch.Tensor) else None
+        ctx.shared = points.dim() == 2
+        ctx.save_for_backward(dp, dl)
+        return loss.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        dp, dl = ctx.saved_tensors
+        gp = glod = None
+        if ctx.needs_input_grad[0]:
+            gp = g.reshape(-1, 1, 1) * dp
+            gp = gp.sum(0) if ctx.shared else gp
+        if ctx.lod_shape is not None and ctx.needs_input_grad[1]:
+            glod = _batch_lod_grad(g.reshape(-1, 1) * dl, *ctx.lod_shape)
+        return gp, glod, None, None, None
 
 
 def _table_of_u8(geo: HashGeometry, stored: torch.Tensor, num_bits: int) -> torch.Tensor:
@@ -2903,8 +3045,14 @@ class HashGridFieldBatch:
     (nic_hash_batch_forward_backward_points_grad) - ``HashGridField.train_points(fused=True, dpoints=)`` per field in the batch's three
     launches: the frames of a jittered clip or the tiles of a scan are registered while they are fitted.
 
-    Not built (DESIGN 7): at points, passes in chunks with ragged counts, and the 16-bit modes with ``lod`` or with position gradients;
-    ``fit_points`` with positions; a gradient with respect to the level of detail; 16-bit training; a bit depth per level (a ``/2`` file is
+    Gradients to the level of detail: ``point_gradient_lod`` / ``jacobian_lod`` / ``query_differentiable_lod`` add d y / d
+    lambda of every point of every field to that ONE launch (nic_hash_batch_points_grad_lod), and ``train_points_grad_lod`` /
+    ``train_points_differentiable_lod`` are ``train_points_grad(lod=)`` that also return d loss_b / d lambda, the step's noise counted
+    (nic_hash_batch_forward_backward_points_grad_lod) - ``HashGridField.train_points_grad_lod(fused=True)`` per field in the batch's three
+    launches: the zoom of a frame or the mip bias of a tile is descended on while the fields are fitted.
+
+    Not built: at points, passes in chunks with ragged counts, and the 16-bit modes with ``lod`` or with position or
+    level-of-detail gradients; ``fit_points`` with positions or a level of detail to fit; 16-bit training; a bit depth per level (a ``/2`` file is
     read and refused), fields of differing geometry in one batch, a container format that holds several fields in one file."""
 
     def __init__(self, n_fields: int, field_size: Union[int, Sequence[int]], levels: int = 16, features: int = 2, log2_table: int = 19,
@@ -3163,9 +3311,10 @@ class HashGridFieldBatch:
         return self._train_points(points, target, counts, accumulate, scale, step, noise, order, lod)
 
     @torch.no_grad()
-    def _train_points(self, points, target, counts, accumulate, scale, step, noise, order, lod, dpoints=False):
+    def _train_points(self, points, target, counts, accumulate, scale, step, noise, order, lod, dpoints=False, dlod=False):
         """``train_points`` (``lod`` None: exactly the calls it always made) and ``train_points_lod``; with ``dpoints`` - None or the tensor
-        to fill - ``train_points_grad``: the same bookkeeping around the joint entry, and (loss, dpoints) back"""
+        to fill - ``train_points_grad``: the same bookkeeping around the joint entry, and (loss, dpoints) back; with ``dlod`` on top (``lod``
+        is then given) ``train_points_grad_lod``, and (loss, dpoints, dlod) back"""
         self._refuse_decode_only("train_points")
         frozen = self.frozen
         lod_t, lod_u = (None, 0.0) if lod is None else self._lod_args(lod)
@@ -3185,7 +3334,11 @@ class HashGridFieldBatch:
                 grad.zero_()
             self._pass_samples = 0
         quant = (self.num_bits, self.noise_seed, self.steps, self._pass_samples) if noise else None
-        if dpoints is not False:
+        if dlod is not False:
+            loss, _, dpoints, dlod = hash_batch_forward_backward_points_grad_lod(
+                self.geo, self.tables, pts, self.params, target, self._gm, lod_t, lod_u, self.lod_fade, table_grads=grad, order=order, counts=counts,
+                loss_scale=float(scale), quant=quant, add_grads=accumulate, groups_per_field=self._point_groups(n), dpoints=dpoints, dlod=dlod)
+        elif dpoints is not False:
             loss, _, dpoints = hash_batch_forward_backward_points_grad(
                 self.geo, self.tables, pts, self.params, target, self._gm, lod_t, lod_u, None if lod is None else self.lod_fade, table_grads=grad,
                 order=order, counts=counts, loss_scale=float(scale), quant=quant, add_grads=accumulate, groups_per_field=self._point_groups(n),
@@ -3203,6 +3356,8 @@ class HashGridFieldBatch:
             self._grad_clean = False
         if step:
             self.apply_step()
+        if dlod is not False:
+            return loss, dpoints, dlod
         return loss if dpoints is False else (loss, dpoints)
 
     @torch.no_grad()
@@ -3235,6 +3390,47 @@ class HashGridFieldBatch:
             lod = kwargs.pop("lod", None)
             return self.train_points(points, target, **kwargs) if lod is None else self.train_points_lod(points, target, lod, **kwargs)
         return _BatchTrainPointsFunction.apply(points, self, target, kwargs)
+
+    @torch.no_grad()
+    def train_points_grad_lod(self, points: torch.Tensor, target: torch.Tensor, lod, dpoints: Optional[torch.Tensor] = None,
+                              dlod: Optional[torch.Tensor] = None, counts=None, accumulate: bool = False, scale: float = 1.0, step: bool = True,
+                              noise: Optional[bool] = None, order=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(loss [B], dpoints [B, N, dim], dlod [B, N]): ``train_points_grad(points, target, lod=lod)`` that also returns d loss_b / d
+        lambda_{b, n} of every field's loss - ``HashGridField.train_points_grad_lod(fused=True)`` for every field at once, in
+        the same three launches (nic_hash_batch_forward_backward_points_grad_lod): for a level of detail that comes from parameters fitted
+        with the fields - the zoom of a frame ``lambda_b = log2 s_b + bias_b``, a mip bias per tile or view.  ``lod`` is required: a finite
+        float, a 0-dim tensor, a tensor [N] shared by all fields or [B, N]; the gradient for a shared one is ``dlod.sum(0)``, for a launch-wide
+        one ``dlod.sum()``.  ``dlod`` counts the noise this step's forward added inside the weighed column (the slope on the ramp is
+        -(r + nz)), is the right-hand derivative, exactly 0 where lambda < 0, >= 32 or NaN, and is taken like ``dpoints`` at the parameters
+        the forward used.  ``dpoints`` / ``dlod``: None for fresh tensors (zero at the rows a field does not own), or contiguous fp32
+        [B, N, dim] / [B, N] device tensors that are overwritten at the rows each field owns, whatever ``accumulate`` says.  Every other
+        argument, the bookkeeping and the noise keys are ``train_points``'."""
+        self._refuse_decode_only("train_points_grad_lod")
+        if lod is None:
+            raise ValueError("lod is a float or a [N] / [B, N] tensor: the level of detail the gradient is taken at")
+        if dpoints is not None or dlod is not None:
+            n, _, _ = self._check_train_points(points, target, counts, order)
+            if dpoints is not None:
+                _check_batch_dpoints_shape(self.geo, self.n_fields, n, dpoints)
+            if dlod is not None:
+                _check_batch_dlod_shape(self.n_fields, n, dlod)
+        return self._train_points(points, target, counts, accumulate, scale, step, noise, order, lod, dpoints=dpoints, dlod=dlod)
+
+    def train_points_differentiable_lod(self, points: torch.Tensor, lod, target: torch.Tensor, **kwargs) -> torch.Tensor:
+        """``train_points_grad_lod(points, target, lod, **kwargs)`` as a differentiable op of ``points`` and / or ``lod`` -
+        ``lod`` a [B, N] tensor, a [N] tensor shared by the fields or a 0-dim tensor: the call steps the fields as it always does and returns
+        the [B] losses, whose backward hands upstream[b] * d loss_b / d points[b] and upstream[b] * d loss_b / d lambda[b] to whichever
+        requires a gradient - summed over the fields for shared [N, dim] points or a shared [N] ``lod``, over everything for a 0-dim one.
+        With nothing that requires one, or under ``torch.no_grad()``, it is plain ``train_points_lod``.  No gradient reaches the fields'
+        parameters through autograd: their step is the call's own."""
+        if "dpoints" in kwargs or "dlod" in kwargs:
+            raise TypeError("train_points_differentiable_lod keeps dpoints and dlod for the backward: call train_points_grad_lod for the tensors")
+        wants = any(isinstance(t, torch.Tensor) and t.requires_grad for t in (points, lod))
+        if not (wants and torch.is_grad_enabled()):
+            return self.train_points_lod(points, target, lod, **kwargs)
+        self._refuse_decode_only("train_points_differentiable_lod")
+        _check_batch_points(self.geo, points, self.n_fields)
+        return _BatchTrainPointsLodFunction.apply(points, lod, self, target, kwargs)
 
     def fit_points(self, points: torch.Tensor, target: torch.Tensor, epochs: int, counts=None, order="cell", freeze_at: float = 0.95) -> List[List[float]]:
         """``HashGridField.fit_points(fused=True)`` for every field on its own fixed sample set: ``epochs`` passes over ``points`` / ``target`` /
@@ -3480,6 +3676,66 @@ class HashGridFieldBatch:
             return self.query(points) if lod is None else self.query_lod(points, lod)
         _check_batch_points(self.geo, points, self.n_fields)
         return _BatchQueryPointsFunction.apply(points, self, lod)
+
+    @torch.no_grad()
+    def point_gradient_lod(self, points: torch.Tensor, lod, dy: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None,
+                           scale: float = 1.0, counts=None, order=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(y [B, N, 3], dpoints [B, N, dim], dlod [B, N]): ``point_gradient(points, dy, target, scale, counts, order, lod=lod)`` - y and
+        dpoints bit for bit - and the gradient of the same loss with respect to the LEVEL OF DETAIL of each point of each field (DESIGN
+        4.7.25) - ``HashGridField.point_gradient_lod`` of every field in ONE launch (nic_hash_batch_points_grad_lod), from whatever tables
+        the batch holds: a batch from ``load_compressed`` works.  ``lod`` is required: a finite float, a 0-dim tensor, a tensor [N] shared
+        by all fields or [B, N].  ``dlod[b, n]`` is the right-hand derivative (a level exactly at its fade start counts, one exactly at its
+        end does not), exactly 0 where lambda < 0, >= 32 or NaN and at the rows a field does not own; a point outside the field has the
+        clamped point's.  The gradient for a shared ``lod`` is ``dlod.sum(0)``, for a launch-wide one ``dlod.sum()``.  The fields'
+        parameters are constants here: no ``.grad`` is touched and no optimiser state moves."""
+        n = _check_batch_points(self.geo, points, self.n_fields)
+        if (dy is None) == (target is None):
+            raise ValueError("exactly one of dy and target: the gradient of the output, or the colours of a mean squared error")
+        for name, v in (("dy", dy), ("target", target)):
+            if v is not None and (not isinstance(v, torch.Tensor) or tuple(v.shape) != (self.n_fields, n, 3)):
+                raise ValueError(f"{name} must be [{self.n_fields}, {n}, 3], got {tuple(v.shape) if isinstance(v, torch.Tensor) else type(v).__name__}")
+        counts = _check_batch_counts(counts, self.n_fields, n)
+        if isinstance(order, str):
+            if order != "cell":
+                raise ValueError(f"order {order!r}: None, 'cell' or an int32 [{self.n_fields}, {n}] tensor")
+        else:
+            order = _check_batch_order(order, self.n_fields, n)
+        if lod is None:
+            raise ValueError("lod is a float or a [N] / [B, N] tensor: the level of detail the gradient is taken at")
+        lod_t, lod_u = self._lod_args(lod)
+        lod_t = _check_batch_lod(lod_t, self.n_fields, n)
+        _point_desc(self.geo)
+        _require_on_device(points, "points")
+        pts = _stack_points(points, self.n_fields)
+        if isinstance(order, str):
+            order = hash_batch_point_order(self.geo, pts, counts)
+        data, kind, bits = self._table_source()
+        return hash_batch_points_grad_lod(self.geo, data, pts, [p.detach() for p in self.params], lod_t, lod_u, self.lod_fade, dy=dy, target=target,
+                                          loss_scale=float(scale), counts=counts, order=order, want_y=True, kind=kind, num_bits=bits,
+                                          groups_per_field=self._point_groups(max(n, 1)))
+
+    def jacobian_lod(self, points: torch.Tensor, lod) -> torch.Tensor:
+        """[B, N, 3]: d y[b, n, o] / d lambda_{b, n}, as three ``point_gradient_lod`` calls with a one-hot ``dy``"""
+        n = _check_batch_points(self.geo, points, self.n_fields)
+        cols = []
+        for o in range(3):
+            dy = torch.zeros(self.n_fields, n, 3, dtype=torch.float32, device=points.device)
+            dy[..., o] = 1.0
+            cols.append(self.point_gradient_lod(points, lod, dy=dy)[2])
+        return torch.stack(cols, dim=2)
+
+    def query_differentiable_lod(self, points: torch.Tensor, lod) -> torch.Tensor:
+        """``query_lod(points, lod)`` as a differentiable op of ``points`` and / or ``lod`` - a [B, N] tensor, a [N] tensor shared by the
+        fields, or a 0-dim tensor (one level of detail for the launch): the backward hands the output gradient to ``point_gradient_lod`` -
+        ``dlod`` for a [B, N] ``lod``, its sum over the fields for a shared [N] one, over everything for a 0-dim one; ``dpoints`` summed over
+        the fields for shared [N, dim] points - so a zoom, a blur or a mip bias per field can be descended on with any torch loss and
+        optimiser.  With nothing that requires a gradient, or under ``torch.no_grad()``, it is the plain ``query_lod`` call.  No gradient
+        reaches the fields' parameters through it."""
+        wants = any(isinstance(t, torch.Tensor) and t.requires_grad for t in (points, lod))
+        if not (wants and torch.is_grad_enabled()):
+            return self.query_lod(points, lod)
+        _check_batch_points(self.geo, points, self.n_fields)
+        return _BatchQueryPointsLodFunction.apply(points, lod, self)
 
     @torch.no_grad()
     def resample(self, size: Union[int, Sequence[int]], tile: int = 1024, precision: Optional[str] = None) -> torch.Tensor:
