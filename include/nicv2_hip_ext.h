@@ -261,6 +261,41 @@ int nic_hash_batch_forward_backward_points_grad_lod(const nic_hash_desc *desc, i
                                                     float *table_grads, const nic_mlp_grads *mlp_grads, float *loss, float *y, float *dpoints,
                                                     float *dlod, int flags, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- The training step at points with a WEIGHT PER POINT in its loss (hashgrid.py, hash_fused_forward_backward_points_weighted,
+ *      HashGridField.train_points_weighted / train_points_weighted_differentiable / fit_points_weighted / fit_mips_weighted;
+ *      csrc/hashgrid_weighted.hip, hash_points_weighted_train_kernel).
+ *      weight = NULL, or [n_points] fp32 on the device, read at the row the point is read at (order[pos] clamped with an order, as target and
+ *      lod are).  w_n = weight[n] > 0 ? weight[n] : 0: a NaN and a negative value count 0; +inf is the caller's error - no fault, the results
+ *      are undefined.  weight == NULL is w = 1.
+ *          loss = loss_scale sum_n w_n sum_o (y[n, o] - target[n, o])^2 / (3 n_points)
+ *      - n_points, not sum w: ones give the plain loss, importance weights 1 / (N p_n) go in as they are, and a caller who wants the weighted
+ *      mean divides the weights by their mean.  Every gradient is the derivative of that loss: d loss / d row of point n carries w_n, and so
+ *      do the table gradient, the decoder gradients, dpoints[n] and dlod[n] (the conventions of the two sections above unchanged: the
+ *      right-hand derivative, -(r + nz) on the ramp under noise, exactly 0.0f where lambda is clamped or NaN, a clamped axis zeroes its
+ *      dpoints).  A point of weight 0 still gets its y, adds exactly +0 to the loss, gets dpoints / dlod == 0.0f and adds zeros to every
+ *      gradient: a table entry only such points touch keeps its value.
+ *      The call is nic_hash_fused_forward_backward_points_grad_lod with `weight` after lod, and lodp, dpoints and dlod NULLABLE: without lodp
+ *      there is no level of detail (the plain rows, bit for bit), without dpoints no second walk of the levels, without dlod no lambda
+ *      accumulator.  Everything else is the siblings': the same two launches, records, fixed-order reduction, flags, tail,
+ *      nic_mark_kernel_end, workspace (nic_hash_fused_points_workspace_bytes), noise keys (sample_base + row); table_grad == NULL is a frozen
+ *      table, everything else is still produced.  With weight == NULL, or all ones, loss, y, the six decoder gradients, dpoints and dlod are
+ *      bit for bit those of the sibling that takes the remaining arguments (nic_hash_fused_forward_backward_points, _points_lod,
+ *      _points_grad, _points_grad_lod), and the table gradient agrees with it as two calls of that sibling agree (the order of the atomics).
+ *      Host checks, all before any GPU work, in this order: null desc / mlp (NIC_E_NULL); the fused set (nic_hash_fused_supported's code);
+ *      the descriptor of a point source (NIC_E_SHAPE / NIC_E_ARG); null table, points, decoder layer, target, mlp_grads, loss or workspace
+ *      (NIC_E_NULL; lodp, quant, lod, weight, order, table_grad, y, dpoints, dlod and tail may be null); flags (NIC_E_ARG); lod without
+ *      lodp, dlod without lodp, dlod without dpoints (NIC_E_ARG); the nic_hash_lod where given (NIC_E_ARG); quant (num_bits 1 .. 8,
+ *      sample_base >= 0, noise_mode: NIC_E_ARG; NIC_NOISE_TENSOR is NIC_E_UNSUPPORTED); n_points < 0, or >= 2^31 with an order (NIC_E_ARG);
+ *      the workspace (NIC_E_WORKSPACE); the tail (its codes); n_points == 0 is NIC_OK with nothing written.
+ *      There are no weights on the batched entries (their ragged counts are the 0 / 1 case), none on the crop route, none per channel, no
+ *      bit depth per level and no 16-bit precision mode. */
+int nic_hash_fused_forward_backward_points_weighted(const nic_hash_desc *desc, const nic_hash_lod *lodp, const nic_hash_quant *quant,
+                                                    const float *table, const float *points, const float *lod, const float *weight,
+                                                    int64_t n_points, const int32_t *order, const nic_mlp *mlp, const float *target,
+                                                    float loss_scale, float *table_grad, const nic_mlp_grads *mlp_grads, float *loss, float *y,
+                                                    float *dpoints, float *dlod, int flags, void *workspace, size_t workspace_bytes,
+                                                    const nic_step_tail *tail, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

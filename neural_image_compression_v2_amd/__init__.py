@@ -21,7 +21,7 @@ _HASHGRID_NAMES = ("HashGeometry", "HashGridField", "HashGridFieldBatch", "hash_
                    "hash_batch_forward_points_lod", "hash_batch_forward_backward_points_lod", "hash_batch_points_grad",
                    "hash_batch_forward_backward_points_grad", "hash_encode_points_grad_lod", "hash_fused_points_grad_lod",
                    "hash_encode_points_grad_lod_noisy", "hash_fused_forward_backward_points_grad_lod", "hash_batch_points_grad_lod",
-                   "hash_batch_forward_backward_points_grad_lod")
+                   "hash_batch_forward_backward_points_grad_lod", "hash_fused_forward_backward_points_weighted", "hash_mip_weights")
 
 
 def __getattr__(name):

@@ -18,7 +18,7 @@ OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libnicv2_hip.so")
 SOURCES = ["simple_kernels.hip", "decoder_general.hip", "fused_capi.hip", "fused_m1.hip", "fused_m2.hip", "fused_m3.hip", "fused_m4.hip", "fused_t16.hip", "fused_mlpn.hip", "fused_q1.hip", "fused_q2.hip", "fused_q3.hip", "fused_q4.hip",
            "hash_grid.hip", "hash_fused.hip", "hash_points.hip", "hash_points_train.hip", "hash_mixed.hip", "hashgrid_fused16.hip", "hashgrid_pointgrad.hip", "hashgrid_points_joint.hip", "hashgrid_batch.hip",
-           "hashgrid_batch_grad.hip", "hashgrid_lodgrad.hip", "hashgrid_lodtrain.hip"]
+           "hashgrid_batch_grad.hip", "hashgrid_lodgrad.hip", "hashgrid_lodtrain.hip", "hashgrid_weighted.hip"]
 # the lists of csrc/fused_capi.hip (NIC_CP_LIST, NIC_ML_LIST): one object per entry, compiled from one source with the entry as NIC_ENTRY
 LISTED = {"NIC_CP_LIST": ("fused_qc.hip", "fused_qc_{}_{}_{}.o"),        # (layout, C, P): non-default channel counts on the plain-bf16 kernels
           "NIC_ML_LIST": ("fused_ml.hip", "fused_ml_{}_{}_{}.o")}        # (levels, C, n_linear): multi-level layouts (fused_q16.hpp::QML)

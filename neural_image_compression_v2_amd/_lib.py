@@ -268,6 +268,9 @@ EXT_SIGNATURES = {
                                             _P, _M, _P, _P, _F, _P, _P, _P, _P]),
     "nic_hash_batch_forward_backward_points_grad_lod": (_I, [ctypes.POINTER(NicHashDesc), _I, _I, ctypes.POINTER(NicHashLod), ctypes.POINTER(NicHashQuant),
                                                              _P, _P, _P, _L, _P, _P, _M, _P, _F, _P, _G, _P, _P, _P, _P, _I, _P, _SZ, _P]),
+    "nic_hash_fused_forward_backward_points_weighted": (_I, [ctypes.POINTER(NicHashDesc), ctypes.POINTER(NicHashLod), ctypes.POINTER(NicHashQuant), _P,
+                                                             _P, _P, _P, _L, _P, _M, _P, _F, _P, _G, _P, _P, _P, _P, _I, _P, _SZ,
+                                                             ctypes.POINTER(NicStepTail), _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -606,9 +606,12 @@ __device__ __forceinline__ void decoder_forward_half(const DecoderSmem& sm, cons
 // forward, loss and backward of the 32 samples `32 nt + j` of a wave's row tile `xs` (hash_fused_kernel's training mode, the same products in
 // the same order).  `mine`: this lane (half 0) owns a live sample; it reads its target at `trow`, writes y to `yrow` when that is not null.
 // The weight gradients go into `A`; with `want_dx`, d loss / d row replaces the rows of this half in `xs`.
-template <int KT>
+// WEIGHT (hashgrid_weighted.hip): the owner's sample counts `w` times in the loss - `dscale` arrives as dscale w, the loss partial
+// is (w e) e, the expression of the plain partial with one exact factor at w = 1.  Without WEIGHT `w` is not read.
+template <int KT, bool WEIGHT = false>
 __device__ __forceinline__ void decoder_train_half(TrainSmem& sm, float* xs, float* P, float* Q, int nt, int j, int half, int ks1, bool mine,
-                                                   const float* trow, float* yrow, float dscale, bool want_dx, TrainAcc<KT>& A) {
+                                                   const float* trow, float* yrow, float dscale, bool want_dx, TrainAcc<KT>& A,
+                                                   [[maybe_unused]] float w = 1.0f) {
     const int src = 32 * nt + j;
     const float* xb = xs + src * XS;
     // ---- layer 1
@@ -670,7 +673,12 @@ __device__ __forceinline__ void decoder_train_half(TrainSmem& sm, float* xs, flo
 #pragma unroll
         for (int o = 0; o < 3; ++o) {
             const float e = yv[o] - trow[o];
-            A.sse += e * e;
+            if constexpr (WEIGHT) {
+                const float we = __fmul_rn(w, e);
+                A.sse += we * e;
+            } else {
+                A.sse += e * e;
+            }
             dz3[o] = dscale * e * yv[o] * (1.0f - yv[o]);
         }
     }

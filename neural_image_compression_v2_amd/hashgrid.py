@@ -1178,10 +1178,11 @@ def hash_fused_forward_points(geo: HashGeometry, data: torch.Tensor, points: tor
 
 
 def _fused_forward_backward_points(geo, table, points, params, target, mlp_grads, table_grad, order, loss, loss_scale, want_y, quant, add_grads,
-                                   add_loss, tail, lod, dpoints=None, dlod=None):
+                                   add_loss, tail, lod, dpoints=None, dlod=None, weighted=None):
     """``hash_fused_forward_backward_points`` (``lod`` None) and ``hash_fused_forward_backward_points_lod`` (``lod`` = (lod, lod_uniform, fade));
     with ``dpoints`` (checked by the caller) ``hash_fused_forward_backward_points_grad``, which takes either; with ``dlod`` on top (checked by
-    the caller; ``lod`` is then required) ``hash_fused_forward_backward_points_grad_lod``"""
+    the caller; ``lod`` is then required) ``hash_fused_forward_backward_points_grad_lod``.  ``weighted``: None, or (weight,) - the checked
+    per-point weights or None - for ``hash_fused_forward_backward_points_weighted``, the one entry that takes every combination of the rest"""
     t = _check_table(geo, table.detach())
     params = _check_fused_decoder(geo, [q.detach() for q in params])
     pts = _check_points(geo, points)
@@ -1213,6 +1214,9 @@ def _fused_forward_backward_points(geo, table, points, params, target, mlp_grads
         name, out = "nic_hash_fused_forward_backward_points_grad", (_lib.ptr(y), _lib.ptr(dpoints))
     if dlod is not None:                                   # the same entry with a level of detail always on, and dlod after dpoints
         name, out = "nic_hash_fused_forward_backward_points_grad_lod", (_lib.ptr(y), _lib.ptr(dpoints), _lib.ptr(dlod))
+    if weighted is not None:                               # nullable nic_hash_lod, weight after lod, both gradients nullable
+        head, where = (ctypes.byref(d), None if lp is None else ctypes.byref(lp)), (_lib.ptr(pts), _lib.ptr(lod_tensor), _lib.ptr(weighted[0]), n)
+        name, out = "nic_hash_fused_forward_backward_points_weighted", (_lib.ptr(y), _lib.ptr(dpoints), _lib.ptr(dlod))
     _lib.check(getattr(lib, name)(*head, qp, _lib.ptr(t), *where, _lib.ptr(order), ctypes.byref(m), _lib.ptr(target), float(loss_scale),
                                   _lib.ptr(table_grad), ctypes.byref(gs), _lib.ptr(loss), *out, flags, _lib.ptr(ws), ws.numel(),
                                   None if tail is None else ctypes.byref(tail.struct), _lib.stream_ptr(t.device)), name)
@@ -1537,6 +1541,80 @@ def hash_encode_points_grad_lod_noisy(geo: HashGeometry, table: torch.Tensor, po
     (num_bits, seed, offset, sample_base); with None both outputs are ``hash_encode_points_grad_lod``'s bit for bit."""
     t = _check_table(geo, table.detach())
     return _encode_points_grad(geo, t, points, dx, lod, lod_uniform, fade, "nic_hash_encode_points_grad_lod_noisy", quant=quant)
+
+
+# ---- a weight per point in the loss of the training step (DESIGN 4.7.26; include/nicv2_hip_ext.h) ----------------------------------------------
+def _check_weight(points, weight) -> torch.Tensor:
+    """the loss weights of a step: an fp32 [N] tensor on the points' HIP device, contiguous (``points`` is a [N, dim] tensor) - what the host
+    decides first, then where it lives; the values are the kernel's business (NaN and negative values count 0)"""
+    if not isinstance(weight, torch.Tensor):
+        raise ValueError(f"weight must be an fp32 [N] tensor, one value per point, got {type(weight).__name__}")
+    if tuple(weight.shape) != (points.shape[0],):
+        raise ValueError(f"weight must be [{points.shape[0]}], one value per point, got {tuple(weight.shape)}")
+    if weight.dtype != torch.float32:
+        raise ValueError(f"weight has dtype {weight.dtype}; the kernel reads fp32")
+    if not weight.is_contiguous():
+        raise ValueError("weight must be contiguous: the kernel reads it in place")
+    if not weight.is_cuda:
+        raise RuntimeError(f"weight lives on {weight.device}: this package only runs on a HIP device (no CPU path)")
+    if weight.device != points.device:
+        raise RuntimeError(f"weight lives on {weight.device}, the points on {points.device}")
+    return weight.detach()
+
+
+@fused._on_tensor_device
+def hash_fused_forward_backward_points_weighted(geo: HashGeometry, table: torch.Tensor, points: torch.Tensor, params: Sequence[torch.Tensor],
+                                                target: torch.Tensor, weight: Optional[torch.Tensor], mlp_grads: Sequence[torch.Tensor],
+                                                lod: Optional[torch.Tensor] = None, lod_uniform: float = 0.0, fade=None,
+                                                table_grad: Optional[torch.Tensor] = None, order: Optional[torch.Tensor] = None,
+                                                loss: Optional[torch.Tensor] = None, loss_scale: float = 1.0, want_y: bool = False, quant=None,
+                                                add_grads: bool = False, add_loss: bool = False, tail=None,
+                                                dpoints: Optional[torch.Tensor] = None, dlod: Optional[torch.Tensor] = None):
+    """The fused step at points with a weight per point in its loss (nic_hash_fused_forward_backward_points_weighted):
+    loss = ``loss_scale`` sum_n w_n sum_o (y[n, o] - target[n, o])^2 / (3 N), w_n = ``weight[n]`` where that is > 0 and 0 elsewhere (NaN and
+    negative values count 0; +inf is the caller's error), N the number of points - not the sum of the weights.  Every gradient is that loss's:
+    a point of weight 0 still gets its y and adds nothing anywhere.  ``weight``: fp32 [N] on the device, read at the caller's row like
+    ``target``; None is w = 1.  ``lod`` / ``lod_uniform`` / ``fade``: all at their defaults is the step without a level of detail, anything
+    else ``hash_fused_forward_backward_points_lod``'s.  ``dpoints`` / ``dlod``: None (not computed), or fp32 [N, dim] / [N] device tensors
+    that are overwritten; ``dlod`` needs ``dpoints`` and makes the call a level-of-detail launch (lambda = 0 with the default fades when
+    nothing else says so).  With ``weight`` None or ones the results are the sibling's with the same remaining arguments bit for bit (the
+    table gradient up to the order of its atomics).  Returns (loss [1], y or None, dpoints, dlod)."""
+    if dlod is not None and dpoints is None:
+        raise ValueError("dlod needs dpoints: the gradient for the level of detail comes from the walk that makes the one for the points")
+    if dpoints is not None:
+        dpoints = _check_dpoints(geo, points, dpoints)
+    if dlod is not None:
+        dlod = _check_dlod(dpoints, dlod)
+    if weight is not None:
+        weight = _check_weight(_check_points(geo, points), weight)
+    plain = dlod is None and lod is None and fade is None and float(lod_uniform) == 0.0
+    loss, y = _fused_forward_backward_points(geo, table, points, params, target, mlp_grads, table_grad, order, loss, loss_scale, want_y, quant,
+                                             add_grads, add_loss, tail, None if plain else (lod, lod_uniform, fade), dpoints=dpoints, dlod=dlod,
+                                             weighted=(weight,))
+    return loss, y, dpoints, dlod
+
+
+def hash_mip_weights(n_points_per_mip: Sequence[int], mode="balanced") -> Tuple[float, ...]:
+    """one loss weight per mip of a chain whose mip m holds ``n_points_per_mip[m]`` of the samples (``fit_mips_weighted``).  ``"balanced"``:
+    w_m = N / ((M + 1) N_m) with N = sum N_m - the weighted loss over the joint set is then the mean of the M + 1 per-mip mean squared
+    errors.  A sequence of M + 1 finite values >= 0 is returned as given (as floats).  Host arithmetic only."""
+    counts = [int(c) for c in n_points_per_mip]
+    if len(counts) < 1 or any(c < 1 for c in counts):
+        raise ValueError(f"n_points_per_mip {counts}: at least one mip, each with at least one point")
+    if isinstance(mode, str):
+        if mode != "balanced":
+            raise ValueError(f"mip weights {mode!r}: 'balanced' or a sequence of {len(counts)} values >= 0")
+        total = sum(counts)
+        return tuple(total / (len(counts) * c) for c in counts)
+    try:
+        out = tuple(float(v) for v in mode)
+    except (TypeError, ValueError):
+        raise ValueError(f"mip weights {mode!r}: 'balanced' or a sequence of {len(counts)} values >= 0") from None
+    if len(out) != len(counts):
+        raise ValueError(f"{len(out)} mip weights for {len(counts)} mips")
+    if any(not math.isfinite(v) or v < 0 for v in out):
+        raise ValueError(f"mip weights {out}: each finite and >= 0")
+    return out
 
 
 # ---- B fields per launch with the gradient with respect to the point coordinates (DESIGN 4.7.21; include/nicv2_hip_ext.h) ------------------------
@@ -2040,6 +2118,33 @@ class _TrainPointsLodFunction(torch.autograd.Function):
         return (g * dp if ctx.needs_input_grad[0] else None), glod, None, None, None
 
 
+class _TrainPointsWeightedFunction(torch.autograd.Function):
+    """``HashGridField.train_points_weighted`` as a differentiable op of the points and of the level of detail
+    (``train_points_weighted_differentiable``): ``_TrainPointsLodFunction`` with the loss weights, and with a level of detail that may be
+    absent (then only the points get a gradient)"""
+
+    @staticmethod
+    def forward(ctx, points, lod, field, target, weight, kwargs):
+        dp = torch.empty(points.shape, dtype=torch.float32, device=points.device)
+        dl = None if lod is None else torch.empty(points.shape[0], dtype=torch.float32, device=points.device)
+        with torch.enable_grad():                      # the layer-wise step runs its own backward
+            loss = field.train_points_weighted(points.detach(), target, weight, lod=lod.detach() if isinstance(lod, torch.Tensor) else lod,
+                                               dpoints=dp, dlod=dl, **kwargs)
+        ctx.lod_shape = (lod.shape, lod.dtype) if isinstance(lod, torch.Tensor) else None
+        ctx.save_for_backward(dp, *(() if dl is None else (dl,)))
+        return loss.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        dp, *rest = ctx.saved_tensors
+        g = g.reshape(())
+        glod = None
+        if ctx.lod_shape is not None and ctx.needs_input_grad[1]:
+            shape, dtype = ctx.lod_shape
+            glod = (g * (rest[0] if len(shape) > 0 else rest[0].sum())).to(dtype).reshape(shape)
+        return (g * dp if ctx.needs_input_grad[0] else None), glod, None, None, None, None
+
+
 class _BatchQueryPointsFunction(torch.autograd.Function):
     """``HashGridFieldBatch.query`` / ``query_lod`` as a differentiable op of the points (``query_differentiable``): backward =
     ``point_gradient`` with the output gradient, summed over the fields for shared [N, dim] points; nothing for the fields' parameters"""
@@ -2353,8 +2458,56 @@ class HashGridField:
         loss = self._train_points(points, target, accumulate, scale, step, noise, order, fused, lod, dpoints, dlod)
         return loss, dpoints, dlod
 
-    def _train_points(self, points, target, accumulate, scale, step, noise, order, fused, lod, dpoints, dlod) -> torch.Tensor:
-        """``train_points`` (``dlod`` None) and ``train_points_grad_lod`` (``dlod`` a checked [N] tensor; ``lod`` and ``dpoints`` are then given)"""
+    def train_points_weighted(self, points: torch.Tensor, target: torch.Tensor, weight: torch.Tensor, lod=None,
+                              dpoints: Optional[torch.Tensor] = None, dlod: Optional[torch.Tensor] = None, accumulate: bool = False,
+                              scale: float = 1.0, step: bool = True, noise: Optional[bool] = None, order=None, fused: bool = False) -> torch.Tensor:
+        """``train_points`` with a weight per point in the loss: loss = ``scale`` sum_n w_n sum_o (y[n, o] - target[n, o])^2 /
+        (3 N), w_n = ``weight[n]`` where that is > 0 and 0 elsewhere (NaN and negative values count 0; +inf is the caller's error), N the
+        number of points - NOT the sum of the weights: ones are ``train_points``, importance weights 1 / (N p_n) go in as they are, a mask or a
+        confidence is the weight itself, and a caller who wants the weighted mean divides the weights by their mean.  ``weight``: fp32 [N]
+        on the points' device, contiguous, at the caller's rows like ``target`` whatever the ``order``.  Every gradient is that loss's: a
+        point of weight 0 still costs its gathers, and adds nothing to the table, the decoder or the loss.  ``lod``: ``train_points``'.
+        ``dpoints`` / ``dlod``: None, or fp32 [N, dim] / [N] contiguous device tensors that are OVERWRITTEN with d loss / d points and d
+        loss / d lambda of the loss returned (``train_points_grad_lod``'s conventions, each row carrying its w_n; exactly 0 at weight 0);
+        ``dlod`` needs ``lod`` and ``dpoints``.  ``fused=True``: nic_hash_fused_forward_backward_points_weighted; layer-wise: the existing
+        kernels on the row gradient of the weighted loss.  ``accumulate`` / ``scale`` / ``step`` / ``noise`` / ``order``, the noise keys
+        of a chunked pass and the optimiser bookkeeping are ``train_points``'.  Returns the loss."""
+        if self.table is None:
+            raise RuntimeError("a field from load_compressed decodes only")
+        if self.level_bits is not None:
+            raise NotImplementedError("loss weights with a bit depth per level are not built (DESIGN 7): use a uniform num_bits")
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != self.geo.dim:
+            raise ValueError(f"points must be [N, {self.geo.dim}] for a {self.geo.dim}D field, got "
+                             f"{tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__}")
+        if dlod is not None and lod is None:
+            raise ValueError("dlod needs lod: the level of detail the gradient is taken at")
+        if dlod is not None and dpoints is None:
+            raise ValueError("dlod needs dpoints: both gradients come from one walk of the levels")
+        if dlod is not None:
+            _check_dlod(points, dlod, device=False)
+        weight = _check_weight(points, weight)
+        if dpoints is not None:
+            dpoints = _check_dpoints(self.geo, points, dpoints)
+        if dlod is not None:
+            dlod = _check_dlod(points, dlod)
+        return self._train_points(points, target, accumulate, scale, step, noise, order, fused, lod, dpoints, dlod, weight)
+
+    def train_points_weighted_differentiable(self, points: torch.Tensor, target: torch.Tensor, weight: torch.Tensor, lod=None, **kwargs) -> torch.Tensor:
+        """``train_points_weighted(points, target, weight, lod=lod, **kwargs)`` as a differentiable op of ``points`` and / or ``lod`` (a [N]
+        tensor, or a 0-dim tensor whose gradient is the sum of the per-point ones), built like ``train_points_differentiable_lod``: the call
+        steps the field as it always does, and the loss it returns has a backward that hands upstream * d loss / d points and upstream * d
+        loss / d lambda to whichever requires a gradient.  ``weight`` gets no gradient, and none reaches the field's parameters through
+        autograd.  With nothing that requires one, or under ``torch.no_grad()``, it is plain ``train_points_weighted``."""
+        if "dpoints" in kwargs or "dlod" in kwargs:
+            raise TypeError("train_points_weighted_differentiable keeps dpoints and dlod for the backward: call train_points_weighted for the tensors")
+        wants = any(isinstance(t, torch.Tensor) and t.requires_grad for t in (points, lod))
+        if not (wants and torch.is_grad_enabled()):
+            return self.train_points_weighted(points, target, weight, lod=lod, **kwargs)
+        return _TrainPointsWeightedFunction.apply(points, lod, self, target, weight, kwargs)
+
+    def _train_points(self, points, target, accumulate, scale, step, noise, order, fused, lod, dpoints, dlod, weight=None) -> torch.Tensor:
+        """``train_points`` (``dlod`` None) and ``train_points_grad_lod`` (``dlod`` a checked [N] tensor; ``lod`` and ``dpoints`` are then given);
+        ``weight``: None, or the checked [N] loss weights of ``train_points_weighted``"""
         if self.table is None:
             raise RuntimeError("a field from load_compressed decodes only")
         if dpoints is not None:
@@ -2387,7 +2540,8 @@ class HashGridField:
         if isinstance(order, str):
             order = hash_point_order(self.geo, pts)
         if fused:
-            return self._fused_train_points(pts, target, accumulate, scale, step, noise, order, None if lod is None else (lod_t, lod_u), dpoints, dlod)
+            return self._fused_train_points(pts, target, accumulate, scale, step, noise, order, None if lod is None else (lod_t, lod_u), dpoints, dlod,
+                                            weight)
         if not accumulate:
             for p in params:
                 p.grad = None
@@ -2405,7 +2559,11 @@ class HashGridField:
         if not frozen or dpoints is not None:
             x.requires_grad_(True)
         y = DecoderFunction.apply(x, *params)          # `fused` is this call's argument here
-        loss = ((y - target) ** 2).mean() * scale
+        if weight is None:
+            loss = ((y - target) ** 2).mean() * scale
+        else:                                          # sum_n w_n sum_o e^2 / (3 N): the mean of the weighed squares, the plain expression at w = 1
+            w = torch.where(weight > 0, weight, torch.zeros_like(weight))
+            loss = (w[:, None] * (y - target) ** 2).mean() * scale
         loss.backward()
         if dlod is not None:                           # both gradients from one walk, with the noise this forward added
             dp, dl = hash_encode_points_grad_lod_noisy(self.geo, self.table, pts, x.grad, lod_t, lod_u, self.lod_fade, quant=quant)
@@ -2431,11 +2589,12 @@ class HashGridField:
         return loss.detach()
 
     @torch.no_grad()
-    def _fused_train_points(self, pts, target, accumulate, scale, step, noise, order, lod=None, dpoints=None, dlod=None) -> torch.Tensor:
+    def _fused_train_points(self, pts, target, accumulate, scale, step, noise, order, lod=None, dpoints=None, dlod=None, weight=None) -> torch.Tensor:
         """``train_points`` as two launches, with ``_fused_train_step``'s bookkeeping: persistent decoder-gradient buffers, the chunks of a
         pass adding into them and into the table gradient, the optimiser riding on the last chunk's reduction.  The arguments are checked.
         ``lod``: None or (per-point tensor or None, launch-wide value).  ``dpoints``: None, or the tensor the joint entry overwrites;
-        ``dlod`` (with ``lod`` and ``dpoints``): the tensor the entry with the gradient for the level of detail overwrites."""
+        ``dlod`` (with ``lod`` and ``dpoints``): the tensor the entry with the gradient for the level of detail overwrites.  ``weight``: None,
+        or the [N] loss weights - then every combination of the rest is the weighted entry's."""
         params = self.decoder.linear_params()
         frozen = self.frozen
         grad = None if frozen else self.table.grad
@@ -2452,7 +2611,12 @@ class HashGridField:
         tail = None
         if step:
             tail = self.optimizer.step_tail([] if frozen else [(self.table, grad)], list(zip(params, gm)))
-        if dlod is not None:
+        if weight is not None:
+            loss, _, _, _ = hash_fused_forward_backward_points_weighted(self.geo, self.table, pts, params, target, weight, gm,
+                                                                        *((None, 0.0, None) if lod is None else (lod[0], lod[1], self.lod_fade)),
+                                                                        table_grad=grad, order=order, loss_scale=float(scale), quant=quant,
+                                                                        add_grads=accumulate, tail=tail, dpoints=dpoints, dlod=dlod)
+        elif dlod is not None:
             loss, _, _, _ = hash_fused_forward_backward_points_grad_lod(self.geo, self.table, pts, params, target, gm, lod[0], lod[1], self.lod_fade,
                                                                         table_grad=grad, order=order, loss_scale=float(scale), quant=quant,
                                                                         add_grads=accumulate, tail=tail, dpoints=dpoints, dlod=dlod)
@@ -2516,6 +2680,24 @@ class HashGridField:
         every pass walks it in ``batch``-sized accumulate chunks that are contiguous ranges of the order - each chunk spatially compact (None:
         the whole set in one call).  ``fused``: None = the field's route.  With ``num_bits``: noise while the epoch is below ``freeze_at`` *
         epochs, then ``freeze()``.  ``lod``: ``train_points``' (a [N] tensor is laid out and cut with the points).  Returns the per-pass losses."""
+        return self._fit_points(points, target, epochs, batch, order, fused, freeze_at, lod, None)
+
+    def fit_points_weighted(self, points: torch.Tensor, target: torch.Tensor, weight: torch.Tensor, epochs: int, batch: Optional[int] = None,
+                            order="cell", fused: Optional[bool] = None, freeze_at: float = 0.95, lod=None) -> List[float]:
+        """``fit_points`` with ``train_points_weighted``'s loss weights: ``weight`` fp32 [N] on the device, laid out and cut
+        with the points.  A chunk's ``scale`` stays its share of the points by COUNT, so the pass loss is sum_n w_n sum_o e^2 / (3 N) over
+        the whole set and ones reproduce ``fit_points``.  Returns the per-pass losses."""
+        if self.table is None:
+            raise RuntimeError("a field from load_compressed decodes only")
+        if self.level_bits is not None:
+            raise NotImplementedError("loss weights with a bit depth per level are not built (DESIGN 7): use a uniform num_bits")
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != self.geo.dim:
+            raise ValueError(f"points must be [N, {self.geo.dim}] for a {self.geo.dim}D field, got "
+                             f"{tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__}")
+        return self._fit_points(points, target, epochs, batch, order, fused, freeze_at, lod, _check_weight(points, weight))
+
+    def _fit_points(self, points, target, epochs, batch, order, fused, freeze_at, lod, weight) -> List[float]:
+        """``fit_points`` (``weight`` None) and ``fit_points_weighted`` (``weight`` the checked [N] tensor)"""
         lod_t, lod_u = (None, None) if lod is None else self._lod_args(lod)
         pts = _check_points(self.geo, points)
         n = pts.shape[0]
@@ -2536,6 +2718,7 @@ class HashGridField:
             idx = idx.to(torch.int64).clamp_(0, n - 1)
             pts, target = pts[idx].contiguous(), target[idx].contiguous()       # laid out in the order once: a chunk is a slice
             lod_t = None if lod_t is None else lod_t[idx].contiguous()
+            weight = None if weight is None else weight[idx].contiguous()
         cuts = list(range(0, n, batch))
         freeze_epoch = math.ceil(freeze_at * epochs) if self._codec else None
         hist = []
@@ -2545,8 +2728,11 @@ class HashGridField:
             tot = 0.0
             for k, c0 in enumerate(cuts):
                 c1 = min(c0 + batch, n)
-                tot = tot + self.train_points(pts[c0:c1], target[c0:c1], accumulate=k > 0, scale=(c1 - c0) / n, step=k == len(cuts) - 1, fused=fused,
-                                              lod=lod_u if lod_t is None else lod_t[c0:c1])
+                how = dict(accumulate=k > 0, scale=(c1 - c0) / n, step=k == len(cuts) - 1, fused=fused, lod=lod_u if lod_t is None else lod_t[c0:c1])
+                if weight is None:
+                    tot = tot + self.train_points(pts[c0:c1], target[c0:c1], **how)
+                else:
+                    tot = tot + self.train_points_weighted(pts[c0:c1], target[c0:c1], weight[c0:c1], **how)
             hist.append(tot)
         return [float(h) for h in hist]
 
@@ -2994,6 +3180,20 @@ class HashGridField:
         """fits the whole mip chain of ``target`` [S_x, S_y(, S_z), 3] with one table and one decoder: mip m = the mean over blocks of 2^m samples
         per axis (m = 0 .. ``mips``), its samples at ``decode_mip(m)``'s points with level of detail m; the (point, lod, colour) sets of all mips go
         to ``fit_points`` as one set, so cell order, chunks and the fused route are that method's.  Returns the per-pass losses."""
+        return self._fit_mips(target, epochs, mips, batch, order, fused, freeze_at, False, None)
+
+    def fit_mips_weighted(self, target: torch.Tensor, epochs: int, mips: int = 2, mip_weights=None, batch: Optional[int] = None, order="cell",
+                          fused: Optional[bool] = None, freeze_at: float = 0.95) -> List[float]:
+        """``fit_mips`` with every point of mip m weighed by ``mip_weights[m]`` in the loss (``fit_points_weighted``).  Mip m
+        holds 2^(-dim m) of the points, so in ``fit_mips`` the coarse mips weigh almost nothing.  ``mip_weights``: None (ones: ``fit_mips``'
+        loss), ``"balanced"`` (``hash_mip_weights``: the loss is the mean of the per-mip mean squared errors) or a sequence of ``mips`` + 1
+        values >= 0.  Returns the per-pass losses."""
+        if self.table is None:
+            raise RuntimeError("a field from load_compressed decodes only")
+        return self._fit_mips(target, epochs, mips, batch, order, fused, freeze_at, True, mip_weights)
+
+    def _fit_mips(self, target, epochs, mips, batch, order, fused, freeze_at, weighted, mip_weights) -> List[float]:
+        """``fit_mips`` and (``weighted``) ``fit_mips_weighted``"""
         size, dim = self.field_size, self.geo.dim
         if tuple(target.shape) != (*size, 3):
             raise ValueError(f"target must be {(*size, 3)}, got {tuple(target.shape)}")
@@ -3002,6 +3202,9 @@ class HashGridField:
         sizes = [self._mip_size(m) for m in range(int(mips) + 1)]
         if self.level_bits is not None:
             raise NotImplementedError("a level of detail with a bit depth per level is not built (DESIGN 7): use a uniform num_bits")
+        if weighted:
+            counts = [math.prod(sz) for sz in sizes]
+            mip_weights = hash_mip_weights(counts, [1.0] * len(sizes) if mip_weights is None else mip_weights)
         target = _lib.require_cuda_f32(target, "target")
         pts, lods, cols = [], [], []
         for m, sz in enumerate(sizes):
@@ -3009,6 +3212,10 @@ class HashGridField:
             cols.append(blocks.mean(dim=tuple(range(1, 2 * dim, 2))).reshape(-1, 3))
             pts.append(self._resample_points(sz, [0] * dim, sz))
             lods.append(torch.full((pts[-1].shape[0],), float(m), dtype=torch.float32, device=self.device))
+        if weighted:
+            w = torch.cat([torch.full((p.shape[0],), float(v), dtype=torch.float32, device=self.device) for p, v in zip(pts, mip_weights)])
+            return self.fit_points_weighted(torch.cat(pts).contiguous(), torch.cat(cols).contiguous(), w.contiguous(), epochs, batch=batch,
+                                            order=order, fused=fused, freeze_at=freeze_at, lod=torch.cat(lods).contiguous())
         return self.fit_points(torch.cat(pts).contiguous(), torch.cat(cols).contiguous(), epochs, batch=batch, order=order, fused=fused,
                                freeze_at=freeze_at, lod=torch.cat(lods).contiguous())
 
