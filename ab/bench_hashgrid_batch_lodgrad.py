@@ -1,6 +1,6 @@
 """B hash-grid fields per launch with gradients to the level of detail against a loop of B single fused fields (hashgrid.py,
 HashGridFieldBatch.train_points_grad_lod / point_gradient_lod; csrc/hashgrid_batch.hip, hash_batch_points_joint_lod_kernel;
-csrc/hashgrid_batch_grad.hip, hash_batch_points_grad_lod_kernel); prints one JSON line:
+csrc/hashgrid_batch_grad.hip, hash_batch_points_grad_kernel<.., DLOD>); prints one JSON line:
 
     python ab/bench_hashgrid_batch_lodgrad.py [--out profiles/hashgrid_batch_lodgrad_bench.json] [--rows small|tiles|all]
 

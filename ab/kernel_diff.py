@@ -1,13 +1,15 @@
 """Kernel-by-kernel comparison of two `hipcc -S --cuda-device-only` outputs of one unit, and the resource table of a
 `-Rpass-analysis=kernel-resource-usage` log (profiles/hashgrid_batch_lod_disasm.txt, profiles/hashgrid_batch_lod_resources.txt).
 
-    python ab/kernel_diff.py diff parent.s new.s [--commute]
+    python ab/kernel_diff.py diff parent.s new.s [--commute] [--rename REGEX=REPLACEMENT ...]
     python ab/kernel_diff.py resources remarks.txt [name filter ...]
 
 A kernel's text runs from its label to the end of its "Kernel info" comment block; its own mangled name, the function index of local labels
 (.LBBn_ / BBn_) and of .Lfunc_endN, and runs of blanks are normalised.  Lines that name __hip_cuid are dropped.  --commute: a kernel that is
 the parent's once the two source operands of its commutative two-operand instructions are put in one order - the same opcodes in the same order
-on the same registers, the same resource block - is counted as "operands"  and the swapped lines are counted."""
+on the same registers, the same resource block - is counted as "operands"  and the swapped lines are counted.  --rename: kernels
+are paired by their demangled names; a parent's name goes through each re.sub(REGEX, REPLACEMENT) first, for a kernel that was renamed or
+that became an instantiation of another template."""
 import re
 import subprocess
 import sys
@@ -61,28 +63,34 @@ def commuted(ln):
     return f"{m.group(1)} {m.group(2)}, {x}, {y}"
 
 
-def diff(parent, new, commute=False):
+def diff(parent, new, commute=False, renames=()):
     a, b = kernels(parent), kernels(new)
     names = demangle(sorted(set(a) | set(b)))
+
+    def was(n):                                             # the parent's kernel under the name it has now
+        for pattern, repl in renames:
+            n = re.sub(pattern, repl, n)
+        return n
+    a = {was(short(names[m])): body for m, body in a.items()}
+    b = {short(names[m]): body for m, body in b.items()}
     same = moved = swapped = swapped_lines = 0
     rows = []
-    for m in sorted(names, key=lambda k: names[k]):
-        n = short(names[m])
-        if m not in a:
-            rows.append(f"new       {'':>7} {len(b[m]):>7}  {n}")
-        elif m not in b:
-            rows.append(f"GONE      {len(a[m]):>7} {'':>7}  {n}")
-        elif a[m] == b[m]:
+    for n in sorted(set(a) | set(b)):
+        if n not in a:
+            rows.append(f"new       {'':>7} {len(b[n]):>7}  {n}")
+        elif n not in b:
+            rows.append(f"GONE      {len(a[n]):>7} {'':>7}  {n}")
+        elif a[n] == b[n]:
             same += 1
-            rows.append(f"identical {len(a[m]):>7} {len(b[m]):>7}  {n}")
-        elif commute and len(a[m]) == len(b[m]) and [commuted(ln) for ln in a[m]] == [commuted(ln) for ln in b[m]]:
-            k = sum(x != y for x, y in zip(a[m], b[m]))
+            rows.append(f"identical {len(a[n]):>7} {len(b[n]):>7}  {n}")
+        elif commute and len(a[n]) == len(b[n]) and [commuted(ln) for ln in a[n]] == [commuted(ln) for ln in b[n]]:
+            k = sum(x != y for x, y in zip(a[n], b[n]))
             swapped += 1
             swapped_lines += k
-            rows.append(f"operands  {len(a[m]):>7} {len(b[m]):>7}  {n}  ({k} line{'s' if k > 1 else ''})")
+            rows.append(f"operands  {len(a[n]):>7} {len(b[n]):>7}  {n}  ({k} line{'s' if k > 1 else ''})")
         else:
             moved += 1
-            rows.append(f"DIFFERENT {len(a[m]):>7} {len(b[m]):>7}  {n}")
+            rows.append(f"DIFFERENT {len(a[n]):>7} {len(b[n]):>7}  {n}")
     print(f"{len(a)} kernels at the parent, {len(b)} now; of the parent's: identical {same}, "
           + (f"operand order only {swapped} ({swapped_lines} lines), " if commute else "")
           + f"different {moved}, gone {len(set(a) - set(b))}; new {len(set(b) - set(a))}")
@@ -116,5 +124,7 @@ def resources(path, filters):
 
 if __name__ == "__main__":
     if sys.argv[1] == "diff":
-        sys.exit(1 if diff(sys.argv[2], sys.argv[3], "--commute" in sys.argv[4:]) else 0)
+        rest = sys.argv[4:]
+        renames = [tuple(rest[i + 1].split("=", 1)) for i, x in enumerate(rest) if x == "--rename"]
+        sys.exit(1 if diff(sys.argv[2], sys.argv[3], "--commute" in rest, renames) else 0)
     resources(sys.argv[2], sys.argv[3:])

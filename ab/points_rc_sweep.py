@@ -1,8 +1,10 @@
-"""Return-code sweep of the point-gradient and point-step entry points against the parent commit's library: both libraries in one
-process through ctypes, the same seeded random arguments to each, every return value compared.  Nothing launches: n_points is <= 0, or >= 2^31
-together with an order, and every device pointer is a made-up address that no host path reads.  No GPU is needed.
+"""Return-code sweep of the point-gradient and point-step entry points against the parent commit's library, and with --batch of
+the batched entries at points: both libraries in one process through ctypes, the same seeded random arguments to each, every
+return value compared.  Nothing launches: n_points is <= 0, or >= 2^31 where the entry refuses that (the single field's step: together with an
+order), and every device pointer is a made-up address that no host path reads.  No GPU is needed.
 
     python ab/points_rc_sweep.py PARENT_LIB [NEW_LIB] [--seed 20261021] [--calls 20000] [--out profiles/hashgrid_walk_unify_retcodes.json]
+    python ab/points_rc_sweep.py PARENT_LIB [NEW_LIB] --batch [--out profiles/hashgrid_batch_unify_retcodes.json]
 
 Exit status 1 on a return value that differs, or on a code an entry can return that the sweep did not reach."""
 import argparse, ctypes, json, os, random, sys
@@ -18,6 +20,13 @@ GRAD = ["nic_hash_encode_points_grad", "nic_hash_fused_points_grad", "nic_hash_e
 NOISY, BYTES = "nic_hash_encode_points_grad_lod_noisy", "nic_hash_fused_points_workspace_bytes"
 # the codes each entry can return: the layer-wise entries take no workspace; the workspace size answers 0 or a size
 CAN = {**{e: {OK, NULL, UNSUP, SHAPE, WORKSPACE, ARG} for e in STEP}, **{e: {OK, NULL, UNSUP, SHAPE, ARG} for e in GRAD + [NOISY]}}
+# the batched entries at points (hashgrid_batch.hip, hashgrid_batch_grad.hip): the four steps, the two gradient-only entries, the two decodes
+B_STEP = ["nic_hash_batch_forward_backward_points", "nic_hash_batch_forward_backward_points_lod", "nic_hash_batch_forward_backward_points_grad",
+          "nic_hash_batch_forward_backward_points_grad_lod"]
+B_GRAD = ["nic_hash_batch_points_grad", "nic_hash_batch_points_grad_lod"]
+B_FWD = ["nic_hash_batch_forward_source", "nic_hash_batch_forward_points_lod"]
+B_BYTES = "nic_hash_batch_points_workspace_bytes"
+CAN.update({**{e: {OK, NULL, UNSUP, SHAPE, WORKSPACE, ARG} for e in B_STEP}, **{e: {OK, NULL, UNSUP, SHAPE, ARG} for e in B_GRAD + B_FWD}})
 
 
 def load(path):
@@ -141,12 +150,55 @@ class Gen:
     def n_grad(self):                                       # n_points of an entry without an order
         return 0 if self.good(0.7) else self.r.choice((-1, -(1 << 33)))
 
+    def fields(self):                                       # (n_fields, groups_per_field) of a batched entry
+        r = self.r
+        b = r.choice((1, 2, 3, 8, 64, 65535)) if self.good(0.95) else r.choice((0, -1, 65536))
+        # at no points G is taken on one wave item: 0 and 8 pass there, 16 and 64 only beside an n_points that is refused later
+        return b, (r.choice((0, 0, 8, 16, 64)) if self.good(0.9) else r.choice((-8, 4, 12, 1 << 20)))
+
+    def n_batch(self, high):                                # n_points of a batched entry; `high`: the entry refuses 2^31 and more before it launches
+        k = self.r.random()
+        if k < 0.6:
+            return 0
+        if k < 0.8 or not high:
+            return self.r.choice((-1, -(1 << 40)))
+        return self.r.choice((1 << 31, (1 << 31) + 7, 1 << 40))
+
 
 def make_call(name, rng):
     """(the generator that keeps the ctypes objects alive, the arguments) of one random call of entry `name`"""
     g = Gen(rng)
     if name == BYTES:
         return g, (g.desc(), g.mlp())
+    if name == B_BYTES:
+        d, (b, grp) = g.desc(), g.fields()
+        return g, (d, b, grp, rng.choice((0, 1, 64, 1000, 1 << 20, (1 << 31) - 1)) if g.good() else rng.choice((-1, 1 << 31, 1 << 40)), g.mlp())
+    if name in B_STEP:
+        d, (b, grp), q, m = g.desc(), g.fields(), g.quant(), g.mlp()
+        n, (gp, gs) = g.n_batch(True), g.grads()
+        flags = rng.choice((0, 1, 2, 3)) if g.good(0.93) else rng.choice((4, 8, -1))
+        wbytes = rng.choice((1 << 40, 1 << 34)) if g.good(0.85) else rng.choice((0, 64, 4096))
+        table, points, lod, counts, order, target = g.ptr(0.97), g.ptr(0.97), g.ptr(0.5), g.ptr(0.5), g.ptr(0.5), g.ptr(0.97)
+        tg, loss, y, dp, dl, wsp = g.ptr(0.6), g.ptr(0.97), g.ptr(0.5), g.ptr(0.96), g.ptr(0.96), g.ptr(0.97)
+        if name == B_STEP[0]:
+            return g, (d, b, grp, q, table, points, n, counts, order, m, target, 1.0, tg, gp, loss, y, flags, wsp, wbytes, None)
+        lp = g.lod(0.6 if name == B_STEP[2] else 0.95)
+        head = (d, b, grp, lp, q, table, points, lod, n, counts, order, m, target, 1.0, tg, gp, loss, y)
+        return g, head + {B_STEP[1]: (), B_STEP[2]: (dp,), B_STEP[3]: (dp, dl)}[name] + (flags, wsp, wbytes, None)
+    if name in B_GRAD:
+        d, (b, grp) = g.desc(), g.fields()
+        lp, src = g.lod(0.6 if name == B_GRAD[0] else 0.95), g.source()
+        points, lod, n, counts, order, m = g.ptr(0.96), g.ptr(0.5), g.n_batch(True), g.ptr(0.5), g.ptr(0.5), g.mlp()
+        k = rng.random()
+        dy, target = (g.ptr(1), None) if k < 0.45 else ((None, g.ptr(1)) if k < 0.9 else rng.choice(((None, None), (16, 32))))
+        tail = (g.ptr(0.96),) if name == B_GRAD[0] else (g.ptr(0.96), g.ptr(0.96))
+        return g, (d, b, grp, lp, src, points, lod, n, counts, order, m, dy, target, 1.0, g.ptr(0.5)) + tail + (None,)
+    if name in B_FWD:                                       # at points alone: a lattice launches, and so does a count of 2^31 points
+        d, (b, grp), src, n, m = g.desc(), g.fields(), g.source(), g.n_batch(False), g.mlp()
+        if name == B_FWD[0]:
+            origins, points = (None, g.ptr(1)) if g.good(0.92) else rng.choice(((None, None), (16, 32)))
+            return g, (d, b, grp, src, origins, points, n, m, g.ptr(0.96), None)
+        return g, (d, b, grp, g.lod(0.95), src, g.ptr(0.96), g.ptr(0.5), n, m, g.ptr(0.96), None)
     if name in STEP:
         d, q, m = g.desc(), g.quant(), g.mlp()
         n, order = g.n_order()
@@ -186,10 +238,12 @@ def main():
     ap.add_argument("--seed", type=int, default=20261021)
     ap.add_argument("--calls", type=int, default=20000, help="per entry point")
     ap.add_argument("--out")
+    ap.add_argument("--batch", action="store_true", help="the batched entries at points instead of the single field's")
     a = ap.parse_args()
     parent, new = load(a.parent), load(a.new)
-    res = {"sweep": "hashgrid_walk_unify_retcodes", "seed": a.seed, "calls_per_entry": a.calls, "entries": {}, "differences": 0, "unreached": []}
-    for name in STEP + GRAD + [NOISY, BYTES]:
+    entries, sizes = (B_STEP + B_GRAD + B_FWD + [B_BYTES], B_BYTES) if a.batch else (STEP + GRAD + [NOISY, BYTES], BYTES)
+    res = {"sweep": "hashgrid_batch_unify_retcodes" if a.batch else "hashgrid_walk_unify_retcodes", "seed": a.seed, "calls_per_entry": a.calls, "entries": {}, "differences": 0, "unreached": []}
+    for name in entries:
         rng = random.Random(f"{a.seed}/{name}")
         hist = {}
         for _ in range(a.calls):
@@ -198,13 +252,13 @@ def main():
             if rp != rn:
                 res["differences"] += 1
                 print("DIFFERENT", name, rp, rn, flush=True)
-            key = NAMES[rp] if name != BYTES else ("size > 0" if rp else "0")
+            key = NAMES[rp] if name != sizes else ("size > 0" if rp else "0")
             hist[key] = hist.get(key, 0) + 1
         res["entries"][name] = hist
-        want = {NAMES[c] for c in CAN[name]} if name != BYTES else {"0", "size > 0"}
+        want = {NAMES[c] for c in CAN[name]} if name != sizes else {"0", "size > 0"}
         res["unreached"] += [f"{name}: {c}" for c in sorted(want - set(hist))]
         print(name, hist, flush=True)
-    res["total_calls"] = a.calls * 10
+    res["total_calls"] = a.calls * len(entries)
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:

@@ -231,7 +231,7 @@ int nic_hash_fused_forward_backward_points_grad_lod(const nic_hash_desc *desc, c
 /* ---- B hash-grid fields per launch with the gradient with respect to the LEVEL OF DETAIL, alone and in the training step (hashgrid.py,
  *      hash_batch_points_grad_lod, hash_batch_forward_backward_points_grad_lod, HashGridFieldBatch.point_gradient_lod / jacobian_lod /
  *      query_differentiable_lod / train_points_grad_lod / train_points_differentiable_lod; csrc/hashgrid_batch_grad.hip,
- *      hash_batch_points_grad_lod_kernel; csrc/hashgrid_batch.hip, hash_batch_points_joint_lod_kernel).
+ *      hash_batch_points_grad_kernel<.., DLOD>; csrc/hashgrid_batch.hip, hash_batch_points_joint_lod_kernel).
  *      nic_hash_batch_points_grad_lod is nic_hash_batch_points_grad and nic_hash_batch_forward_backward_points_grad_lod is
  *      nic_hash_batch_forward_backward_points_grad, argument for argument, with dlod after dpoints and a level of detail always on: the
  *      same launches, gathers, records, reduction, flags, workspace, counts and order; y and dpoints (and loss and the decoder gradients

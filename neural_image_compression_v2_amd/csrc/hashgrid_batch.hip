@@ -30,8 +30,13 @@
 //   walked once more for the position gradient (hashgrid_pointgrad.hpp), row `row` of field b's slice of dpoints written once by its lane.
 //   the same step with d loss / d lambda on top (nic_hash_batch_forward_backward_points_grad_lod): hash_batch_points_joint_lod_kernel,
 //   after it, asks that walk for the level-of-detail accumulator and the noise term and stores dlod[b, row] beside dpoints.
-// Every device helper is hash_common.hpp's or hashgrid_pointgrad.hpp's; this unit holds the eight kernels, their parameters and the host side.  What the 16-bit batched
-// kernel (hashgrid_fused16.hip) shares with them - field_range, SParams, StoredSrc, the rules on B and G - is hashgrid_batch.hpp's.
+//   the host side of the four training entries at points is one path: open_batch_points, the entry's own null list and
+//   level-of-detail lines, batch_points_step - the batch counterpart of hash_common.hpp's points_fused_step -, launch_batch_reduce.
+// Every device helper is hash_common.hpp's or hashgrid_pointgrad.hpp's; this unit holds the crop-route kernel, the two decode kernels, the four
+// training kernels at points - still written out one by one: as one template the text of all 160 instantiations moved -, the
+// reduction, their parameters and the host side.  What the 16-bit batched kernel (hashgrid_fused16.hip) and the gradient-only unit
+// (hashgrid_batch_grad.hip) share with them - field_range, SParams, StoredSrc, the rules on B and G, the stride of a stacked source, the decoder
+// fill - is hashgrid_batch.hpp's.
 #include "hash_common.hpp"
 #include "hashgrid_batch.hpp"
 #include "hashgrid_pointgrad.hpp"
@@ -464,7 +469,7 @@ static int check_batch_desc(const nic_hash_desc* d, int n_linear) {
 static int batch_groups(const nic_hash_desc* d, int n_fields, int groups_per_field) { return batch_groups_of(count_patches(d), n_fields, groups_per_field); }
 static void fill(BParams& p, const nic_hash_desc* d, const float* tables, const int32_t* origins, const nic_mlp* mlp, float* y, int groups) {
     p.d = *d; p.tables = tables; p.origins = origins; p.y = y; p.groups = groups;
-    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
+    fill_decoder(p, mlp);
     p.n_patches = count_patches(d);
     p.n_samples = (int64_t)d->num_crops * d->extent[0] * d->extent[1] * (d->dim == 3 ? d->extent[2] : 1);
     p.noise.mode = NIC_NOISE_NONE;
@@ -690,6 +695,53 @@ static int launch_points_joint_lod(const PJLParams& p, int n_fields, void* strea
     });
 }
 
+// the fixed-order sum of the G records of every field into the stacked gradients and loss [B]; `counts` / `n_points` / `loss_scale` as the kernel reads them
+static int launch_batch_reduce(const float* partials, int g, int lf, int n_fields, const nic_mlp_grads* mlp_grads, float* loss, float loss_mul, int flags,
+                               const int32_t* counts, int64_t n_points, float loss_scale, void* stream) {
+    hipLaunchKernelGGL(hash_batch_reduce_kernel, dim3((unsigned)((RecLayout(lf).rec + 31) / 32), (unsigned)n_fields), dim3(256), 0, (hipStream_t)stream,
+                       partials, g, lf, *mlp_grads, loss, loss_mul, (flags & NIC_HASH_FUSED_ADD_GRADS) ? 1 : 0, (flags & NIC_HASH_FUSED_ADD_LOSS) ? 1 : 0,
+                       counts, n_points, loss_scale);
+    return (int)hipGetLastError();
+}
+
+// ---- the training step at points, the same at its four entry points: the batch counterpart of hash_common.hpp's points_fused_step ----------------
+// The opening of an entry: the descriptor, the number of fields and G.  Each entry follows it with its own null list and, where it has a level of
+// detail, its lodp / check_lod lines (_points_grad: a lod without lodp is refused, then check_lod where lodp is given), then the step below.
+static int open_batch_points(const nic_hash_desc* desc, const nic_mlp* mlp, int n_fields, int groups_per_field, int64_t n_points, int& g) {
+    if (!desc || !mlp) return NIC_E_NULL;
+    const int rc = check_batch_desc(desc, mlp->n_linear);
+    if (rc) return rc;
+    if (n_fields < 1 || n_fields > kMaxFields) return NIC_E_ARG;
+    g = point_groups(n_points, n_fields, groups_per_field);
+    return g < 0 ? NIC_E_ARG : NIC_OK;
+}
+// From the flags on.  `p` arrives zeroed but for what only its entry has (the level of detail, dpoints, dlod); `launch(noise)` starts the entry's
+// training kernel, `noise` a std::bool_constant
+template <class Params, class Launch>
+static int batch_points_step(Params& p, const nic_hash_desc* desc, int n_fields, int g, const nic_hash_quant* quant, const float* tables,
+                             const float* points, int64_t n_points, const int32_t* counts, const int32_t* order, const nic_mlp* mlp, const float* target,
+                             float loss_scale, float* table_grads, const nic_mlp_grads* mlp_grads, float* loss, float* y, int flags, void* workspace,
+                             size_t workspace_bytes, void* stream, Launch launch) {
+    if (flags & ~(NIC_HASH_FUSED_ADD_GRADS | NIC_HASH_FUSED_ADD_LOSS)) return NIC_E_ARG;
+    p.d = *desc; p.tables = tables; p.points = points; p.counts = counts; p.order = order; p.target = target; p.y = y; p.grads = table_grads;
+    fill_decoder(p, mlp);
+    p.n = n_points; p.groups = g; p.loss_scale = loss_scale;
+    p.noise.mode = NIC_NOISE_NONE;
+    int rc = set_noise(quant, true, p.noise, p.sample_base);
+    if (rc) return rc;
+    const int lf = desc->levels * desc->features;
+    if (workspace_bytes < (size_t)n_fields * g * RecLayout(lf).rec * sizeof(float)) return NIC_E_WORKSPACE;
+    if ((rc = check_point_desc(desc)) != NIC_OK) return rc;
+    if (n_points < 0 || n_points >= (int64_t(1) << 31)) return NIC_E_ARG;
+    if (n_points == 0) return NIC_OK;                                   // nothing to launch: loss and every gradient output stay as they are
+    p.partials = (float*)workspace;
+    rc = p.noise.mode == NIC_NOISE_KERNEL ? launch(std::true_type{}) : launch(std::false_type{});
+    if (rc != NIC_OK) return rc;
+    kernel_end_mark((hipStream_t)stream);
+    return launch_batch_reduce(p.partials, g, lf, n_fields, mlp_grads, loss, counts ? 0.f : field_loss_mul(loss_scale, n_points), flags, counts, n_points,
+                               loss_scale, stream);
+}
+
 }  // namespace hbatch
 }  // namespace nic
 
@@ -742,11 +794,10 @@ int nic_hash_batch_forward_source(const nic_hash_desc* desc, int n_fields, int g
     if ((rc = set_point_source(p, src)) != NIC_OK) return rc;
     if (points && n_points < 0) return NIC_E_ARG;
     if (points && n_points == 0) return NIC_OK;
-    p.stride = src->kind == NIC_HASH_SRC_F32 ? (((int64_t)desc->levels << desc->log2_table) * desc->features) * (int64_t)sizeof(float)
-             : src->kind == NIC_HASH_SRC_U8 ? nic_hash_stored_bytes(desc) : nic_hash_packed_bytes(desc, src->num_bits);
+    p.stride = stacked_source_stride(desc, src);
     if (p.stride <= 0) return NIC_E_ARG;
     p.n_rows = origins ? (int64_t)desc->num_crops * desc->extent[0] * desc->extent[1] * (desc->dim == 3 ? desc->extent[2] : 1) : n_points;
-    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
+    fill_decoder(p, mlp);
     return dispatch_source(src->kind, [&](auto kind) { return launch_source<decltype(kind)::value>(p, n_fields, stream); });
 }
 
@@ -768,58 +819,13 @@ int nic_hash_batch_forward_backward(const nic_hash_desc* desc, int n_fields, int
     p.target = target; p.grads = table_grads;
     if ((rc = set_noise(quant, true, p.noise, p.sample_base)) != NIC_OK) return rc;
     const int lf = desc->levels * desc->features;
-    const RecLayout rl(lf);
-    if (workspace_bytes < (size_t)n_fields * g * rl.rec * sizeof(float)) return NIC_E_WORKSPACE;
+    if (workspace_bytes < (size_t)n_fields * g * RecLayout(lf).rec * sizeof(float)) return NIC_E_WORKSPACE;
     const float loss_mul = field_loss_mul(loss_scale, p.n_samples);
     p.dscale = 2.0f * loss_mul;
     p.partials = (float*)workspace;
     if ((rc = p.noise.mode == NIC_NOISE_KERNEL ? launch<HB_TRAIN_NOISY>(p, n_fields, stream) : launch<HB_TRAIN>(p, n_fields, stream)) != NIC_OK) return rc;
     kernel_end_mark((hipStream_t)stream);
-    hipLaunchKernelGGL(hash_batch_reduce_kernel, dim3((unsigned)((rl.rec + 31) / 32), (unsigned)n_fields), dim3(256), 0, (hipStream_t)stream, p.partials, g,
-                       lf, *mlp_grads, loss, loss_mul, (flags & NIC_HASH_FUSED_ADD_GRADS) ? 1 : 0, (flags & NIC_HASH_FUSED_ADD_LOSS) ? 1 : 0,
-                       (const int32_t*)nullptr, (int64_t)0, loss_scale);
-    return (int)hipGetLastError();
-}
-
-size_t nic_hash_batch_points_workspace_bytes(const nic_hash_desc* desc, int n_fields, int groups_per_field, int64_t n_points, const nic_mlp* mlp) {
-    if (!desc || !mlp || check_batch_desc(desc, mlp->n_linear) != NIC_OK || n_fields < 1 || n_fields > kMaxFields) return 0;
-    const int g = point_groups(n_points, n_fields, groups_per_field);
-    if (g < 0 || check_point_desc(desc) != NIC_OK || n_points < 0 || n_points >= (int64_t(1) << 31)) return 0;
-    return (size_t)n_fields * g * RecLayout(desc->levels * desc->features).rec * sizeof(float);
-}
-
-int nic_hash_batch_forward_backward_points(const nic_hash_desc* desc, int n_fields, int groups_per_field, const nic_hash_quant* quant, const float* tables,
-                                           const float* points, int64_t n_points, const int32_t* counts, const int32_t* order, const nic_mlp* mlp,
-                                           const float* target, float loss_scale, float* table_grads, const nic_mlp_grads* mlp_grads, float* loss,
-                                           float* y, int flags, void* workspace, size_t workspace_bytes, void* stream) {
-    const KernelEndDrop end;
-    if (!desc || !mlp) return NIC_E_NULL;
-    int rc = check_batch_desc(desc, mlp->n_linear);
-    if (rc) return rc;
-    if (n_fields < 1 || n_fields > kMaxFields) return NIC_E_ARG;
-    const int g = point_groups(n_points, n_fields, groups_per_field);
-    if (g < 0) return NIC_E_ARG;
-    if (!tables || !points || !mlp3_ok(mlp) || !target || !mlp_grads || !loss || !workspace) return NIC_E_NULL;
-    if (flags & ~(NIC_HASH_FUSED_ADD_GRADS | NIC_HASH_FUSED_ADD_LOSS)) return NIC_E_ARG;
-    PParams p{};
-    p.d = *desc; p.tables = tables; p.points = points; p.counts = counts; p.order = order; p.target = target; p.y = y; p.grads = table_grads;
-    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
-    p.n = n_points; p.groups = g; p.loss_scale = loss_scale;
-    p.noise.mode = NIC_NOISE_NONE;
-    if ((rc = set_noise(quant, true, p.noise, p.sample_base)) != NIC_OK) return rc;
-    const int lf = desc->levels * desc->features;
-    const RecLayout rl(lf);
-    if (workspace_bytes < (size_t)n_fields * g * rl.rec * sizeof(float)) return NIC_E_WORKSPACE;
-    if ((rc = check_point_desc(desc)) != NIC_OK) return rc;
-    if (n_points < 0 || n_points >= (int64_t(1) << 31)) return NIC_E_ARG;
-    if (n_points == 0) return NIC_OK;                                   // nothing to launch: loss and every gradient stay as they are
-    p.partials = (float*)workspace;
-    if ((rc = p.noise.mode == NIC_NOISE_KERNEL ? launch_points<true>(p, n_fields, stream) : launch_points<false>(p, n_fields, stream)) != NIC_OK) return rc;
-    kernel_end_mark((hipStream_t)stream);
-    hipLaunchKernelGGL(hash_batch_reduce_kernel, dim3((unsigned)((rl.rec + 31) / 32), (unsigned)n_fields), dim3(256), 0, (hipStream_t)stream, p.partials, g,
-                       lf, *mlp_grads, loss, counts ? 0.f : field_loss_mul(loss_scale, n_points), (flags & NIC_HASH_FUSED_ADD_GRADS) ? 1 : 0,
-                       (flags & NIC_HASH_FUSED_ADD_LOSS) ? 1 : 0, counts, n_points, loss_scale);
-    return (int)hipGetLastError();
+    return launch_batch_reduce(p.partials, g, lf, n_fields, mlp_grads, loss, loss_mul, flags, nullptr, 0, loss_scale, stream);
 }
 
 // ---- with a level of detail per point: the siblings' checks in their order, lodp with the other pointers, check_lod right after them
@@ -841,96 +847,82 @@ int nic_hash_batch_forward_points_lod(const nic_hash_desc* desc, int n_fields, i
     if ((rc = set_point_source(p, src)) != NIC_OK) return rc;
     if (n_points < 0) return NIC_E_ARG;
     if (n_points == 0) return NIC_OK;
-    p.stride = src->kind == NIC_HASH_SRC_F32 ? (((int64_t)desc->levels << desc->log2_table) * desc->features) * (int64_t)sizeof(float)
-             : src->kind == NIC_HASH_SRC_U8 ? nic_hash_stored_bytes(desc) : nic_hash_packed_bytes(desc, src->num_bits);
+    p.stride = stacked_source_stride(desc, src);
     if (p.stride <= 0) return NIC_E_ARG;
-    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
+    fill_decoder(p, mlp);
     return dispatch_source(src->kind, [&](auto kind) { return launch_source_lod<decltype(kind)::value>(p, n_fields, stream); });
 }
 
+size_t nic_hash_batch_points_workspace_bytes(const nic_hash_desc* desc, int n_fields, int groups_per_field, int64_t n_points, const nic_mlp* mlp) {
+    if (!desc || !mlp || check_batch_desc(desc, mlp->n_linear) != NIC_OK || n_fields < 1 || n_fields > kMaxFields) return 0;
+    const int g = point_groups(n_points, n_fields, groups_per_field);
+    if (g < 0 || check_point_desc(desc) != NIC_OK || n_points < 0 || n_points >= (int64_t(1) << 31)) return 0;
+    return (size_t)n_fields * g * RecLayout(desc->levels * desc->features).rec * sizeof(float);
+}
+
+// ---- the training step at points: open_batch_points, the entry's own null list and level-of-detail lines, batch_points_step ----------------------
+int nic_hash_batch_forward_backward_points(const nic_hash_desc* desc, int n_fields, int groups_per_field, const nic_hash_quant* quant, const float* tables,
+                                           const float* points, int64_t n_points, const int32_t* counts, const int32_t* order, const nic_mlp* mlp,
+                                           const float* target, float loss_scale, float* table_grads, const nic_mlp_grads* mlp_grads, float* loss,
+                                           float* y, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+    const KernelEndDrop end;
+    int g;
+    const int rc = open_batch_points(desc, mlp, n_fields, groups_per_field, n_points, g);
+    if (rc) return rc;
+    if (!tables || !points || !mlp3_ok(mlp) || !target || !mlp_grads || !loss || !workspace) return NIC_E_NULL;
+    PParams p{};
+    return batch_points_step(p, desc, n_fields, g, quant, tables, points, n_points, counts, order, mlp, target, loss_scale, table_grads, mlp_grads, loss, y,
+                             flags, workspace, workspace_bytes, stream,
+                             [&](auto noise) { return launch_points<decltype(noise)::value>(p, n_fields, stream); });
+}
+
+// with a level of detail per point: lodp with the other pointers, check_lod right after them
 int nic_hash_batch_forward_backward_points_lod(const nic_hash_desc* desc, int n_fields, int groups_per_field, const nic_hash_lod* lodp,
                                                const nic_hash_quant* quant, const float* tables, const float* points, const float* lod, int64_t n_points,
                                                const int32_t* counts, const int32_t* order, const nic_mlp* mlp, const float* target, float loss_scale,
                                                float* table_grads, const nic_mlp_grads* mlp_grads, float* loss, float* y, int flags, void* workspace,
                                                size_t workspace_bytes, void* stream) {
     const KernelEndDrop end;
-    if (!desc || !mlp) return NIC_E_NULL;
-    int rc = check_batch_desc(desc, mlp->n_linear);
+    int g;
+    int rc = open_batch_points(desc, mlp, n_fields, groups_per_field, n_points, g);
     if (rc) return rc;
-    if (n_fields < 1 || n_fields > kMaxFields) return NIC_E_ARG;
-    const int g = point_groups(n_points, n_fields, groups_per_field);
-    if (g < 0) return NIC_E_ARG;
     if (!lodp || !tables || !points || !mlp3_ok(mlp) || !target || !mlp_grads || !loss || !workspace) return NIC_E_NULL;
     if ((rc = check_lod(desc, lodp)) != NIC_OK) return rc;
-    if (flags & ~(NIC_HASH_FUSED_ADD_GRADS | NIC_HASH_FUSED_ADD_LOSS)) return NIC_E_ARG;
     PLParams p{};
-    p.d = *desc; p.tables = tables; p.points = points; p.counts = counts; p.order = order; p.target = target; p.y = y; p.grads = table_grads;
-    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
-    p.n = n_points; p.groups = g; p.loss_scale = loss_scale;
+    p.d = *desc;                                                         // set_lod reads the levels
     set_lod(p, lodp, lod);
-    p.noise.mode = NIC_NOISE_NONE;
-    if ((rc = set_noise(quant, true, p.noise, p.sample_base)) != NIC_OK) return rc;
-    const int lf = desc->levels * desc->features;
-    const RecLayout rl(lf);
-    if (workspace_bytes < (size_t)n_fields * g * rl.rec * sizeof(float)) return NIC_E_WORKSPACE;
-    if ((rc = check_point_desc(desc)) != NIC_OK) return rc;
-    if (n_points < 0 || n_points >= (int64_t(1) << 31)) return NIC_E_ARG;
-    if (n_points == 0) return NIC_OK;                                   // nothing to launch: loss and every gradient stay as they are
-    p.partials = (float*)workspace;
-    if ((rc = p.noise.mode == NIC_NOISE_KERNEL ? launch_points_lod<true>(p, n_fields, stream) : launch_points_lod<false>(p, n_fields, stream)) != NIC_OK)
-        return rc;
-    kernel_end_mark((hipStream_t)stream);
-    hipLaunchKernelGGL(hash_batch_reduce_kernel, dim3((unsigned)((rl.rec + 31) / 32), (unsigned)n_fields), dim3(256), 0, (hipStream_t)stream, p.partials, g,
-                       lf, *mlp_grads, loss, counts ? 0.f : field_loss_mul(loss_scale, n_points), (flags & NIC_HASH_FUSED_ADD_GRADS) ? 1 : 0,
-                       (flags & NIC_HASH_FUSED_ADD_LOSS) ? 1 : 0, counts, n_points, loss_scale);
-    return (int)hipGetLastError();
+    return batch_points_step(p, desc, n_fields, g, quant, tables, points, n_points, counts, order, mlp, target, loss_scale, table_grads, mlp_grads, loss, y,
+                             flags, workspace, workspace_bytes, stream,
+                             [&](auto noise) { return launch_points_lod<decltype(noise)::value>(p, n_fields, stream); });
 }
 
-// ---- the training step that also writes d loss / d points: nic_hash_batch_forward_backward_points with lodp == NULL, else
-// ..._points_lod, argument for argument - their checks in their order (dpoints with the other pointers), their records, reduction and flags
+// the step that also writes d loss / d points: nic_hash_batch_forward_backward_points with lodp == NULL, else ..._points_lod,
+// argument for argument, dpoints with the other pointers
 int nic_hash_batch_forward_backward_points_grad(const nic_hash_desc* desc, int n_fields, int groups_per_field, const nic_hash_lod* lodp,
                                                 const nic_hash_quant* quant, const float* tables, const float* points, const float* lod, int64_t n_points,
                                                 const int32_t* counts, const int32_t* order, const nic_mlp* mlp, const float* target, float loss_scale,
                                                 float* table_grads, const nic_mlp_grads* mlp_grads, float* loss, float* y, float* dpoints, int flags,
                                                 void* workspace, size_t workspace_bytes, void* stream) {
     const KernelEndDrop end;
-    if (!desc || !mlp) return NIC_E_NULL;
-    int rc = check_batch_desc(desc, mlp->n_linear);
+    int g;
+    int rc = open_batch_points(desc, mlp, n_fields, groups_per_field, n_points, g);
     if (rc) return rc;
-    if (n_fields < 1 || n_fields > kMaxFields) return NIC_E_ARG;
-    const int g = point_groups(n_points, n_fields, groups_per_field);
-    if (g < 0) return NIC_E_ARG;
     if (!tables || !points || !mlp3_ok(mlp) || !target || !mlp_grads || !loss || !dpoints || !workspace) return NIC_E_NULL;
     if (!lodp && lod) return NIC_E_ARG;                                  // a null nic_hash_lod is "no level of detail" and takes no per-point array
     if (lodp && (rc = check_lod(desc, lodp)) != NIC_OK) return rc;
-    if (flags & ~(NIC_HASH_FUSED_ADD_GRADS | NIC_HASH_FUSED_ADD_LOSS)) return NIC_E_ARG;
     PJParams p{};
-    p.d = *desc; p.tables = tables; p.points = points; p.counts = counts; p.order = order; p.target = target; p.y = y; p.grads = table_grads;
-    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
-    p.n = n_points; p.groups = g; p.loss_scale = loss_scale; p.dpoints = dpoints;
+    p.d = *desc;                                                         // set_lod reads the levels
+    p.dpoints = dpoints;
     if (lodp) set_lod(p, lodp, lod);
-    p.noise.mode = NIC_NOISE_NONE;
-    if ((rc = set_noise(quant, true, p.noise, p.sample_base)) != NIC_OK) return rc;
-    const int lf = desc->levels * desc->features;
-    const RecLayout rl(lf);
-    if (workspace_bytes < (size_t)n_fields * g * rl.rec * sizeof(float)) return NIC_E_WORKSPACE;
-    if ((rc = check_point_desc(desc)) != NIC_OK) return rc;
-    if (n_points < 0 || n_points >= (int64_t(1) << 31)) return NIC_E_ARG;
-    if (n_points == 0) return NIC_OK;                                   // nothing to launch: loss, dpoints and every gradient stay as they are
-    p.partials = (float*)workspace;
-    const bool noisy = p.noise.mode == NIC_NOISE_KERNEL;
-    rc = lodp ? (noisy ? launch_points_joint<true, true>(p, n_fields, stream) : launch_points_joint<false, true>(p, n_fields, stream))
-              : (noisy ? launch_points_joint<true, false>(p, n_fields, stream) : launch_points_joint<false, false>(p, n_fields, stream));
-    if (rc != NIC_OK) return rc;
-    kernel_end_mark((hipStream_t)stream);
-    hipLaunchKernelGGL(hash_batch_reduce_kernel, dim3((unsigned)((rl.rec + 31) / 32), (unsigned)n_fields), dim3(256), 0, (hipStream_t)stream, p.partials, g,
-                       lf, *mlp_grads, loss, counts ? 0.f : field_loss_mul(loss_scale, n_points), (flags & NIC_HASH_FUSED_ADD_GRADS) ? 1 : 0,
-                       (flags & NIC_HASH_FUSED_ADD_LOSS) ? 1 : 0, counts, n_points, loss_scale);
-    return (int)hipGetLastError();
+    return batch_points_step(p, desc, n_fields, g, quant, tables, points, n_points, counts, order, mlp, target, loss_scale, table_grads, mlp_grads, loss, y,
+                             flags, workspace, workspace_bytes, stream, [&](auto noise) {
+                                 constexpr bool NOISE = decltype(noise)::value;
+                                 return lodp ? launch_points_joint<NOISE, true>(p, n_fields, stream) : launch_points_joint<NOISE, false>(p, n_fields, stream);
+                             });
 }
 
-// ---- the same step that also writes d loss / d lambda: the entry above with a level of detail always on and dlod after dpoints -
-// its checks in its order, lodp and dlod with the other pointers, its records, reduction and flags
+// the same step that also writes d loss / d lambda: the entry above with a level of detail always on and dlod after dpoints, lodp
+// and dlod with the other pointers
 int nic_hash_batch_forward_backward_points_grad_lod(const nic_hash_desc* desc, int n_fields, int groups_per_field, const nic_hash_lod* lodp,
                                                     const nic_hash_quant* quant, const float* tables, const float* points, const float* lod,
                                                     int64_t n_points, const int32_t* counts, const int32_t* order, const nic_mlp* mlp,
@@ -938,36 +930,18 @@ int nic_hash_batch_forward_backward_points_grad_lod(const nic_hash_desc* desc, i
                                                     float* loss, float* y, float* dpoints, float* dlod, int flags, void* workspace,
                                                     size_t workspace_bytes, void* stream) {
     const KernelEndDrop end;
-    if (!desc || !mlp) return NIC_E_NULL;
-    int rc = check_batch_desc(desc, mlp->n_linear);
+    int g;
+    int rc = open_batch_points(desc, mlp, n_fields, groups_per_field, n_points, g);
     if (rc) return rc;
-    if (n_fields < 1 || n_fields > kMaxFields) return NIC_E_ARG;
-    const int g = point_groups(n_points, n_fields, groups_per_field);
-    if (g < 0) return NIC_E_ARG;
     if (!lodp || !tables || !points || !mlp3_ok(mlp) || !target || !mlp_grads || !loss || !dpoints || !dlod || !workspace) return NIC_E_NULL;
     if ((rc = check_lod(desc, lodp)) != NIC_OK) return rc;
-    if (flags & ~(NIC_HASH_FUSED_ADD_GRADS | NIC_HASH_FUSED_ADD_LOSS)) return NIC_E_ARG;
     PJLParams p{};
-    p.d = *desc; p.tables = tables; p.points = points; p.counts = counts; p.order = order; p.target = target; p.y = y; p.grads = table_grads;
-    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
-    p.n = n_points; p.groups = g; p.loss_scale = loss_scale; p.dpoints = dpoints; p.dlod = dlod;
+    p.d = *desc;                                                         // set_lod reads the levels
+    p.dpoints = dpoints; p.dlod = dlod;
     set_lod(p, lodp, lod);
-    p.noise.mode = NIC_NOISE_NONE;
-    if ((rc = set_noise(quant, true, p.noise, p.sample_base)) != NIC_OK) return rc;
-    const int lf = desc->levels * desc->features;
-    const RecLayout rl(lf);
-    if (workspace_bytes < (size_t)n_fields * g * rl.rec * sizeof(float)) return NIC_E_WORKSPACE;
-    if ((rc = check_point_desc(desc)) != NIC_OK) return rc;
-    if (n_points < 0 || n_points >= (int64_t(1) << 31)) return NIC_E_ARG;
-    if (n_points == 0) return NIC_OK;                                   // nothing to launch: loss, dpoints, dlod and every gradient stay as they are
-    p.partials = (float*)workspace;
-    rc = p.noise.mode == NIC_NOISE_KERNEL ? launch_points_joint_lod<true>(p, n_fields, stream) : launch_points_joint_lod<false>(p, n_fields, stream);
-    if (rc != NIC_OK) return rc;
-    kernel_end_mark((hipStream_t)stream);
-    hipLaunchKernelGGL(hash_batch_reduce_kernel, dim3((unsigned)((rl.rec + 31) / 32), (unsigned)n_fields), dim3(256), 0, (hipStream_t)stream, p.partials, g,
-                       lf, *mlp_grads, loss, counts ? 0.f : field_loss_mul(loss_scale, n_points), (flags & NIC_HASH_FUSED_ADD_GRADS) ? 1 : 0,
-                       (flags & NIC_HASH_FUSED_ADD_LOSS) ? 1 : 0, counts, n_points, loss_scale);
-    return (int)hipGetLastError();
+    return batch_points_step(p, desc, n_fields, g, quant, tables, points, n_points, counts, order, mlp, target, loss_scale, table_grads, mlp_grads, loss, y,
+                             flags, workspace, workspace_bytes, stream,
+                             [&](auto noise) { return launch_points_joint_lod<decltype(noise)::value>(p, n_fields, stream); });
 }
 
 }  // extern "C"

@@ -76,6 +76,16 @@ static bool mlp3_ok(const nic_mlp* m) {
         if (!m->w[i] || !m->b[i]) return false;
     return true;
 }
+// the bases of the stacked decoder, into any parameter struct of a batch
+template <class Params>
+static void fill_decoder(Params& p, const nic_mlp* mlp) {
+    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
+}
+// SParams::stride of a stack of sources of src's kind: fp32 [L, T, F], the compact uint8 table or the bit-packed one.  <= 0: refused
+static int64_t stacked_source_stride(const nic_hash_desc* desc, const nic_hash_source* src) {
+    return src->kind == NIC_HASH_SRC_F32 ? (((int64_t)desc->levels << desc->log2_table) * desc->features) * (int64_t)sizeof(float)
+         : src->kind == NIC_HASH_SRC_U8 ? nic_hash_stored_bytes(desc) : nic_hash_packed_bytes(desc, src->num_bits);
+}
 
 }  // namespace hbatch
 }  // namespace nic

@@ -357,11 +357,10 @@ int nic_hash_batch_forward_p16(const nic_hash_desc* desc, int n_fields, int grou
     if (precision != NIC_HASH_PREC_SPLIT && precision != NIC_HASH_PREC_BF16) return NIC_E_ARG;
     if (points && n_points < 0) return NIC_E_ARG;
     if (points && n_points == 0) return NIC_OK;
-    p.stride = src->kind == NIC_HASH_SRC_F32 ? (((int64_t)desc->levels << desc->log2_table) * desc->features) * (int64_t)sizeof(float)
-             : src->kind == NIC_HASH_SRC_U8 ? nic_hash_stored_bytes(desc) : nic_hash_packed_bytes(desc, src->num_bits);
+    p.stride = hbatch::stacked_source_stride(desc, src);
     if (p.stride <= 0) return NIC_E_ARG;
     p.n_rows = origins ? (int64_t)desc->num_crops * desc->extent[0] * desc->extent[1] * (desc->dim == 3 ? desc->extent[2] : 1) : n_points;
-    p.w1 = mlp->w[0]; p.b1 = mlp->b[0]; p.w2 = mlp->w[1]; p.b2 = mlp->b[1]; p.w3 = mlp->w[2]; p.b3 = mlp->b[2];
+    hbatch::fill_decoder(p, mlp);
     return dispatch_source(src->kind, [&](auto kind) {
         constexpr int SRC = decltype(kind)::value;
         return precision == NIC_HASH_PREC_SPLIT ? launch_batch16<SRC, P16_SPLIT>(p, n_fields, stream) : launch_batch16<SRC, P16_BF16>(p, n_fields, stream);

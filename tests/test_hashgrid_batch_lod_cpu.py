@@ -312,7 +312,10 @@ def test_the_kernels_are_in_the_batch_unit_outside_the_older_slices_and_restate_
         e = e[:e.index("\n}\n")]
         assert e.index("!lodp") < e.index("check_lod(desc, lodp)") < e.index("set_lod(p, lodp, lod)")
     e = unit[unit.index("int nic_hash_batch_forward_backward_points_lod("):]
-    assert "const KernelEndDrop end;" in e and "kernel_end_mark((hipStream_t)stream);" in e and e.index("check_lod(desc, lodp)") < e.index("flags & ~")
+    e = e[:e.index("\n}\n")]
+    st = unit[unit.index("static int batch_points_step("):unit.index("}  // namespace hbatch")]       # the step's host path
+    assert "const KernelEndDrop end;" in e and e.index("check_lod(desc, lodp)") < e.index("batch_points_step(p,") and "flags & ~" not in e
+    assert st.index("{") < st.index("flags & ~") < st.index("p.d = *desc") and "kernel_end_mark((hipStream_t)stream);" in st
 
 
 # ------------------------------------------------------------------------------------------------------------------ the Python surface

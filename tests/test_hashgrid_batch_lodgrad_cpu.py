@@ -360,18 +360,21 @@ def test_the_kernels_call_the_one_walk_and_restate_no_shared_helper():
         assert found == [WALK], (name, found)
     # the gradient-only kernel: the sibling's shape, the walk asked for d / d lambda, one writer per row, no atomics and no workspace
     assert "atomic" not in grad and "workspace" not in re.sub(r"//.*", "", grad)
-    k = _kernel(grad, "hash_batch_points_grad_lod_kernel")
+    k = _kernel(grad, "hash_batch_points_grad_kernel")                     # the one kernel of the unit, its DLOD branch
     for call in ("load_decoder(", "DecoderSmem", "blockIdx.x / (unsigned)p.groups", "field_count(p.counts, b, p.n)", "field_loss_mul(p.loss_scale, n_b)",
                  "field_range(n_waves, lb, p.groups)", "ordered_row(order, n_b, live_lane ? pos : n_b - 1)", "point_lambda(lod_b, p.lod_uniform, row)",
-                 "point_fixed<D>(p.d, points, row, t)", "encode_point<D, F, SRC, false, false, true>(src_b, t, row, lam, xrow)", "decoder_dx_half<KT>(",
+                 "point_fixed<D>(p.d, points, row, t)", "encode_point<D, F, SRC, false, false, LOD>(src_b, t, row, lam, xrow)", "decoder_dx_half<KT>(",      # LOD is true under DLOD: the static_assert below
                  "point_walk<D, F, SRC, true, true, false>(src_b, t, row, lam, grow, gp, gl)",
                  "store_point_grad<D>(dpoints, row, kept_axes<D>(p.d, points, row), gp)", "dlod[row] = lambda_passes(lod_b, p.lod_uniform, row) ? gl : 0.0f"):
         assert call in k, call
     assert k.count("__syncthreads()") == 1 and k.index("__syncthreads()") < k.index("for (int64_t g")
     assert k.index("encode_point<") < k.index("decoder_dx_half<KT>(") < k.index("point_walk<") < k.index("if (live_lane) {") < k.index("dlod[row] =")
-    assert "float* dlod = p.dlod + (int64_t)b * p.n;" in k
-    assert "hash_batch_points_grad_lod_kernel<D, F, SRC, 2>" in grad and "hash_batch_points_grad_lod_kernel<D, F, SRC, 1>" in grad
-    assert grad.index("hash_batch_points_grad_kernel(const") < grad.index("hash_batch_points_grad_lod_kernel(const") < grad.index("// ---- host side")
+    assert "if constexpr (DLOD) dlod = p.dlod + (int64_t)b * p.n;" in k and k.index("if constexpr (DLOD) dlod =") < k.index("for (int64_t g")
+    assert k.index("if constexpr (DLOD) {") < k.index("point_walk<") < k.index("} else {") < k.index(" point_grad<D, F, SRC, LOD>(")
+    assert "static_assert(LOD || !DLOD" in k                               # a level of detail always on under DLOD
+    assert "hash_batch_points_grad_kernel<D, F, SRC, 2, LOD, DLOD, P>" in grad and "hash_batch_points_grad_kernel<D, F, SRC, 1, LOD, DLOD, P>" in grad
+    assert "launch<SRC, true, true>(p," in grad and "hash_batch_points_grad_lod_kernel" not in grad
+    assert grad.index("hash_batch_points_grad_kernel(const") < grad.index("// ---- host side")
     # the training kernel: at the end of the device part, the sibling's shape, the walk after the scatter with the noise
     k = _kernel(joint, "hash_batch_points_joint_lod_kernel")
     for call in ("load_decoder(", "TrainSmem", "field_count(p.counts, b, p.n)", "field_loss_mul(p.loss_scale, n_b)", "field_range(n_waves, lb, p.groups)",
@@ -387,10 +390,16 @@ def test_the_kernels_call_the_one_walk_and_restate_no_shared_helper():
     assert "hash_batch_points_joint_lod_kernel<D, F, 2, NOISE>" in joint and "hash_batch_points_joint_lod_kernel<D, F, 1, NOISE>" in joint
     assert joint.index("hash_batch_points_joint_kernel(const") < joint.index("hash_batch_points_joint_lod_kernel(const") < joint.index("}  // namespace hbatch")
     e = joint[joint.index(f"int {JOINT}("):]
-    assert "const KernelEndDrop end;" in e and "kernel_end_mark((hipStream_t)stream);" in e and "hash_batch_reduce_kernel" in e
-    assert e.index("!lodp") < e.index("check_lod(desc, lodp)") < e.index("flags & ~") < e.index("set_noise(") < e.index("NIC_E_WORKSPACE")
-    e = grad[grad.index(f"int {GRAD}("):]
+    e = e[:e.index("\n}\n")]
+    assert "const KernelEndDrop end;" in e and e.index("open_batch_points(") < e.index("!lodp") < e.index("check_lod(desc, lodp)") < e.index("batch_points_step(p,")
+    st = joint[joint.index("static int batch_points_step("):joint.index("}  // namespace hbatch")]     # the rest of the order, in the shared step
+    assert st.index("flags & ~") < st.index("set_noise(") < st.index("NIC_E_WORKSPACE") < st.index("check_point_desc(desc)") < st.index("n_points == 0")
+    assert st.index("n_points == 0") < st.index("kernel_end_mark((hipStream_t)stream);") < st.index("launch_batch_reduce(")
+    e = grad[grad.index("static int batch_points_grad("):]                 # both gradient entries sit on it
     assert e.index("!lodp") < e.index("set_point_source(p, src)") < e.index("check_lod(desc, lodp)") < e.index("(dy != nullptr) == (target != nullptr)")
+    for name, last in ((GRAD, "dlod, true, stream);"), ("nic_hash_batch_points_grad", "nullptr, false, stream);")):
+        w = grad[grad.index(f"int {name}("):]
+        assert "return batch_points_grad(" in w[:w.index("\n}\n")] and last in w[:w.index("\n}\n")], name
 
 
 # ------------------------------------------------------------------------------------------------------------------ the inputs

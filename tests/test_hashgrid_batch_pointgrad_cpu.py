@@ -271,11 +271,15 @@ def test_the_kernels_call_the_shared_helpers_and_restate_none():
     for call in ("load_decoder(", "DecoderSmem", "blockIdx.x / (unsigned)p.groups", "field_count(p.counts, b, p.n)", "field_loss_mul(p.loss_scale, n_b)",
                  "field_range(n_waves, lb, p.groups)", "ordered_row(order, n_b, live_lane ? pos : n_b - 1)", "point_lambda(lod_b, p.lod_uniform, row)",
                  "point_fixed<D>(p.d, points, row, t)", "encode_point<D, F, SRC, false, false, LOD>(src_b, t, row, lam, xrow)", "decoder_dx_half<KT>(",
-                 "point_grad<D, F, SRC, LOD>(src_b, t, lam,", "if (live_lane) store_point_grad<D>(dpoints, row, kept_axes<D>(p.d, points, row), gp)"):
+                 "point_grad<D, F, SRC, LOD>(src_b, t, lam, grow, gp)", "if (live_lane) store_point_grad<D>(dpoints, row, kept_axes<D>(p.d, points, row), gp)"):
         assert call in k, call
     assert k.count("__syncthreads()") == 1 and k.index("__syncthreads()") < k.index("for (int64_t g")
-    assert k.index("encode_point<") < k.index("decoder_dx_half<KT>(") < k.index("point_grad<") < k.index("store_point_grad<D>(")
-    assert "hash_batch_points_grad_kernel<D, F, SRC, 2, LOD>" in grad and "hash_batch_points_grad_kernel<D, F, SRC, 1, LOD>" in grad and "p.d.levels * F > 32" in grad
+    plain = k[k.index("} else {"):]                                        # the branch without d / d lambda, after the DLOD one
+    assert k.index("encode_point<") < k.index("decoder_dx_half<KT>(") < k.index("} else {") and "point_walk<" not in plain
+    assert plain.index("point_grad<") < plain.index("store_point_grad<D>(")
+    # one kernel for this entry and its _lod sibling: the parameter struct a template argument, both KT behind the one launch
+    assert "hash_batch_points_grad_kernel<D, F, SRC, 2, LOD, DLOD, P>" in grad and "hash_batch_points_grad_kernel<D, F, SRC, 1, LOD, DLOD, P>" in grad
+    assert "p.d.levels * F > 32" in grad and grad.count("__global__") == 1 and "launch<SRC, true, false>(q," in grad and "launch<SRC, false, false>(q," in grad
     # the joint kernel: the training kernels' shape, the backward always to the row, the walk after the scatter
     k = _kernel(joint, "hash_batch_points_joint_kernel")
     for call in ("load_decoder(", "TrainSmem", "field_count(p.counts, b, p.n)", "field_loss_mul(p.loss_scale, n_b)", "field_range(n_waves, lb, p.groups)",
@@ -289,7 +293,11 @@ def test_the_kernels_call_the_shared_helpers_and_restate_none():
     assert "hash_batch_points_joint_kernel<D, F, 2, NOISE, LOD>" in joint and "hash_batch_points_joint_kernel<D, F, 1, NOISE, LOD>" in joint
     assert joint.index("hash_batch_points_joint_kernel(const") > joint.index("// ---- host side")          # outside the slices the older tests read
     e = joint[joint.index("int nic_hash_batch_forward_backward_points_grad("):]
-    assert "const KernelEndDrop end;" in e and "kernel_end_mark((hipStream_t)stream);" in e and "hash_batch_reduce_kernel" in e and "tail_block" not in joint
+    assert "const KernelEndDrop end;" in e and "batch_points_step(p," in e and "tail_block" not in joint
+    # the step's host path, shared by the four entries: the launch, the end mark, the one reduction
+    st = joint[joint.index("static int batch_points_step("):joint.index("}  // namespace hbatch")]
+    assert st.index("launch(std::true_type{})") < st.index("kernel_end_mark((hipStream_t)stream);") < st.index("launch_batch_reduce(")
+    assert "hash_batch_reduce_kernel" in joint[joint.index("static int launch_batch_reduce("):joint.index("static int open_batch_points(")]
 
 
 # ------------------------------------------------------------------------------------------------------------------ the Python surface

@@ -285,7 +285,10 @@ def test_the_kernel_is_in_the_batch_unit_and_restates_no_shared_helper():
     assert "tail_block" not in unit                                      # still no optimiser tail on the reduction
     assert "hash_batch_points_kernel<D, F, 2, NOISE>" in unit and "hash_batch_points_kernel<D, F, 1, NOISE>" in unit and "p.d.levels * F > 32" in unit
     e = unit[unit.index("int nic_hash_batch_forward_backward_points("):]
-    assert "const KernelEndDrop end;" in e and "kernel_end_mark((hipStream_t)stream);" in e
+    e = e[:e.index("\n}\n")]
+    assert "const KernelEndDrop end;" in e and e.index("open_batch_points(") < e.index("!tables") < e.index("batch_points_step(p,")
+    st = unit[unit.index("static int batch_points_step("):unit.index("}  // namespace hbatch")]       # the step's host path
+    assert st.index("launch(std::true_type{})") < st.index("kernel_end_mark((hipStream_t)stream);") < st.index("launch_batch_reduce(")
 
 
 # ------------------------------------------------------------------------------------------------------------------ the Python surface

@@ -119,3 +119,38 @@ def test_the_point_walk_and_the_step_host_path_are_defined_once_in_all_of_csrc()
     assert not _function_re("point_walk").match("__device__ __forceinline__ void point_walk_levels(const Src& s, const uint32_t (&t)[3]) {")
     assert _function_re("fused_step").match("static int fused_step(Params& p, const nic_hash_quant* quant) {")
     assert not _function_re("fused_step").match("inline int points_fused_step(Params& p, const nic_hash_quant* quant) {")
+
+
+# ---- the batched entries at points: one step host path, one gradient-only kernel, one copy of the repeated host snippets -------
+BATCH_UNIT, BATCH_GRAD_UNIT, BATCH_HEADER = "hashgrid_batch.hip", "hashgrid_batch_grad.hip", "hashgrid_batch.hpp"
+BATCH_ONCE = {"batch_points_step": BATCH_UNIT, "open_batch_points": BATCH_UNIT, "launch_batch_reduce": BATCH_UNIT, "batch_points_grad": BATCH_GRAD_UNIT,
+              "stacked_source_stride": BATCH_HEADER, "fill_decoder": BATCH_HEADER}
+# the gradient-only pair is one kernel behind one launch; the four training kernels at points stay written out (their merge moved the text of all
+# 160 instantiations), so their names and launch helpers are not retired
+BATCH_RETIRED = ["hash_batch_points_grad_lod_kernel", "launch_lod"]
+
+
+def test_the_batch_step_host_path_and_its_helpers_are_defined_once_in_all_of_csrc():
+    src = _all_sources()
+    assert all(f in src for f in (BATCH_UNIT, BATCH_GRAD_UNIT, BATCH_HEADER, "hashgrid_fused16.hip")) and BATCH_HEADER in _build.HEADERS
+    for name, where in BATCH_ONCE.items():
+        found = _definitions(_function_re(name), src)
+        assert len(found) == 1 and found[0][0] == where, (name, found)
+    text = {f: "\n".join(lines) for f, lines in src.items()}
+    for name in BATCH_RETIRED:
+        assert not any(re.search(rf"\b{name}\b", t) for t in text.values()), name
+    # the stride of a stacked source, the six decoder pointers of a batch and the launch of the batched reduction: written out once each
+    assert [f for f, t in text.items() if "nic_hash_packed_bytes(desc, src->num_bits)" in t] == [BATCH_HEADER]
+    assert sum(t.count("nic_hash_stored_bytes(desc) : nic_hash_packed_bytes(") for t in text.values()) == 1
+    batch = [BATCH_UNIT, BATCH_GRAD_UNIT, BATCH_HEADER]
+    assert sum(text[f].count("p.w1 = mlp->w[0]") for f in batch) == 1 and "p.w1 = mlp->w[0]" in text[BATCH_HEADER]
+    assert sum(t.count("hipLaunchKernelGGL(hash_batch_reduce_kernel") for t in text.values()) == 1
+    # the eight entries sit on the shared paths: the four steps on open_batch_points + batch_points_step, the two gradient entries on one function
+    unit = text[BATCH_UNIT]
+    assert unit.count("open_batch_points(desc, mlp, n_fields, groups_per_field, n_points, g)") == 4 and unit.count("return batch_points_step(p,") == 4
+    assert text[BATCH_GRAD_UNIT].count("return batch_points_grad(") == 2 and text[BATCH_GRAD_UNIT].count("__global__") == 1
+    for f in (BATCH_UNIT, BATCH_GRAD_UNIT, "hashgrid_fused16.hip"):
+        assert "stacked_source_stride(desc, src)" in text[f], f
+    # the pattern sees the definitions it is asked about
+    assert _function_re("batch_points_step").match("static int batch_points_step(Params& p, const nic_hash_desc* desc) {")
+    assert not _function_re("launch_lod").match("static int launch_source_lod(const SLParams& p, int n_fields, void* stream) {")
